@@ -14,14 +14,19 @@ touches a GPU, or runs as one of the ranks when launched by torch.distributed.ru
 must equal WORLD_SIZE).  Each rank solves an independent 256^2 problem (replicas, weak scaling,
 no data-path collective).  Timing: barrier + device sync on both sides of exactly
 --steps steps, max over ranks; value = total steps of all ranks / that time.  With N > 1 the
-line also carries `sharded`: ONE C4 and ONE C5 problem row-sharded over the N ranks with RCCL
-(strong scaling of a single problem).
+line of a `--full` run also carries `sharded`: ONE C4 and ONE C5 problem row-sharded over the N
+ranks with RCCL (strong scaling of a single problem).
 
-Also reported: the dominant kernel's roofline (HIP events on the library's stream, algorithmic
-bytes/flops per launch), fp64 SPD factor+inverse GFLOP/s, a step(1)-per-call
-rate (the reference's loop shape), the CPU oracle timed on this host on bounded samples (all
-cores and 1 core; rank 0, N = 1 only; child processes, so no thread setting leaks into the GPU
-process), and `large_factors`: the MFMA-bound kernels at C5's 4096^2 size (rank 0, N = 1).
+A plain run does only what the headline needs: set-up, warm-up, the timed steps, the result
+line (the fields below stay in it, null).  `--dump-outputs DIR` writes what the timed step(K)
+call handed its caller (dump_outputs).
+
+`--full` also reports: the dominant kernel's roofline (HIP events on the library's stream,
+algorithmic bytes/flops per launch), fp64 SPD factor+inverse GFLOP/s, the training
+regime's rate, a step(1)-per-call rate (the reference's loop shape), the CPU oracle timed on this
+host on bounded samples (all cores and 1 core; rank 0, N = 1 only; child processes, so no thread
+setting leaks into the GPU process), `large_factors`: the MFMA-bound kernels at C5's 4096^2
+size (rank 0, N = 1), and with N > 1 the `sharded` section.
 """
 import argparse
 import json
@@ -416,6 +421,31 @@ class _DryRunSolver:
         pass
 
 
+DUMP_BUDGET_BYTES = 48 << 20   # all files of one --dump-outputs run together (limit: 64 MB)
+
+
+def dump_outputs(directory, s, losses, rank, world):
+    """--dump-outputs DIR: what the timed step(K) call handed its caller, as DIR/<name>.npy
+    (float64; ranks > 0 write <name>.rank<r>.npy): `losses`, the K log-joint values step()
+    returned (the last one is the last step's), and the state its last step left on the device:
+    `params` (flat, gpk_get_params) and Adam's `adam_mu` / `adam_nu`.  The problem and U are
+    seeded by rank, so the same arguments give the same inputs in every run and build.  An array
+    over its share of the byte budget is written as a fixed sample (sorted indices drawn with
+    seed 0)."""
+    import numpy as np
+    arrays = {"losses": np.asarray(losses, dtype=np.float64)}
+    if hasattr(s, "get_flat"):      # (the dry-run stand-in has no state)
+        arrays["params"] = s.get_flat()
+        _, arrays["adam_mu"], arrays["adam_nu"] = s.get_opt_state()
+    cap = DUMP_BUDGET_BYTES // (8 * world * len(arrays))
+    os.makedirs(directory, exist_ok=True)
+    for name, arr in arrays.items():
+        arr = np.ascontiguousarray(arr, dtype=np.float64).reshape(-1)
+        if arr.size > cap:
+            arr = arr[np.sort(np.random.default_rng(0).choice(arr.size, cap, replace=False))]
+        np.save(os.path.join(directory, name + (f".rank{rank}" if rank else "") + ".npy"), arr)
+
+
 def spawn_ranks(n):
     """One process per GPU, started before this process touches a GPU (children get the
     torch.distributed.run environment); exits with the worst child status."""
@@ -439,6 +469,11 @@ def main():
     ap.add_argument("--steps", type=int, default=500)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--config", default="C4")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every section beside the headline (roofline, SPD inverse rate, training "
+                         "regime, step(1) per call, C5-size factors, CPU baselines, N > 1: sharded)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed steps returned and left on the device as DIR/<name>.npy")
     ap.add_argument("--cpu-seconds", type=float, default=10.0)
     ap.add_argument("--cpu-threads", type=int, default=16)
     ap.add_argument("--cpu-blas-threads", type=int, default=1, help=argparse.SUPPRESS)
@@ -492,9 +527,11 @@ def main():
     rollbacks = rb1 - rb0
     dt = replicas.max_over_ranks(t1 - t0, ctx)
     value = world * a.steps / dt
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, s, losses, rank, world)
 
     extra = {}
-    if not a.dry_run:
+    if a.full and not a.dry_run:
         # the training regime (model_GP_solver_2d.py:285-332 runs nepoch steps): the same
         # step(K) call after >= 200 more Adam steps, with the graph it ran on (the refinement gate
         # follows the params, so the first 25 steps alone do not show a long run's rate)
@@ -537,7 +574,7 @@ def main():
     s.close()
 
     failed = None
-    if world > 1 and (a.dry_run_sharded or (not a.dry_run and not a.no_sharded)):
+    if a.full and world > 1 and (a.dry_run_sharded or (not a.dry_run and not a.no_sharded)):
         # strong scaling of ONE problem.  A failure or a stuck collective is a FAILED run: the
         # line is still printed (rank 0, the replicas' value + the error), the failing rank and
         # stage go to stderr, and the process exits non-zero -- never a clean-looking rc 0.
@@ -565,7 +602,7 @@ def main():
         done.set()
         extra.update(result)
 
-    if rank == 0 and world == 1 and not a.dry_run:
+    if a.full and rank == 0 and world == 1 and not a.dry_run:
         if not a.no_large:
             try:
                 extra["large_factors"] = large_factors()
@@ -593,6 +630,7 @@ def emit(a, value, dt, world, fast_graph, fast_end, rollbacks, final_loss, path,
         "n_gpus": world,
         "steps": a.steps,
         "warmup": a.warmup,
+        "full": bool(a.full),
         "ms_per_step": dt / a.steps * 1e3,
         "higher_is_better": True,
         "scaling": "weak",

@@ -34,6 +34,51 @@ def test_gpus_n_spawns_n_ranks(n):
     assert "NOT a measurement" in out["data"]
 
 
+def test_plain_run_is_headline_only(tmp_path):
+    """Without --full the line keeps its fields but runs no section beside the timed steps (a
+    requested stand-in sharded section included); --steps is the number of timed steps, and
+    --dump-outputs writes the K losses the timed call returned as float64."""
+    import numpy as np
+    r = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--steps", "5", "--warmup", "1", "--dry-run",
+                        "--dry-run-sharded", "ok", "--dump-outputs", str(tmp_path / "o")],
+                       env=_env(), capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr
+    out = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])
+    assert out["full"] is False and out["steps"] == 5 and out["ms_per_step"] > 0
+    assert out["value"] == pytest.approx(2 * 1e3 / out["ms_per_step"])
+    for key in ("sharded", "roofline", "train_regime", "step1_per_call", "cpu_baseline", "large_factors"):
+        assert key in out and out[key] is None, key
+    for rank, name in ((0, "losses.npy"), (1, "losses.rank1.npy")):
+        losses = np.load(tmp_path / "o" / name)
+        assert losses.dtype == np.float64 and losses.shape == (5,)
+        assert np.array_equal(losses, np.full(5, float(rank)))  # the stand-in's loss is its seed
+
+
+def test_dump_outputs_samples_large_arrays(tmp_path, monkeypatch):
+    """An array over its share of the byte budget is written as the same sorted sample every time."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+
+    class S:
+        def get_flat(self):
+            return np.arange(1000.0)
+
+        def get_opt_state(self):
+            return 3, np.arange(1000.0) * 2, np.arange(10.0)
+
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 4 * 8 * 100)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), S(), [1.0, 2.0], 0, 1)
+    got = {n: np.load(tmp_path / "a" / f"{n}.npy") for n in ("losses", "params", "adam_mu", "adam_nu")}
+    assert sum(v.nbytes for v in got.values()) <= 4 * 8 * 100
+    assert got["params"].shape == (100,) and np.all(np.diff(got["params"]) > 0)
+    assert np.array_equal(got["adam_mu"], 2 * got["params"])       # the same indices in every array
+    assert np.array_equal(got["adam_nu"], np.arange(10.0)) and np.array_equal(got["losses"], [1.0, 2.0])
+    for n, v in got.items():
+        assert np.array_equal(v, np.load(tmp_path / "b" / f"{n}.npy"))
+
+
 def test_gpus_must_match_world_size():
     r = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--steps", "2", "--dry-run"],
                        env=_env(WORLD_SIZE="1", RANK="0", LOCAL_RANK="0"),
@@ -54,7 +99,7 @@ def test_cpu_baseline_child_1d_and_2d(config):
 
 
 def test_sharded_section_ok_exits_zero():
-    r = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--steps", "2", "--warmup", "1",
+    r = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--steps", "2", "--warmup", "1", "--full",
                         "--dry-run", "--dry-run-sharded", "ok"], env=_env(), capture_output=True,
                        text=True, timeout=300)
     assert r.returncode == 0, r.stderr
@@ -74,7 +119,7 @@ def test_sharded_section_failure_exits_nonzero(mode):
     """A stuck collective (the watchdog fires) or a failing rank in the sharded section makes
     bench.py --gpus 2 exit non-zero, naming the rank and the stage on stderr; rank 0 still prints
     its line, with the error in `sharded`."""
-    r = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--steps", "2", "--warmup", "1",
+    r = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--steps", "2", "--warmup", "1", "--full",
                         "--dry-run", "--dry-run-sharded", mode, "--sharded-timeout", "8"],
                        env=_env(), capture_output=True, text=True, timeout=300)
     assert r.returncode != 0, (r.stdout, r.stderr)
