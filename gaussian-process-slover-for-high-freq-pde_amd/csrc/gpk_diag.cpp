@@ -1,0 +1,593 @@
+// gpk_diag.cpp — measurement and diagnostic entry points: per-stage and per-kernel timing, the
+// forward fields, the standalone GEMM, the trace hooks.  No solver entry point (gpk_create,
+// gpk_step, gpk_prepare, gpk_loss_grad, gpk_predict) reaches this file, and it reaches the step
+// only through the functions gpk_host.h declares.
+#include "gpk_host.h"
+#include "gpk_trace.h"
+
+namespace {
+
+struct EventPair {  // two HIP events, destroyed on every path
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  ~EventPair() {
+    if (e0) (void)hipEventDestroy(e0);
+    if (e1) (void)hipEventDestroy(e1);
+  }
+  hipError_t create() {
+    const hipError_t e = hipEventCreate(&e0);
+    return e != hipSuccess ? e : hipEventCreate(&e1);
+  }
+  hipError_t elapsed_us(double* us) {  // waits for e1
+    float ms = 0.f;
+    hipError_t e = hipEventSynchronize(e1);
+    if (e == hipSuccess) e = hipEventElapsedTime(&ms, e0, e1);
+    *us = ms * 1000.0;
+    return e;
+  }
+};
+
+// `warm` untimed launches, then `iters` launches back to back between two events: their average
+hipError_t time_launches(hipStream_t s, int iters, int warm, const std::function<hipError_t()>& body,
+                         double* avg_us) {
+  EventPair ev;
+  hipError_t e = ev.create();
+  for (int it = 0; it < warm && e == hipSuccess; ++it) e = body();
+  if (e == hipSuccess) e = hipEventRecord(ev.e0, s);
+  for (int it = 0; it < iters && e == hipSuccess; ++it) e = body();
+  if (e == hipSuccess) e = hipEventRecord(ev.e1, s);
+  double us = 0.0;
+  if (e == hipSuccess) e = ev.elapsed_us(&us);
+  if (e == hipSuccess) *avg_us = us / iters;  // (untouched on failure)
+  return e;
+}
+
+// `warm` + `iters` rounds of an untimed `prime` and a `timed` region between two events, one
+// synchronisation per round: the total of the last `iters` timed regions
+int time_each(hipStream_t s, int iters, int warm, const std::function<int()>& prime,
+              const std::function<int()>& timed, double* total_us) {
+  EventPair ev;
+  HIPCHK(ev.create());
+  *total_us = 0.0;
+  for (int it = 0; it < warm + iters; ++it) {
+    TRY(prime());
+    HIPCHK(hipEventRecord(ev.e0, s));
+    TRY(timed());
+    HIPCHK(hipEventRecord(ev.e1, s));
+    double us = 0.0;
+    HIPCHK(ev.elapsed_us(&us));
+    if (it >= warm) *total_us += us;
+  }
+  return GPK_OK;
+}
+
+}  // namespace
+
+int gpk_trace_reset(void) {
+  trace_reset_assemble();
+  trace_reset_spdinv();
+  trace_reset_pgrad();
+  trace_reset_gemm();
+  trace_reset_spdbig();
+  return GPK_OK;
+}
+
+int gpk_trace_read(uint64_t* lo, uint64_t* hi, int32_t n) {
+  if (!lo || !hi || n < TRACE_SLOTS) return fail(GPK_EINVAL, "need TRACE_SLOTS (256) slots");
+  uint64_t l[5][TRACE_SLOTS], h[5][TRACE_SLOTS];
+  trace_fetch_assemble(l[0], h[0]);
+  trace_fetch_spdinv(l[1], h[1]);
+  trace_fetch_pgrad(l[2], h[2]);
+  trace_fetch_gemm(l[3], h[3]);
+  trace_fetch_spdbig(l[4], h[4]);
+  for (int i = 0; i < TRACE_SLOTS; ++i) {
+    lo[i] = l[0][i];
+    hi[i] = h[0][i];
+    for (int u = 1; u < 5; ++u) {
+      lo[i] = std::min(lo[i], l[u][i]);
+      hi[i] = std::max(hi[i], h[u][i]);
+    }
+  }
+#ifdef GPK_TRACE
+  return GPK_OK;
+#else
+  return fail(GPK_EINVAL, "built without GPK_TRACE (make trace -> libgpk_trace.so)");
+#endif
+}
+
+int gpk_profile_stages(gpk_handle* h, int32_t iters, double* out_us, int32_t cap, int32_t* n) {
+  if (!h || !out_us || !n || iters <= 0) return fail(GPK_EINVAL, "bad argument");
+  DevSwitch ds(h->dev);
+  std::vector<double> acc(kMaxStages, 0.0);
+  // run on a copy of the state: save params + opt state, restore afterwards
+  const int64_t np = h->L.nparams;
+  std::vector<double> p(np), mu(np), nu(np);
+  int64_t cnt = 0;
+  TRY(gpk_get_params(h, p.data(), np));
+  TRY(gpk_get_opt_state(h, &cnt, mu.data(), nu.data(), np));
+  h->profiling = true;
+  for (int it = 0; it < iters; ++it) {
+    HIPCHK(hipMemsetAsync(h->loss_slot, 0, sizeof(int), h->s));
+    int rc = enqueue_step(h, 1);
+    if (rc) { h->profiling = false; return rc; }
+    HIPCHK(hipStreamSynchronize(h->s));
+    for (int k = 0; k < h->nstage; ++k) {
+      float ms = 0.f;
+      HIPCHK(hipEventElapsedTime(&ms, h->ev[k], h->ev[k + 1]));
+      acc[k] += ms * 1000.0;
+    }
+  }
+  h->profiling = false;
+  TRY(gpk_set_params(h, p.data(), np));
+  TRY(gpk_set_opt_state(h, cnt, mu.data(), nu.data(), np));
+  const int ns = std::min<int>(h->nstage, cap);
+  for (int k = 0; k < ns; ++k) out_us[k] = acc[k] / iters;
+  *n = ns;
+  return read_status(h);
+}
+
+const char* gpk_stage_name(const gpk_handle* h, int32_t stage) {
+  if (!h || stage < 0) return "?";
+  if (stage >= h->nstage || stage >= kMaxStages || !h->sname[stage]) return "?";
+  return h->sname[stage];
+}
+
+// the per-pair assembly of K and D into the handle's buffers (no kept copy, no classes)
+static int assemble_plain(gpk_handle* h, const AssembleArgs* aa) {
+  return check_launch(launch_assemble(h->prob.kind, h->L.q, aa, h->L.naxes, make_prep(h, 0), h->s), "assemble");
+}
+
+int gpk_time_spd_inverse(gpk_handle* h, int32_t iters, double* avg_us) {
+  if (!h || !avg_us || iters <= 0) return fail(GPK_EINVAL, "bad argument");
+  DevSwitch ds(h->dev);
+  AssembleArgs aa[2] = {};
+  SpdArgs sa[2];
+  fill_assemble(h, aa);
+  fill_spd(h, sa);
+  double total = 0.0;
+  // re-assemble K (the inverse consumes it), time only the inverse
+  TRY(time_each(h->s, iters, 0, [&] { return assemble_plain(h, aa); },
+                [&] {
+                  double* fin[2];
+                  return check_launch(launch_inverse(h, sa, fin, false), "spd_inverse");
+                },
+                &total));
+  *avg_us = total / iters;
+  return read_status(h);
+}
+
+int gpk_forward_field(gpk_handle* h, int32_t what, double* out, int64_t n) {
+  if (!h || !out) return fail(GPK_EINVAL, "NULL argument");
+  const Layout& L = h->L;
+  const int64_t n1 = L.n1, n2 = L.n2;
+  int64_t want;
+  if (L.dim == 2) {
+    const int64_t sizes[26] = {n1 * n1, n2 * n2, n1 * n2, n2 * n1, n1 * n2, n1 * n2,
+                               n1 * n1, n1 * n1, n2 * n2, n2 * n2, n1 * n1, n2 * n2,
+                               n1 * n1, n2 * n2, n1 * n2, n1 * n2, n1 * n2, n1 * n2,
+                               n1 * n1, n2 * n2, n1 * n1, n2 * n2, n1 * n1, n2 * n2, n1 * n1, n2 * n2};
+    if (what < 0 || what > 25) return fail(GPK_EINVAL, "what must be 0..25 (2D)");
+    if (what >= 22 && h->cls[0].ncls <= 0) return fail(GPK_EINVAL, "this handle does not use distance classes");
+    if ((what == 18 || what == 19) && !h->Kc[what - 18])
+      return fail(GPK_EINVAL, "this handle keeps no copy of K");
+    if ((what == 12 || what == 13) && !h->PD[what - 12])
+      return fail(GPK_EINVAL, "K^{-1} D^T is formed on the augmented chain path only");
+    want = sizes[what];
+  } else {
+    if (what != 0 && what != 2 && what != 4 && what != 6 && what != 7)
+      return fail(GPK_EINVAL, "what must be 0, 2, 4, 6 or 7 (1D)");
+    want = (what == 0 || what >= 6) ? n1 * n1 : n1;
+  }
+  if (n != want) return fail(GPK_EINVAL, "output size mismatch");
+  DevSwitch ds(h->dev);
+  std::vector<double> host;
+  double* tmp = nullptr;
+  auto cleanup = [&]() {
+    if (tmp) (void)hipFree(tmp);
+  };
+  if (what <= 1) {  // K factor: assemble at the current params (kappa + jitter I)
+    const int a = what;
+    const int na = axis_n(L, a);
+    TRY(check_launch(launch_prep2(h->params, L, h->kc, h->sc, h->count, 0, h->hyper.b1, h->hyper.b2, h->s), "prep"));
+    HIPCHK(hipMalloc(&tmp, (size_t)na * na * sizeof(double)));
+    const double* xa = axis_x(h, a);
+    int rc = check_launch(launch_cross(h->prob.kind, L.q, xa, na, xa, na, na, h->kc + a, h->prob.jitter,
+                                       0, tmp, nullptr, h->s), "cross");
+    if (rc == GPK_OK && hipMemcpyAsync(out, tmp, n * sizeof(double), hipMemcpyDeviceToHost, h->s) != hipSuccess)
+      rc = fail(GPK_EHIP, "copy");
+    if (rc == GPK_OK && hipStreamSynchronize(h->s) != hipSuccess) rc = fail(GPK_EHIP, "sync");
+    cleanup();
+    return rc;
+  }
+  double loss = 0.0;
+  TRY(gpk_loss_grad(h, &loss, nullptr));  // device buffers now hold the forward quantities
+  if (L.dim == 1 && what >= 6) {  // the step's K (6) and D (7), as its last step assembled them
+    const int P = L.p1, na = L.n1;
+    const ClassArgs& C = h->cls[0];
+    if (C.ncls > 0) {  // class ids + class values (K and D are never materialised on this path)
+      std::vector<int> cid((size_t)P * P);
+      std::vector<double> cv(C.ncls);
+      HIPCHK(hipMemcpy(cid.data(), C.cid, cid.size() * sizeof(int), hipMemcpyDeviceToHost));
+      HIPCHK(hipMemcpy(cv.data(), what == 6 ? C.kval : C.dval, cv.size() * sizeof(double), hipMemcpyDeviceToHost));
+      for (int i = 0; i < na; ++i)
+        for (int j = 0; j < na; ++j) {
+          double v = cv[cid[(size_t)i * P + j]];
+          if (what == 6 && i == j) v += h->prob.jitter;  // (the gather adds it per element)
+          out[(size_t)i * na + j] = v;
+        }
+      return GPK_OK;
+    }
+    const double* m = what == 6 ? h->Kc[0] : h->D[0];
+    if (!m) return fail(GPK_EINVAL, "this handle keeps no copy of K / D");
+    host.resize((size_t)P * P);
+    HIPCHK(hipMemcpy(host.data(), m, host.size() * sizeof(double), hipMemcpyDeviceToHost));
+    for (int i = 0; i < na; ++i)
+      for (int j = 0; j < na; ++j) out[(size_t)i * na + j] = host[(size_t)i * P + j];
+    return GPK_OK;
+  }
+  if (L.dim == 1) {
+    const int P = L.p1;
+    const double* src = h->alpha;
+    if (what == 4) {  // u_xx = D alpha
+      HIPCHK(hipMalloc(&tmp, P * sizeof(double)));
+      GemvDesc g{};
+      g.A = h->D[0]; g.lda = P; g.x = h->alpha; g.y = tmp; g.p = P; g.rows = P; g.alpha = 1.0;
+      g.epi = EPI_STORE;
+      gemv_operand(h, g);
+      int rc = check_launch(launch_gemv(g, h->s), "gemv");
+      if (rc) { cleanup(); return rc; }
+      src = tmp;
+    }
+    hipError_t e = hipMemcpyAsync(out, src, n * sizeof(double), hipMemcpyDeviceToHost, h->s);
+    if (e == hipSuccess) e = hipStreamSynchronize(h->s);
+    cleanup();
+    if (e != hipSuccess) return fail(GPK_EHIP, hipGetErrorString(e));
+    return GPK_OK;
+  }
+  const int P1 = L.p1, P2 = L.p2;
+  if (what >= 22) {  // K (22, 23) / D (24, 25) expanded on the host from the class table (cid + values)
+    const int a = (what == 22 || what == 24) ? 0 : 1;
+    const ClassArgs& C = h->cls[a];
+    const int P = axis_p(L, a), na = axis_n(L, a);
+    std::vector<int> cid((size_t)P * P);
+    std::vector<double> cv(C.ncls), x(na);
+    HIPCHK(hipMemcpy(cid.data(), C.cid, cid.size() * sizeof(int), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(cv.data(), what <= 23 ? C.kval : C.dval, cv.size() * sizeof(double), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(x.data(), axis_x(h, a), na * sizeof(double), hipMemcpyDeviceToHost));
+    const bool sgn = what >= 24 && h->prob.eq == GPK_ADVECTION;  // D_x1: s_ij (JAX abs'(0) = +1)
+    for (int i = 0; i < na; ++i)
+      for (int j = 0; j < na; ++j) {
+        double v = cv[cid[(size_t)i * P + j]];
+        if (what <= 23 && i == j) v += h->prob.jitter;
+        if (sgn && !(x[i] - x[j] >= 0.0)) v = -v;
+        out[(size_t)i * na + j] = v;
+      }
+    return GPK_OK;
+  }
+  if ((what >= 6 && what <= 13) || what >= 18) {  // work matrices, K^{-1}, K^{-1} D^T, Kc, D (P x P)
+    const int a = (what == 6 || what == 7 || what == 10 || what == 12 || what == 18 || what == 20) ? 0 : 1;
+    const int P = axis_p(L, a), na = axis_n(L, a);
+    const double* m = what >= 20 ? h->D[a] : what >= 18 ? h->Kc[a] : what >= 12 ? h->PD[a]
+                    : what >= 10 ? h->Kinv[a] : (what == 6 || what == 8) ? h->GK[a] : h->GD[a];
+    host.resize((size_t)P * P);
+    hipError_t e = hipMemcpyAsync(host.data(), m, host.size() * sizeof(double), hipMemcpyDeviceToHost, h->s);
+    if (e == hipSuccess) e = hipStreamSynchronize(h->s);
+    if (e != hipSuccess) return fail(GPK_EHIP, hipGetErrorString(e));
+    for (int i = 0; i < na; ++i)
+      for (int j = 0; j < na; ++j) out[(size_t)i * na + j] = host[(size_t)i * P + j];
+    return GPK_OK;
+  }
+  if (what >= 14) {  // grid work matrices R, X1, X2, S (P1 x P2)
+    const double* m = what == 14 ? h->R : what == 15 ? h->X1 : what == 16 ? h->X2 : h->S;
+    host.resize((size_t)P1 * P2);
+    hipError_t e = hipMemcpyAsync(host.data(), m, host.size() * sizeof(double), hipMemcpyDeviceToHost, h->s);
+    if (e == hipSuccess) e = hipStreamSynchronize(h->s);
+    if (e != hipSuccess) return fail(GPK_EHIP, hipGetErrorString(e));
+    for (int64_t i = 0; i < n1; ++i)
+      for (int64_t j = 0; j < n2; ++j) out[i * n2 + j] = host[(size_t)i * P2 + j];
+    return GPK_OK;
+  }
+  const double* src = (what == 3) ? h->Bt : h->A;
+  if (what >= 4) {  // U_xx = D1 A  /  U_yy = Bt D2^T
+    HIPCHK(hipMalloc(&tmp, (size_t)P1 * P2 * sizeof(double)));
+    GemmDesc g{};
+    if (what == 4) {
+      g.A = h->D[0]; g.lda = P1; g.B = h->A; g.ldb = P2; g.K = P1;
+    } else {
+      g.A = h->Bt; g.lda = P2; g.B = h->D[1]; g.ldb = P2; g.tb = 1; g.K = P2;
+    }
+    g.C = tmp; g.ldc = P2; g.M = P1; g.N = P2; g.alpha = 1.0; g.epi = EPI_STORE;
+    hipError_t e = launch_gemm_auto(&g, 1, h->sc, h->s,
+                                    gemm_variant(&g, 1, gemm_force(h->prob.flags)));
+    if (e != hipSuccess) { cleanup(); return fail(GPK_EHIP, hipGetErrorString(e)); }
+    src = tmp;
+  }
+  host.resize((size_t)P1 * P2);
+  hipError_t e = hipMemcpyAsync(host.data(), src, host.size() * sizeof(double), hipMemcpyDeviceToHost, h->s);
+  if (e == hipSuccess) e = hipStreamSynchronize(h->s);
+  cleanup();
+  if (e != hipSuccess) return fail(GPK_EHIP, hipGetErrorString(e));
+  for (int64_t i = 0; i < n1; ++i)
+    for (int64_t j = 0; j < n2; ++j) {
+      const double v = host[(size_t)i * P2 + j];
+      if (what == 3)
+        out[j * n1 + i] = v;  // K2inv_Ut = (U K2^{-1})^T
+      else
+        out[i * n2 + j] = v;
+    }
+  return GPK_OK;
+}
+
+// large path: a freshly assembled K with pivot block 0 factored and (panel) sweep 0's panel formed
+static int prime_big_inverse(gpk_handle* h, const AssembleArgs* aa, SpdArgs* sa, bool panel = true) {
+  TRY(assemble_plain(h, aa));
+  TRY(check_launch(launch_spd_big_stage(sa, h->L.naxes, -1, h->s), "pivot_init"));
+  if (panel) TRY(check_launch(launch_spd_big_stage(sa, h->L.naxes, 0, h->s), "panel"));
+  return GPK_OK;
+}
+
+// class path: the gather's arguments (classes, the kept copy Kc) and freshly evaluated class values
+static int prime_gather(gpk_handle* h, AssembleArgs* aa) {
+  const Layout& L = h->L;
+  if (h->cls[0].ncls <= 0) return fail(GPK_EINVAL, "gather: this handle does not use distance classes");
+  for (int a = 0; a < L.naxes; ++a) {
+    aa[a].cls = h->cls[a];
+    aa[a].Kc = h->Kc[a];
+  }
+  return check_launch(launch_assemble(h->prob.kind, L.q, aa, L.naxes, make_prep(h, 0), h->s, true), "class_eval");
+}
+
+// The K-assembly launch of the class path (the large-factor step's, gpk_step.cpp
+// enqueue_assemble_inverse): K (+ jitter), its kept copy Kc (when the handle keeps one) and D
+// written, the class id of every element read (its variant byte ClassArgs::vidx where the
+// handle built them, p >= 1024; else the int32 id) -- the bytes it really moves; the class
+// values and cbase entries are L2-resident gathers and not counted
+static double gather_bytes(const gpk_handle* h) {
+  double bytes = 0.0;
+  for (int a = 0; a < h->L.naxes; ++a) {
+    const double P = axis_p(h->L, a);
+    bytes += P * P * ((h->cls[a].vidx ? 1.0 : 4.0) + 8.0 + (h->Kc[a] ? 8.0 : 0.0) + (step_deriv(h) ? 8.0 : 0.0));
+  }
+  return bytes;
+}
+
+int gpk_bench_kernel(gpk_handle* h, const char* name, int32_t iters, double* avg_us,
+                     double* alg_flops, double* alg_bytes) {
+  if (!h || !name || !avg_us || !alg_flops || !alg_bytes || iters <= 0)
+    return fail(GPK_EINVAL, "bad argument");
+  const std::string nm(name);
+  const Layout& L = h->L;
+  // one full step (no update) so every kernel's inputs are valid
+  double loss = 0.0;
+  TRY(gpk_loss_grad(h, &loss, nullptr));
+  DevSwitch ds(h->dev);
+  AssembleArgs aa[2] = {};
+  SpdArgs sa[2];
+  fill_assemble(h, aa);
+  fill_spd(h, sa);
+  // a case either sets `launch` (warmed once, then timed `iters` times back to back) or times
+  // each iteration itself into `total`, `per` launches per timed region
+  std::function<hipError_t()> launch;
+  double flops = 0.0, bytes = 0.0, total = 0.0;
+  int per = 1;
+  const double n1 = L.n1, n2 = L.dim == 2 ? L.n2 : 0.0, nn[2] = {n1, n2};
+  const size_t grid_bytes = (size_t)L.p1 * L.p2 * sizeof(double);
+  auto copy_twice = [&]() -> int {  // an HBM-bound copy of other buffers
+    for (int c = 0; c < 2; ++c) HIPCHK(hipMemcpyAsync(h->S, h->R, grid_bytes, hipMemcpyDeviceToDevice, h->s));
+    return GPK_OK;
+  };
+  if (nm == "spd_chain") {
+    // the step's persistent inverse launch as the step runs it (gather mode after the class
+    // values; idempotent: it rebuilds K from the classes each time)
+    if (!h->chain) return fail(GPK_EINVAL, "spd_chain: this handle does not use the chain inverse");
+    const bool gather = h->cls[0].ncls > 0;
+    for (int a = 0; a < L.naxes; ++a) aa[a].cls = h->cls[a];
+    TRY(check_launch(launch_assemble(h->prob.kind, L.q, aa, L.naxes, make_prep(h, 0), h->s, gather),
+                     "assemble"));
+    launch = [&, gather]() {
+      double* fin[2];
+      return launch_chain(h, gather, fin);
+    };
+    // potrf + potri = n^3 per factor; each augmented column a triangular solve pair, 2 n^2
+    // bytes: K^{-1}, Kc, D written (24 n^2), augmented outputs written (8 n m), U read
+    for (int a = 0; a < L.naxes; ++a) {
+      const double n = nn[a], m = h->chain_aug ? n1 + n2 : 0.0;
+      flops += n * n * n + 2.0 * n * n * m;
+      bytes += 24.0 * n * n + 8.0 * n * m + (h->chain_aug ? 8.0 * n1 * n2 : 0.0);
+    }
+  } else if (nm == "sweep" && h->bigspd) {
+    // large path: time the update launch of sweep 0 (in place, so every timed launch gets a
+    // freshly assembled K, pivot 0 and panel 0 first; only the update is between the events)
+    TRY(time_each(h->s, iters, 0, [&] { return prime_big_inverse(h, aa, sa); },
+                  [&] { return check_launch(launch_spd_big_stage(sa, L.naxes, 1, h->s), "update"); }, &total));
+    // the MFMA work launch 0 schedules (its tile lists: under the two-sweep schedule launch 0
+    // updates only its own parity class + the eager row / column, all at K = 128), + the next
+    // pivot and panel; HBM: read + write the lower triangle
+    flops = spd_big_update_flops(sa, L.naxes, 0, true);
+    for (int a = 0; a < L.naxes; ++a) bytes += 8.0 * nn[a] * nn[a];
+  } else if (nm == "spd_tiles" && h->bigspd) {
+    // the update launch's tile work alone (no pivot workgroup), sweep 0; idempotent enough for
+    // timing (each launch re-reads X and Z; values drift but stay finite over a few launches)
+    TRY(prime_big_inverse(h, aa, sa));
+    launch = [&]() { return launch_spd_big_tiles(sa, L.naxes, 0, h->s); };
+    // the tile products launch 0's lists schedule (no pivot workgroup) -- the work actually done
+    flops = spd_big_update_flops(sa, L.naxes, 0, false);
+    for (int a = 0; a < L.naxes; ++a) bytes += 8.0 * nn[a] * nn[a];
+  } else if (nm == "spd_updates" && h->bigspd) {
+    // every update launch of one inverse (sweeps 0 .. last, each with its fused next pivot and
+    // panel; the final mirror left out), between two events after pivot 0 and panel 0: the
+    // average update launch as the step runs it, even and odd launches of the two-sweep schedule
+    // alike, credited with the work their tile lists schedule (spd_big_update_flops)
+    int nsw = 0;
+    for (int a = 0; a < L.naxes; ++a) nsw = std::max(nsw, spd_big_sweeps(axis_p(L, a), h->bigwide));
+    for (int k = 0; k < nsw; ++k) flops += spd_big_update_flops(sa, L.naxes, k, true);
+    TRY(time_each(h->s, iters, 0, [&] { return prime_big_inverse(h, aa, sa); },
+                  [&]() -> int {
+                    for (int k = 0; k < nsw; ++k)
+                      TRY(check_launch(launch_spd_big_stage(sa, L.naxes, 2 * k + 1, h->s, false), "update"));
+                    return GPK_OK;
+                  },
+                  &total));
+    for (int a = 0; a < L.naxes; ++a)  // read + write the lower triangle per sweep
+      bytes += 8.0 * nn[a] * nn[a] * spd_big_sweeps(axis_p(L, a), h->bigwide);
+    per = nsw;  // time, flops and bytes per update launch
+  } else if ((nm == "spd_pivot" || nm == "spd_panel") && h->bigspd) {
+    // large path pieces (idempotent): the 64-pivot factorisation of block 0, the panel of sweep 0
+    TRY(prime_big_inverse(h, aa, sa, false));
+    const int stage = nm == "spd_pivot" ? -1 : 0;
+    launch = [&, stage]() { return launch_spd_big_stage(sa, L.naxes, stage, h->s); };
+  } else if (nm == "sweep") {
+    // re-assemble K and factor pivot 0, then time sweep 0 (idempotent: X -> Y, piv[1]).
+    TRY(assemble_plain(h, aa));
+    TRY(check_launch(launch_spd_stage(sa, L.naxes, -1, h->s), "pivot_init"));
+    launch = [&]() { return launch_spd_stage(sa, L.naxes, 0, h->s); };
+    // potrf+potri-equivalent flops (n^3 per factor) spread over the T = p/32 sweeps;
+    // HBM bytes: read X + write Y per factor
+    for (int a = 0; a < L.naxes; ++a) {
+      flops += nn[a] * nn[a] * nn[a] / (axis_p(L, a) / 32);
+      bytes += 16.0 * nn[a] * nn[a];
+    }
+  } else if (nm == "gather") {
+    TRY(prime_gather(h, aa));
+    launch = [&]() { return launch_gather_only(aa, L.naxes, h->s); };
+    bytes = gather_bytes(h);
+  } else if ((nm == "write_stream" || nm == "write_stream_after_copy") && L.dim == 2) {
+    // a pure write stream of the gather's bytes (hipMemsetD32 of K, Kc, D of both factors),
+    // back to back or right after an HBM-bound copy of other buffers: whether the gather's
+    // in-step rate is the write-heavy HBM rate once the memory-side cache holds other lines
+    const bool after = nm == "write_stream_after_copy";
+    TRY(time_each(h->s, iters, 1, [&]() -> int { return after ? copy_twice() : GPK_OK; },
+                  [&]() -> int {
+                    for (int a = 0; a < L.naxes; ++a) {
+                      const size_t P = axis_p(L, a);
+                      for (double* q : {h->K[a], h->Kc[a], h->D[a]}) HIPCHK(hipMemsetD32Async(q, 0, 2 * P * P, h->s));
+                    }
+                    return GPK_OK;
+                  },
+                  &total));
+    for (int a = 0; a < L.naxes; ++a) bytes += 24.0 * axis_p(L, a) * (double)axis_p(L, a);
+  } else if ((nm == "gather_after_gemm" || nm == "gather_after_copy") && L.dim == 2) {
+    // the gather timed alone (events around it) right after a C5-size GEMM stage (gemm_B: an
+    // MFMA-bound launch writing 2 x 134 MB) or after an HBM-bound copy of the same bytes: which
+    // state makes the in-step gather run at half its back-to-back rate
+    TRY(prime_gather(h, aa));
+    const bool gemm = nm == "gather_after_gemm";
+    TRY(time_each(h->s, iters, 1,  // (the first round is a warm-up)
+                  [&]() -> int {
+                    if (!gemm) return copy_twice();
+                    HIPCHK(launch_gemm_stage(h, 3));
+                    return GPK_OK;
+                  },
+                  [&]() -> int {
+                    HIPCHK(launch_gather_only(aa, L.naxes, h->s));
+                    return GPK_OK;
+                  },
+                  &total));
+    bytes = gather_bytes(h);
+  } else if (nm == "class_eval") {
+    // the class-value launch (every field at every class distance + the step constants): it
+    // reads the U class distances and writes K and D values per class (24 B per class and axis)
+    if (h->cls[0].ncls <= 0) return fail(GPK_EINVAL, "class_eval: this handle does not use distance classes");
+    for (int a = 0; a < L.naxes; ++a) aa[a].cls = h->cls[a];
+    launch = [&]() {
+      return launch_assemble(h->prob.kind, L.q, aa, L.naxes, make_prep(h, 0), h->s, true);
+    };
+    for (int a = 0; a < L.naxes; ++a) bytes += 24.0 * h->cls[a].ncls;
+  } else if (nm == "assemble") {
+    // the step's assembly launch(es): class values only when the chain gathers K itself
+    const bool eval_only = h->chain && h->cls[0].ncls > 0;
+    for (int a = 0; a < L.naxes; ++a) aa[a].cls = h->cls[a];
+    launch = [&, eval_only]() {
+      return launch_assemble(h->prob.kind, L.q, aa, L.naxes, make_prep(h, 0), h->s, eval_only);
+    };
+    // the bytes the launch really moves: with classes and the chain, the class values (24 B per
+    // class: distance read, K and D value written); otherwise K and D written per element (P^2
+    // per axis, 8 B each); flops not counted (transcendental-bound)
+    for (int a = 0; a < L.naxes; ++a) {
+      const double P = axis_p(L, a);
+      bytes += eval_only ? 24.0 * h->cls[a].ncls : 16.0 * P * P;
+    }
+  } else if (nm == "gemm_B" && L.dim == 2) {
+    launch = [&]() { return launch_gemm_stage(h, 3); };
+    // S = A K2^{-1} (2 n1 n2^2); R = D1 A + Bt D2^T (2 n1^2 n2 + 2 n1 n2^2)
+    flops = 2 * n1 * n2 * n2 + 2 * n1 * n1 * n2 + 2 * n1 * n2 * n2;
+    // reads A, K2^{-1}, D1, Bt, D2, F, U; writes S, R
+    bytes = 8.0 * (n1 * n2 + n2 * n2 + n1 * n1 + n1 * n2 + n2 * n2 + 2 * n1 * n2 + 2 * n1 * n2);
+  } else if (nm == "pgrad" && L.dim == 2) {
+    // the base arguments only, without the step tail: partials as the per-pair / class path
+    // forms them (no low parts, no class partials from the GEMM epilogues)
+    PGradArgs pa[2];
+    fill_pgrad2d(h, pa);
+    launch = [&, pa]() mutable { return launch_pgrad(h->prob.kind, L.q, 0, pa, 2, h->bpa, h->sc, h->s); };
+    bytes = 16.0 * (n1 * n1 + n2 * n2);  // G_K, G_D read
+  } else {
+    return fail(GPK_EINVAL, "unknown kernel name (spd_chain | sweep | assemble | gemm_B | pgrad[2D])");
+  }
+  if (launch) {
+    HIPCHK(time_launches(h->s, iters, 1, launch, avg_us));
+  } else {
+    *avg_us = total / iters / per;
+  }
+  *alg_flops = flops / per;
+  *alg_bytes = bytes / per;
+  return read_status(h);
+}
+
+int gpk_dgemm(int32_t variant, int32_t M, int32_t N, int32_t K, double alpha, const double* A,
+              int32_t lda, int32_t ta, const double* B, int32_t ldb, int32_t tb, int32_t K2,
+              double alpha2, const double* A2, int32_t lda2, int32_t ta2, const double* B2,
+              int32_t ldb2, int32_t tb2, double beta, const double* C0, double* C, int32_t ldc,
+              int32_t iters, double* avg_us) {
+  if (variant < 0 || variant > 3 || M <= 0 || N <= 0 || K <= 0 || K2 < 0 || (M | N | K | K2) & 31 ||
+      !A || !B || !C || (K2 && (!A2 || !B2)) || iters < 0 || (iters && !avg_us))
+    return fail(GPK_EINVAL, "gpk_dgemm: bad argument (M, N, K, K2 multiples of 32)");
+  // stored extents of op(A) = M x K etc.: rows x row length, each row length <= its ld
+  auto ext = [](int rows, int cols, int t, int ld, size_t* n) {
+    const int r = t ? cols : rows, c = t ? rows : cols;
+    *n = (size_t)(r - 1) * ld + c;
+    return ld >= c;
+  };
+  size_t na = 0, nb = 0, na2 = 0, nb2 = 0, nc = 0;
+  if (!ext(M, K, ta, lda, &na) || !ext(K, N, tb, ldb, &nb) || !ext(M, N, 0, ldc, &nc) ||
+      (K2 && (!ext(M, K2, ta2, lda2, &na2) || !ext(K2, N, tb2, ldb2, &nb2))))
+    return fail(GPK_EINVAL, "gpk_dgemm: leading dimension shorter than a row");
+  TRY(check_device(0));
+  DevSwitch dsw(0);
+  std::vector<void*> mem;
+  auto cleanup = [&]() { for (void* p : mem) (void)hipFree(p); };
+  auto up = [&](const double* src, size_t n, double** dst) -> hipError_t {
+    hipError_t e = hipMalloc(dst, n * 8);
+    if (e != hipSuccess) return e;
+    mem.push_back(*dst);
+    return src ? hipMemcpy(*dst, src, n * 8, hipMemcpyHostToDevice) : hipSuccess;
+  };
+  GemmDesc d{};
+  double *dA = nullptr, *dB = nullptr, *dA2 = nullptr, *dB2 = nullptr, *dC = nullptr, *dC0 = nullptr;
+  hipError_t e = up(A, na, &dA);
+  if (e == hipSuccess) e = up(B, nb, &dB);
+  if (e == hipSuccess && K2) e = up(A2, na2, &dA2);
+  if (e == hipSuccess && K2) e = up(B2, nb2, &dB2);
+  if (e == hipSuccess) e = up(C0 == C ? C : nullptr, nc, &dC);
+  if (e == hipSuccess && C0 && C0 != C) e = up(C0, nc, &dC0);
+  if (e != hipSuccess) {
+    cleanup();
+    return fail(e == hipErrorOutOfMemory ? GPK_ENOMEM : GPK_EHIP, std::string("gpk_dgemm: ") + hipGetErrorString(e));
+  }
+  d.A = dA; d.lda = lda; d.ta = ta ? 1 : 0; d.B = dB; d.ldb = ldb; d.tb = tb ? 1 : 0;
+  d.A2 = dA2; d.lda2 = lda2; d.ta2 = ta2 ? 1 : 0; d.B2 = dB2; d.ldb2 = ldb2; d.tb2 = tb2 ? 1 : 0;
+  d.alpha = alpha; d.alpha2 = alpha2; d.K2 = K2;
+  d.beta = C0 ? beta : 0.0; d.C0 = C0 ? (C0 == C ? dC : dC0) : nullptr; d.ldc0 = ldc;
+  d.C = dC; d.ldc = ldc; d.M = M; d.N = N; d.K = K; d.epi = EPI_STORE;
+  const int v = variant ? variant : gemm_variant(&d, 1, 0);
+  auto launch = [&]() { return launch_gemm_auto(&d, 1, nullptr, 0, v); };
+  // (an in-place C0 == C update is checked once; timed launches then repeat it on their own output)
+  e = launch();
+  if (e == hipSuccess) e = hipDeviceSynchronize();
+  if (e == hipSuccess) e = hipMemcpy(C, dC, nc * 8, hipMemcpyDeviceToHost);
+  // (timing only: with C0 == C every timed launch updates dC in place, so each one reads the
+  // previous launch's output as its C0 -- same shapes and work, different values; the result
+  // copied back above is the first launch's)
+  if (e == hipSuccess && iters) e = time_launches(0, iters, 1, launch, avg_us);
+  cleanup();
+  if (e != hipSuccess) return fail(GPK_EHIP, std::string("gpk_dgemm: ") + hipGetErrorString(e));
+  return GPK_OK;
+}

@@ -1,0 +1,256 @@
+// gpk_host.h — what the host translation units of libgpk share (never included by device code):
+// the solver handle, the error helpers, and the functions that cross translation units.
+//   gpk_api.cpp     errors, device check, standalone kernels, predict, getters and setters
+//   gpk_create.cpp  handle construction (validate, choose path, allocate, classes, upload), state
+//   gpk_step.cpp    the step: plan (build_descs), enqueue, graph capture, batch protocol, gpk_step
+//   gpk_shard.cpp   the row-sharded step and its collective backends (the only user of RCCL)
+//   gpk_diag.cpp    measurement and diagnostic entry points (reached from no solver entry point)
+//   gpk_kron3.cpp   the 3-axis solver
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <functional>
+#include <map>
+#include <string>
+#include <vector>
+
+#include "../../include/gpk.h"
+#include "gpk_internal.h"
+#include "stepk.h"
+
+using namespace gpk;
+
+// helpers and cross-unit functions stay out of the library's dynamic symbol table
+#pragma GCC visibility push(hidden)
+int fail(int code, const std::string& msg);  // sets gpk_last_error, returns code (gpk_api.cpp)
+int check_launch(hipError_t e, const char* what);
+int check_device(int dev);
+#pragma GCC visibility pop
+
+#define HIPCHK(x)                                                                      \
+  do {                                                                                 \
+    hipError_t e_ = (x);                                                               \
+    if (e_ != hipSuccess)                                                              \
+      return fail(e_ == hipErrorOutOfMemory ? GPK_ENOMEM : GPK_EHIP,                   \
+                  std::string(#x) + ": " + hipGetErrorString(e_));                     \
+  } while (0)
+
+constexpr int LOSS_CAP = 4096;
+constexpr int kMaxStages = 18;
+constexpr int kGemmStages = 11;  // A, A_res, A_fix, B, B_res, B_fix, C, D, D_res, D_fix, E
+
+// restore the caller's current device on scope exit
+struct __attribute__((visibility("hidden"))) DevSwitch {
+  int prev = -1;
+  explicit DevSwitch(int dev) {
+    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
+    (void)hipSetDevice(dev);
+  }
+  ~DevSwitch() {
+    if (prev >= 0) (void)hipSetDevice(prev);
+  }
+};
+
+struct Stage {
+  int off = 0, n = 0, variant = 0;
+  bool gated = false;  // every descriptor is a refinement GEMM (left out of the fast graph)
+};
+
+struct gpk_handle;
+// collective backend of a row-sharded handle (RCCL, or an in-process group: gpk_shard.cpp)
+struct ShardComm {
+  virtual ~ShardComm() {}
+  virtual int allgather(gpk_handle* h, double* buf, size_t chunk) = 0;  // in place
+  virtual int allreduce(gpk_handle* h, double* buf, size_t n) = 0;      // in place, sum
+  virtual int broadcast(gpk_handle* h, double* buf, size_t n, int root) = 0;  // in place
+  virtual bool capturable() const = 0;
+};
+struct ShardGather {
+  double* buf;
+  size_t chunk;     // doubles per rank (a block of rows), rank r's block at buf + r * chunk
+};
+
+struct gpk_handle {
+  gpk_problem prob{};
+  double freq_scale = 0.0;
+  Layout L{};
+  AdamHyper hyper{};
+  int dev = 0;
+  hipStream_t s = nullptr;
+  std::vector<void*> allocs;
+
+  double *x1 = nullptr, *x2 = nullptr, *F = nullptr, *bvals = nullptr;
+  int* bidx = nullptr;
+  double *params = nullptr, *grad = nullptr, *m = nullptr, *v = nullptr, *Up = nullptr;
+  AxisConst* kc = nullptr;
+  StepScalars* sc = nullptr;
+  int *count = nullptr, *loss_slot = nullptr, *status = nullptr;
+  // batch begin / report folded into the next enqueued step (capture_call, capture_calln): the
+  // step that takes one clears its pointer
+  const StepBegin* fold_begin = nullptr;
+  const StepReport* fold_report = nullptr;
+  double *losses = nullptr, *diag = nullptr;
+  double* stat_x = nullptr;  // [2] status bits as doubles (split-factor group all-reduce)
+
+  double *K[2] = {}, *Kb[2] = {}, *D[2] = {}, *Kinv[2] = {}, *piv[2] = {}, *ldet[2] = {};
+  int nldet[2] = {0, 0};
+  // 2D work
+  double *A = nullptr, *Bt = nullptr, *S = nullptr, *R = nullptr, *T1 = nullptr, *T2 = nullptr,
+         *X1 = nullptr, *X2 = nullptr, *W1 = nullptr, *W2 = nullptr;  // W: refinement residuals
+  double *Y1 = nullptr, *Y2 = nullptr;  // S/2 + v X1, S/2 + v X2 (the G_K operands)
+  double *GK[2] = {}, *GD[2] = {};
+  // 2D class path: class tile partials of G_K / G_D written by their GEMM epilogues
+  // ([class_slots(P/16)][ncls] per axis; GemmDesc::cpart); cp_on: the stages use them
+  double *cpK[2] = {}, *cpD[2] = {};
+  bool cp_on = false;
+  // 1D work
+  double *alpha = nullptr, *tvec = nullptr, *beta = nullptr;
+  double *red_quad = nullptr, *red_egap = nullptr;
+  int nquad = 0, negap = 0;
+  double *pgpart = nullptr, *pg = nullptr;
+  double *pgpart_lo = nullptr, *tgpart_lo = nullptr;  // DD contraction (pg_dd): low parts
+  bool pg_dd = false;                 // kernel-parameter contraction in double-double
+  int bpa = 0;
+  // fused step tail (pgrad launch): group counters / partials, boundary gap
+  unsigned int *tcount = nullptr, *ttop = nullptr;
+  double *tgpart = nullptr, *bgap = nullptr;
+  int bgap_parts = 1;                 // PrepArgs::bgap_parts
+  int ttg = 0, tngpa = 0;
+  std::vector<GemmDesc> hdescs;  // per-stage GEMM descriptors (kernel arguments)
+  Stage st[kGemmStages];
+  double *Kc[2] = {}, *pst[2] = {};  // kept K (refinement residuals), pivot stats (gate)
+  unsigned int* aflag[2] = {};        // assembly -> pivot-0 hand-off counters (small path) /
+                                      // update -> pivot hand-off counters (large path)
+  bool bigspd = false;                // large-factor SPD inverse (spdinv_big.hip)
+  bool bigwide = false;               // ... with 128-wide sweeps
+  bool chain_multi = false;           // persistent inverse on macro tiles (large 1D factors)
+  // large 1D factors with distance classes: the GEMVs read Kc and D as class ids + class values
+  // (GemvDesc::cid), so the inverse launch's gather writes neither matrix (64 MB at C2)
+  bool cls_gemv = false;
+  double* Zp[2] = {};                 // ... its panel buffers [3][128][P] (by sweep mod 3)
+  unsigned* wsched[2] = {};           // ... its two-sweep update schedule (wide_schedule)
+  bool chain = false;                 // small factors: persistent one-launch inverse (chain_kernel)
+  bool chain_aug = false;             // ... which also solves A, Bt^T and K^{-1} D^T (2D, unsharded)
+  unsigned int* cflags[2] = {};       // its hand-off flags [T*(T+taug) + 2T + 1] per factor
+  double* cgran[2] = {};              // its pivot-chain input slots [T][2][1024] per factor
+  double* PB2[2] = {};                // chain_multi: panel slots [2][P*P] by launch parity
+  unsigned int* cepoch[2] = {};       // chain_multi: launch counter per factor
+  double *PD[2] = {}, *PBa[2] = {};   // K_a^{-1} D_a^T; augmented panel buffers
+  ClassArgs cls[2] = {};              // distance classes per axis (ncls = 0: per-pair path)
+  double* rvec = nullptr;            // 1D refinement residual
+  double* uoff = nullptr;            // 1D Allen-Cahn offset (gpk_problem.uoff), or null
+  // predict scratch
+  GemmDesc* pdescs = nullptr;
+
+  // row-sharded step: this rank computes rows [rank*h, (rank+1)*h) of every GEMM output
+  bool shard = false;
+  int rank = 0, nranks = 1;
+  int split_axis = -1;                // GPK_FLAG_SPLIT_FACTORS: the factor this rank inverts
+  int h1 = 0, h2 = 0;                 // row-block heights of the P1- and P2-row outputs
+  ShardComm* comm = nullptr;
+  std::vector<GemmDesc> sdescs;       // row slices of hdescs
+  Stage sst[kGemmStages];
+  std::vector<ShardGather> sgather[kGemmStages];
+  // the one per-step all-reduce of a sharded handle: [status (2) | pg | egap | quad] contiguous
+  double* sred = nullptr;
+  std::string splan;                  // the step's shard plan (gpk_shard_plan; gpk/shard.py)
+
+  hipGraphExec_t g_exec[2] = {nullptr, nullptr};  // [apply] full step graph
+  hipGraphExec_t g_fast[2] = {nullptr, nullptr};  // [apply] without the refinement stages
+  // STEP_GRAPH_REPS training steps back to back in one graph ([0] fast, [1] full): one host
+  // launch per group of steps (a graph launch boundary costs ~5-9 us of idle GPU)
+  hipGraphExec_t g_multi[2] = {nullptr, nullptr};
+  // batch graphs of exactly `reps` steps ([0] fast, [1] full), captured by gpk_prepare for the
+  // chunk sizes a call of its step count runs (FAST_CHUNK and the remainder): a prepared call is
+  // one graph launch per chunk
+  std::map<int, hipGraphExec_t> g_batch[2];
+  // fast chunks of a prepared step(n) call as whole-call graphs: batch begin (the rollback
+  // snapshot) + `reps` steps + the pinned-memory report -- one launch and one synchronisation
+  // per chunk (capture_call's form for step(1))
+  std::map<int, hipGraphExec_t> g_calln;
+  // one step(1) call as one graph ([0] fast, [1] full): batch begin (snapshot, counters), the
+  // step, and the pinned-memory report -- the reference's one-call-per-iteration loop shape
+  hipGraphExec_t g_call[2] = {nullptr, nullptr};
+  bool fast_ok = false;    // the fast graph exists for this handle (not row-sharded)
+  int fast_mode = 0;       // next step(s) run the fast graph (gate closed with margin last time)
+  long long rollbacks = 0;
+  double* snap = nullptr;  // [3 * nparams] params, m, v at the start of a fast batch
+  int* snap_count = nullptr;
+  unsigned int* viol = nullptr;  // the fast graph met an open refinement gate
+  // pipelined class values (TailArgs::nce_flag): the parameter-gradient launch of step s of a
+  // captured batch evaluates step s + 1's class values after the kernel-parameter Adam.
+  // cls_next: the step being enqueued does that; cls_have: the previous enqueued step did, so
+  // this one needs no class-value launch.  Both false outside a multi-step capture.
+  unsigned int* nce_flag = nullptr;  // raised by the Adam block, reset by the next publish_prep
+  double* nce_kp = nullptr;          // [nsmall] the kernel parameters it hands over (sc1)
+  bool cls_next = false, cls_have = false;
+  double* rep_host = nullptr;    // [8 + LOSS_CAP] pinned: status, viol, gates, losses (step_report)
+  double* pend_losses = nullptr; // caller's buffer for the last batch's losses (finish_batch)
+  int pend_n = 0;
+  hipEvent_t ev[kMaxStages + 1] = {};
+  bool profiling = false;
+  int nstage = 0;
+  const char* sname[kMaxStages] = {};  // name of each launched (profiled) stage
+
+  template <class T>
+  int alloc(T** p, size_t count_) {
+    void* q = nullptr;
+    size_t bytes = std::max<size_t>(count_ * sizeof(T), 16);
+    hipError_t e = hipMalloc(&q, bytes);
+    if (e != hipSuccess) return fail(GPK_ENOMEM, std::string("hipMalloc failed: ") + hipGetErrorString(e));
+    e = hipMemsetAsync(q, 0, bytes, s);
+    if (e != hipSuccess) return fail(GPK_EHIP, hipGetErrorString(e));
+    allocs.push_back(q);
+    *p = static_cast<T*>(q);
+    return GPK_OK;
+  }
+};
+
+#define TRY(x)                  \
+  do {                          \
+    int r_ = (x);               \
+    if (r_ != GPK_OK) return r_; \
+  } while (0)
+
+// padded size, size and coordinates of axis a (0 or 1)
+inline int axis_p(const Layout& L, int a) { return a ? L.p2 : L.p1; }
+inline int axis_n(const Layout& L, int a) { return a ? L.n2 : L.n1; }
+inline const double* axis_x(const gpk_handle* h, int a) { return a ? h->x2 : h->x1; }
+inline int step_deriv(const gpk_handle* h) { return h->prob.eq == GPK_ADVECTION ? 1 : 2; }
+
+#pragma GCC visibility push(hidden)
+// gpk_create.cpp
+bool build_classes(const double* x, int n, int P, std::vector<double>& dist, std::vector<int>& cid,
+                   std::vector<int>& cbase, int& vmax);
+int create_impl(const gpk_problem* p, double freq_scale, int rank, int nranks, bool shard,
+                gpk_handle** out, bool local_group = false);
+// gpk_step.cpp: argument fillers, the enqueue, and the batch protocol
+PrepArgs make_prep(gpk_handle* h, int apply);
+bool cls_pipe_ok(const gpk_handle* h);
+void fill_spd(gpk_handle* h, SpdArgs* sa);
+void fill_assemble(const gpk_handle* h, AssembleArgs* aa);  // base fields: callers add their own
+void fill_pgrad2d(const gpk_handle* h, PGradArgs* pa);       // base fields: callers add their own
+hipError_t launch_chain(gpk_handle* h, bool gather, double** fin, bool aug = true,
+                        const PrepArgs* prep = nullptr);
+hipError_t launch_inverse(gpk_handle* h, SpdArgs* sa, double** fin, bool pivot0_done);
+hipError_t launch_gemm_stage(gpk_handle* h, int k);  // stage k of the unsharded 2D plan
+int enqueue_assemble_inverse(gpk_handle* h, int apply, bool have_cls = false);
+TailArgs make_tail(gpk_handle* h, int apply, bool refine = true);
+void gemv_operand(const gpk_handle* h, GemvDesc& g);
+int enqueue_step(gpk_handle* h, int apply, bool refine = true);
+int gemm_force(int flags);
+int build_descs(gpk_handle* h);
+int capture_graph(hipStream_t s, hipGraphExec_t* slot, const std::function<int()>& body);
+StepBegin make_begin(gpk_handle* h, bool fast);
+int reset_handoffs(gpk_handle* h);
+int restore_snapshot(gpk_handle* h);
+int status_error(int st, int* status, hipStream_t s, gpk_handle* h, bool undo_batch, bool handoffs);
+int read_status(gpk_handle* h);
+// gpk_shard.cpp
+int build_shard(gpk_handle* h);
+int split_broadcast(gpk_handle* h);
+int enqueue_step_shard(gpk_handle* h, int apply);
+#pragma GCC visibility pop

@@ -11,38 +11,8 @@
 //     S = K^{-1} U,  R = sum_k D_k x_k A_k - F,  dL/dU = S + v sum_k X_k  (+ AC, boundary)
 //     G_Kk = c/2 (N / N_k) K_k^{-1} - (S/2 + v X_k)_(k) A_k,(k)^T,   G_Dk = v R_(k) A_k,(k)^T
 // (the 2-axis adjoints of SURVEY.md Appendix A, one per axis).
-#include <hip/hip_runtime.h>
-
-#include <algorithm>
-#include <cmath>
-#include <cstring>
-#include <string>
-#include <vector>
-
-#include "../../include/gpk.h"
-#include "gpk_internal.h"
+#include "gpk_host.h"
 #include "gpk_kron3.h"
-#include "stepk.h"
-
-namespace gpk {
-int api_fail(int code, const std::string& msg);
-int api_check_device(int dev);
-}  // namespace gpk
-
-using namespace gpk;
-
-#define K3TRY(x)                   \
-  do {                             \
-    int r_ = (x);                  \
-    if (r_ != GPK_OK) return r_;   \
-  } while (0)
-#define K3HIP(x)                                                                          \
-  do {                                                                                    \
-    hipError_t e_ = (x);                                                                  \
-    if (e_ != hipSuccess)                                                                 \
-      return api_fail(e_ == hipErrorOutOfMemory ? GPK_ENOMEM : GPK_EHIP,                  \
-                      std::string(#x) + ": " + hipGetErrorString(e_));                    \
-  } while (0)
 
 namespace {
 constexpr int K3_LOSS_CAP = 4096;
@@ -85,9 +55,9 @@ struct gpk_handle3 {
     void* q_ = nullptr;
     const size_t bytes = std::max<size_t>(count_ * sizeof(T), 16);
     hipError_t e = hipMalloc(&q_, bytes);
-    if (e != hipSuccess) return api_fail(GPK_ENOMEM, std::string("hipMalloc failed: ") + hipGetErrorString(e));
+    if (e != hipSuccess) return fail(GPK_ENOMEM, std::string("hipMalloc failed: ") + hipGetErrorString(e));
     e = hipMemsetAsync(q_, 0, bytes, s);
-    if (e != hipSuccess) return api_fail(GPK_EHIP, hipGetErrorString(e));
+    if (e != hipSuccess) return fail(GPK_EHIP, hipGetErrorString(e));
     allocs.push_back(q_);
     *p = static_cast<T*>(q_);
     return GPK_OK;
@@ -166,14 +136,7 @@ void build_stages(gpk_handle3* h) {
 int launch_stage(gpk_handle3* h, int k) {
   const auto& d = h->stages[k];
   const int variant = gemm_variant(d.data(), (int)d.size(), 0);
-  hipError_t e = launch_gemm_auto(d.data(), (int)d.size(), h->sc, h->s, variant);
-  if (e != hipSuccess) return api_fail(GPK_EHIP, std::string("gemm: ") + hipGetErrorString(e));
-  return GPK_OK;
-}
-
-int chk(hipError_t e, const char* what) {
-  if (e != hipSuccess) return api_fail(GPK_EHIP, std::string(what) + ": " + hipGetErrorString(e));
-  return GPK_OK;
+  return check_launch(launch_gemm_auto(d.data(), (int)d.size(), h->sc, h->s, variant), "gemm");
 }
 
 int enqueue_step3(gpk_handle3* h, int apply) {
@@ -187,7 +150,7 @@ int enqueue_step3(gpk_handle3* h, int apply) {
   P.b1 = h->prob.b1; P.b2 = h->prob.b2;
   P.Up = h->Up; P.bvals = h->bvals; P.nb = (int)(2 * ((long)g.n[1] * g.n[2] + (long)g.n[0] * g.n[2] + (long)g.n[0] * g.n[1]));
   P.bgap = h->bgap;
-  K3TRY(chk(k3_launch_prep(P, h->s), "k3_prep"));
+  TRY(check_launch(k3_launch_prep(P, h->s), "k3_prep"));
   // K_k, D_k: the 2-axis assembly kernel (per-pair path), its axis constants from the params
   AssembleArgs aa[3] = {};
   for (int a = 0; a < 3; ++a) {
@@ -201,8 +164,8 @@ int enqueue_step3(gpk_handle3* h, int apply) {
   PrepArgs p3 = p12;
   p3.off_kp[0] = h->off_kp[2];
   p3.naxes = 1;
-  K3TRY(chk(launch_assemble(kind, q, aa, 2, p12, h->s), "assemble"));
-  K3TRY(chk(launch_assemble(kind, q, aa + 2, 1, p3, h->s), "assemble"));
+  TRY(check_launch(launch_assemble(kind, q, aa, 2, p12, h->s), "assemble"));
+  TRY(check_launch(launch_assemble(kind, q, aa + 2, 1, p3, h->s), "assemble"));
   // K_k^{-1} and log det K_k (per-sweep Cholesky-Gauss-Jordan inverse; the output buffer of
   // each factor is fixed by its sweep count)
   SpdArgs sa[3] = {};
@@ -212,21 +175,21 @@ int enqueue_step3(gpk_handle3* h, int apply) {
     sa[a].status = h->status; sa[a].flag = h->aflag[a];
   }
   double* fin[3] = {};
-  K3TRY(chk(launch_spd_inverse(sa, 2, fin, h->s, false), "spd_inverse"));
-  K3TRY(chk(launch_spd_inverse(sa + 2, 1, fin + 2, h->s, false), "spd_inverse"));
+  TRY(check_launch(launch_spd_inverse(sa, 2, fin, h->s, false), "spd_inverse"));
+  TRY(check_launch(launch_spd_inverse(sa + 2, 1, fin + 2, h->s, false), "spd_inverse"));
   // forward products
-  K3TRY(launch_stage(h, 0));
-  K3TRY(chk(k3_launch_permute(h->Up, h->Upp, g, h->s), "k3_permute"));
-  K3TRY(launch_stage(h, 1));
-  K3TRY(chk(k3_launch_permute(h->Tm, h->Tp, g, h->s), "k3_permute"));
-  K3TRY(launch_stage(h, 2));
+  TRY(launch_stage(h, 0));
+  TRY(check_launch(k3_launch_permute(h->Up, h->Upp, g, h->s), "k3_permute"));
+  TRY(launch_stage(h, 1));
+  TRY(check_launch(k3_launch_permute(h->Tm, h->Tp, g, h->s), "k3_permute"));
+  TRY(launch_stage(h, 2));
   K3Combine C{};
   C.g = g; C.Rx = h->Rx; C.Rz = h->Rz; C.Ryp = h->Ryp; C.F = h->F; C.Up = h->Up; C.Sp = h->Sp;
   C.ac = h->prob.eq == GPK_ALLENCAHN; C.R = h->R; C.Rp = h->Rp; C.S = h->S;
   C.red_egap = h->red_egap; C.red_quad = h->red_quad;
-  K3TRY(chk(k3_launch_combine(C, h->s), "k3_combine"));
+  TRY(check_launch(k3_launch_combine(C, h->s), "k3_combine"));
   // reverse products and G_K, G_D
-  for (int k = 3; k < (int)h->stages.size(); ++k) K3TRY(launch_stage(h, k));
+  for (int k = 3; k < (int)h->stages.size(); ++k) TRY(launch_stage(h, k));
   // kernel-parameter contraction (the 2-axis kernels: axes 1-2, then axis 3)
   PGradArgs pg[3] = {};
   for (int a = 0; a < 3; ++a) {
@@ -234,9 +197,9 @@ int enqueue_step3(gpk_handle3* h, int apply) {
     pg[a].GK = h->GK[a]; pg[a].GD = h->GD[a]; pg[a].deriv = 2;
     pg[a].part = h->pgpart + (size_t)a * h->bpa * 3 * QMAX;
   }
-  K3TRY(chk(launch_pgrad(kind, q, 0, pg, 2, h->bpa, h->sc, h->s), "pgrad"));
-  K3TRY(chk(launch_pgrad(kind, q, 0, pg + 2, 1, h->bpa, h->sc, h->s), "pgrad"));
-  K3TRY(chk(launch_reduce_parts(h->pgpart, h->bpa, 3, q, h->pg, h->s), "reduce_parts"));
+  TRY(check_launch(launch_pgrad(kind, q, 0, pg, 2, h->bpa, h->sc, h->s), "pgrad"));
+  TRY(check_launch(launch_pgrad(kind, q, 0, pg + 2, 1, h->bpa, h->sc, h->s), "pgrad"));
+  TRY(check_launch(launch_reduce_parts(h->pgpart, h->bpa, 3, q, h->pg, h->s), "reduce_parts"));
   // loss + small-parameter Adam, then dL/dU + Adam on U (U is read by nothing after this)
   K3Final F{};
   F.g = g; F.hyper = AdamHyper{h->prob.lr, h->prob.b1, h->prob.b2, h->prob.eps};
@@ -248,53 +211,27 @@ int enqueue_step3(gpk_handle3* h, int apply) {
   F.off_tau = h->off_tau; F.off_v = h->off_v; F.off_small = (int)h->nu; F.nsmall = h->nsmall;
   F.params = h->params; F.grad = h->grad; F.m = h->m; F.v = h->v;
   F.losses = h->losses; F.loss_slot = h->loss_slot; F.diag = h->diag;
-  K3TRY(chk(k3_launch_finalize(F, h->s), "k3_finalize"));
+  TRY(check_launch(k3_launch_finalize(F, h->s), "k3_finalize"));
   K3AdamU A{};
   A.g = g; A.hyper = F.hyper; A.llk_weight = h->prob.llk_weight; A.apply = apply; A.ac = C.ac;
   A.sc = h->sc; A.S = h->S; A.X1 = h->X1; A.X2p = h->X2p; A.X3 = h->X3; A.R = h->R; A.Up = h->Up;
   A.bvals = h->bvals; A.off_u = 0; A.params = h->params; A.grad = h->grad; A.m = h->m; A.v = h->v;
-  K3TRY(chk(k3_launch_adam_u(A, h->s), "k3_adam_u"));
+  TRY(check_launch(k3_launch_adam_u(A, h->s), "k3_adam_u"));
   return GPK_OK;
 }
 
 int capture3(gpk_handle3* h, int apply) {
   if (h->exec[apply]) return GPK_OK;
-  hipGraph_t gr = nullptr;
-  K3HIP(hipStreamBeginCapture(h->s, hipStreamCaptureModeThreadLocal));
-  const int rc = enqueue_step3(h, apply);
-  hipError_t e = hipStreamEndCapture(h->s, &gr);
-  if (rc != GPK_OK) {
-    if (gr) (void)hipGraphDestroy(gr);
-    return rc;
-  }
-  if (e != hipSuccess) return api_fail(GPK_EHIP, std::string("capture: ") + hipGetErrorString(e));
-  e = hipGraphInstantiate(&h->exec[apply], gr, nullptr, nullptr, 0);
-  (void)hipGraphDestroy(gr);
-  if (e != hipSuccess) return api_fail(GPK_EHIP, std::string("instantiate: ") + hipGetErrorString(e));
-  return GPK_OK;
+  return capture_graph(h->s, &h->exec[apply], [&] { return enqueue_step3(h, apply); });
 }
 
 int read_status3(gpk_handle3* h) {
   int st = 0;
-  K3HIP(hipMemcpyAsync(&st, h->status, sizeof(int), hipMemcpyDeviceToHost, h->s));
-  K3HIP(hipStreamSynchronize(h->s));
-  if (st) {
-    (void)hipMemsetAsync(h->status, 0, sizeof(int), h->s);
-    return api_fail(GPK_ENOTPD, "covariance factor is not positive definite (non-positive pivot in SPD inverse)");
-  }
-  return GPK_OK;
+  HIPCHK(hipMemcpyAsync(&st, h->status, sizeof(int), hipMemcpyDeviceToHost, h->s));
+  HIPCHK(hipStreamSynchronize(h->s));
+  // (no hand-off waits and no batches here: any status is a non-positive pivot)
+  return st ? status_error(st, h->status, h->s, nullptr, false, false) : GPK_OK;
 }
-
-struct Dev3 {  // restore the caller's current device on scope exit
-  int prev = -1;
-  explicit Dev3(int d) {
-    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-    (void)hipSetDevice(d);
-  }
-  ~Dev3() {
-    if (prev >= 0) (void)hipSetDevice(prev);
-  }
-};
 
 }  // namespace
 
@@ -302,7 +239,7 @@ extern "C" {
 
 int gpk_destroy3(gpk_handle3* h) {
   if (!h) return GPK_OK;
-  Dev3 ds(h->dev);
+  DevSwitch ds(h->dev);
   if (h->s) (void)hipStreamSynchronize(h->s);
   for (auto& e : h->exec)
     if (e) (void)hipGraphExecDestroy(e);
@@ -313,18 +250,18 @@ int gpk_destroy3(gpk_handle3* h) {
 }
 
 int gpk_create3(const gpk_problem3* p, double freq_scale, gpk_handle3** out) {
-  if (!p || !out) return api_fail(GPK_EINVAL, "NULL argument");
+  if (!p || !out) return fail(GPK_EINVAL, "NULL argument");
   *out = nullptr;
-  if (p->kind < 0 || p->kind > 3) return api_fail(GPK_EINVAL, "Invalid Kernel");
+  if (p->kind < 0 || p->kind > 3) return fail(GPK_EINVAL, "Invalid Kernel");
   if (p->eq != GPK_POISSON && p->eq != GPK_ALLENCAHN)
-    return api_fail(GPK_EINVAL, "equation type not supported for the 3-axis solver");
-  if (p->q <= 0 || p->q > QMAX) return api_fail(GPK_EINVAL, "Q must be in [1, 64]");
+    return fail(GPK_EINVAL, "equation type not supported for the 3-axis solver");
+  if (p->q <= 0 || p->q > QMAX) return fail(GPK_EINVAL, "Q must be in [1, 64]");
   const int ns[3] = {p->n1, p->n2, p->n3};
   for (int a = 0; a < 3; ++a)
-    if (ns[a] < 2 || ns[a] > K3_MAX_N) return api_fail(GPK_EINVAL, "need 2..1024 collocation points per axis");
-  if (!p->x1 || !p->x2 || !p->x3 || !p->src || !p->bvals) return api_fail(GPK_EINVAL, "NULL problem array");
-  K3TRY(api_check_device(p->device));
-  Dev3 ds(p->device);
+    if (ns[a] < 2 || ns[a] > K3_MAX_N) return fail(GPK_EINVAL, "need 2..1024 collocation points per axis");
+  if (!p->x1 || !p->x2 || !p->x3 || !p->src || !p->bvals) return fail(GPK_EINVAL, "NULL problem array");
+  TRY(check_device(p->device));
+  DevSwitch ds(p->device);
   gpk_handle3* h = new gpk_handle3();
   h->prob = *p;
   h->prob.x1 = h->prob.x2 = h->prob.x3 = h->prob.src = h->prob.bvals = nullptr;
@@ -346,7 +283,7 @@ int gpk_create3(const gpk_problem3* p, double freq_scale, gpk_handle3** out) {
     return rc;
   };
   if (hipStreamCreateWithFlags(&h->s, hipStreamNonBlocking) != hipSuccess)
-    return bail(api_fail(GPK_EHIP, "hipStreamCreate failed"));
+    return bail(fail(GPK_EHIP, "hipStreamCreate failed"));
   const size_t np = (size_t)g.padded();
   const long nb = 2 * ((long)ns[1] * ns[2] + (long)ns[0] * ns[2] + (long)ns[0] * ns[1]);
   int rc = GPK_OK;
@@ -388,7 +325,7 @@ int gpk_create3(const gpk_problem3* p, double freq_scale, gpk_handle3** out) {
   const double* xs[3] = {p->x1, p->x2, p->x3};
   for (int a = 0; a < 3; ++a)
     if (hipMemcpyAsync(h->x[a], xs[a], ns[a] * sizeof(double), hipMemcpyHostToDevice, h->s) != hipSuccess)
-      return bail(api_fail(GPK_EHIP, "upload x"));
+      return bail(fail(GPK_EHIP, "upload x"));
   {
     std::vector<double> Fp(np, 0.0);
     for (int i1 = 0; i1 < ns[0]; ++i1)
@@ -404,7 +341,7 @@ int gpk_create3(const gpk_problem3* p, double freq_scale, gpk_handle3** out) {
         hipMemcpyAsync(h->bvals, p->bvals, nb * sizeof(double), hipMemcpyHostToDevice, h->s) != hipSuccess ||
         hipMemcpyAsync(h->params, init.data(), init.size() * sizeof(double), hipMemcpyHostToDevice, h->s) != hipSuccess ||
         hipStreamSynchronize(h->s) != hipSuccess)
-      return bail(api_fail(GPK_EHIP, "upload failed"));
+      return bail(fail(GPK_EHIP, "upload failed"));
   }
   build_stages(h);
   *out = h;
@@ -412,52 +349,52 @@ int gpk_create3(const gpk_problem3* p, double freq_scale, gpk_handle3** out) {
 }
 
 int gpk_num_params3(const gpk_handle3* h, int64_t* n) {
-  if (!h || !n) return api_fail(GPK_EINVAL, "NULL argument");
+  if (!h || !n) return fail(GPK_EINVAL, "NULL argument");
   *n = h->nparams;
   return GPK_OK;
 }
 
 int gpk_set_params3(gpk_handle3* h, const double* flat, int64_t n) {
-  if (!h || !flat) return api_fail(GPK_EINVAL, "NULL argument");
-  if (n != h->nparams) return api_fail(GPK_EINVAL, "flat parameter vector has the wrong length");
-  Dev3 ds(h->dev);
-  K3HIP(hipMemcpyAsync(h->params, flat, n * sizeof(double), hipMemcpyHostToDevice, h->s));
-  K3TRY(chk(k3_launch_sync_u(h->params, 0, h->g, h->Up, h->s), "k3_sync_u"));
-  K3HIP(hipStreamSynchronize(h->s));
+  if (!h || !flat) return fail(GPK_EINVAL, "NULL argument");
+  if (n != h->nparams) return fail(GPK_EINVAL, "flat parameter vector has the wrong length");
+  DevSwitch ds(h->dev);
+  HIPCHK(hipMemcpyAsync(h->params, flat, n * sizeof(double), hipMemcpyHostToDevice, h->s));
+  TRY(check_launch(k3_launch_sync_u(h->params, 0, h->g, h->Up, h->s), "k3_sync_u"));
+  HIPCHK(hipStreamSynchronize(h->s));
   return GPK_OK;
 }
 
 int gpk_get_params3(gpk_handle3* h, double* flat, int64_t n) {
-  if (!h || !flat) return api_fail(GPK_EINVAL, "NULL argument");
-  if (n != h->nparams) return api_fail(GPK_EINVAL, "flat parameter vector has the wrong length");
-  Dev3 ds(h->dev);
-  K3HIP(hipMemcpyAsync(flat, h->params, n * sizeof(double), hipMemcpyDeviceToHost, h->s));
-  K3HIP(hipStreamSynchronize(h->s));
+  if (!h || !flat) return fail(GPK_EINVAL, "NULL argument");
+  if (n != h->nparams) return fail(GPK_EINVAL, "flat parameter vector has the wrong length");
+  DevSwitch ds(h->dev);
+  HIPCHK(hipMemcpyAsync(flat, h->params, n * sizeof(double), hipMemcpyDeviceToHost, h->s));
+  HIPCHK(hipStreamSynchronize(h->s));
   return GPK_OK;
 }
 
 int gpk_loss_grad3(gpk_handle3* h, double* loss, double* grad_flat) {
-  if (!h || !loss) return api_fail(GPK_EINVAL, "NULL argument");
-  Dev3 ds(h->dev);
-  K3TRY(capture3(h, 0));
-  K3HIP(hipMemsetAsync(h->loss_slot, 0, sizeof(int), h->s));
-  K3HIP(hipGraphLaunch(h->exec[0], h->s));
-  K3TRY(read_status3(h));
-  K3HIP(hipMemcpy(loss, h->diag, sizeof(double), hipMemcpyDeviceToHost));
-  if (grad_flat) K3HIP(hipMemcpy(grad_flat, h->grad, h->nparams * sizeof(double), hipMemcpyDeviceToHost));
+  if (!h || !loss) return fail(GPK_EINVAL, "NULL argument");
+  DevSwitch ds(h->dev);
+  TRY(capture3(h, 0));
+  HIPCHK(hipMemsetAsync(h->loss_slot, 0, sizeof(int), h->s));
+  HIPCHK(hipGraphLaunch(h->exec[0], h->s));
+  TRY(read_status3(h));
+  HIPCHK(hipMemcpy(loss, h->diag, sizeof(double), hipMemcpyDeviceToHost));
+  if (grad_flat) HIPCHK(hipMemcpy(grad_flat, h->grad, h->nparams * sizeof(double), hipMemcpyDeviceToHost));
   return GPK_OK;
 }
 
 int gpk_step3(gpk_handle3* h, int32_t n_steps, double* losses) {
-  if (!h) return api_fail(GPK_EINVAL, "NULL handle");
-  if (n_steps < 0 || n_steps > K3_LOSS_CAP) return api_fail(GPK_EINVAL, "n_steps must be in [0, 4096]");
-  Dev3 ds(h->dev);
-  K3TRY(capture3(h, 1));
-  K3HIP(hipMemsetAsync(h->loss_slot, 0, sizeof(int), h->s));
-  for (int i = 0; i < n_steps; ++i) K3HIP(hipGraphLaunch(h->exec[1], h->s));
-  K3TRY(read_status3(h));
+  if (!h) return fail(GPK_EINVAL, "NULL handle");
+  if (n_steps < 0 || n_steps > K3_LOSS_CAP) return fail(GPK_EINVAL, "n_steps must be in [0, 4096]");
+  DevSwitch ds(h->dev);
+  TRY(capture3(h, 1));
+  HIPCHK(hipMemsetAsync(h->loss_slot, 0, sizeof(int), h->s));
+  for (int i = 0; i < n_steps; ++i) HIPCHK(hipGraphLaunch(h->exec[1], h->s));
+  TRY(read_status3(h));
   if (losses && n_steps > 0)
-    K3HIP(hipMemcpy(losses, h->losses, n_steps * sizeof(double), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(losses, h->losses, n_steps * sizeof(double), hipMemcpyDeviceToHost));
   return GPK_OK;
 }
 

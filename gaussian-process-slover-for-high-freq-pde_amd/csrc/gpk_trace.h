@@ -2,7 +2,7 @@
 // defines GPK_TRACE and writes libgpk_trace.so; the product build compiles them away).
 //
 // Every translation unit owns two slot arrays (first arrival / last departure, read from the
-// 100 MHz constant clock, s_memrealtime) and exposes them to gpk_api.cpp through
+// 100 MHz constant clock, s_memrealtime) and exposes them to gpk_diag.cpp through
 // trace_fetch_<tu> / trace_reset_<tu>.  Slots are global across TUs (see SLOT_* below), so
 // one step's timeline is the union of all TUs' arrays.
 #pragma once

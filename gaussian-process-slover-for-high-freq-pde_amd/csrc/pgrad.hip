@@ -123,7 +123,7 @@ __device__ void pgrad_tail(const PGradBatch& b, int axis, int blk, int q) {
   }
 }
 
-// Pipelined class values (TailArgs::nce_flag; gpk_api.cpp cls_pipe_ok): plane naxes + 2 + ax of
+// Pipelined class values (TailArgs::nce_flag; gpk_step.cpp cls_pipe_ok): plane naxes + 2 + ax of
 // the launch evaluates the NEXT step's class values of axis ax -- the same 8 classes per
 // workgroup and the same code as class_eval_kernel (class_value_store), from the parameters the
 // kernel-parameter Adam of this launch has just written: bitwise the values the next step's

@@ -12,7 +12,7 @@ typedef __attribute__((address_space(3))) double* lds_ptr;
 // (seconds, far beyond any hand-off of a running step) and the wait gives up, setting status
 // bit 2 -- the step then reports GPK_ENOTPD ("hand-off timed out") instead of hanging the device
 // (a producer that is not resident, e.g. another process holding the CUs).  The host resets the
-// hand-off slots after such a launch (gpk_api.cpp reset_handoffs).
+// hand-off slots after such a launch (gpk_step.cpp reset_handoffs).
 // The poll budget, per translation unit that waits (spdinv, spdinv_big, assemble): SPIN_CAP
 // unless gpk_set_wait_limit lowered it (tests force a timeout with 1: every wait whose first
 // poll fails gives up).  A scalar constant-cache load per poll.

@@ -267,7 +267,7 @@ __device__ __forceinline__ void signal_flag(unsigned int* f) {
 // written.  The producer neither drains its stores nor raises a flag; the pivot chain, the
 // slot's only reader, loads the words, re-loads any that still hold the sentinel, and after
 // consuming a slot writes the sentinel back (ready for the next launch; the buffer is
-// initialised to the sentinel at create, gpk_api.cpp).  Slot k (hop k, the inputs of pivot
+// initialised to the sentinel at create, gpk_create.cpp).  Slot k (hop k, the inputs of pivot
 // k+1): [0] panel tile (k, k+1), [1] diagonal tile (k+1, k+1), both after sweep k-1; element
 // e = 32 row + col of the tile.
 __device__ __forceinline__ double* gran_at(const ChainFactor& F, int slot, int which, int e) {

@@ -133,7 +133,7 @@ hipError_t launch_add_into(double* dst, const double* src, size_t n, hipStream_t
 }
 
 // Status word <-> two doubles (bit 1: non-positive pivot, bit 2: hand-off timeout), so that a
-// summing all-reduce makes the status of a split-factor rank group group-wide (gpk_api.cpp
+// summing all-reduce makes the status of a split-factor rank group group-wide (gpk_shard.cpp
 // split_broadcast): mode 0 packs, mode 1 ORs the summed bits back into the word.
 __global__ void status_f64_kernel(int* st, double* x, int mode) {
   if (threadIdx.x != 0) return;

@@ -48,9 +48,9 @@ def make_sharded_solver(config, ctx, seed=0, Q=30, lr=0.01, flags=0):
 
 
 # ------------------------------------------------------------------------------------------
-# The sharded step's plan (csrc/gpk_api.cpp build_shard; gpk_shard_plan returns the library's)
+# The sharded step's plan (csrc/gpk_shard.cpp build_shard; gpk_shard_plan returns the library's)
 # ------------------------------------------------------------------------------------------
-PADM = 32  # padding multiple of a matrix dimension (gpk_api.cpp make_layout), x nranks when sharded
+PADM = 32  # padding multiple of a matrix dimension (gpk_create.cpp make_layout), x nranks when sharded
 
 
 def shard_rows(n, nranks, rank):
@@ -64,7 +64,7 @@ def shard_rows(n, nranks, rank):
 
 
 def shard_plan(aug, refine_fwd=True, refine_rev=True, refine_fwd2=True):
-    """The plan the library builds for a row-sharded 2D handle (gpk_api.cpp build_shard):
+    """The plan the library builds for a row-sharded 2D handle (gpk_shard.cpp build_shard):
     "s<k>:<modes>" per GEMM stage with products -- r = this rank's output rows, k = its share of
     the contraction index, f = whole (replicated) -- and " g<buf>" per all-gather after the
     stage; then "ar" (the step's one all-reduce) and "gU" (U rows after Adam).

@@ -13,7 +13,7 @@ import pytest
 
 def classes(x):
     """cid [n, n], cbase [n + 1]: per diagonal k the distinct exact |x_{j+k} - x_j| in order of
-    first appearance (gpk_api.cpp build_classes)."""
+    first appearance (gpk_create.cpp build_classes)."""
     n = len(x)
     cid = -np.ones((n, n), dtype=np.int64)
     cbase = np.zeros(n + 1, dtype=np.int64)
@@ -74,7 +74,7 @@ def test_class_slots_cover_every_pair_once(n, scale):
     P = (n + 31) // 32 * 32
     cid, cbase = classes(x)
     vmax = int(np.max(np.diff(cbase)))
-    assert vmax <= 16  # the epilogue's variant range (gpk_api.cpp enables it for vmax <= CB_VMAX)
+    assert vmax <= 16  # the epilogue's variant range (gpk_create.cpp enables it for vmax <= CB_VMAX)
     rng = np.random.default_rng(n)
     G = np.zeros((P, P))
     G[:n, :n] = rng.normal(size=(n, n))

@@ -120,7 +120,7 @@ def test_group_timeout_is_enotpd(wait_limit):
 
 def test_group_step_timeout_undone_on_every_rank(wait_limit):
     """A hand-off timeout inside a group's step batch: the status bits are summed over the group
-    every sharded step (gpk_api.cpp status_allreduce), so every rank fails the batch and restores
+    every sharded step (gpk_shard.cpp enqueue_step_shard), so every rank fails the batch and restores
     its snapshot -- params and Adam state equal the pre-call state on every rank, the ranks agree,
     and the next batch equals a group that never timed out."""
     from gpk._lib import GPKError, GPK_ENOTPD
