@@ -219,9 +219,9 @@ static int allocate_buffers(gpk_handle* h, const gpk_problem* p) {
         return fail(GPK_EHIP, "upload the update schedule");
     }
     A_(h->cflags[a], (size_t)(P / 32) * (P / 32 + (P1 + P2) / 32) + 2 * (P / 32) + 1);
-    A_(h->cgran[a], (size_t)(P / 32) * 2048);
+    A_(h->cgran[a], (size_t)(P / 32) * 3072);  // [T][3][1024]
     // every hand-off slot starts unwritten (spdinv.hip chain_master / chain_multi_kernel)
-    if (hipMemsetD32Async(h->cgran[a], CHAIN_SENTINEL32, (size_t)(P / 32) * 4096, h->s) != hipSuccess)
+    if (hipMemsetD32Async(h->cgran[a], CHAIN_SENTINEL32, (size_t)(P / 32) * 6144, h->s) != hipSuccess)
       return fail(GPK_EHIP, "initialise the pivot-chain input slots");
     if (h->chain) {  // chain_multi: panel + L^{-1} slots; chain_kernel: the L^{-1} slots
       A_(h->PB2[a], 2 * chain_half(P, h->chain_multi));

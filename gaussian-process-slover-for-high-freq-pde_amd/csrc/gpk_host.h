@@ -135,7 +135,7 @@ struct gpk_handle {
   bool chain = false;                 // small factors: persistent one-launch inverse (chain_kernel)
   bool chain_aug = false;             // ... which also solves A, Bt^T and K^{-1} D^T (2D, unsharded)
   unsigned int* cflags[2] = {};       // its hand-off flags [T*(T+taug) + 2T + 1] per factor
-  double* cgran[2] = {};              // its pivot-chain input slots [T][2][1024] per factor
+  double* cgran[2] = {};              // its pivot-chain input slots [T][3][1024] per factor
   double* PB2[2] = {};                // chain_multi: panel slots [2][P*P] by launch parity
   unsigned int* cepoch[2] = {};       // chain_multi: launch counter per factor
   double *PD[2] = {}, *PBa[2] = {};   // K_a^{-1} D_a^T; augmented panel buffers

@@ -250,8 +250,8 @@ hipError_t launch_spd_stage(SpdArgs* args, int nmat, int stage, hipStream_t s);
 // the step's first solves (A = K1^{-1} U, Bt^T = K2^{-1} U^T) and the derivative solves
 // (K^{-1} D^T) without GEMM launches of their own.
 // Every workgroup waits on others, so the grid must be co-resident: gpk_create checks the
-// grid against spd_chain_capacity (occupancy per CU x CUs: two per CU on a full MI355X -- 235
-// VGPRs, 50 KB LDS each fit twice -- i.e. 512) and caps it at CHAIN_MAX_BLOCKS.
+// grid against spd_chain_capacity (occupancy per CU x CUs: two per CU on a full MI355X -- 255
+// VGPRs, 59 KB LDS each fit twice -- i.e. 512) and caps it at CHAIN_MAX_BLOCKS.
 constexpr int CHAIN_MAX_BLOCKS = 512;
 struct ChainArgs {
   double* X; double* PB; double* piv; double* ldet; double* pst; int* status;
@@ -264,7 +264,10 @@ struct ChainArgs {
   double* Ou; int ldou, ou_t;              // K^{-1} B_u (stored transposed when ou_t)
   double* Od; int ldod;                    // K^{-1} D^T
   double* PBa; int ldpba;                  // augmented panel buffer [p][32*(tu+td)]
-  double* gran;                            // pivot-chain input slots [T][2][1024], CHAIN_SENTINEL
+  double* gran;                            // pivot-chain input slots [T][3][1024], CHAIN_SENTINEL
+                                           // (plain protocol: [T][2][1024] of them)
+  int lookahead;                           // chain_kernel: two-block look-ahead in the pivot chain
+                                           // (spdinv.hip chain_master_la; chain_multi ignores it)
   double* PB2; unsigned int* epoch;        // chain_multi: hand-off slots [2][multi_half(p)]
                                            // (CHAIN_SENTINEL), launch counter (zeroed)
 };

@@ -87,6 +87,7 @@ hipError_t launch_chain(gpk_handle* h, bool gather, double** fin, bool aug, cons
     c.X = h->K[a]; c.PB = h->Kb[a]; c.piv = h->piv[a]; c.ldet = h->ldet[a]; c.pst = h->pst[a];
     c.status = h->status; c.flags = h->cflags[a]; c.gran = h->cgran[a];
     c.PB2 = h->PB2[a]; c.epoch = h->cepoch[a];
+    c.lookahead = (h->prob.flags & GPK_FLAG_NO_CHAIN_LOOKAHEAD) ? 0 : 1;
     c.p = axis_p(L, a);
     c.n = axis_n(L, a);
     if (gather) {
@@ -709,7 +710,7 @@ int reset_handoffs(gpk_handle* h) {
   for (int a = 0; a < L.naxes; ++a) {
     const size_t P = axis_p(L, a), T = P / 32;
     const size_t nflags = T * (T + (L.p1 + L.p2) / 32) + 2 * T + 1;
-    HIPCHK(hipMemsetD32Async(h->cgran[a], CHAIN_SENTINEL32, T * 4096, h->s));
+    HIPCHK(hipMemsetD32Async(h->cgran[a], CHAIN_SENTINEL32, T * 6144, h->s));
     if (h->PB2[a]) HIPCHK(hipMemsetD32Async(h->PB2[a], CHAIN_SENTINEL32, 4 * chain_half((int)P, h->chain_multi), h->s));
     if (h->cepoch[a]) HIPCHK(hipMemsetAsync(h->cepoch[a], 0, 4 * sizeof(unsigned int), h->s));
     HIPCHK(hipMemsetAsync(h->cflags[a], 0, nflags * sizeof(unsigned int), h->s));

@@ -219,7 +219,8 @@ struct ChainFactor {
   int* status;
   unsigned int* flags;  // [T*TC] panel ready, [T] pivot ready, [T] (unused), [1] done counter
                         // (zero; re-armed by the last workgroup)
-  double* gran;              // the pivot chain's input slots [T][2][1024] (chain_master)
+  double* gran;              // the pivot chain's input slots [T][3][1024] (chain_master)
+  int la;                    // chain_kernel: two-block look-ahead in the pivot chain (chain_master)
   double* PB2;               // chain_multi: panel slots [2][p*p] by launch parity (self-validating)
   unsigned int* epoch;       // chain_multi: launch counter (its parity selects the PB2 half)
   int piv_off;               // offset of the pivot-ready flags (T * TC)
@@ -269,21 +270,251 @@ __device__ __forceinline__ void signal_flag(unsigned int* f) {
 // consuming a slot writes the sentinel back (ready for the next launch; the buffer is
 // initialised to the sentinel at create, gpk_create.cpp).  Slot k (hop k, the inputs of pivot
 // k+1): [0] panel tile (k, k+1), [1] diagonal tile (k+1, k+1), both after sweep k-1; element
-// e = 32 row + col of the tile.
+// e = 32 row + col of the tile.  Look-ahead mode (chain_master, below) hands over the tiles one
+// sweep older instead: slot h (read while pivot h+1 is factored): [0] tile (h, h+2),
+// [1] tile (h+1, h+2), [2] tile (h+2, h+2), all after sweep h-1.
 __device__ __forceinline__ double* gran_at(const ChainFactor& F, int slot, int which, int e) {
   return F.gran + (size_t)(2 * slot + which) * 1024 + e;
+}
+__device__ __forceinline__ double* gran3_at(const ChainFactor& F, int slot, int which, int e) {
+  return F.gran + (size_t)(3 * slot + which) * 1024 + e;
 }
 __device__ __forceinline__ bool gran_ok(double v) {
   return __double_as_longlong(v) != (long long)CHAIN_SENTINEL;
 }
 
+// one 16x16 quadrant product with both operands in registers: a[kk] = A(i, 4 kk + lk),
+// b[kk] = B(4 kk + lk, j) of lane (li, lk) -- mma_t's operation sequence
+__device__ __forceinline__ d4 mma_r(const double (&a)[8], const double (&b)[8], d4 acc) {
+#pragma unroll
+  for (int kk = 0; kk < 8; ++kk) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a[kk], b[kk], acc, 0, 0, 0);
+  return acc;
+}
+// ... with A from LDS (element (i, k) at a[i * sai + k * sak], i = 16 wr + li)
+__device__ __forceinline__ d4 mma_lr(const double* a, int sai, int sak, const double (&b)[8], int wr,
+                                     int lane, d4 acc) {
+  const int li = lane & 15, lk = lane >> 4;
+#pragma unroll
+  for (int kk = 0; kk < 8; ++kk)
+    acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a[(16 * wr + li) * sai + (4 * kk + lk) * sak], b[kk], acc, 0, 0, 0);
+  return acc;
+}
+
+struct NoTileSource {  // (chain_multi_kernel: no look-ahead)
+  __device__ double operator()(int, int) const { return 0.0; }
+};
+
+// The pivot chain with a two-block window (chain_kernel, ChainFactor::la).  The plain form below
+// receives pivot h+1's inputs -- tiles (h, h+1) and (h+1, h+1) after sweep h-1 -- from their
+// owners, who can start them only when L_{h-1}^{-1} is visible: that path (L^{-1} words landing,
+// loads, LDS, three barriers and MFMAs, stores landing, re-load) is longer than this
+// workgroup's own period (hop + factorisation), so every hop began with a 0.4-0.6 us wait
+// (C4, profiles/r7_c4_timeline.txt).  Here the
+// workgroup forms those inputs itself: while wave 0 factors pivot h+1 (the one-wave form), waves
+// 1-3 apply sweep h to the 2x2 window's remaining tiles with the L_h^{-1} and V1 = L_h^{-1}
+// X_{h,h+1} that are still in LDS,
+//     V2 = L_h^{-1} P2,   Q' = Q - V1^T V2,   D2' = D2 - V2^T V2,
+// where P2, Q, D2 = tiles (h, h+2), (h+1, h+2), (h+2, h+2) after sweep h-1 are what the owners
+// hand over (slot h, self-validating words): one sweep older than before, i.e. a whole period
+// more slack.  Q' and D2' are tiles (h+1, h+2) and (h+2, h+2) after sweep h: the next hop's
+// inputs, left in LDS before the factorisation's closing barrier.  Hop 0's own inputs, tiles
+// (0, 1) and (1, 1), are K itself: read through `kf` (class tables or X) like tile (0, 0), by
+// waves 1-3 while pivot 0 is factored; slot 0 holds K's tiles (0, 2), (1, 2), (2, 2).
+// Every product is the owner's own operation sequence (mma_t's operand roles and k order, the
+// product accumulated from zero and then subtracted): the pivots receive bit for bit the inputs
+// they receive in the plain form.
+// Waves 1-3 must not meet at the workgroup barrier (wave 0 is factoring), so each is
+// self-sufficient, operands in registers: wave 1 + c (c = 0, 1) forms the 16-column half c of V2
+// (its C-layout quadrants ARE the B operand of V1^T V2 and both operands of V2^T V2), that half
+// of Q' and the diagonal quadrant (c, c) of D2'; wave 3 forms both halves of V2 again and the two
+// mixed quadrants of D2'.  About 40 (48) MFMAs per wave against a 4.3-us factorisation.
+// L_h^{-1} must survive factorisation h+1: the factorisations alternate between sM and sM2; the
+// panel tile alternates between sX and sX2 (V1 is read while Q' is written).
+// Consumed slots get the sentinel back after the closing barrier (P2's words are read by two
+// waves).  LDS: sX, sX2 [32][SB]; sP, sM, sM2, sD [32][SP]; pv [32].
+template <class KF>
+__device__ __forceinline__ void chain_master_la(const ChainFactor& F, int T, d4 acc, double* sX,
+                                                double* sX2, double* sP, double* sM, double* sM2,
+                                                double* sD, double* pv, bool trm, bool trla,
+                                                double* lw, KF kf) {
+  const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
+  const int wr = wv >> 1, wc = wv & 1;
+  // (the lane's row / column, re-derived from an opaque copy of the lane id wherever the
+  // look-ahead forms addresses: hoisted out of the hop loop, its element offsets would stay live
+  // across the factorisation, which is the kernel's register peak -- they spilled)
+  int li = lane & 15, lk = lane >> 4;
+  int wq = __builtin_amdgcn_readfirstlane(wv), c = 0, nw = 0;  // wave, its column half, its words
+  auto fresh_lane = [&]() {
+    int l = lane, w = __builtin_amdgcn_readfirstlane(wv);
+    asm volatile("" : "+v"(l), "+s"(w));
+    li = l & 15;
+    lk = l >> 4;
+    wq = w;
+    c = wq == 2 ? 1 : 0;
+    nw = wq == 3 ? 24 : 20;
+  };
+  unsigned int* piv_rdy = F.flags + F.piv_off;
+  __builtin_amdgcn_s_setprio(3);
+  const double snan = __longlong_as_double((long long)CHAIN_SENTINEL);
+  // word i of this wave's look-ahead inputs, as an offset into the slot's three tiles (0: P2,
+  // 1: Q, 2: D2; element e = 32 row + col) from the lane's own 32 lk + li -- wave-uniform.
+  // Waves 1, 2 (c = wv - 1): 0..7 P2 as B operand of column half c, 8..15 Q's quadrants (0, c),
+  // (1, c), 16..19 D2's quadrant (c, c).  Wave 3: 0..15 P2 as B operand of both halves, 16..19
+  // D2's quadrant (0, 1), 20..23 its quadrant (1, 0).
+  auto woff = [&](int i) -> int {
+    if (i < 8) return 128 * i + 16 * c;
+    if (i < 16) return wq == 3 ? 16 + 128 * (i - 8) : 1024 + 512 * ((i - 8) >> 2) + 128 * (i & 3) + 16 * c;
+    if (i < 20) return 2048 + 128 * (i & 3) + (wq == 3 ? 16 : 528 * c);
+    return 2048 + 512 + 128 * (i & 3);
+  };
+  // waves 1-3, during factorisation h+1: the window's sweep h (h + 2 < T)
+  auto lookahead = [&](int h) {
+    double* sV1 = (h & 1) ? sX2 : sX;   // V1 (this hop's panel tile)
+    double* sQn = (h & 1) ? sX : sX2;   // <- Q': the next hop's panel tile
+    const double* Lh = (h & 1) ? sM2 : sM;
+    fresh_lane();
+    const double* g = gran3_at(F, h, 0, 32 * lk + li);
+    double w[24];
+    // (per lane) words not yet written hold the sentinel: load again.  Bounded like every
+    // hand-off wait.
+    for (unsigned spins = 0;; ++spins) {
+      bool ok = true;
+#pragma unroll
+      for (int i = 0; i < 24; ++i) {
+        w[i] = i < nw ? ld_sc1(g + woff(i)) : 0.0;
+        ok = ok && gran_ok(w[i]);
+      }
+#ifdef GPK_TRACE
+      const bool late = spins == 0 && __any(!ok);  // (some word of this wave was not there yet)
+      if (trla && late) { TR_LO(SLOT_LOOKAHEAD_LATE); TR_HI(SLOT_LOOKAHEAD_LATE); }
+#endif
+      if (ok || spin_give_up(spins, F.status)) break;
+      __builtin_amdgcn_s_sleep(1);
+    }
+    const d4 zero = {0.0, 0.0, 0.0, 0.0};
+    double pa[8], va[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) pa[i] = w[i];
+    // V2, column half c (wave 3: half 0): quadrants (0, c), (1, c); as an operand, k = 4 kk + lk
+    // is row lk + 4 (kk & 3) of quadrant row kk >> 2
+    const d4 v0 = mma_lr(Lh, SP, 1, pa, 0, lane, zero), v1 = mma_lr(Lh, SP, 1, pa, 1, lane, zero);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) { va[i] = v0[i]; va[4 + i] = v1[i]; }
+    if (wq != 3) {
+      d4 q0 = {w[8], w[9], w[10], w[11]}, q1 = {w[12], w[13], w[14], w[15]};
+      d4 d2 = {w[16], w[17], w[18], w[19]};
+      q0 = q0 - mma_lr(sV1, 1, SB, va, 0, lane, zero);  // Q - V1^T V2
+      q1 = q1 - mma_lr(sV1, 1, SB, va, 1, lane, zero);
+      d2 = d2 - mma_r(va, va, zero);                     // D2 - V2^T V2
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        sQn[(lk + 4 * r) * SB + 16 * c + li] = q0[r];
+        sQn[(16 + lk + 4 * r) * SB + 16 * c + li] = q1[r];
+        sD[(16 * c + lk + 4 * r) * SP + 16 * c + li] = d2[r];
+      }
+    } else {
+      double pb[8], vb[8];
+#pragma unroll
+      for (int i = 0; i < 8; ++i) pb[i] = w[8 + i];
+      const d4 u0 = mma_lr(Lh, SP, 1, pb, 0, lane, zero), u1 = mma_lr(Lh, SP, 1, pb, 1, lane, zero);
+#pragma unroll
+      for (int i = 0; i < 4; ++i) { vb[i] = u0[i]; vb[4 + i] = u1[i]; }
+      d4 d01 = {w[16], w[17], w[18], w[19]}, d10 = {w[20], w[21], w[22], w[23]};
+      d01 = d01 - mma_r(va, vb, zero);
+      d10 = d10 - mma_r(vb, va, zero);
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        sD[(lk + 4 * r) * SP + 16 + li] = d01[r];
+        sD[(16 + lk + 4 * r) * SP + li] = d10[r];
+      }
+    }
+  };
+  // slot h consumed: the sentinel back for the next launch (waves 1, 2: their words; wave 3: its
+  // D2 quadrants -- P2's words are waves 1 and 2's)
+  auto rearm = [&](int h) {
+    fresh_lane();
+    double* g = gran3_at(F, h, 0, 32 * lk + li);
+#pragma unroll
+    for (int i = 0; i < 24; ++i)
+      if (i < nw && !(wq == 3 && i < 16)) st_sc1(g + woff(i), snan);
+  };
+  auto factor = [&](int kp) {
+    if (trm && kp > 0 && kp < 17) TR_HI(SLOT_SWEEP + kp - 1);
+    store_quad(sP, SP, wr, wc, lane, acc);
+    __syncthreads();
+    if (trm && kp > 0 && kp < 17) TR_LO(SLOT_SWEEP_PIVOT + kp - 1);
+    if (trm && kp == 0) TR_LO(SLOT_PIVOT0);
+    double* Mk = (kp & 1) ? sM2 : sM;
+    if (wv > 0) {  // (wave 0 goes straight to the factorisation)
+      if (kp >= 2) rearm(kp - 2);  // the slot read during factorisation kp - 1
+      if (kp == 0 && T > 1) {
+        // hop 0's inputs: tiles (0, 1) and (1, 1) of K
+#pragma unroll
+        for (int it = 0; it < 11; ++it) {
+          const int e = t - 64 + 192 * it;
+          if (e >= 2048) continue;
+          const int row = (e >> 5) & 31, col = e & 31;
+          if (e < 1024) sX[row * SB + col] = kf(row, 32 + col);
+          else sD[row * SP + col] = kf(32 + row, 32 + col);
+        }
+      } else if (kp > 0 && kp + 1 < T) {
+        lookahead(kp - 1);
+      }
+    }
+    const double ls = pivot_chol_inv_1w<double*, NoPivotHook>(sP, Mk, pv, t, F.status);
+    double* ldst = (lw ? lw : F.piv) + (size_t)kp * 1024;
+    for (int e = t; e < 1024; e += 256) st_sc1(ldst + e, Mk[(e >> 5) * SP + (e & 31)]);
+    if (t == 0) F.ldet[kp] = ls;
+    if (kp + 1 == T && !lw) signal_flag(piv_rdy + kp);
+    if (trm && kp > 0 && kp < 17) TR_HI(SLOT_SWEEP_PIVOT + kp - 1);
+    if (trm && kp == 0) TR_HI(SLOT_PIVOT0);
+  };
+  if (t == 0) {  // refinement gate (as the plain form)
+    st_sc1(F.pst, acc[0]);
+    __hip_atomic_store(reinterpret_cast<unsigned long long*>(F.pst + 1), 0ull, __ATOMIC_RELAXED,
+                       __HIP_MEMORY_SCOPE_AGENT);
+  }
+  if (lw) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  factor(0);
+  for (int h = 0; h + 1 < T; ++h) {
+    if (trm && h < 16) TR_LO(SLOT_SWEEP + h);
+    double* sXh = (h & 1) ? sX2 : sX;
+    const double* Lh = (h & 1) ? sM2 : sM;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) acc[r] = sD[(16 * wr + lk + 4 * r) * SP + 16 * wc + li];
+    d4 vj = {0.0, 0.0, 0.0, 0.0};
+    vj = mma_t(Lh, SP, 1, sXh, SB, 1, wr, wc, lane, vj);  // V1 = L_h^{-1} X_{h,h+1}
+    if (!lw) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // L^{-1}_h's stores, before its flag
+    __syncthreads();
+    if (t == 0 && !lw) __hip_atomic_store(piv_rdy + h, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    store_quad(sXh, SB, wr, wc, lane, vj);
+    __syncthreads();
+    d4 prod = {0.0, 0.0, 0.0, 0.0};
+    prod = mma_t(sXh, 1, SB, sXh, SB, 1, wr, wc, lane, prod);  // V1^T V1
+    acc = acc - prod;
+    factor(h + 1);
+  }
+}
+
 // The pivot chain of one factor (chain_kernel, chain_multi_kernel): one workgroup factors every
 // pivot block in order.  acc: this wave's quadrant of tile (0, 0) of K.  LDS: sXJ [32][SB],
-// sP / sM [32][SP], pv [32].
-template <bool ONEWAVE>
+// sP / sM [32][SP], pv [32].  LOOKAHEAD (chain_kernel): the two-block window above when the
+// launch asks for it (ChainFactor::la), with its extra LDS (win) and K's tiles (kf).
+struct ChainWindow {
+  double *sX2, *sM2, *sD;
+  bool trla;  // probes: lane 0 of wave 1, factor 0
+};
+template <bool ONEWAVE, bool LOOKAHEAD = false, class KF = NoTileSource>
 __device__ __forceinline__ void chain_master(const ChainFactor& F, int T, d4 acc, double* sXJ,
                                              double* sP, double* sM, double* pv, bool trm,
-                                             bool early_flag, double* lw = nullptr) {
+                                             bool early_flag, double* lw = nullptr,
+                                             ChainWindow win = ChainWindow(), KF kf = KF()) {
+  if constexpr (LOOKAHEAD) {
+    if (F.la) {  // (launch-uniform)
+      chain_master_la(F, T, acc, sXJ, win.sX2, sP, sM, win.sM2, win.sD, pv, trm, win.trla, lw, kf);
+      return;
+    }
+  }
   const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
   const int wr = wv >> 1, wc = wv & 1;
   const int tx = t & 31, ty = t >> 5;
@@ -440,6 +671,7 @@ __global__ __launch_bounds__(256, 2) void chain_kernel(ChainBatch b) {
   __shared__ double sL[32 * SA];
   __shared__ double sXI[32 * SB], sXJ[32 * SB];
   __shared__ double sP[32 * SP], sM[32 * SP], pv[32];
+  __shared__ double sD[32 * SP];  // the pivot chain's look-ahead: its next diagonal tile
   __shared__ unsigned int s_last;
   // L_k^{-1} as self-validating words (chain_multi_kernel's form) in this launch's half of the
   // L^{-1} slots (PB2, launch parity; the other half is reset by the tile workgroups): the tile
@@ -500,16 +732,39 @@ __global__ __launch_bounds__(256, 2) void chain_kernel(ChainBatch b) {
   };
   // the pivot chain's inputs of hop kk (after sweep kk-1): panel tile (kk, kk+1) and diagonal
   // tile (kk+1, kk+1) as granules (chain_master), before any other store of the tile
+  // Look-ahead mode (F.la): the chain forms those two itself and takes the window's other tiles,
+  // one sweep older: (kk, kk+2), (kk+1, kk+2), (kk+2, kk+2) after sweep kk-1 into slot kk
   auto chain_inputs = [&](int kk) {
-    const int which = (I == kk && J == kk + 1) ? 0 : (I == J && I == kk + 1) ? 1 : -1;
-    if (which < 0 || kk + 1 >= T) return;
+    int which;
+    if (F.la) {
+      which = (J != kk + 2 || kk + 2 >= T) ? -1 : I - kk;
+      if (which < 0 || which > 2) return;
+    } else {
+      which = (I == kk && J == kk + 1) ? 0 : (I == J && I == kk + 1) ? 1 : -1;
+      if (which < 0 || kk + 1 >= T) return;
+    }
+    double* slot = F.la ? gran3_at(F, kk, which, 0) : gran_at(F, kk, which, 0);
 #pragma unroll
     for (int r = 0; r < 4; ++r)
-      st_sc1(gran_at(F, kk, which, (16 * wr + (lane >> 4) + 4 * r) * 32 + 16 * wc + (lane & 15)), acc[r]);
+      st_sc1(slot + (16 * wr + (lane >> 4) + 4 * r) * 32 + 16 * wc + (lane & 15), acc[r]);
+  };
+  // K's element (i, j) as the gather above forms it (the pivot chain's hop-0 tiles)
+  auto k_at = [&](int i, int j) -> double {
+    const size_t o = (size_t)i * p + j;
+    if (GATHER) {
+      const int u = F.cid[o];
+      if (u < 0) return (i == j) ? 1.0 : 0.0;
+      double kv = F.kval[u];
+      if (i == j) kv += F.jitter;
+      return kv;
+    }
+    return F.X[o];
   };
   const bool trm = t == 0 && m == 0;  // probes (gpk_trace.h): factor 0's pivot owners
   if (master) {
-    chain_master<true>(F, T, acc, sXJ, sP, sM, pv, trm, false, PLc);
+    // (a tile workgroup's sL and sXI are free here: the second L^{-1} and panel buffers)
+    const ChainWindow win{sXI, sL, sD, t == 64 && m == 0};
+    chain_master<true, true>(F, T, acc, sXJ, sP, sM, pv, trm, false, PLc, win, k_at);
   } else {
     if (trm && tile == 0) TR_LO(SLOT_GATHER);
     chain_inputs(0);                       // tiles (0, 1) and (1, 1) as they are before sweep 0
@@ -1186,7 +1441,7 @@ hipError_t launch_spd_chain(const ChainArgs* a, int nmat, int deriv, hipStream_t
     f.tu = a[m].tu; f.td = a[m].td; f.Bu = a[m].Bu; f.ldbu = a[m].ldbu; f.bu_t = a[m].bu_t;
     f.Ou = a[m].Ou; f.ldou = a[m].ldou; f.ou_t = a[m].ou_t; f.Od = a[m].Od; f.ldod = a[m].ldod;
     f.PBa = a[m].PBa; f.ldpba = a[m].ldpba;
-    f.gran = a[m].gran; f.piv_off = f.T * (f.T + f.tu + f.td);
+    f.gran = a[m].gran; f.piv_off = f.T * (f.T + f.tu + f.td); f.la = a[m].lookahead;
     f.PB2 = a[m].PB2; f.epoch = a[m].epoch;  // (both null: L^{-1} hand-off by flag + load)
     if ((a[m].cid != nullptr) != gather || !f.gran || !f.PB2 != !f.epoch) return hipErrorInvalidValue;
     Tmax = std::max(Tmax, f.T * (f.T + f.tu + f.td) + 1);  // + the pivot chain's workgroup

@@ -153,6 +153,11 @@ typedef struct gpk_problem {
  * end of step s's parameter-gradient launch, right after the kernel-parameter Adam, so steps
  * 2.. of a batch start with the inverse launch).  Bitwise the same results; A/B only. */
 #define GPK_FLAG_NO_CLASS_PIPE 8388608
+/* Persistent chain inverse on 32x32 tiles: the pivot workgroup receives each pivot's two input
+ * tiles from their owners (default: it keeps a two-block window and forms them itself while one
+ * of its waves factors the previous pivot, from tiles handed over one sweep earlier).  Bitwise
+ * the same results; A/B only. */
+#define GPK_FLAG_NO_CHAIN_LOOKAHEAD 16777216
 
 typedef struct gpk_handle gpk_handle;
 
