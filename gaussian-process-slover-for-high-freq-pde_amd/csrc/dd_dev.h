@@ -2,7 +2,8 @@
 // transcendentals to ~1e-30 relative, for the kernel-parameter contraction of large factors
 // (pgrad.hip, DD): sum_c S_c f_c(theta) cancels ~1e8-fold at C5, so the fp64 rounding of the
 // derivative fields f_c themselves -- not the solves -- sets its accuracy (DESIGN.md §3,
-// tools/c5_kp_split.py).  Host and device (tools/probes/dd_check.hip checks exp / sincos against
+// tools/c5_kp_split.py).  Host and device (tests/test_dd_fields.py checks the fields built on them
+// against 50-digit arithmetic on both; tools/probes/dd_check.hip checks exp / sincos alone against
 // quad precision on the host).
 #pragma once
 #include <hip/hip_runtime.h>

@@ -1,5 +1,6 @@
 // fields_dd.h — the kernel-parameter contraction's derivative fields in double-double (pgrad.hip
-// DD; host-checked against quad precision by tools/probes/dd_check.hip).
+// DD; checked field by field against 50-digit arithmetic on the device, through gpk_fields_dd, and
+// on the host: tests/test_dd_fields.py).
 #pragma once
 #include "gpk_internal.h"
 #include "dd_dev.h"

@@ -4,8 +4,36 @@
 // only through the functions gpk_host.h declares.
 #include "gpk_host.h"
 #include "gpk_trace.h"
+#include "fields_dd.h"
 
 namespace {
+
+// gpk_fields_dd: one thread per distance, the call pgrad_kernel's DD loop makes (pgrad.hip);
+// row e of hi / lo = the high / low parts of (f_w, f_l, f_f, d_w, d_l, d_f)
+template <bool MATERN, bool COS, int DERIV>
+__global__ void fields_dd_kernel(const double* __restrict__ d, int n, double a, double om, double oml,
+                                 double* __restrict__ hi, double* __restrict__ lo) {
+  const int e = blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= n) return;
+  dd::D F[6];
+  fields_dd<MATERN, COS, DERIV>(d[e], a, om, oml, F[0], F[1], F[2], F[3], F[4], F[5]);
+#pragma unroll
+  for (int x = 0; x < 6; ++x) {
+    hi[(size_t)e * 6 + x] = F[x].h;
+    lo[(size_t)e * 6 + x] = F[x].l;
+  }
+}
+
+template <bool MATERN, bool COS>
+hipError_t launch_fields_dd(int deriv, const double* d, int n, double a, double om, double oml, double* hi,
+                            double* lo) {
+  const dim3 grid((n + 63) / 64), block(64);
+  if (deriv == 2)
+    hipLaunchKernelGGL((fields_dd_kernel<MATERN, COS, 2>), grid, block, 0, 0, d, n, a, om, oml, hi, lo);
+  else
+    hipLaunchKernelGGL((fields_dd_kernel<MATERN, COS, 1>), grid, block, 0, 0, d, n, a, om, oml, hi, lo);
+  return hipGetLastError();
+}
 
 struct EventPair {  // two HIP events, destroyed on every path
   hipEvent_t e0 = nullptr, e1 = nullptr;
@@ -314,6 +342,42 @@ int gpk_forward_field(gpk_handle* h, int32_t what, double* out, int64_t n) {
       else
         out[i * n2 + j] = v;
     }
+  return GPK_OK;
+}
+
+int gpk_fields_dd(int32_t kind, int32_t deriv, const double* d, int32_t n, double a, double freq,
+                  double* hi, double* lo) {
+  if (kind < 0 || kind > 3) return fail(GPK_EINVAL, "Invalid Kernel");
+  if (deriv != 1 && deriv != 2) return fail(GPK_EINVAL, "deriv must be 1 or 2");
+  if (n <= 0 || !d || !hi || !lo) return fail(GPK_EINVAL, "bad argument");
+  for (int e = 0; e < n; ++e)
+    if (!(d[e] >= 0.0)) return fail(GPK_EINVAL, "distances must be >= 0");
+  int dev = 0;
+  (void)hipGetDevice(&dev);
+  TRY(check_device(dev));
+  const double om = TWO_PI * freq, oml = om_low(freq, om);  // (gpk_api.cpp host_axis_const)
+  const size_t nb = (size_t)n * sizeof(double);
+  double *dd_ = nullptr, *dh = nullptr, *dl = nullptr;
+  auto cleanup = [&]() {
+    if (dd_) (void)hipFree(dd_);
+    if (dh) (void)hipFree(dh);
+    if (dl) (void)hipFree(dl);
+  };
+  if (hipMalloc(&dd_, nb) != hipSuccess || hipMalloc(&dh, 6 * nb) != hipSuccess ||
+      hipMalloc(&dl, 6 * nb) != hipSuccess) {
+    cleanup();
+    return fail(GPK_ENOMEM, "hipMalloc failed");
+  }
+  hipError_t e = hipMemcpy(dd_, d, nb, hipMemcpyHostToDevice);
+  if (e == hipSuccess)
+    e = kind == SE_COS         ? launch_fields_dd<false, true>(deriv, dd_, n, a, om, oml, dh, dl)
+        : kind == MATERN52_COS ? launch_fields_dd<true, true>(deriv, dd_, n, a, om, oml, dh, dl)
+        : kind == SE           ? launch_fields_dd<false, false>(deriv, dd_, n, a, om, oml, dh, dl)
+                               : launch_fields_dd<true, false>(deriv, dd_, n, a, om, oml, dh, dl);
+  if (e == hipSuccess) e = hipMemcpy(hi, dh, 6 * nb, hipMemcpyDeviceToHost);
+  if (e == hipSuccess) e = hipMemcpy(lo, dl, 6 * nb, hipMemcpyDeviceToHost);
+  cleanup();
+  if (e != hipSuccess) return fail(GPK_EHIP, std::string("fields_dd: ") + hipGetErrorString(e));
   return GPK_OK;
 }
 

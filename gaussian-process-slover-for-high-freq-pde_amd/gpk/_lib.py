@@ -111,6 +111,8 @@ EXPORTS = {
     "gpk_bench_kernel": ([ctypes.c_void_p, ctypes.c_char_p, ctypes.c_int32, _dp, _dp, _dp], ctypes.c_int),
     "gpk_kernel_pairs": ([ctypes.c_int32, ctypes.c_int32, _dp, _dp, ctypes.c_int64, _dp, _dp, _dp,
                           ctypes.c_int32, _dp], ctypes.c_int),
+    "gpk_fields_dd": ([ctypes.c_int32, ctypes.c_int32, _dp, ctypes.c_int32, ctypes.c_double,
+                       ctypes.c_double, _dp, _dp], ctypes.c_int),
     "gpk_forward_field": ([ctypes.c_void_p, ctypes.c_int32, _dp, ctypes.c_int64], ctypes.c_int),
     "gpk_comm_unique_id": ([ctypes.POINTER(ctypes.c_uint8), ctypes.c_int32], ctypes.c_int),
     "gpk_create_sharded": ([ctypes.POINTER(gpk_problem), ctypes.c_double, ctypes.c_int32, ctypes.c_int32,

@@ -317,6 +317,17 @@ def kernel_matrices(kind, x1, x2, paras, jitter=0.0, deriv=0):
     return K, D
 
 
+def fields_dd(kind, deriv, d, a, freq):
+    """gpk_fields_dd: (hi, lo) [n, 6], the double-double derivative fields (f_w, f_l, f_f, d_w, d_l,
+    d_f) of one mixture component (a = e^{log-ls}, freq) at the distances d, on the device."""
+    d = f64(d).reshape(-1)
+    hi, lo = np.empty((d.size, 6)), np.empty((d.size, 6))
+    k = _lib.KIND_IDS[kind] if isinstance(kind, str) else int(kind)
+    check(_lib.load().gpk_fields_dd(k, int(deriv), dptr(d), d.size, float(a), float(freq), dptr(hi),
+                                    dptr(lo)))
+    return hi, lo
+
+
 def set_chain_capacity(workgroups):
     """Override the co-resident workgroup budget gpk_create checks the persistent chain inverse
     against (0: query the device).  Tests use it to force the per-sweep fallback."""

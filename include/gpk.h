@@ -183,6 +183,16 @@ int gpk_kernel_pairs(int32_t kind, int32_t deriv, const double* x1, const double
                      const double* logw, const double* logls, const double* freq, int32_t q,
                      double* out);
 
+/* Diagnostic: the six double-double derivative fields of ONE mixture component, as the
+ * double-double kernel-parameter contraction (GPK_FLAG_DD_CONTRACTION) evaluates them on the
+ * device, at n distances d[e] >= 0.  a = e^{log-ls} is taken as given (no device exp); the
+ * angular frequency is 2*pi*freq as the exact pair (om, om_low).  deriv 1 or 2.
+ * hi / lo [n*6], row e = (f_w, f_l, f_f, d_w, d_l, d_f): the high and low parts of
+ * kappa_c / w_c, its d/dlog-ls and d/dfreq, and the same three of D_x1_kappa (deriv 1, unsigned)
+ * or DD_x1_kappa (deriv 2). */
+int gpk_fields_dd(int32_t kind, int32_t deriv, const double* d, int32_t n, double a, double freq,
+                  double* hi, double* lo);
+
 /* Solver object: copies the problem to device memory; params start at the reference init
  * (train(), model_GP_solver_2d.py:245-261 / model_GP_solver_1d.py:203-213) with zero Adam
  * state.  freq_scale sets the initial frequencies linspace(0,1,Q)*freq_scale. */

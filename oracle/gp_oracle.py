@@ -274,12 +274,18 @@ def param_grad_contract(kind, x, paras, GK, GD, deriv):
 # (tools/c5_kp_split.py); an fp64 yardstick shares them with the fp64 LU oracle.
 # One evaluation per distinct pair distance |x_i - x_j| (grids repeat them: ~n variants).
 # ----------------------------------------------------------------------------------------
-def _distance_classes(x):
-    x = np.asarray(x, np.float64).reshape(-1)
-    diff = x[:, None] - x[None, :]
+def _block_classes(x1, x2):
+    """Distinct |x1_i - x2_j| of a block, each pair's index into them, and _pairs' sign."""
+    x1 = np.asarray(x1, np.float64).reshape(-1)
+    x2 = np.asarray(x2, np.float64).reshape(-1)
+    diff = x1[:, None] - x2[None, :]
     du, inv = np.unique(np.abs(diff).ravel(), return_inverse=True)
     s = np.where(diff >= 0.0, 1.0, -1.0)
     return du, inv.reshape(diff.shape), s
+
+
+def _distance_classes(x):
+    return _block_classes(x, x)
 
 
 def _two_prod(a, b):
@@ -324,20 +330,75 @@ def _exact_field_terms(kind, du, paras):
     return k, rad, cos
 
 
-def kernel_kd_exact(kind, x, paras, jitter, deriv):
-    """kernel_kd with the fields evaluated exactly (long double), then rounded to fp64."""
-    du, inv, s = _distance_classes(x)
+def _blocks_exact(kind, x1, x2, paras, derivs):
+    """The long-double blocks of kernel_block for each deriv of `derivs`, from one field
+    evaluation per distinct |x1_i - x2_j|."""
+    du, inv, s = _block_classes(x1, x2)
     k, (m0, m1, m2, _, _, _), (c0, c1, c2, _, _, _) = _exact_field_terms(kind, du, paras)
     w = np.exp(np.asarray(paras["log-w"], np.float64)).astype(np.longdouble)
-    Ku = ((m0 * c0) @ w).astype(np.float64)
-    if deriv == 2:
-        Du = ((m2 * c0 + 2.0 * m1 * c1 + m0 * c2) @ w).astype(np.float64)
-    else:
-        Du = ((m1 * c0 + m0 * c1) @ w).astype(np.float64)
-    K = Ku[inv]
+    out = []
+    for deriv in derivs:
+        if deriv == 0:
+            out.append(((m0 * c0) @ w)[inv])
+        elif deriv == 2:
+            out.append(((m2 * c0 + 2.0 * m1 * c1 + m0 * c2) @ w)[inv])
+        else:
+            out.append(((m1 * c0 + m0 * c1) @ w)[inv] * s)
+    return out
+
+
+def kernel_block_exact(kind, x1, x2, paras, deriv=0):
+    """kernel_block with the fields evaluated exactly: long double on the reference's fp64 inputs
+    and constants, the phase as an exact fp64 pair (_exact_field_terms).  Same sign convention
+    (_pairs), no jitter.  Returns long double [n1, n2]; callers round."""
+    return _blocks_exact(kind, x1, x2, paras, (deriv,))[0]
+
+
+def kernel_kd_exact(kind, x, paras, jitter, deriv):
+    """kernel_kd with the fields evaluated exactly (long double), then rounded to fp64."""
+    K, D = (b.astype(np.float64) for b in _blocks_exact(kind, x, x, paras, (0, deriv)))
     K[np.diag_indices_from(K)] += jitter
-    D = Du[inv] * s if deriv == 1 else Du[inv]
     return K, D
+
+
+def field_scale(kind, x1, x2, paras, deriv, want_l=False):
+    """(B_K, B_D): kernel_block's K and D with every monomial of the closed forms taken in absolute
+    value (|cos|, |sin| -> 1), the scale rounding errors of a field evaluation are measured in --
+    zeros of the polynomials and cancellation between components do not shrink it.  Per component,
+    om = 2 pi f (0 without a cosine):
+      B_K = sum w M0,  B_D = sum w (M2 + 2 M1 om + M0 om^2) (deriv 2) | sum w (M1 + M0 om) (deriv 1)
+      Matern52: M0 = (1 + r + r^2/3) E, M1 = (sqrt5 a/3) r (1 + r) E, M2 = (5 a^2/3)(r^2 + r + 1) E
+      SE:       M0 = E, M1 = 2 a d E, M2 = (4 a^2 d^2 + 2 a) E.
+    B_D is None for deriv 0.  want_l: also (L_K, L_D), the same sums over |d field_c / d log-ls|
+    (the derivatives of _radial, cosine factors at their bounds): what a relative perturbation of
+    a = e^{log-ls} moves the fields by."""
+    k = _kind_id(kind)
+    d = _pairs(x1, x2)[0][:, :, None]
+    w = np.exp(np.asarray(paras["log-w"], np.float64))
+    a = np.exp(np.asarray(paras["log-ls"], np.float64))
+    om = TWO_PI * np.abs(np.asarray(paras["freq"], np.float64)) if _has_cos(k) else np.zeros_like(a)
+    if _is_matern(k):
+        r = SQRT5 * a * d
+        E = np.exp(-r)
+        M0 = (1.0 + r + r * r / 3.0) * E
+        M1 = (SQRT5 * a / 3.0) * r * (1.0 + r) * E
+        M2 = (5.0 * a * a / 3.0) * (r * r + r + 1.0) * E
+    else:
+        E = np.exp(-a * d * d)
+        M0 = E + 0.0 * d
+        M1 = 2.0 * a * d * E
+        M2 = (4.0 * a * a * d * d + 2.0 * a) * E
+
+    def comb(t0, t1, t2):
+        if deriv == 2:
+            return (t2 + 2.0 * t1 * om + t0 * om * om) @ w
+        return (t1 + t0 * om) @ w if deriv == 1 else None
+
+    out = (M0 @ w, comb(M0, M1, M2))
+    if want_l:
+        l0, l1, l2 = (np.abs(t) for t in _radial(k, d, a, True)[3:])
+        out += (l0 @ w, comb(l0, l1, l2))
+    return out
 
 
 def param_grad_contract_exact(kind, x, paras, GK, GD, deriv):

@@ -93,6 +93,30 @@ def extra_params(rng, n):
             "u": 0.05 * rng.normal(size=(n, 1))}
 
 
+# The field-accuracy tests' error unit and bar (tests/test_gpu_field_ulps.py, tests/test_oracle.py).
+def field_units(v, exact, B, bar=1.0):
+    """max |v - exact| / (eps B bar) over the block; where B = 0 the value must be exactly 0."""
+    from tests.field_ulp_inputs import EPS
+    err = np.abs(np.asarray(v, np.longdouble) - exact).astype(np.float64)
+    z = B == 0
+    assert np.all(np.asarray(v)[z] == 0)
+    bar = np.broadcast_to(bar, B.shape)
+    return float(np.max(err[~z] / (EPS * B[~z] * bar[~z]))) if np.any(~z) else 0.0
+
+
+def field_bars(regime, kind, x1, x2, kp, deriv):
+    """(B_K, B_D, bar_K, bar_D) of a block: N_K / N_D units, plus for the generic regimes the
+    fields' sensitivity to a 2-ulp difference in the device's own a = exp(log-ls), w = exp(log-w):
+    2 (sum_c w_c |d field_c / d log-ls| + B) / B units (per element)."""
+    from tests.field_ulp_inputs import N_D, N_K
+    BK, BD, LK, LD = O.field_scale(kind, x1, x2, kp, deriv, want_l=True)
+    if not regime.startswith("generic"):
+        return BK, BD, N_K, N_D
+    with np.errstate(invalid="ignore", divide="ignore"):
+        bd = N_D + 2.0 * (LD + BD) / BD if deriv else None
+    return BK, BD, N_K + 2.0 * (LK + BK) / BK, bd
+
+
 def record_parity(test, config, errors, tol=None, extra=None):
     """Append one line of observed parity errors (per key) to $GPK_PARITY_LOG (default
     gpurun_out/parity.jsonl): the GPU parity tests' margins, summarised into profiles/r*_parity.json

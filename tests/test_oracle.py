@@ -16,7 +16,7 @@ import pytest
 
 from oracle import gp_oracle as O
 from tests import autograd_ref as AR
-from tests.helpers import problem_1d, problem_2d, rel
+from tests.helpers import field_bars, field_units as _units, problem_1d, problem_2d, rel
 
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 KINDS = ["SE_Cos_1d", "Matern52_Cos_1d", "SE_1d", "Matern52_1d"]
@@ -299,3 +299,131 @@ def test_replay_2d_reference_run():
     params = O.init_params_2d(c["N_col"], c["N_col"], c["Q"], c["freq_scale"])
     _, _, rec = O.train_replay(2, prob, params, c["lr"], c["nepoch"], (Xte, ute))
     assert abs(rec["min_err"] - r["min_err"][0]) / r["min_err"][0] < 1e-4, rec["min_err"]
+
+
+# ------------------------------------------------------------------------------------------------
+# The exact-field yardstick itself, and the power of the GPU field test (tests/test_gpu_field_ulps.py)
+# checked without a GPU on exactly its inputs (tests/field_ulp_inputs.py).  Error unit:
+# |value - exact| / (eps * B), B the field with every monomial in absolute value (O.field_scale).
+# ------------------------------------------------------------------------------------------------
+def _corrected_block(kind, x1, x2, kp, deriv):
+    """fp64 NumPy emulation of the device's corrected field evaluation (csrc/gpk_internal.h
+    om_low, phase_sincos, radial_exp; csrc/prep_dev.h eval_kd_part): the arguments as fp64 pairs
+    (two-product residuals in place of the fma residuals), sincos / exp at the high part,
+    corrected to first order; components added serially."""
+    k = O._kind_id(kind)
+    d, s = O._pairs(x1, x2)
+    d = d[:, :, None]
+    w = np.exp(np.asarray(kp["log-w"], np.float64))
+    a = np.exp(np.asarray(kp["log-ls"], np.float64))
+    f = np.asarray(kp["freq"], np.float64)
+    full = np.zeros(d.shape[:2] + (len(w),))
+    if O._is_matern(k):
+        p, pe = O._two_prod(np.full_like(a, O.SQRT5), a)
+        r, re = O._two_prod(p + full, d + full)
+        l = re + pe * d
+        E = np.exp(-r)
+        E = E - l * E
+        m0 = (1.0 + r + r * r * (1.0 / 3.0)) * E
+        m1 = -(O.SQRT5 / 3.0) * a * r * (1.0 + r) * E
+        m2 = (5.0 / 3.0) * a * a * (r * r - r - 1.0) * E
+    else:
+        d2, d2e = O._two_prod(d, d)
+        r, re = O._two_prod(a + full, d2 + full)
+        l = re + a * d2e
+        E = np.exp(-r)
+        E = E - l * E
+        m0, m1, m2 = E, -2.0 * a * d * E, (4.0 * a * a * d2 - 2.0 * a) * E
+    if O._has_cos(k):
+        om, oml = O._two_prod(np.full_like(f, O.TWO_PI), f)
+        h, he = O._two_prod(om + full, d + full)
+        l = he + oml * d
+        S0, C0 = np.sin(h), np.cos(h)
+        S, C = S0 + l * C0, C0 - l * S0
+        tK = m0 * C
+        tD = (m2 * C - 2.0 * m1 * (om * S) - m0 * (om * om * C)) if deriv == 2 else (m1 * C - m0 * (om * S))
+    else:
+        tK, tD = m0, (m2 if deriv == 2 else m1)
+    K, D = np.zeros(d.shape[:2]), np.zeros(d.shape[:2])
+    for c in range(len(w)):
+        K += w[c] * tK[:, :, c]
+        D += w[c] * tD[:, :, c]
+    return K, (D * s if deriv == 1 else D)
+
+
+def test_kernel_kd_exact_is_the_rounded_exact_block():
+    x = np.linspace(0, 1, 21) * 2 * np.pi
+    kp = {"log-w": np.array([-1.0, -0.5]), "log-ls": np.array([0.2, -0.1]), "freq": np.array([3.3, 17.9])}
+    for kind in KINDS:
+        for deriv in (1, 2):
+            K, D = O.kernel_kd_exact(kind, x, kp, 1e-6, deriv)
+            Kb = O.kernel_block_exact(kind, x, x, kp, 0).astype(np.float64)
+            Kb[np.diag_indices_from(Kb)] += 1e-6
+            assert np.array_equal(K, Kb)
+            assert np.array_equal(D, O.kernel_block_exact(kind, x, x, kp, deriv).astype(np.float64))
+        # the sign of D_x1 (JAX abs'(0) = +1): antisymmetric off the diagonal, rectangular too
+        D1 = O.kernel_block_exact(kind, x[:7], x[3:12], kp, 1)
+        assert np.array_equal(D1[3:7, 0:4], -D1[3:7, 0:4].T)
+
+
+@pytest.mark.parametrize("kind", KINDS)
+@pytest.mark.parametrize("deriv", [1, 2])
+def test_exact_fields_vs_mpmath(kind, deriv):
+    """The long-double yardstick (kernel_block_exact) against 50-digit mpmath on the reference's
+    fp64 constants, at ~50 pairs of the GPU field test's inputs, the largest phase and the largest
+    radial argument among them: within 0.1 units (long double carries 11 bits more than fp64: a
+    handful of its roundings is < 0.01 units).  O.field_scale agrees with the mpmath scale."""
+    pytest.importorskip("mpmath")
+    from tests import field_ulp_inputs as FI
+    from tests import mp_fields as MP
+    rng = np.random.default_rng(5)
+    worst = 0.0
+    for regime in ("phase", "radial", "generic5"):
+        kp = FI.kernel_paras(regime)
+        x1, x2 = FI.rect_block(regime, kind)
+        x2[0] = 0.0   # with x1[36] below: the grids' full extent, the largest argument of all
+        x1[36] = FI.extent(regime, kind)
+        Ke = O.kernel_block_exact(kind, x1, x2, kp, 0)
+        De = O.kernel_block_exact(kind, x1, x2, kp, deriv)
+        BK, BD = O.field_scale(kind, x1, x2, kp, deriv)
+        d = np.abs(x1[:, None] - x2[None, :])
+        pairs = {tuple(int(v) for v in np.unravel_index(np.argmax(d), d.shape)), (7, 4), (20, 0), (21, 0)}
+        while len(pairs) < 17:
+            pairs.add((int(rng.integers(37)), int(rng.integers(29))))
+        for i, j in sorted(pairs):
+            K, D, bK, bD = MP.block_entry(kind, deriv, x1[i], x2[j], kp)
+            assert abs(float(bK) - BK[i, j]) <= 1e-12 * float(bK)
+            assert abs(float(bD) - BD[i, j]) <= 1e-12 * float(bD)
+            eK = abs(float(MP.mp_of(Ke[i, j]) - K)) / (FI.EPS * float(bK))
+            eD = abs(float(MP.mp_of(De[i, j]) - D)) / (FI.EPS * float(bD)) if bD != 0 else float(De[i, j] != 0)
+            worst = max(worst, eK, eD)
+            assert eK <= 0.1 and eD <= 0.1, (regime, i, j, eK, eD)
+    assert worst > 0.0  # (the comparison resolved something: the two are not the same code)
+
+
+@pytest.mark.parametrize("kind", KINDS)
+@pytest.mark.parametrize("regime", ["phase", "radial", "single", "generic5", "generic40"])
+def test_field_test_power(kind, regime):
+    """On exactly the GPU field test's inputs: the plain fp64 restatement (kernel_block, NumPy --
+    the evaluation WITHOUT the low-part corrections) misses the bar by at least 2x on every
+    discriminating case, and an fp64 emulation of the corrected algorithm passes it on every
+    case.  So the GPU test fails a device that loses the corrections on a route, and passes one
+    that has them, with room for the device's own exp / sincos."""
+    from tests import field_ulp_inputs as FI
+    kp = FI.kernel_paras(regime)
+    O.set_backend(False)
+    try:
+        for name, x1, x2 in FI.blocks(regime, kind):
+            for deriv in (1, 2):
+                Ke = O.kernel_block_exact(kind, x1, x2, kp, 0)
+                De = O.kernel_block_exact(kind, x1, x2, kp, deriv)
+                BK, BD, barK, barD = field_bars(regime, kind, x1, x2, kp, deriv)
+                Kc, Dc = _corrected_block(kind, x1, x2, kp, deriv)
+                cK, cD = _units(Kc, Ke, BK, barK), _units(Dc, De, BD, barD)
+                assert cK <= 1.0 and cD <= 1.0, (name, deriv, cK, cD)
+                if FI.discriminating(regime, kind):
+                    pK = _units(O.kernel_block(kind, x1, x2, kp, 0), Ke, BK, barK)
+                    pD = _units(O.kernel_block(kind, x1, x2, kp, deriv), De, BD, barD)
+                    assert pK >= 2.0 and pD >= 2.0, (name, deriv, pK, pD)
+    finally:
+        O.set_backend(True)
