@@ -675,6 +675,89 @@ __global__ __launch_bounds__(256) void gemm_big_kernel(GemmBatch batch, const St
 }
 
 // ---------------------------------------------------------------------------------------
+// Slab-batched product (the 3-axis predictions' mode-2 products, gpk_kron3.cpp): mode 2 of a
+// row-major [nb][K][N] tensor is nb independent row-major K x N matrices, so
+//   C_b = alpha A B_b + beta C0_b,   B_b = B + b sB,  C_b = C + b sC,  C0_b = C0 + b sC0
+// needs no permuted copy: the slab index is the grid's y dimension and offsets B, C and C0, one
+// M x K operand A serves every slab.  TILE 32: gemm_kernel's 32x32 tile loop (stage_tiles /
+// mma32); TILE 64: gemm_big_kernel's double-buffered 64x64 loop (big_product; edge tiles of a
+// 32-padded matrix half empty).  Plain store epilogue; C0 == C is an in-place update (every
+// element is read and written by the same lane).
+// ---------------------------------------------------------------------------------------
+template <int TILE>
+__global__ __launch_bounds__(256) void gemm_slab_kernel(SlabGemm g) {
+  const int tn = (g.N + TILE - 1) / TILE;
+  const int i0 = ((int)blockIdx.x / tn) * TILE, j0 = ((int)blockIdx.x % tn) * TILE;
+  const size_t b = blockIdx.y;
+  const double* B = g.B + b * g.sB;
+  double* C = g.C + b * g.sC;
+  const double* C0 = (g.C0 && g.beta != 0.0) ? g.C0 + b * g.sC0 : nullptr;
+  const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
+  const int wr = wv >> 1, wc = wv & 1;
+  if constexpr (TILE == 32) {
+    __shared__ double sA[32 * GSA];
+    __shared__ double sB[32 * GSB];
+    d4 acc = {0.0, 0.0, 0.0, 0.0};
+    for (int k0 = 0; k0 < g.K; k0 += 32) {
+      stage_tiles(sA, sB, g.A, g.K, 0, B, g.N, 0, i0, j0, k0, t);
+      __syncthreads();
+      acc = mma32(sA, sB, wr, wc, lane, acc);
+      __syncthreads();
+    }
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const size_t o = (size_t)(i0 + 16 * wr + (lane >> 4) + 4 * r) * g.N + j0 + 16 * wc + (lane & 15);
+      double c = g.alpha * acc[r];
+      if (C0) c += g.beta * C0[o];
+      C[o] = c;
+    }
+  } else {
+    __shared__ double sA[2 * 64 * BSA], sB[2 * 32 * BSB];
+    d4 acc[2][2];
+#pragma unroll
+    for (int x = 0; x < 2; ++x)
+#pragma unroll
+      for (int y = 0; y < 2; ++y) acc[x][y] = d4{0.0, 0.0, 0.0, 0.0};
+    big_product(g.A, g.K, 0, B, g.N, 0, g.K, g.M, g.N, i0, j0, sA, sB, t, wr, wc, lane, acc);
+#pragma unroll
+    for (int bi = 0; bi < 2; ++bi)
+#pragma unroll
+      for (int bj = 0; bj < 2; ++bj)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int row = i0 + 32 * wr + 16 * bi + (lane >> 4) + 4 * r;
+          const int col = j0 + 32 * wc + 16 * bj + (lane & 15);
+          if (row < g.M && col < g.N) {
+            const size_t o = (size_t)row * g.N + col;
+            double c = g.alpha * acc[bi][bj][r];
+            if (C0) c += g.beta * C0[o];
+            C[o] = c;
+          }
+        }
+  }
+}
+
+int slab_gemm_tile(const SlabGemm& g) {
+  return (g.M >= SLAB_TILE64_MIN && g.N >= SLAB_TILE64_MIN) ? 64 : 32;
+}
+
+hipError_t launch_gemm_slab(const SlabGemm& g, hipStream_t s, int tile) {
+  if (g.nb < 1 || g.nb > 65535 || g.M < 32 || g.N < 32 || g.K < 32 || ((g.M | g.N | g.K) & 31) || !g.A ||
+      !g.B || !g.C)
+    return hipErrorInvalidValue;
+  if (!tile) tile = slab_gemm_tile(g);
+  if (tile == 64) {
+    const int tiles = ((g.M + 63) / 64) * ((g.N + 63) / 64);
+    hipLaunchKernelGGL(gemm_slab_kernel<64>, dim3(tiles, g.nb), dim3(256), 0, s, g);
+  } else if (tile == 32) {
+    hipLaunchKernelGGL(gemm_slab_kernel<32>, dim3((g.M / 32) * (g.N / 32), g.nb), dim3(256), 0, s, g);
+  } else {
+    return hipErrorInvalidValue;
+  }
+  return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------
 // Largest-size variant (M, N >= ~2048, e.g. the 4096^2 advection grid): a 128x128 output tile
 // per 256-thread workgroup, each wave a 64x64 quadrant = 4x4 v_mfma_f64_16x16x4 blocks, the
 // software-pipelined product loop of gemm_tile_dev.h (no operand transposed on its way into LDS,

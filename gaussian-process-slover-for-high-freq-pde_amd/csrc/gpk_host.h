@@ -5,7 +5,7 @@
 //   gpk_step.cpp    the step: plan (build_descs), enqueue, graph capture, batch protocol, gpk_step
 //   gpk_shard.cpp   the row-sharded step and its collective backends (the only user of RCCL)
 //   gpk_diag.cpp    measurement and diagnostic entry points (reached from no solver entry point)
-//   gpk_kron3.cpp   the 3-axis solver
+//   gpk_kron3.cpp   the 3-axis solver (step, predictions, criterion, Adam state) and gpk_mode_gemm
 #pragma once
 #include <hip/hip_runtime.h>
 

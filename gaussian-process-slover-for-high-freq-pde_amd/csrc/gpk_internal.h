@@ -424,6 +424,27 @@ int gemm_tiles(const GemmDesc& d, int variant);
 hipError_t launch_gemm_auto(const GemmDesc* descs, int ndesc, const StepScalars* sc, hipStream_t s,
                             int variant);
 
+// Slab-batched product (gemm.hip gemm_slab_kernel): for every slab b < nb,
+// C_b = alpha A B_b + beta C0_b with A M x K shared by all slabs, B_b = B + b sB (K x N),
+// C_b = C + b sC and C0_b = C0 + b sC0 (M x N); everything row-major and dense (leading
+// dimensions K, N, N), strides in elements, M, N, K multiples of 32.  C0 may be null or equal C.
+struct SlabGemm {
+  const double* A; const double* B; size_t sB;
+  double* C; size_t sC;
+  const double* C0; size_t sC0;
+  int M, N, K, nb;          // nb <= 65535 (a grid dimension)
+  double alpha, beta;
+};
+// 64x64 tiles once every slab's output is at least this large in both dimensions, else 32x32.
+// Measured (tools/mode_gemm_ab.py): the slab count alone fills the chip, so the
+// 32x32 tile wins up to 320-size slabs (by 5 % at 320^4, by 10-40 % at 64-size slabs with 128 to
+// 1024 of them, whatever the 64x64 tile count); the two are level at 512-size slabs and the
+// 64x64 tile is 2 % ahead at 1024.
+constexpr int SLAB_TILE64_MIN = 512;
+int slab_gemm_tile(const SlabGemm& g);
+// tile: 0 = by the tile count (slab_gemm_tile), 32 or 64 forced
+hipError_t launch_gemm_slab(const SlabGemm& g, hipStream_t s, int tile = 0);
+
 __device__ __forceinline__ bool gate_open(const double* gate) {
   if (!gate) return true;
   const double k00 = gate[0];

@@ -11,6 +11,10 @@
 //     S = K^{-1} U,  R = sum_k D_k x_k A_k - F,  dL/dU = S + v sum_k X_k  (+ AC, boundary)
 //     G_Kk = c/2 (N / N_k) K_k^{-1} - (S/2 + v X_k)_(k) A_k,(k)^T,   G_Dk = v R_(k) A_k,(k)^T
 // (the 2-axis adjoints of SURVEY.md Appendix A, one per axis).
+//
+// Beyond the step: gpk_predict3 (test-grid predictions, T <- Kmn_k x_k solve(K_k, T) axis after
+// axis; its mode-2 products are slab-batched launches, gemm.hip, with no permuted copy),
+// gpk_criterion3, the Adam state, and gpk_mode_gemm (one mode-k product on host operands).
 #include "gpk_host.h"
 #include "gpk_kron3.h"
 
@@ -139,7 +143,9 @@ int launch_stage(gpk_handle3* h, int k) {
   return check_launch(launch_gemm_auto(d.data(), (int)d.size(), h->sc, h->s, variant), "gemm");
 }
 
-int enqueue_step3(gpk_handle3* h, int apply) {
+// Step constants, K_k and D_k, then K_k^{-1} and log det K_k at the current params: the front of
+// the step, and all gpk_predict3 needs of it (apply = 0 leaves the Adam count alone).
+int enqueue_inverse3(gpk_handle3* h, int apply) {
   const K3Geom& g = h->g;
   const int q = h->q, kind = h->prob.kind;
   K3Prep P{};
@@ -177,6 +183,13 @@ int enqueue_step3(gpk_handle3* h, int apply) {
   double* fin[3] = {};
   TRY(check_launch(launch_spd_inverse(sa, 2, fin, h->s, false), "spd_inverse"));
   TRY(check_launch(launch_spd_inverse(sa + 2, 1, fin + 2, h->s, false), "spd_inverse"));
+  return GPK_OK;
+}
+
+int enqueue_step3(gpk_handle3* h, int apply) {
+  const K3Geom& g = h->g;
+  const int q = h->q, kind = h->prob.kind;
+  TRY(enqueue_inverse3(h, apply));
   // forward products
   TRY(launch_stage(h, 0));
   TRY(check_launch(k3_launch_permute(h->Up, h->Upp, g, h->s), "k3_permute"));
@@ -395,6 +408,230 @@ int gpk_step3(gpk_handle3* h, int32_t n_steps, double* losses) {
   TRY(read_status3(h));
   if (losses && n_steps > 0)
     HIPCHK(hipMemcpy(losses, h->losses, n_steps * sizeof(double), hipMemcpyDeviceToHost));
+  return GPK_OK;
+}
+
+int gpk_set_opt_state3(gpk_handle3* h, int64_t count, const double* mu, const double* nu, int64_t n) {
+  if (!h || !mu || !nu) return fail(GPK_EINVAL, "NULL argument");
+  if (n != h->nparams) return fail(GPK_EINVAL, "parameter count mismatch");
+  if (count < 0 || count > 0x7fffffff) return fail(GPK_EINVAL, "bad count");
+  DevSwitch ds(h->dev);
+  const int c = (int)count;
+  HIPCHK(hipMemcpyAsync(h->m, mu, n * sizeof(double), hipMemcpyHostToDevice, h->s));
+  HIPCHK(hipMemcpyAsync(h->v, nu, n * sizeof(double), hipMemcpyHostToDevice, h->s));
+  HIPCHK(hipMemcpyAsync(h->count, &c, sizeof(int), hipMemcpyHostToDevice, h->s));
+  HIPCHK(hipStreamSynchronize(h->s));
+  return GPK_OK;
+}
+
+int gpk_get_opt_state3(gpk_handle3* h, int64_t* count, double* mu, double* nu, int64_t n) {
+  if (!h || !count || !mu || !nu) return fail(GPK_EINVAL, "NULL argument");
+  if (n != h->nparams) return fail(GPK_EINVAL, "parameter count mismatch");
+  DevSwitch ds(h->dev);
+  int c = 0;
+  HIPCHK(hipMemcpyAsync(mu, h->m, n * sizeof(double), hipMemcpyDeviceToHost, h->s));
+  HIPCHK(hipMemcpyAsync(nu, h->v, n * sizeof(double), hipMemcpyDeviceToHost, h->s));
+  HIPCHK(hipMemcpyAsync(&c, h->count, sizeof(int), hipMemcpyDeviceToHost, h->s));
+  HIPCHK(hipStreamSynchronize(h->s));
+  *count = c;
+  return GPK_OK;
+}
+
+int gpk_criterion3(gpk_handle3* h, double* out) {
+  if (!h || !out) return fail(GPK_EINVAL, "NULL argument");
+  double loss;
+  TRY(gpk_loss_grad3(h, &loss, nullptr));
+  DevSwitch ds(h->dev);
+  double diag[8];
+  HIPCHK(hipMemcpy(diag, h->diag, sizeof(diag), hipMemcpyDeviceToHost));
+  const double n1 = h->g.n[0], n2 = h->g.n[1], n3 = h->g.n[2];
+  const double Nb = 2.0 * (n2 * n3 + n1 * n3 + n1 * n2), Nc = n1 * n2 * n3;
+  *out = diag[6] / Nb + diag[5] / Nc;  // boundary_gap/Nb + eq_gap/Nc (K3Final::diag)
+  return GPK_OK;
+}
+
+int gpk_predict3(gpk_handle3* h, const double* xte1, int32_t m1, const double* xte2, int32_t m2,
+                 const double* xte3, int32_t m3, double* out) {
+  if (!h || !xte1 || !xte2 || !xte3 || !out) return fail(GPK_EINVAL, "NULL argument");
+  const int ms[3] = {m1, m2, m3};
+  const double* xte[3] = {xte1, xte2, xte3};
+  for (int a = 0; a < 3; ++a)
+    if (ms[a] < 1 || ms[a] > K3_MAX_N) return fail(GPK_EINVAL, "need 1..1024 test points per axis");
+  DevSwitch ds(h->dev);
+  const K3Geom& g = h->g;
+  const int P1 = g.p[0], P2 = g.p[1], P3 = g.p[2];
+  const int M1p = pad_up(m1), M2p = pad_up(m2), M3p = pad_up(m3);
+  const int Mp[3] = {M1p, M2p, M3p};
+  // scratch, allocated per call: test coordinates, Kmn_k (zero-padded to Mp_k x P_k), K_k again
+  // (the sweeps overwrote it) and three work tensors W that take every intermediate in turn
+  std::vector<void*> tmp;
+  auto dalloc = [&](double** p, size_t n) -> int {
+    const size_t bytes = std::max<size_t>(n, 2) * sizeof(double);
+    hipError_t e = hipMalloc((void**)p, bytes);
+    if (e != hipSuccess) {
+      (void)hipGetLastError();
+      return fail(GPK_ENOMEM, std::string("gpk_predict3: hipMalloc failed: ") + hipGetErrorString(e));
+    }
+    tmp.push_back(*p);
+    HIPCHK(hipMemsetAsync(*p, 0, bytes, h->s));
+    return GPK_OK;
+  };
+  auto done = [&](int rc) {
+    (void)hipStreamSynchronize(h->s);
+    for (void* p : tmp) (void)hipFree(p);
+    return rc;
+  };
+  const size_t N1 = (size_t)P2 * P3, R3 = (size_t)M1p * M2p;
+  const size_t big = std::max(std::max((size_t)P1 * N1, (size_t)M1p * N1),
+                              std::max(R3 * P3, R3 * M3p));
+  double *xt[3], *Kmn[3], *Kc[3], *W[3];
+  int rc = GPK_OK;
+  for (int a = 0; a < 3 && !rc; ++a) {
+    if ((rc = dalloc(&xt[a], ms[a])) || (rc = dalloc(&Kmn[a], (size_t)Mp[a] * g.p[a])) ||
+        (rc = dalloc(&Kc[a], (size_t)g.p[a] * g.p[a])) || (rc = dalloc(&W[a], big)))
+      break;
+  }
+  if (rc) return done(rc);
+  for (int a = 0; a < 3; ++a)
+    if (hipMemcpyAsync(xt[a], xte[a], ms[a] * sizeof(double), hipMemcpyHostToDevice, h->s) != hipSuccess)
+      return done(fail(GPK_EHIP, "gpk_predict3: upload of the test coordinates failed"));
+  // K_k^{-1} at the current params (the step's own front), then Kmn_k = kappa(xte_k, x_k) without
+  // jitter and K_k with it, for the refinement residuals
+  if ((rc = enqueue_inverse3(h, 0))) return done(rc);
+  const int kind = h->prob.kind, q = h->q;
+  for (int a = 0; a < 3; ++a) {
+    if ((rc = check_launch(launch_cross(kind, q, xt[a], ms[a], h->x[a], g.n[a], g.p[a], h->kc + a, 0.0, 0,
+                                        Kmn[a], nullptr, h->s), "cross")) ||
+        (rc = check_launch(launch_cross(kind, q, h->x[a], g.n[a], h->x[a], g.n[a], g.p[a], h->kc + a,
+                                        h->prob.jitter, 0, Kc[a], nullptr, h->s), "cross")))
+      return done(rc);
+  }
+  // T <- Kmn_k x_k solve(K_k, T) for k = 1, 2, 3 from T = U (the reference's 2-axis association,
+  // model_GP_solver_2d.py:185-220, axis after axis: every intermediate stays O(|U_pred|)); each
+  // solve is A = K^{-1} T, A += K^{-1} (T - K A).  Modes 1 and 3 are GEMMs on the row-major
+  // unfoldings; mode 2 of [B][P2][P3] is B slabs of P2 x P3 (launch_gemm_slab: no permuted copy).
+  double* const* Ki = h->Kinv;
+  auto gemm = [&](GemmDesc d, double alpha, double beta, const double* C0) {
+    d.alpha = alpha;
+    if (C0) { d.beta = beta; d.C0 = C0; d.ldc0 = d.ldc; }
+    return check_launch(launch_gemm_auto(&d, 1, h->sc, h->s, gemm_variant(&d, 1, 0)), "gemm");
+  };
+  auto slab = [&](const double* A, int M, const double* B, double* C, double alpha, double beta,
+                  const double* C0) {
+    SlabGemm sg{};
+    sg.A = A; sg.B = B; sg.sB = N1; sg.C = C; sg.sC = (size_t)M * P3; sg.C0 = C0; sg.sC0 = sg.sC;
+    sg.M = M; sg.N = P3; sg.K = P2; sg.nb = M1p; sg.alpha = alpha; sg.beta = beta;
+    return check_launch(launch_gemm_slab(sg, h->s), "gemm_slab");
+  };
+  const int n1 = (int)N1, r3 = (int)R3;
+  if ((rc = gemm(mk(Ki[0], P1, 0, h->Up, n1, 0, W[0], n1, P1, n1, P1), 1.0, 0.0, nullptr)) ||
+      (rc = gemm(mk(Kc[0], P1, 0, W[0], n1, 0, W[1], n1, P1, n1, P1), -1.0, 1.0, h->Up)) ||
+      (rc = gemm(mk(Ki[0], P1, 0, W[1], n1, 0, W[0], n1, P1, n1, P1), 1.0, 1.0, W[0])) ||
+      (rc = gemm(mk(Kmn[0], P1, 0, W[0], n1, 0, W[1], n1, M1p, n1, P1), 1.0, 0.0, nullptr)) ||  // [M1p][P2][P3]
+      (rc = slab(Ki[1], P2, W[1], W[0], 1.0, 0.0, nullptr)) ||
+      (rc = slab(Kc[1], P2, W[0], W[2], -1.0, 1.0, W[1])) ||
+      (rc = slab(Ki[1], P2, W[2], W[0], 1.0, 1.0, W[0])) ||
+      (rc = slab(Kmn[1], M2p, W[0], W[1], 1.0, 0.0, nullptr)) ||                               // [M1p][M2p][P3]
+      (rc = gemm(mk(W[1], P3, 0, Ki[2], P3, 0, W[0], P3, r3, P3, P3), 1.0, 0.0, nullptr)) ||
+      (rc = gemm(mk(W[0], P3, 0, Kc[2], P3, 0, W[2], P3, r3, P3, P3), -1.0, 1.0, W[1])) ||
+      (rc = gemm(mk(W[2], P3, 0, Ki[2], P3, 0, W[0], P3, r3, P3, P3), 1.0, 1.0, W[0])) ||
+      (rc = gemm(mk(W[0], P3, 0, Kmn[2], P3, 1, W[2], M3p, r3, M3p, P3), 1.0, 0.0, nullptr)))   // [M1p][M2p][M3p]
+    return done(rc);
+  for (int i1 = 0; i1 < m1; ++i1)
+    if (hipMemcpy2DAsync(out + (size_t)i1 * m2 * m3, m3 * sizeof(double), W[2] + (size_t)i1 * M2p * M3p,
+                         M3p * sizeof(double), m3 * sizeof(double), m2, hipMemcpyDeviceToHost, h->s) != hipSuccess)
+      return done(fail(GPK_EHIP, "gpk_predict3: download failed"));
+  const hipError_t e = hipStreamSynchronize(h->s);
+  (void)done(GPK_OK);
+  if (e != hipSuccess) return fail(GPK_EHIP, std::string("gpk_predict3: ") + hipGetErrorString(e));
+  return read_status3(h);
+}
+
+int gpk_mode_gemm(int32_t variant, int32_t k, int32_t d1, int32_t d2, int32_t d3, int32_t m, double alpha,
+                  const double* Mat, const double* T, double beta, const double* C0, double* C,
+                  int32_t iters, double* avg_us) {
+  if (variant < 0 || variant > 3 || k < 1 || k > 3 || d1 <= 0 || d2 <= 0 || d3 <= 0 || m <= 0 ||
+      ((d1 | d2 | d3 | m) & 31) || !Mat || !T || !C || iters < 0 || (iters && !avg_us))
+    return fail(GPK_EINVAL, "gpk_mode_gemm: bad argument (k in 1..3, sizes multiples of 32)");
+  if (k == 2 && d1 > 65535) return fail(GPK_EINVAL, "gpk_mode_gemm: mode 2 takes at most 65535 slabs");
+  const int dk = k == 1 ? d1 : k == 2 ? d2 : d3;
+  const size_t nt = (size_t)d1 * d2 * d3, nc = nt / dk * m, nm = (size_t)m * dk;
+  if (nt / dk > 0x7fffffff / 2) return fail(GPK_EINVAL, "gpk_mode_gemm: tensor too large");
+  TRY(check_device(0));
+  DevSwitch dsw(0);
+  std::vector<void*> mem;
+  auto cleanup = [&]() { for (void* p : mem) (void)hipFree(p); };
+  auto up = [&](const double* src, size_t n, double** dst) -> hipError_t {
+    hipError_t e = hipMalloc(dst, n * 8);
+    if (e != hipSuccess) return e;
+    mem.push_back(*dst);
+    return src ? hipMemcpy(*dst, src, n * 8, hipMemcpyHostToDevice) : hipSuccess;
+  };
+  const bool permute = k == 2 && variant == 1;
+  double *dM = nullptr, *dT = nullptr, *dC = nullptr, *dC0 = nullptr, *dTp = nullptr, *dCp = nullptr,
+         *dC0p = nullptr;
+  hipError_t e = up(Mat, nm, &dM);
+  if (e == hipSuccess) e = up(T, nt, &dT);
+  if (e == hipSuccess) e = up(C0 == C ? C : nullptr, nc, &dC);
+  if (e == hipSuccess && C0 && C0 != C) e = up(C0, nc, &dC0);
+  if (e == hipSuccess && permute) e = up(nullptr, nt, &dTp);
+  if (e == hipSuccess && permute) e = up(nullptr, nc, &dCp);
+  if (e == hipSuccess && permute && C0) e = up(nullptr, nc, &dC0p);
+  if (e != hipSuccess) {
+    cleanup();
+    return fail(e == hipErrorOutOfMemory ? GPK_ENOMEM : GPK_EHIP, std::string("gpk_mode_gemm: ") + hipGetErrorString(e));
+  }
+  const double* c0 = C0 ? (C0 == C ? dC : dC0) : nullptr;
+  const double be = C0 ? beta : 0.0;
+  auto one = [&](GemmDesc d, const double* c0_) {
+    d.alpha = alpha;
+    if (c0_) { d.beta = be; d.C0 = c0_; d.ldc0 = d.ldc; }
+    return launch_gemm_auto(&d, 1, nullptr, 0, gemm_variant(&d, 1, 0));
+  };
+  const int n23 = d2 * d3, n13 = d1 * d3, n12 = d1 * d2;
+  auto launch = [&]() -> hipError_t {
+    if (k == 1) return one(mk(dM, d1, 0, dT, n23, 0, dC, n23, m, n23, d1), c0);
+    if (k == 3) return one(mk(dT, d3, 0, dM, d3, 1, dC, m, n12, m, d3), c0);
+    if (!permute) {  // the slab kernel (variant 2 / 3: its 32 / 64 tile forced)
+      SlabGemm sg{};
+      sg.A = dM; sg.B = dT; sg.sB = (size_t)n23; sg.C = dC; sg.sC = (size_t)m * d3; sg.C0 = c0; sg.sC0 = sg.sC;
+      sg.M = m; sg.N = d3; sg.K = d2; sg.nb = d1; sg.alpha = alpha; sg.beta = be;
+      return launch_gemm_slab(sg, 0, variant == 2 ? 32 : variant == 3 ? 64 : 0);
+    }
+    // the step's route: permuted copy [d2][d1][d3], one GEMM on its rows, permuted back
+    K3Geom gi{}, go{};
+    gi.p[0] = gi.n[0] = d1; gi.p[1] = gi.n[1] = d2; gi.p[2] = gi.n[2] = d3;
+    go.p[0] = go.n[0] = m; go.p[1] = go.n[1] = d1; go.p[2] = go.n[2] = d3;   // [m][d1][d3] -> [d1][m][d3]
+    K3Geom gc = go;
+    gc.p[0] = gc.n[0] = d1; gc.p[1] = gc.n[1] = m;                             // [d1][m][d3] -> [m][d1][d3]
+    hipError_t r = k3_launch_permute(dT, dTp, gi, 0);
+    if (r == hipSuccess && c0) r = k3_launch_permute(c0, dC0p, gc, 0);
+    if (r == hipSuccess) r = one(mk(dM, d2, 0, dTp, n13, 0, dCp, n13, m, n13, d2), c0 ? dC0p : nullptr);
+    if (r == hipSuccess) r = k3_launch_permute(dCp, dC, go, 0);
+    return r;
+  };
+  // (as gpk_dgemm: C receives the checked launch's result; with C0 == C the timed launches keep
+  // updating the device copy in place -- same work, each on the last one's output)
+  e = launch();
+  if (e == hipSuccess) e = hipDeviceSynchronize();
+  if (e == hipSuccess) e = hipMemcpy(C, dC, nc * 8, hipMemcpyDeviceToHost);
+  if (e == hipSuccess && iters) {
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    e = hipEventCreate(&e0);
+    if (e == hipSuccess) e = hipEventCreate(&e1);
+    if (e == hipSuccess) e = launch();  // one untimed launch, then `iters` back to back
+    if (e == hipSuccess) e = hipEventRecord(e0, 0);
+    for (int it = 0; it < iters && e == hipSuccess; ++it) e = launch();
+    if (e == hipSuccess) e = hipEventRecord(e1, 0);
+    if (e == hipSuccess) e = hipEventSynchronize(e1);
+    float ms = 0.f;
+    if (e == hipSuccess) e = hipEventElapsedTime(&ms, e0, e1);
+    if (e == hipSuccess) *avg_us = ms * 1000.0 / iters;
+    if (e0) (void)hipEventDestroy(e0);
+    if (e1) (void)hipEventDestroy(e1);
+  }
+  cleanup();
+  if (e != hipSuccess) return fail(GPK_EHIP, std::string("gpk_mode_gemm: ") + hipGetErrorString(e));
   return GPK_OK;
 }
 

@@ -141,6 +141,15 @@ EXPORTS = {
     "gpk_get_params3": ([ctypes.c_void_p, _dp, ctypes.c_int64], ctypes.c_int),
     "gpk_loss_grad3": ([ctypes.c_void_p, _dp, _dp], ctypes.c_int),
     "gpk_step3": ([ctypes.c_void_p, ctypes.c_int32, _dp], ctypes.c_int),
+    "gpk_set_opt_state3": ([ctypes.c_void_p, ctypes.c_int64, _dp, _dp, ctypes.c_int64], ctypes.c_int),
+    "gpk_get_opt_state3": ([ctypes.c_void_p, ctypes.POINTER(ctypes.c_int64), _dp, _dp,
+                            ctypes.c_int64], ctypes.c_int),
+    "gpk_predict3": ([ctypes.c_void_p, _dp, ctypes.c_int32, _dp, ctypes.c_int32, _dp, ctypes.c_int32,
+                      _dp], ctypes.c_int),
+    "gpk_criterion3": ([ctypes.c_void_p, _dp], ctypes.c_int),
+    "gpk_mode_gemm": ([ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                       ctypes.c_int32, ctypes.c_double, _dp, _dp, ctypes.c_double, _dp, _dp,
+                       ctypes.c_int32, _dp], ctypes.c_int),
     "gpk_dgemm": ([ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_double, _dp,
                    ctypes.c_int32, ctypes.c_int32, _dp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
                    ctypes.c_double, _dp, ctypes.c_int32, ctypes.c_int32, _dp, ctypes.c_int32, ctypes.c_int32,
@@ -209,4 +218,30 @@ def dgemm(A, B, ta=False, tb=False, alpha=1.0, A2=None, B2=None, ta2=False, tb2=
                            int(tb), K2, alpha2, pa2, lda2, int(ta2), pb2, ldb2, int(tb2), beta,
                            dptr(C) if C0 is not None else None, dptr(C), N, iters,
                            ctypes.byref(us) if iters else None))
+    return C, (us.value if iters else None)
+
+
+MODE_SLAB, MODE_PERMUTE, MODE_SLAB32, MODE_SLAB64 = 0, 1, 2, 3
+
+
+def mode_gemm(Mat, T, k, alpha=1.0, beta=0.0, C0=None, inplace=False, variant=MODE_SLAB, iters=0):
+    """One mode-k product (gpk_mode_gemm) on host arrays: returns (C, avg_us) with
+    C = alpha (Mat x_k T) [+ beta C0], T a 3-axis array, Mat (m, T.shape[k - 1]), k in 1..3.
+    inplace: C0 is passed as C itself (the in-place update).  Mode 2: variant MODE_SLAB is the
+    slab-batched kernel, MODE_PERMUTE the permute -> GEMM -> permute route.  Sizes are multiples
+    of 32; avg_us is None when iters = 0."""
+    Mat, T = f64(Mat), f64(T)
+    d1, d2, d3 = T.shape
+    m = Mat.shape[0]
+    shape = [d1, d2, d3]
+    if 1 <= k <= 3:  # (the library rejects any other k)
+        shape[k - 1] = m
+    C = np.zeros(shape) if C0 is None else f64(C0).copy().reshape(shape)
+    c0 = None
+    if C0 is not None:
+        c0 = C if inplace else f64(C0).copy().reshape(shape)
+    us = ctypes.c_double(0.0)
+    check(load().gpk_mode_gemm(int(variant), int(k), d1, d2, d3, m, float(alpha), dptr(Mat), dptr(T),
+                               float(beta), dptr(c0) if c0 is not None else None, dptr(C), int(iters),
+                               ctypes.byref(us) if iters else None))
     return C, (us.value if iters else None)

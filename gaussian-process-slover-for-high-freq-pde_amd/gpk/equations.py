@@ -78,6 +78,23 @@ def solution_2d(equation, beta=None):
     raise KeyError(equation)
 
 
+EQUATIONS_3D = ["poisson_3d-mix_sin", "allencahn_3d-sin"]
+
+
+def solution_3d(equation):
+    """(u, src) of the 3-axis equations: src = lap u (Poisson) or lap u + u(u^2-1) (Allen-Cahn).
+    poisson_3d-mix_sin is a smooth mode plus a 10x finer one per axis; the reference stops at two
+    axes, so these are the project's own cases (the oracle's setup_3d uses the same closed forms)."""
+    if equation == "poisson_3d-mix_sin":
+        return (lambda x, y, z: s_(x) * s_(y) * s_(z) + 0.05 * s_(10 * x) * s_(10 * y) * s_(10 * z)), \
+               (lambda x, y, z: -3.0 * s_(x) * s_(y) * s_(z) - 15.0 * s_(10 * x) * s_(10 * y) * s_(10 * z))
+    if equation == "allencahn_3d-sin":
+        u = lambda x, y, z: s_(2 * x) * s_(2 * y) * s_(2 * z)
+        return u, (lambda x, y, z: -12.0 * s_(2 * x) * s_(2 * y) * s_(2 * z)
+                   + u(x, y, z) * (u(x, y, z) ** 2 - 1.0))
+    raise KeyError(equation)
+
+
 def boundary_2d(u_mesh):
     """get_boundary_vals: hstack(U[0,:], U[-1,:], U[:,0], U[:,-1]) (model_GP_solver_2d.py:377-379)."""
     return np.hstack((u_mesh[0, :], u_mesh[-1, :], u_mesh[:, 0], u_mesh[:, -1]))

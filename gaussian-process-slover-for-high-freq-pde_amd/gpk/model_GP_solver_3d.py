@@ -6,14 +6,28 @@ a tensor grid: prior -1/2 c sum_k (prod_{j != k} N_j) logdet K_k - 1/2 <U, K^{-1
 log-det weights :157-162), residual sum_k (D_k K_k^{-1}) x_k U - F [+ U(U^2-1)], boundary on the
 six faces.  The whole step (assembly, SPD inverses, mode-k products, adjoints, Adam) runs on the
 MI355X through gpk_create3 / gpk_step3 (include/gpk.h); there is no CPU fallback.
+
+Same surface as the 2-axis module: GP_solver_3d_single (train with checkpoint / resume, preds,
+compute_early_stopping), test() / evals() and the CLI
+(`python -m gpk.model_GP_solver_3d -equation=poisson_3d-mix_sin -kernel=Matern52_Cos_1d
+-nepoch=200`), with its configs in gpk/config3d/.
 """
 import ctypes
+import os
+import sys
+import time
 
 import numpy as np
+import yaml
 
-from . import _lib
+from . import _lib, init_func, replicas, utils
 from ._lib import check, dptr, f64
+from .cli import parse_flags
 from .core import tree_flatten, tree_unflatten
+from .equations import EQUATIONS_3D, solution_3d
+from .infras.exp_config import ExpConfig
+from .kernel_matrix import kernel_class
+from .solver_common import SolverBase
 
 
 def params_template_3d(n1, n2, n3, Q):
@@ -102,42 +116,234 @@ class DeviceSolver3:
         check(_lib.load().gpk_step3(self._h, int(n), dptr(out)))
         return out[:n]
 
+    def sync(self):
+        """gpk_step3 returns synchronised (its losses are read back): nothing left to wait for."""
 
-class GP_solver_3d_single:
-    """GP_solver_2d_single's interface (model_GP_solver_2d.py:40-48, :176-183) on three axes.
+    def get_opt_state(self):
+        mu = np.empty(self.nparams)
+        nu = np.empty(self.nparams)
+        c = ctypes.c_int64()
+        check(_lib.load().gpk_get_opt_state3(self._h, ctypes.byref(c), dptr(mu), dptr(nu), self.nparams))
+        return int(c.value), mu, nu
+
+    def set_opt_state(self, count, mu, nu):
+        mu, nu = f64(mu).reshape(-1), f64(nu).reshape(-1)
+        if mu.size != self.nparams or nu.size != self.nparams:
+            raise ValueError("mu and nu must have nparams entries")
+        check(_lib.load().gpk_set_opt_state3(self._h, int(count), dptr(mu), dptr(nu), self.nparams))
+
+    def predict(self, xte1, xte2, xte3):
+        """U_pred on the test grid, (m1, m2, m3), at the current params (gpk_predict3)."""
+        xs = [None if x is None else f64(x).reshape(-1) for x in (xte1, xte2, xte3)]
+        ms = [0 if x is None else x.size for x in xs]
+        out = np.empty(max(ms[0] * ms[1] * ms[2], 1))
+        check(_lib.load().gpk_predict3(self._h, *[a for x, m in zip(xs, ms)
+                                                   for a in (None if x is None else dptr(x), m)],
+                                       dptr(out)))
+        return out[:ms[0] * ms[1] * ms[2]].reshape(ms)
+
+    def criterion(self):
+        c = ctypes.c_double()
+        check(_lib.load().gpk_criterion3(self._h, ctypes.byref(c)))
+        return c.value
+
+
+class GP_solver_3d_single(SolverBase):
+    """GP_solver_2d_single's interface (model_GP_solver_2d.py:31-352) on three axes: SolverBase's
+    train (checkpoint, resume, stop_at, perf_log), step(params, opt_state), preds,
+    compute_early_stopping.
 
     bvals: boundary_3d(U) of the solution; X_col = (x, y, z); src_vals: N1 x N2 x N3;
     trick_paras: {'kernel': class, 'equation': 'poisson_3d-...' | 'allencahn_3d-...',
-    'llk_weight', 'logdet', 'lr', 'Q', 'freq_scale'}."""
+    'llk_weight', 'logdet', 'lr', 'Q', 'freq_scale'} (+ 'nepoch', 'tol' for train);
+    X_test = (x, y, z) test axes and u_test: M1 x M2 x M3, needed by train() and preds()."""
 
+    dim = 3
     eq_types = ("poisson_3d", "allencahn_3d")
+    early_stop_enabled = True
 
-    def __init__(self, bvals, X_col, src_vals, jitter, trick_paras, device=0):
+    def __init__(self, bvals, X_col, src_vals, jitter, trick_paras, device=0, X_test=None, u_test=None):
         self.eq_type = trick_paras["equation"].split("-")[0]
         assert self.eq_type in self.eq_types
         self.cov_func = trick_paras["kernel"]()
         self.trick_paras = trick_paras
-        eq = {"poisson_3d": "poisson", "allencahn_3d": "allencahn"}[self.eq_type]
-        self.dev = DeviceSolver3(eq, self.cov_func.KIND, X_col, src_vals, bvals,
-                                 Q=trick_paras.get("Q", 30), jitter=jitter,
-                                 llk_weight=trick_paras["llk_weight"],
-                                 logdet=trick_paras.get("logdet", True), lr=trick_paras.get("lr", 0.01),
-                                 freq_scale=trick_paras.get("freq_scale", 20.0), device=device)
+        self.bvals = np.asarray(bvals, np.float64)
+        self.X_col = X_col
+        self.jitter = jitter
+        self.N1, self.N2, self.N3 = (np.asarray(x).size for x in X_col)
+        self.Nb = self.bvals.size
+        self.Nc = self.N1 * self.N2 * self.N3
+        self.src_vals = np.asarray(src_vals, np.float64)
+        self.llk_weight = trick_paras["llk_weight"]
+        self.Xte = X_test
+        self.ute = u_test
+        self._make_device(device=device)
 
+    def _make_device(self, device=0):
+        tp = self.trick_paras
+        eq = {"poisson_3d": "poisson", "allencahn_3d": "allencahn"}[self.eq_type]
+        self.dev = DeviceSolver3(eq, self.cov_func.KIND, self.X_col, self.src_vals, self.bvals,
+                                 Q=tp.get("Q", 30), jitter=self.jitter, llk_weight=tp["llk_weight"],
+                                 logdet=tp.get("logdet", True), lr=tp.get("lr", 0.01),
+                                 freq_scale=tp.get("freq_scale", 20.0), device=int(tp.get("device", device)))
+        self._version = 0
+
+    # the device holds the params: reading fetches them, train()'s final assignment is a no-op
     @property
     def params(self):
         return self.dev.get_params()
 
-    def loss(self, params):
+    @params.setter
+    def params(self, value):
+        pass
+
+    def init_params(self):
+        """The 2-axis train() init (model_GP_solver_2d.py:245-261) with a third factor."""
+        Q, fs = self.dev.Q, float(self.trick_paras.get("freq_scale", 20.0))
+        kp = lambda: {"log-w": np.log(1 / Q) * np.ones(Q), "log-ls": np.zeros(Q),
+                      "freq": np.linspace(0, 1, Q) * fs}
+        return {"log_tau": 0.0, "log_v": 0.0, "kernel_paras_1": kp(), "kernel_paras_2": kp(),
+                "kernel_paras_3": kp(), "U": np.zeros((self.N1, self.N2, self.N3))}
+
+    def loss(self, params, key=None):
         """Negative log joint at params (model_GP_solver_2d.py:145-174 on three axes)."""
-        self.dev.set_params(params)
+        self._sync(params)
         return self.dev.loss_grad()[0]
 
-    def value_and_grad(self, params):
-        self.dev.set_params(params)
+    def value_and_grad(self, params, key=None):
+        self._sync(params)
         loss, g = self.dev.loss_grad()
         return loss, tree_unflatten(self.dev.template, g)
 
-    def step(self, n=1):
-        """n Adam steps (step(), model_GP_solver_2d.py:176-183); the per-step losses."""
-        return self.dev.step(n)
+    def step(self, params=1, opt_state=None, key=None):
+        """step(n): n Adam steps, the per-step losses.  step(params, opt_state[, key]): one step
+        in the reference's form (model_GP_solver_2d.py:176-183), (params, opt_state, loss)."""
+        if isinstance(params, (int, np.integer)):
+            losses = self.dev.step(int(params))
+            self._version += 1
+            return losses
+        return SolverBase.step(self, params, opt_state, key)
+
+    def steps(self, n):
+        """n steps in device batches of at most 4096 (gpk_step3's loss buffer); the n losses."""
+        out = [self.dev.step(min(4096, n - k)) for k in range(0, n, 4096)]
+        self._version += 1
+        return np.concatenate(out) if out else np.zeros(0)
+
+    def preds(self, params):
+        """U_pred on the test grid, axis after axis as 2d.py:185-220 (gpk_predict3)."""
+        if self.Xte is None:
+            raise ValueError("preds() needs X_test")
+        self._sync(params)
+        return self.dev.predict(*self.Xte), None
+
+    def _err(self, params):
+        if self.ute is None:
+            raise ValueError("the relative L2 error needs u_test")
+        preds, _ = self.preds(params)
+        ute = np.asarray(self.ute).reshape(-1)
+        return float(np.linalg.norm(preds.reshape(-1) - ute) / np.linalg.norm(ute))
+
+    def _kernel_lists(self, params, log):
+        for a in (1, 2, 3):
+            kp = params["kernel_paras_%d" % a]
+            log.setdefault("w_list_k%d" % a, []).append(np.exp(kp["log-w"]))
+            log.setdefault("freq_list_k%d" % a, []).append(np.asarray(kp["freq"]))
+            log.setdefault("ls_list_k%d" % a, []).append(np.exp(kp["log-ls"]))
+
+    def _finish_log(self, log):
+        keys = ["loss_list", "err_list"] + ["%s_list_k%d" % (w, a) for a in (1, 2, 3)
+                                             for w in ("w", "freq", "ls")] + ["epoch_list"]
+        return {k: log.get(k, []) for k in keys}
+
+
+# ---------------------------------------------------------------------------------------
+# experiment driver (the 2-axis module's test() / evals(), 2d.py:355-510, on three axes)
+# ---------------------------------------------------------------------------------------
+def get_mesh_data(u, Ms, scale):
+    """(axes, u_mesh) on linspace(0,1,M_k)*scale per axis (2d.py:369-374)."""
+    axes = [np.linspace(0, 1, num=M) * scale for M in Ms]
+    mesh = np.meshgrid(*axes, indexing="ij")
+    return axes, u(*mesh) * np.ones_like(mesh[0])
+
+
+SOLVER = GP_solver_3d_single
+
+
+def test(trick_paras, solver_cls=None):
+    """Run num_fold trainings of one equation and write result_log (2d.py:382-464)."""
+    solver_cls = solver_cls or SOLVER
+    u, src = solution_3d(trick_paras["equation"])
+    scale = trick_paras["scale"]
+    M, N = trick_paras["M_test"], trick_paras["N_col"]
+    X_test, u_test = get_mesh_data(u, (M, M, M), scale)
+    X_col, u_mh = get_mesh_data(u, (N, N, N), scale)
+    bvals = boundary_3d(u_mh)
+    _, src_vals = get_mesh_data(src, (N, N, N), scale)
+    ctx = replicas.init()
+    if ctx.world > 1:
+        trick_paras = dict(trick_paras, device=ctx.local)
+    results = {}
+    start_time = time.time()
+    model = None
+    for fold in replicas.owned(trick_paras["num_fold"], ctx):
+        print("fold %d training" % fold)
+        model = solver_cls(bvals, X_col, src_vals, 1e-6, trick_paras, X_test=X_test, u_test=u_test)
+        log_dict, early_stopping, min_err = model.train(trick_paras["nepoch"], fold)
+        results[fold] = (min_err, early_stopping["epoch"])
+        if fold == 0:
+            utils.store_model(model, log_dict, trick_paras)
+    allres = replicas.gather_by_index(results, trick_paras["num_fold"], ctx)
+    err_list = [r[0] for r in allres]
+    early_stopping_list = [r[1] for r in allres]
+    end_time = time.time()
+    err_dict = {"mean": np.mean(err_list), "std": np.std(err_list), "err_list": err_list,
+                "stop_epoch_mean": np.mean(early_stopping_list), "used_time": end_time - start_time,
+                "avg_time": (end_time - start_time) / trick_paras["num_fold"]}
+    if ctx.rank == 0:
+        utils.wrirte_log(model, err_dict, trick_paras)
+        print("finish writing log ...")
+    return err_dict
+
+
+def load_config(equation):
+    """./config3d/<equation>.yaml, falling back to the package's copy."""
+    for base in (os.getcwd(), os.path.dirname(os.path.abspath(__file__))):
+        p = os.path.join(base, "config3d", equation + ".yaml")
+        if os.path.exists(p):
+            with open(p, "r") as f:
+                return yaml.safe_load(f)
+    raise FileNotFoundError("config3d/" + equation + ".yaml")
+
+
+def build_config(args, allowed=EQUATIONS_3D):
+    """The 2-axis build_config (scale, kernel class, other_paras) on the config3d files."""
+    assert args.equation in allowed
+    config = load_config(args.equation)
+    config["equation"] = args.equation
+    config["init_u_trick"] = init_func.zeros
+    config["kernel_extra"] = None
+    config["scale"] = 2 * np.pi if config["scale"] == "2pi" else 1.0
+    if args.nepoch is not None:
+        config["nepoch"] = args.nepoch
+    config["kernel"] = kernel_class(args.kernel)
+    if getattr(args, "device", None) is not None:
+        config["device"] = int(args.device)
+    print("equation: %s, kernel: %s, freq_scale: %d" % (config["equation"], config["kernel"].__name__,
+                                                        config["freq_scale"]))
+    config["other_paras"] = config["other_paras"] + "-Ncol-%d" % config["N_col"]
+    return config
+
+
+def evals(**kwargs):
+    args = ExpConfig()
+    args.parse(kwargs)
+    return test(build_config(args))
+
+
+def main(argv=None):
+    return evals(**parse_flags(sys.argv[1:] if argv is None else argv))
+
+
+if __name__ == "__main__":
+    main()

@@ -418,6 +418,33 @@ int gpk_get_params3(gpk_handle3* h, double* flat, int64_t n);
 int gpk_loss_grad3(gpk_handle3* h, double* loss, double* grad_flat);
 /* n_steps of loss + gradient + Adam, device-resident; losses[n_steps] nullable */
 int gpk_step3(gpk_handle3* h, int32_t n_steps, double* losses);
+/* Adam state of a 3-axis handle: the step count and the first / second moments, each in the
+ * flat params' layout (n = gpk_num_params3). */
+int gpk_set_opt_state3(gpk_handle3* h, int64_t count, const double* mu, const double* nu, int64_t n);
+int gpk_get_opt_state3(gpk_handle3* h, int64_t* count, double* mu, double* nu, int64_t n);
+/* Predictions on the test grid xte1 x xte2 x xte3 at the current params: out[m1*m2*m3] row-major.
+ * The reference's 2-axis association (model_GP_solver_2d.py:185-220) axis after axis,
+ * T <- Kmn_k x_k solve(K_k, T) for k = 1, 2, 3 from T = U, each solve through K_k^{-1} with one
+ * refinement step.  1 <= m_k <= 1024.  Scratch is allocated for the call and freed before it
+ * returns (GPK_ENOMEM when it does not fit); GPK_ENOTPD on a non-positive pivot.  Params and Adam
+ * state are untouched. */
+int gpk_predict3(gpk_handle3* h, const double* xte1, int32_t m1, const double* xte2, int32_t m2,
+                 const double* xte3, int32_t m3, double* out);
+/* compute_early_stopping (model_GP_solver_2d.py:222-233) on three axes: boundary_gap / Nb +
+ * eq_gap / Nc at the current params, Nb = 2 (n2 n3 + n1 n3 + n1 n2), Nc = n1 n2 n3. */
+int gpk_criterion3(gpk_handle3* h, double* out);
+
+/* One mode-k product on host operands (tests, A/B timing; the counterpart of gpk_dgemm):
+ *   C = alpha (Mat x_k T) + beta C0,   T [d1][d2][d3] row-major, Mat m x d_k row-major,
+ * C and C0 shaped as T with d_k replaced by m; every size a multiple of 32; C0 may be NULL or
+ * equal C.  Modes 1 and 3 are single GEMMs on the row-major unfoldings under every variant.
+ * Mode 2: variant 0 the slab-batched kernel (one launch over the d1 slabs of d2 x d3, no copy;
+ * 2 / 3 the same with its 32x32 / 64x64 tile forced), variant 1 the step's route (permuted
+ * copy, one GEMM, permuted back).  iters > 0 times that many back-to-back runs of the whole
+ * route with HIP events after the checked one; *avg_us as gpk_dgemm. */
+int gpk_mode_gemm(int32_t variant, int32_t k, int32_t d1, int32_t d2, int32_t d3, int32_t m, double alpha,
+                  const double* Mat, const double* T, double beta, const double* C0, double* C,
+                  int32_t iters, double* avg_us);
 
 #ifdef __cplusplus
 }
