@@ -205,7 +205,23 @@ __device__ __forceinline__ double pivot_chol_inv_block(LP A, LP M, LP pv, int t,
 // (register r of lane (li, lk) = element (16 I + lk + 4 r, 16 J + li)), so a block step needs no
 // workgroup barrier (LDS operations of one wave are in order), and it publishes to LDS only what
 // the NEXT block step reads -- A's next column block (rows at and below it) and M's next block
-// rows -- instead of every updated entry.  4.3 us against 5.0 us per factorisation.
+// rows -- instead of every updated entry.
+// The wave is issue-bound, so a block step issues only the rank-4 updates whose operands are not
+// structurally zero (kb and with it every mask below is a constant of the unrolled step):
+//   kb 0-2   a00 a10 m00 | a11 m10     (M's tile-row-0 rows of tile column 1 are zero: no m11)
+//   kb 3     a11 m10                   (no row of tile row 0 is below the block)
+//   kb 4-6   a11 m10 m11
+//   kb 7     none                      (nothing is below the block: only M_B = X)
+// 26 MFMAs instead of 36; what is dropped only added +-0 to an accumulator (equal results, a
+// -0 may become +0), together with the loads and products that fed only them: 3.77-3.82 us
+// against 3.98-4.08 us per factorisation (pivot_variants_probe V13 / V5).  Every accumulator
+// still receives its updates in kb order.
+// PUBFIRST (off; the probe's V14): in steps 0-2 the next step reads tile column 0 alone, so
+// those three updates go first, then the publishing LDS writes, then a11 / m10 (the scheduler
+// held to that order), to put the LDS round trip and the head of the next 4x4 factorisation
+// under the two trailing MFMAs.  No gain beyond the run-to-run spread (3.72-3.80 us, the ranges
+// overlap): one wave's v_fma_f64 hardly issue under its own fp64 MFMAs
+// (tools/probes/mfma_f64_probe.hip: 2 MFMAs 53 ns, 32 fmas 80 ns, together 123 ns).
 // The upper tile of A in LDS is left stale (read only for rows above the block, whose operand is
 // masked to zero); the upper tile of M is zero.  M's LDS copy is complete on return.
 // Hook: wave 0 runs early() after block step 2 and pre() / post() after block step 5, then meets
@@ -214,7 +230,7 @@ __device__ __forceinline__ double pivot_chol_inv_block(LP A, LP M, LP pv, int t,
 // prefetches (chain_master's PivotPrefetch) are issued at the same point of the factorisation as
 // with the four-wave form.  hook.waves() == false (NoPivotHook): waves 1-3 go straight to the
 // closing barrier.  (sflag: unused, kept for the call signature.)
-template <typename LP = double*, typename Hook = NoPivotHook>
+template <typename LP = double*, typename Hook = NoPivotHook, bool PUBFIRST = false>
 __device__ __forceinline__ double pivot_chol_inv_1w(LP A, LP M, LP pv, int t, int* status,
                                                     volatile int* sflag = nullptr, Hook hook = Hook()) {
   typedef double dv4 __attribute__((ext_vector_type(4)));
@@ -242,6 +258,8 @@ __device__ __forceinline__ double pivot_chol_inv_1w(LP A, LP M, LP pv, int t, in
 #pragma unroll
     for (int kb = 0; kb < 8; ++kb) {
       const int b0 = 4 * kb, b1 = b0 + 4, J0 = kb >> 2;
+      // what this step's operands feed (the table above)
+      const bool col0 = kb < 3, below = kb < 7, col1 = J0 == 1;
       double D[4][4], ar0[4], ar1[4], mb0[4], mb1[4];
 #pragma unroll
       for (int x = 0; x < 4; ++x)
@@ -249,10 +267,10 @@ __device__ __forceinline__ double pivot_chol_inv_1w(LP A, LP M, LP pv, int t, in
         for (int y = 0; y <= x; ++y) D[x][y] = A[(b0 + x) * SP + b0 + y];
 #pragma unroll
       for (int z = 0; z < 4; ++z) {
-        ar0[z] = J0 == 0 ? A[li * SP + b0 + z] : 0.0;
-        ar1[z] = A[(16 + li) * SP + b0 + z];
+        if (col0) ar0[z] = A[li * SP + b0 + z];
+        if (below) ar1[z] = A[(16 + li) * SP + b0 + z];
         mb0[z] = M[(b0 + z) * SP + li];
-        mb1[z] = J0 == 1 ? M[(b0 + z) * SP + 16 + li] : 0.0;
+        if (col1) mb1[z] = M[(b0 + z) * SP + 16 + li];
       }
       // D = L_D L_D^T, W = L_D^{-1}: pivot_chol_inv_block's arithmetic
       double L[4][4], rinv[4], W[4][4];
@@ -281,36 +299,25 @@ __device__ __forceinline__ double pivot_chol_inv_1w(LP A, LP M, LP pv, int t, in
           for (int z = x; z < y; ++z) q = fma(L[y][z], W[z][x], q);
           W[y][x] = -q * rinv[y];
         }
-#pragma unroll
-        for (int y = 0; y < x; ++y) W[y][x] = 0.0;
       }
+      // row lk of W by 0/1 weights, over its lower triangle (W[y][z] = 0 for y < z: the four-wave
+      // form's fma chain with its zero terms left out)
+      const double w[4] = {fma(W[0][0], s0, fma(W[1][0], s1, fma(W[2][0], s2, W[3][0] * s3))),
+                           fma(W[1][1], s1, fma(W[2][1], s2, W[3][1] * s3)),
+                           fma(W[2][2], s2, W[3][2] * s3), W[3][3] * s3};
       double l0 = 0.0, l1 = 0.0, x0 = 0.0, x1 = 0.0;
 #pragma unroll
       for (int z = 0; z < 4; ++z) {
-        const double w = fma(W[0][z], s0, fma(W[1][z], s1, fma(W[2][z], s2, W[3][z] * s3)));
-        l0 = fma(ar0[z], w, l0);
-        l1 = fma(ar1[z], w, l1);
-        x0 = fma(w, mb0[z], x0);
-        x1 = fma(w, mb1[z], x1);
+        if (col0) l0 = fma(ar0[z], w[z], l0);
+        if (below) l1 = fma(ar1[z], w[z], l1);
+        x0 = fma(w[z], mb0[z], x0);
+        if (col1) x1 = fma(w[z], mb1[z], x1);
       }
       const double oa0 = (li >= b1) ? -l0 : 0.0, oa1 = (16 + li >= b1) ? -l1 : 0.0;
       const double ob0 = (li >= b1) ? l0 : 0.0, ob1 = (16 + li >= b1) ? l1 : 0.0;
-      if (J0 == 0) {
-        a00 = __builtin_amdgcn_mfma_f64_16x16x4f64(oa0, ob0, a00, 0, 0, 0);
-        a10 = __builtin_amdgcn_mfma_f64_16x16x4f64(oa1, ob0, a10, 0, 0, 0);
-        m00 = __builtin_amdgcn_mfma_f64_16x16x4f64(oa0, x0, m00, 0, 0, 0);
-      }
-      a11 = __builtin_amdgcn_mfma_f64_16x16x4f64(oa1, ob1, a11, 0, 0, 0);
-      m10 = __builtin_amdgcn_mfma_f64_16x16x4f64(oa1, x0, m10, 0, 0, 0);
-      m11 = __builtin_amdgcn_mfma_f64_16x16x4f64(oa1, x1, m11, 0, 0, 0);
       const int rb = kb & 3;  // the block's rows: register rb of tile row J0 (final: M_B = X)
-      if (J0 == 0) {
-        m00[rb] = x0;
-      } else {
-        m10[rb] = x0;
-        m11[rb] = x1;
-      }
-      if (kb < 7) {  // publish what block step kb + 1 reads
+      // publish what block step kb + 1 reads
+      auto publish = [&]() {
         const int J1 = b1 >> 4, c1 = b1 & 15, r1 = (b1 & 15) >> 2;
         const bool mine = li >= c1 && li < c1 + 4;
 #pragma unroll
@@ -329,6 +336,33 @@ __device__ __forceinline__ double pivot_chol_inv_1w(LP A, LP M, LP pv, int t, in
           M[(16 + lk + 4 * r1) * SP + li] = m10[r1];
           M[(16 + lk + 4 * r1) * SP + 16 + li] = m11[r1];
         }
+      };
+      if (col0) {
+        a00 = __builtin_amdgcn_mfma_f64_16x16x4f64(oa0, ob0, a00, 0, 0, 0);
+        a10 = __builtin_amdgcn_mfma_f64_16x16x4f64(oa1, ob0, a10, 0, 0, 0);
+        m00 = __builtin_amdgcn_mfma_f64_16x16x4f64(oa0, x0, m00, 0, 0, 0);
+        m00[rb] = x0;
+        if (PUBFIRST) {
+          __builtin_amdgcn_sched_barrier(0);
+          publish();
+          __builtin_amdgcn_sched_barrier(0);
+        }
+        a11 = __builtin_amdgcn_mfma_f64_16x16x4f64(oa1, ob1, a11, 0, 0, 0);
+        m10 = __builtin_amdgcn_mfma_f64_16x16x4f64(oa1, x0, m10, 0, 0, 0);
+        if (!PUBFIRST) publish();
+      } else {
+        if (below) {
+          a11 = __builtin_amdgcn_mfma_f64_16x16x4f64(oa1, ob1, a11, 0, 0, 0);
+          m10 = __builtin_amdgcn_mfma_f64_16x16x4f64(oa1, x0, m10, 0, 0, 0);
+        }
+        if (below && col1) m11 = __builtin_amdgcn_mfma_f64_16x16x4f64(oa1, x1, m11, 0, 0, 0);
+        if (col1) {
+          m10[rb] = x0;
+          m11[rb] = x1;
+        } else {
+          m00[rb] = x0;
+        }
+        if (below) publish();
       }
       if (kb == 2) hook.early();
       if (kb == 5) {

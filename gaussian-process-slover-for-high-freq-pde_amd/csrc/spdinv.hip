@@ -448,10 +448,14 @@ __device__ __forceinline__ void chain_master_la(const ChainFactor& F, int T, d4 
     if (wv > 0) {  // (wave 0 goes straight to the factorisation)
       if (kp >= 2) rearm(kp - 2);  // the slot read during factorisation kp - 1
       if (kp == 0 && T > 1) {
-        // hop 0's inputs: tiles (0, 1) and (1, 1) of K
+        // hop 0's inputs: tiles (0, 1) and (1, 1) of K.  (From an opaque copy of the thread id,
+        // as fresh_lane: this branch now sits in the pivot loop, and its 11 element offsets,
+        // hoisted out of the loop, would stay live across every factorisation -- they spilled)
+        int t0 = t;
+        asm volatile("" : "+v"(t0));
 #pragma unroll
         for (int it = 0; it < 11; ++it) {
-          const int e = t - 64 + 192 * it;
+          const int e = t0 - 64 + 192 * it;
           if (e >= 2048) continue;
           const int row = (e >> 5) & 31, col = e & 31;
           if (e < 1024) sX[row * SB + col] = kf(row, 32 + col);
@@ -475,24 +479,29 @@ __device__ __forceinline__ void chain_master_la(const ChainFactor& F, int T, d4 
                        __HIP_MEMORY_SCOPE_AGENT);
   }
   if (lw) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  factor(0);
-  for (int h = 0; h + 1 < T; ++h) {
-    if (trm && h < 16) TR_LO(SLOT_SWEEP + h);
-    double* sXh = (h & 1) ? sX2 : sX;
-    const double* Lh = (h & 1) ? sM2 : sM;
+  // ONE call site of factor(): the unrolled factorisation (~10 KB) is inlined once, so pivot 0
+  // runs the loop's copy and leaves it warm in the instruction cache for pivot 1 (with a call
+  // ahead of the loop, pivot 0 ran a copy used once per launch and pivot 1 the loop's copy cold)
+  for (int kp = 0; kp < T; ++kp) {
+    if (kp > 0) {  // hop kp - 1: acc = tile (kp, kp) after sweep kp - 1
+      const int h = kp - 1;
+      if (trm && h < 16) TR_LO(SLOT_SWEEP + h);
+      double* sXh = (h & 1) ? sX2 : sX;
+      const double* Lh = (h & 1) ? sM2 : sM;
 #pragma unroll
-    for (int r = 0; r < 4; ++r) acc[r] = sD[(16 * wr + lk + 4 * r) * SP + 16 * wc + li];
-    d4 vj = {0.0, 0.0, 0.0, 0.0};
-    vj = mma_t(Lh, SP, 1, sXh, SB, 1, wr, wc, lane, vj);  // V1 = L_h^{-1} X_{h,h+1}
-    if (!lw) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // L^{-1}_h's stores, before its flag
-    __syncthreads();
-    if (t == 0 && !lw) __hip_atomic_store(piv_rdy + h, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    store_quad(sXh, SB, wr, wc, lane, vj);
-    __syncthreads();
-    d4 prod = {0.0, 0.0, 0.0, 0.0};
-    prod = mma_t(sXh, 1, SB, sXh, SB, 1, wr, wc, lane, prod);  // V1^T V1
-    acc = acc - prod;
-    factor(h + 1);
+      for (int r = 0; r < 4; ++r) acc[r] = sD[(16 * wr + lk + 4 * r) * SP + 16 * wc + li];
+      d4 vj = {0.0, 0.0, 0.0, 0.0};
+      vj = mma_t(Lh, SP, 1, sXh, SB, 1, wr, wc, lane, vj);  // V1 = L_h^{-1} X_{h,h+1}
+      if (!lw) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // L^{-1}_h's stores, before its flag
+      __syncthreads();
+      if (t == 0 && !lw) __hip_atomic_store(piv_rdy + h, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      store_quad(sXh, SB, wr, wc, lane, vj);
+      __syncthreads();
+      d4 prod = {0.0, 0.0, 0.0, 0.0};
+      prod = mma_t(sXh, 1, SB, sXh, SB, 1, wr, wc, lane, prod);  // V1^T V1
+      acc = acc - prod;
+    }
+    factor(kp);
   }
 }
 
@@ -590,51 +599,55 @@ __device__ __forceinline__ void chain_master(const ChainFactor& F, int T, d4 acc
   // lw: no pivot flags -- the zeroing above completes before any L^{-1} word is stored (every
   // diagonal tile's atomicMax comes after it has read L^{-1}_0's words)
   if (lw) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  factor(0);  // acc = tile (0, 0) of K, gathered above
-  for (int k = 0; k + 1 < T; ++k) {
-    // L_k's flag: raised inside the hop (below); with early_flag (chain_multi, whose inputs are
-    // usually late) at once -- its stores drain while the inputs are awaited, and the tile
-    // workgroups' sweep k (which produces pivot k+2's inputs) does not wait for this hop
-    if (early_flag) {
-      if (lw) __syncthreads();
-      else signal_flag(piv_rdy + k);
-    }
-    bool ok = true;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) ok = ok && gran_ok(gx[r]) && gran_ok(gd[r]);
-    if (trm && !ok) { TR_LO(SLOT_PREFETCH_MISS); TR_HI(SLOT_PREFETCH_MISS); }  // (thread 0's words)
-    // (per lane) words not yet written when they were loaded: load them again.  Bounded: a
-    // hand-off that never arrives flags the status word (the step reports an error) instead of
-    // hanging the device.
-    for (unsigned spins = 0; !ok; ++spins) {
-      if (spin_give_up(spins, F.status)) break;
-      __builtin_amdgcn_s_sleep(1);
-      issue(k);
-      ok = true;
+  // ONE call site of factor() (one inlined copy of the factorisation, as in chain_master_la):
+  // pivot 0 factors acc = tile (0, 0) of K, gathered above; pivot kp > 0 follows hop kp - 1
+  for (int kp = 0; kp < T; ++kp) {
+    if (kp > 0) {
+      const int k = kp - 1;
+      // L_k's flag: raised inside the hop (below); with early_flag (chain_multi, whose inputs are
+      // usually late) at once -- its stores drain while the inputs are awaited, and the tile
+      // workgroups' sweep k (which produces pivot k+2's inputs) does not wait for this hop
+      if (early_flag) {
+        if (lw) __syncthreads();
+        else signal_flag(piv_rdy + k);
+      }
+      bool ok = true;
 #pragma unroll
       for (int r = 0; r < 4; ++r) ok = ok && gran_ok(gx[r]) && gran_ok(gd[r]);
-    }
-    if (trm && k < 16) TR_LO(SLOT_SWEEP + k);
+      if (trm && !ok) { TR_LO(SLOT_PREFETCH_MISS); TR_HI(SLOT_PREFETCH_MISS); }  // (thread 0's words)
+      // (per lane) words not yet written when they were loaded: load them again.  Bounded: a
+      // hand-off that never arrives flags the status word (the step reports an error) instead of
+      // hanging the device.
+      for (unsigned spins = 0; !ok; ++spins) {
+        if (spin_give_up(spins, F.status)) break;
+        __builtin_amdgcn_s_sleep(1);
+        issue(k);
+        ok = true;
 #pragma unroll
-    for (int r = 0; r < 4; ++r) {  // prefetched during pivot k's factorisation
-      sXJ[(ty + 8 * r) * SB + tx] = gx[r];
-      acc[r] = gd[r];
-      // consumed: the sentinel back into the slot for the next launch
-      st_sc1(gran_at(F, k, 0, ex(r)), __longlong_as_double((long long)CHAIN_SENTINEL));
-      st_sc1(gran_at(F, k, 1, ed(r)), __longlong_as_double((long long)CHAIN_SENTINEL));
+        for (int r = 0; r < 4; ++r) ok = ok && gran_ok(gx[r]) && gran_ok(gd[r]);
+      }
+      if (trm && k < 16) TR_LO(SLOT_SWEEP + k);
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {  // prefetched during pivot k's factorisation
+        sXJ[(ty + 8 * r) * SB + tx] = gx[r];
+        acc[r] = gd[r];
+        // consumed: the sentinel back into the slot for the next launch
+        st_sc1(gran_at(F, k, 0, ex(r)), __longlong_as_double((long long)CHAIN_SENTINEL));
+        st_sc1(gran_at(F, k, 1, ed(r)), __longlong_as_double((long long)CHAIN_SENTINEL));
+      }
+      __syncthreads();
+      d4 vj = {0.0, 0.0, 0.0, 0.0};
+      vj = mma_t(sM, SP, 1, sXJ, SB, 1, wr, wc, lane, vj);  // V = L_k^{-1} X_{k,k+1}
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // L^{-1}_k's stores (long drained)
+      __syncthreads();
+      if (t == 0 && !early_flag && !lw) __hip_atomic_store(piv_rdy + k, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      store_quad(sXJ, SB, wr, wc, lane, vj);
+      __syncthreads();
+      d4 prod = {0.0, 0.0, 0.0, 0.0};
+      prod = mma_t(sXJ, 1, SB, sXJ, SB, 1, wr, wc, lane, prod);  // V^T V
+      acc = acc - prod;
     }
-    __syncthreads();
-    d4 vj = {0.0, 0.0, 0.0, 0.0};
-    vj = mma_t(sM, SP, 1, sXJ, SB, 1, wr, wc, lane, vj);  // V = L_k^{-1} X_{k,k+1}
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // L^{-1}_k's stores (long drained)
-    __syncthreads();
-    if (t == 0 && !early_flag && !lw) __hip_atomic_store(piv_rdy + k, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    store_quad(sXJ, SB, wr, wc, lane, vj);
-    __syncthreads();
-    d4 prod = {0.0, 0.0, 0.0, 0.0};
-    prod = mma_t(sXJ, 1, SB, sXJ, SB, 1, wr, wc, lane, prod);  // V^T V
-    acc = acc - prod;
-    factor(k + 1);
+    factor(kp);
   }
 }
 

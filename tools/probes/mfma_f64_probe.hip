@@ -42,6 +42,39 @@ __global__ void fma_rate(double* out, int iters) {
   out[blockIdx.x * blockDim.x + threadIdx.x] = x0 + x1 + x2 + x3 + x4 + x5 + x6 + x7;
 }
 
+// Can ONE wave's independent v_fma_f64 issue under its own fp64 MFMAs?  (The one-wave pivot,
+// spd_pivot.h: the next block step's 4x4 square-root chain behind two trailing MFMAs.)  One wave
+// on one CU; per iteration MODE & 1: two independent MFMAs (2 x 64 cycles of the matrix pipe),
+// MODE & 2: 32 v_fma_f64 on 8 independent chains (32 x 4 cycles at full rate).  Overlap: the
+// mixed loop takes about the longer of the two; none: about their sum.
+template <int MODE>
+__global__ void mfma_fma_mix(double* out, int iters, long long* cyc) {
+  double a = threadIdx.x * 1e-3, b = 1.0 + threadIdx.x * 1e-4;
+  double4_t c0 = {0, 0, 0, 0}, c1 = c0;
+  double x[8];
+  for (int j = 0; j < 8; ++j) x[j] = threadIdx.x + j;
+  const double m = 0.999999, d = 1e-7;
+  const long long t0 = wall_clock64();
+#pragma unroll 1
+  for (int i = 0; i < iters; ++i) {
+    if (MODE & 1) {
+      c0 = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c0, 0, 0, 0);
+      c1 = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c1, 0, 0, 0);
+    }
+    if (MODE & 2) {
+#pragma unroll
+      for (int k = 0; k < 4; ++k)
+#pragma unroll
+        for (int j = 0; j < 8; ++j) x[j] = fma(x[j], m, d);
+    }
+  }
+  const long long t1 = wall_clock64();
+  double s = c0[0] + c1[1];
+  for (int j = 0; j < 8; ++j) s += x[j];
+  out[threadIdx.x] = s;
+  if (threadIdx.x == 0) cyc[0] = t1 - t0;
+}
+
 __global__ void trans_rate(double* out, int iters) {
   double x = threadIdx.x * 1e-3 + blockIdx.x * 1e-6, acc = 0;
   for (int i = 0; i < iters; ++i) {
@@ -103,6 +136,24 @@ int main() {
     hipEventElapsedTime(&ms, e0, e1);
     double evals = (double)cus * 4 * 256 * titers;
     printf("exp+sincos f64: %.3f ms  %.3f G(exp+sincos)/s\n", ms, evals / ms / 1e6);
+  }
+  {  // one wave: fp64 VALU under fp64 MFMA
+    long long* dcyc; hipMalloc(&dcyc, 8);
+    int rate = 0;
+    hipDeviceGetAttribute(&rate, hipDeviceAttributeWallClockRate, 0);
+    const int iters = 20000;
+    double ns[4] = {0, 0, 0, 0};
+    for (int rep = 0; rep < 2; ++rep)
+      for (int mode = 1; mode <= 3; ++mode) {
+        if (mode == 1) mfma_fma_mix<1><<<1, 64>>>(dout, iters, dcyc);
+        if (mode == 2) mfma_fma_mix<2><<<1, 64>>>(dout, iters, dcyc);
+        if (mode == 3) mfma_fma_mix<3><<<1, 64>>>(dout, iters, dcyc);
+        long long c = 0;
+        hipMemcpy(&c, dcyc, 8, hipMemcpyDeviceToHost);
+        ns[mode] = (double)c / iters / (rate * 1e-6);
+      }
+    printf("one wave, per iteration: 2 MFMA f64 %.1f ns, 32 v_fma_f64 %.1f ns, both %.1f ns "
+           "(sum %.1f, max %.1f)\n", ns[1], ns[2], ns[3], ns[1] + ns[2], fmax(ns[1], ns[2]));
   }
   // launch latency: empty kernel chain
   hipEventRecord(e0);

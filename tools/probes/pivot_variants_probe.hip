@@ -7,6 +7,12 @@
 //   V2  one wave (64 lanes) holds the lower 16x16 tiles of A and M in MFMA accumulators: no
 //       barriers at all, 6 MFMAs per step
 //   V3  V2 + the look-ahead of V1
+//   V5  V2 publishing only what the next block step reads: all 36 MFMAs (the shipped form until
+//       the two below)
+//   V13 spd_pivot.h pivot_chol_inv_1w as shipped: V5 without the 10 MFMAs whose operands are
+//       structurally zero, and without the loads and products that fed only them
+//   V14 V13 with PUBFIRST: block steps 0-2 publish right after the three updates the next step
+//       reads, ahead of a11 / m10
 // build: hipcc --offload-arch=gfx950 -O3 -std=c++17 pivot_variants_probe.hip -o pivot_variants_probe
 #include "../../gaussian-process-slover-for-high-freq-pde_amd/csrc/spd_pivot.h"
 #include <cmath>
@@ -715,7 +721,9 @@ __global__ __launch_bounds__(256) void bench(const double* Kin, double* out, int
     else if (V == 9) l = piv_pipe(A, M, pv, Wb, Hb, fl, t, st);
     else if (V == 10) l = piv_1w2<false, false, true>(A, M, pv, t, st);
     else if (V == 11) l = piv_1w2<false, false, false, 1>(A, M, pv, t, st);
-    else l = piv_1w2<false, false, false, 2>(A, M, pv, t, st);
+    else if (V == 12) l = piv_1w2<false, false, false, 2>(A, M, pv, t, st);
+    else if (V == 13) l = pivot_chol_inv_1w(A, M, pv, t, st);
+    else l = pivot_chol_inv_1w<double*, NoPivotHook, true>(A, M, pv, t, st);
     tot += wall_clock64() - t0;
     ls += l;
   }
@@ -779,6 +787,11 @@ int main() {
     run<10>("V5 without the 4x4 factorisation (timing)", dK, dout, cyc, st, rate, r);
     run<11>("V5 without MFMAs (timing)", dK, dout, cyc, st, rate, r);
     run<12>("V5, next step's tiles' MFMAs first", dK, dout, cyc, st, rate, r); cmp(12);
+    run<13>("V5, needed MFMAs only (shipped)", dK, dout, cyc, st, rate, r); cmp(13);
+    run<14>("V13 + publish first in steps 0-2", dK, dout, cyc, st, rate, r); cmp(14);
+    run<5>("V5 (again)", dK, dout, cyc, st, rate, r);
+    run<13>("V13 (again)", dK, dout, cyc, st, rate, r);
+    run<14>("V14 (again)", dK, dout, cyc, st, rate, r);
     run<0>("spd_pivot.h (again)", dK, dout, cyc, st, rate, r);
     int s = 0;
     CHK(hipMemcpy(&s, st, 4, hipMemcpyDeviceToHost));
