@@ -16,11 +16,21 @@
 // log det K = sum_k 2 sum_i log L_ii over pivot blocks.  A non-positive pivot raises
 // GPK_ENOTPD through *status.
 //
-// One launch per pivot block (ping-pong X -> Y, no intra-launch hazards); a 256-thread
-// workgroup owns one 32x32 output tile (4 waves x 16x16 v_mfma_f64_16x16x4 quadrants) and
-// recomputes the two 32x32 panel pieces it needs; the workgroup that produces the NEXT
-// pivot tile factors it in its tail, so the next launch finds L^{-1} ready: N/32 launches,
-// batched over both Kronecker factors.
+// Three forms of the same arithmetic, bitwise equal to one another:
+//   * sweep_kernel: one launch per pivot block (ping-pong X -> Y, no intra-launch hazards); a
+//     256-thread workgroup owns one 32x32 output tile (4 waves x 16x16 v_mfma_f64_16x16x4
+//     quadrants) and recomputes the two 32x32 panel pieces it needs; the workgroup that produces
+//     the NEXT pivot tile factors it in its tail, so the next launch finds L^{-1} ready: N/32
+//     launches, batched over both Kronecker factors.  The reference of the other two.
+//   * chain_kernel: every sweep in ONE launch, a workgroup per tile, ordered by flags and
+//     self-validating words; one workgroup per factor runs the pivot chain (chain_master, with a
+//     two-block look-ahead in chain_master_la).
+//   * chain_multi_kernel: the same with a macro tile per workgroup, for large 1D factors.
+// sweep_kernel and chain_kernel share the accumulator layout (q_row, q_col, q_elem), the
+// quadrant product (mma_f) and the four-case tile update (sweep_update), and chain_kernel's
+// gather sites share gather_k / gather_d; the host side has one batch builder and one (deriv,
+// gather) dispatch for both chain launches.  chain_multi_kernel, the two pivot-chain masters
+// and ChainFactor keep their own text: folded, the C2 step measured slower.
 #include <algorithm>
 
 #include "gpk_internal.h"
@@ -68,24 +78,61 @@ __global__ __launch_bounds__(256) void pivot_init_kernel(SpdBatch b) {
   }
 }
 
-// acc += A(32x32, element (i,k) at a[i*sai + k*sak]) * B(32x32, (k,j) at bm[k*sbk + j*sbj]),
-// this wave's 16x16 quadrant (wr, wc).  Strides let one LDS image serve transposed reads.
-__device__ __forceinline__ d4 mma_t(const double* a, int sai, int sak, const double* bm, int sbk,
-                                    int sbj, int wr, int wc, int lane, d4 acc) {
+// The MFMA accumulator layout: element r of wave quadrant (wr, wc) of a 32x32 tile is the tile's
+// row q_row(wr, lane, r), column q_col(wc, lane).
+__device__ __forceinline__ int q_row(int wr, int lane, int r) { return 16 * wr + (lane >> 4) + 4 * r; }
+__device__ __forceinline__ int q_col(int wc, int lane) { return 16 * wc + (lane & 15); }
+// ... and element 32 row + col of the tile stored densely (the pivot chain's input slots)
+__device__ __forceinline__ int q_elem(int wr, int wc, int lane, int r) {
+  return q_row(wr, lane, r) * 32 + q_col(wc, lane);
+}
+
+// The one 32-deep quadrant product: acc += A B, this wave's 16x16 quadrant (wr, wc); fa(i, k),
+// fb(k, j) give the operands.  The k order (4 kk + lk) and the operand roles are what keeps the
+// three inverse paths (sweep, chain, multi-tile chain) bitwise equal.
+template <class FA, class FB>
+__device__ __forceinline__ d4 mma_f(FA fa, FB fb, int wr, int wc, int lane, d4 acc) {
   const int li = lane & 15, lk = lane >> 4;
 #pragma unroll
   for (int kk = 0; kk < 8; ++kk) {
     const int k = 4 * kk + lk;
-    const double av = a[(16 * wr + li) * sai + k * sak];
-    const double bv = bm[k * sbk + (16 * wc + li) * sbj];
-    acc = __builtin_amdgcn_mfma_f64_16x16x4f64(av, bv, acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f64_16x16x4f64(fa(16 * wr + li, k), fb(k, 16 * wc + li), acc, 0, 0, 0);
   }
   return acc;
+}
+// ... with A (i, k) at a[i*sai + k*sak] and B (k, j) at bm[k*sbk + j*sbj]: strides let one LDS
+// image serve transposed reads
+__device__ __forceinline__ d4 mma_t(const double* a, int sai, int sak, const double* bm, int sbk,
+                                    int sbj, int wr, int wc, int lane, d4 acc) {
+  return mma_f([&](int i, int k) { return a[i * sai + k * sak]; },
+               [&](int k, int j) { return bm[k * sbk + j * sbj]; }, wr, wc, lane, acc);
+}
+
+// One sweep's update of tile (I, J) by pivot block P, this wave's quadrant (ip: I == P, jp:
+// J == P).  lt = L^{-T} (i, k), l = L^{-1} (k, j), vit = V_I^T (i, k), vj = V_J (k, j); x: the
+// tile before the sweep.  Every product is accumulated from zero and then negated / subtracted.
+template <class LT, class L, class VIT, class VJ>
+__device__ __forceinline__ d4 sweep_update(bool ip, bool jp, LT lt, L l, VIT vit, VJ vj, int wr,
+                                           int wc, int lane, d4 x) {
+  const d4 zero = {0.0, 0.0, 0.0, 0.0};
+  if (ip && jp) return -mma_f(lt, l, wr, wc, lane, zero);  // -L^{-T} L^{-1}
+  if (ip) return mma_f(lt, vj, wr, wc, lane, zero);        // L^{-T} V_J
+  if (jp) return mma_f(vit, l, wr, wc, lane, zero);        // V_I^T L^{-1}
+  return x - mma_f(vit, vj, wr, wc, lane, zero);           // x - V_I^T V_J
+}
+
+// ... with L^{-1} in sL [32][SA] and V_I, V_J in sVI, sVJ [32][SB] (sweep_kernel, chain_kernel)
+__device__ __forceinline__ d4 sweep_update_lds(bool ip, bool jp, const double* sL, const double* sVI,
+                                               const double* sVJ, int wr, int wc, int lane, d4 x) {
+  return sweep_update(
+      ip, jp, [&](int i, int k) { return sL[k * SA + i]; }, [&](int k, int j) { return sL[k * SA + j]; },
+      [&](int i, int k) { return sVI[k * SB + i]; }, [&](int k, int j) { return sVJ[k * SB + j]; }, wr, wc,
+      lane, x);
 }
 
 __device__ __forceinline__ void store_quad(double* s, int ld, int wr, int wc, int lane, d4 v) {
 #pragma unroll
-  for (int r = 0; r < 4; ++r) s[(16 * wr + (lane >> 4) + 4 * r) * ld + 16 * wc + (lane & 15)] = v[r];
+  for (int r = 0; r < 4; ++r) s[q_row(wr, lane, r) * ld + q_col(wc, lane)] = v[r];
 }
 
 __global__ __launch_bounds__(256) void sweep_kernel(SpdBatch b, int k) {
@@ -116,11 +163,11 @@ __global__ __launch_bounds__(256) void sweep_kernel(SpdBatch b, int k) {
   const int P = k;
 
   // prefetch this wave's quadrant of X_IJ (consumed only in the epilogue)
-  double xij[4] = {0.0, 0.0, 0.0, 0.0};
+  d4 xij = {0.0, 0.0, 0.0, 0.0};
   if (I != P && J != P) {
 #pragma unroll
     for (int r = 0; r < 4; ++r)
-      xij[r] = X[(size_t)(I * 32 + 16 * wr + (lane >> 4) + 4 * r) * p + J * 32 + 16 * wc + (lane & 15)];
+      xij[r] = X[(size_t)(I * 32 + q_row(wr, lane, r)) * p + J * 32 + q_col(wc, lane)];
   }
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
@@ -140,30 +187,15 @@ __global__ __launch_bounds__(256) void sweep_kernel(SpdBatch b, int k) {
   if (J != P && J != I) store_quad(sXJ, SB, wr, wc, lane, vj);
   __syncthreads();
 
-  d4 acc = {0.0, 0.0, 0.0, 0.0};
-  if (I == P && J == P) {
-    acc = mma_t(sL, 1, SA, sL, SA, 1, wr, wc, lane, acc);   // L^{-T} L^{-1}
-  } else if (I == P) {
-    acc = mma_t(sL, 1, SA, sVJ, SB, 1, wr, wc, lane, acc);  // L^{-T} V_J
-  } else if (J == P) {
-    acc = mma_t(sXI, 1, SB, sL, SA, 1, wr, wc, lane, acc);  // V_I^T L^{-1}
-  } else {
-    acc = mma_t(sXI, 1, SB, sVJ, SB, 1, wr, wc, lane, acc); // V_I^T V_J
-  }
+  const d4 acc = sweep_update_lds(I == P, J == P, sL, sXI, sVJ, wr, wc, lane, xij);
 
   const double fin = last ? -1.0 : 1.0;
   const bool nextpiv = (!last) && I == k + 1 && J == k + 1;
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
-    const int row = 16 * wr + (lane >> 4) + 4 * r, col = 16 * wc + (lane & 15);
+    const int row = q_row(wr, lane, r), col = q_col(wc, lane);
     const size_t o = (size_t)(I * 32 + row) * p + J * 32 + col;
-    double y;
-    if (I == P && J == P)
-      y = -acc[r];
-    else if (I == P || J == P)
-      y = acc[r];
-    else
-      y = xij[r] - acc[r];
+    const double y = acc[r];
     Y[o] = y * fin;
     if (nextpiv) sP[row * SP + col] = y;
     if (last && I == J && row == col) pv[row] = (I * 32 + row < b.n[m]) ? y * fin : 0.0;
@@ -210,6 +242,7 @@ __global__ __launch_bounds__(256) void sweep_kernel(SpdBatch b, int k) {
 // only when the grid fits the device's co-resident capacity (spd_chain_capacity: occupancy per CU
 // x CUs; two per CU on a full MI355X) and at most CHAIN_MAX_BLOCKS.  The arithmetic is the
 // sweep kernel's operation for operation: the results are bitwise equal.
+
 struct ChainFactor {
   double* X;            // in: assembled K (read mode); out: K^{-1}
   double* PB;           // panel buffer [p*p]: tile (I, J) as it is after sweep I-1
@@ -217,8 +250,8 @@ struct ChainFactor {
   double* ldet;         // [T]
   double* pst;          // refinement gate [2]
   int* status;
-  unsigned int* flags;  // [T*TC] panel ready, [T] pivot ready, [T] (unused), [1] done counter
-                        // (zero; re-armed by the last workgroup)
+  unsigned int* flags;  // [T*TC] panel ready, [T] pivot ready, a T-word gap (the ABI's
+                        // allocation), the done counter at T*TC + 2T (zero; re-armed by the last workgroup)
   double* gran;              // the pivot chain's input slots [T][3][1024] (chain_master)
   int la;                    // chain_kernel: two-block look-ahead in the pivot chain (chain_master)
   double* PB2;               // chain_multi: panel slots [2][p*p] by launch parity (self-validating)
@@ -281,6 +314,42 @@ __device__ __forceinline__ double* gran3_at(const ChainFactor& F, int slot, int 
 }
 __device__ __forceinline__ bool gran_ok(double v) {
   return __double_as_longlong(v) != (long long)CHAIN_SENTINEL;
+}
+// The one gather.  D(i, j) of distance class u (zero on the pads, u < 0; advection, DERIV 1: signed
+// by x_i - x_j) ...
+template <int DERIV>
+__device__ __forceinline__ double class_d(const ChainFactor& F, int u, int i, int j) {
+  double dv = u >= 0 ? F.dval[u] : 0.0;
+  if (DERIV == 1 && u >= 0 && !(F.x[i] - F.x[j] >= 0.0)) dv = -dv;  // JAX abs'(0) = +1
+  return dv;
+}
+// ... D(i, j) from the class tables, or the stored D in read mode (the augmented D^T columns)
+template <int DERIV, bool GATHER>
+__device__ __forceinline__ double gather_d(const ChainFactor& F, int i, int j) {
+  const size_t o = (size_t)i * F.p + j;
+  return GATHER ? class_d<DERIV>(F, F.cid[o], i, j) : F.D[o];
+}
+// K(i, j) from the distance classes (+ jitter on the diagonal; identity on the pads), or from X in
+// read mode.  write (gather mode): the kept copy Kc and D are stored on the way.
+template <int DERIV, bool GATHER>
+__device__ __forceinline__ double gather_k(const ChainFactor& F, int i, int j, bool write) {
+  const size_t o = (size_t)i * F.p + j;
+  if (!GATHER) return F.X[o];
+  const int u = F.cid[o];
+  double kv, dv;
+  if (u >= 0) {  // (both table reads in one branch: they are in flight together)
+    kv = F.kval[u];
+    if (i == j) kv += F.jitter;
+    dv = class_d<DERIV>(F, u, i, j);
+  } else {
+    kv = (i == j) ? 1.0 : 0.0;
+    dv = 0.0;
+  }
+  if (write) {
+    if (F.Kc) F.Kc[o] = kv;
+    if (DERIV && F.D) F.D[o] = dv;
+  }
+  return kv;
 }
 
 // one 16x16 quadrant product with both operands in registers: a[kk] = A(i, 4 kk + lk),
@@ -488,6 +557,8 @@ __device__ __forceinline__ void chain_master_la(const ChainFactor& F, int T, d4 
       if (trm && h < 16) TR_LO(SLOT_SWEEP + h);
       double* sXh = (h & 1) ? sX2 : sX;
       const double* Lh = (h & 1) ? sM2 : sM;
+      // (q_row / q_col's layout with the opaque li, lk of fresh_lane: formed from `lane`, these
+      // offsets are hoisted out of the hop loop and stay live across the factorisation -- above)
 #pragma unroll
       for (int r = 0; r < 4; ++r) acc[r] = sD[(16 * wr + lk + 4 * r) * SP + 16 * wc + li];
       d4 vj = {0.0, 0.0, 0.0, 0.0};
@@ -693,54 +764,25 @@ __global__ __launch_bounds__(256, 2) void chain_kernel(ChainBatch b) {
   const unsigned ep = F.PB2 ? __hip_atomic_load(F.epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0u;
   double* PLc = F.PB2 ? F.PB2 + (size_t)(ep & 1u) * chain_half(p, false) : nullptr;
 
-  // own tile, this wave's quadrant: rows 16 wr + (lane >> 4) + 4 r, column 16 wc + (lane & 15)
+  // own tile, this wave's quadrant
   d4 acc;
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
-    const int i = I * 32 + 16 * wr + (lane >> 4) + 4 * r, j = J * 32 + 16 * wc + (lane & 15);
-    const size_t o = (size_t)i * p + j;
-    if (aug) {  // B_u[i][j'] or D^T[i][j'] = D[j'][i] (j' = column inside the part)
-      const int jl = ja * 32 + 16 * wc + (lane & 15);
-      if (ja < F.tu) {
-        acc[r] = F.bu_t ? F.Bu[(size_t)(jl) * F.ldbu + i] : F.Bu[(size_t)i * F.ldbu + jl];
-      } else {
-        const int jd = jl - 32 * F.tu;
-        const size_t od = (size_t)jd * p + i;
-        if (GATHER) {
-          const int u = F.cid[od];
-          double dv = u >= 0 ? F.dval[u] : 0.0;
-          if (DERIV == 1 && u >= 0 && !(F.x[jd] - F.x[i] >= 0.0)) dv = -dv;
-          acc[r] = dv;
-        } else {
-          acc[r] = F.D[od];
-        }
-      }
+    const int i = I * 32 + q_row(wr, lane, r);
+    if (!aug) {  // (the pivot chain's copy of tile (0, 0) leaves Kc and D to the tile's owner)
+      acc[r] = gather_k<DERIV, GATHER>(F, i, J * 32 + q_col(wc, lane), !master);
       continue;
     }
-    if (GATHER) {
-      const int u = F.cid[o];
-      double kv, dv;
-      if (u >= 0) {
-        kv = F.kval[u];
-        if (i == j) kv += F.jitter;
-        dv = F.dval[u];
-        if (DERIV == 1 && !(F.x[i] - F.x[j] >= 0.0)) dv = -dv;  // JAX abs'(0) = +1
-      } else {
-        kv = (i == j) ? 1.0 : 0.0;
-        dv = 0.0;
-      }
-      if (!master) {
-        if (F.Kc) F.Kc[o] = kv;
-        if (DERIV && F.D) F.D[o] = dv;
-      }
-      acc[r] = kv;
-    } else {
-      acc[r] = F.X[o];
-    }
+    // B_u[i][j'] or D^T[i][j'] = D[j'][i] (j' = column inside the part)
+    const int jl = ja * 32 + q_col(wc, lane);
+    if (ja < F.tu)
+      acc[r] = F.bu_t ? F.Bu[(size_t)(jl) * F.ldbu + i] : F.Bu[(size_t)i * F.ldbu + jl];
+    else
+      acc[r] = gather_d<DERIV, GATHER>(F, jl - 32 * F.tu, i);
   }
   auto publish_tile = [&](void) {  // panel tile (I, J) <- acc, then its flag
 #pragma unroll
-    for (int r = 0; r < 4; ++r) st_sc1(panel_ptr(I, 16 * wr + (lane >> 4) + 4 * r, 16 * wc + (lane & 15)), acc[r]);
+    for (int r = 0; r < 4; ++r) st_sc1(panel_ptr(I, q_row(wr, lane, r), q_col(wc, lane)), acc[r]);
     signal_flag(panel_rdy + I * TC + J);
   };
   // the pivot chain's inputs of hop kk (after sweep kk-1): panel tile (kk, kk+1) and diagonal
@@ -759,20 +801,10 @@ __global__ __launch_bounds__(256, 2) void chain_kernel(ChainBatch b) {
     double* slot = F.la ? gran3_at(F, kk, which, 0) : gran_at(F, kk, which, 0);
 #pragma unroll
     for (int r = 0; r < 4; ++r)
-      st_sc1(slot + (16 * wr + (lane >> 4) + 4 * r) * 32 + 16 * wc + (lane & 15), acc[r]);
+      st_sc1(slot + q_elem(wr, wc, lane, r), acc[r]);
   };
   // K's element (i, j) as the gather above forms it (the pivot chain's hop-0 tiles)
-  auto k_at = [&](int i, int j) -> double {
-    const size_t o = (size_t)i * p + j;
-    if (GATHER) {
-      const int u = F.cid[o];
-      if (u < 0) return (i == j) ? 1.0 : 0.0;
-      double kv = F.kval[u];
-      if (i == j) kv += F.jitter;
-      return kv;
-    }
-    return F.X[o];
-  };
+  auto k_at = [&](int i, int j) -> double { return gather_k<DERIV, GATHER>(F, i, j, false); };
   const bool trm = t == 0 && m == 0;  // probes (gpk_trace.h): factor 0's pivot owners
   if (master) {
     // (a tile workgroup's sL and sXI are free here: the second L^{-1} and panel buffers)
@@ -862,18 +894,7 @@ __global__ __launch_bounds__(256, 2) void chain_kernel(ChainBatch b) {
     if (needI) store_quad(sXI, SB, wr, wc, lane, vi);
     if (needJ) store_quad(sXJ, SB, wr, wc, lane, vj);
     __syncthreads();
-    d4 prod = {0.0, 0.0, 0.0, 0.0};
-    if (I == k && J == k) {
-      prod = mma_t(sL, 1, SA, sL, SA, 1, wr, wc, lane, prod);   // L^{-T} L^{-1}
-      acc = -prod;
-    } else if (I == k) {
-      acc = mma_t(sL, 1, SA, sVJ, SB, 1, wr, wc, lane, prod);  // L^{-T} V_J
-    } else if (J == k) {
-      acc = mma_t(sXI, 1, SB, sL, SA, 1, wr, wc, lane, prod);  // V_I^T L^{-1}
-    } else {
-      prod = mma_t(sXI, 1, SB, sVJ, SB, 1, wr, wc, lane, prod); // V_I^T V_J
-      acc = acc - prod;
-    }
+    acc = sweep_update_lds(I == k, J == k, sL, sXI, sVJ, wr, wc, lane, acc);
     // panel of sweep k + 1 (the diagonal tile's panel slot is the pivot chain's: nobody reads
     // a (k, k) panel tile)
     chain_inputs(k + 1);  // tiles (k+1, k+2), (k+2, k+2) after sweep k: pivot k+2's inputs
@@ -884,6 +905,8 @@ __global__ __launch_bounds__(256, 2) void chain_kernel(ChainBatch b) {
   if (aug && !master) {  // upper-right block: +K^{-1} B (B_u part possibly stored transposed)
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
+      // (q_row / q_col written out: called here they cost chain_kernel 4 VGPRs, 250 -> 254, which
+      // <0, false> does not have -- see DESIGN section 5)
       const int i = I * 32 + 16 * wr + (lane >> 4) + 4 * r, jl = ja * 32 + 16 * wc + (lane & 15);
       if (ja < F.tu) {
         if (F.ou_t) F.Ou[(size_t)jl * F.ldou + i] = acc[r];
@@ -896,7 +919,7 @@ __global__ __launch_bounds__(256, 2) void chain_kernel(ChainBatch b) {
   // K^{-1} = -X after the last sweep
 #pragma unroll
   for (int r = 0; r < 4 && !aug && !master; ++r) {
-    const int row = 16 * wr + (lane >> 4) + 4 * r, col = 16 * wc + (lane & 15);
+    const int row = q_row(wr, lane, r), col = q_col(wc, lane);
     const double y = -acc[r];
     F.X[(size_t)(I * 32 + row) * p + J * 32 + col] = y;
     if (I == J && row == col) pv[row] = (I * 32 + row < F.n) ? y : 0.0;
@@ -943,18 +966,6 @@ __global__ __launch_bounds__(256, 2) void chain_kernel(ChainBatch b) {
 // triangles at the end.  V tiles are XOR-swizzled in LDS (element (k, j) at 32k + (j ^ 16(k&1)):
 // conflict-free fragment reads without padding), so the workgroup needs 42 KB.
 __device__ __forceinline__ int vsw(int k, int j) { return 32 * k + (j ^ ((k & 1) << 4)); }
-
-// acc += A B over one 32-deep product, this wave's quadrant; fa(i, k), fb(k, j) give the operands
-template <class FA, class FB>
-__device__ __forceinline__ d4 mma_f(FA fa, FB fb, int wr, int wc, int lane, d4 acc) {
-  const int li = lane & 15, lk = lane >> 4;
-#pragma unroll
-  for (int kk = 0; kk < 8; ++kk) {
-    const int k = 4 * kk + lk;
-    acc = __builtin_amdgcn_mfma_f64_16x16x4f64(fa(16 * wr + li, k), fb(k, 16 * wc + li), acc, 0, 0, 0);
-  }
-  return acc;
-}
 
 // slot s of a macro-tile workgroup: s < 4 the column pair c0 (rows 2R + (s >> 1), column
 // 2 c0 + (s & 1)), s = 4..6 the diagonal block (2R,2R), (2R+1,2R), (2R+1,2R+1)
@@ -1392,34 +1403,26 @@ __global__ __launch_bounds__(256, 2) void chain_multi_kernel(ChainBatch b) {
   }
 }
 
-// Workgroups of chain_kernel<DERIV, GATHER> the current device keeps resident at once:
-// occupancy per CU (its VGPR / LDS footprint) x the CUs this device (or partition) exposes.
-int spd_chain_capacity(int deriv, bool gather) {
-  int dev = 0, cus = 0, per = 0;
-  if (hipGetDevice(&dev) != hipSuccess) return 0;
-  if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return 0;
-  hipError_t e;
-  if (!gather)
-    e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, chain_kernel<0, false>, 256, 0);
-  else if (deriv == 1)
-    e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, chain_kernel<1, true>, 256, 0);
-  else
-    e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, chain_kernel<2, true>, 256, 0);
-  return e == hipSuccess ? per * cus : 0;
+// The (deriv, gather) instance of chain_kernel / chain_multi_kernel (multi): the one dispatch of
+// both launches and both capacity queries.
+using ChainKernel = void (*)(ChainBatch);
+static ChainKernel chain_instance(bool multi, int deriv, bool gather) {
+  if (!gather) return multi ? chain_multi_kernel<0, false> : chain_kernel<0, false>;
+  if (deriv == 1) return multi ? chain_multi_kernel<1, true> : chain_kernel<1, true>;
+  return multi ? chain_multi_kernel<2, true> : chain_kernel<2, true>;
 }
 
-int spd_chain_multi_capacity(int deriv, bool gather) {
+// Workgroups of a chain kernel instance the current device keeps resident at once:
+// occupancy per CU (its VGPR / LDS footprint) x the CUs this device (or partition) exposes.
+static int chain_capacity(ChainKernel kern) {
   int dev = 0, cus = 0, per = 0;
   if (hipGetDevice(&dev) != hipSuccess) return 0;
   if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return 0;
-  hipError_t e;
-  if (!gather)
-    e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, chain_multi_kernel<0, false>, 256, 0);
-  else if (deriv == 1)
-    e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, chain_multi_kernel<1, true>, 256, 0);
-  else
-    e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, chain_multi_kernel<2, true>, 256, 0);
-  return e == hipSuccess ? per * cus : 0;
+  return hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, kern, 256, 0) == hipSuccess ? per * cus : 0;
+}
+int spd_chain_capacity(int deriv, bool gather) { return chain_capacity(chain_instance(false, deriv, gather)); }
+int spd_chain_multi_capacity(int deriv, bool gather) {
+  return chain_capacity(chain_instance(true, deriv, gather));
 }
 
 int spd_chain_multi_blocks(const int* p, int nmat) {
@@ -1435,16 +1438,17 @@ int spd_chain_blocks(const int* p, int nmat, bool aug) {
   return blocks;
 }
 
-hipError_t launch_spd_chain(const ChainArgs* a, int nmat, int deriv, hipStream_t s,
-                            const PrepArgs* prep, int q) {
-  ChainBatch b{};
+// The launch's batch: every factor's ChainArgs copied into ChainFactor's own layout (kept: the
+// kernels' argument layout is part of what C2's speed was measured with), T and piv_off derived,
+// and the step constants.
+// False when the factors mix gather and read mode or lack the pivot chain's input slots; each
+// launcher adds its own argument checks.
+static bool chain_batch(ChainBatch& b, const ChainArgs* a, int nmat, const PrepArgs* prep, int q) {
   b.nmat = nmat;
   if (prep) {
     b.prep = *prep;
     b.q = q;
   }
-  int Tmax = 0;
-  bool gather = a[0].cid != nullptr;
   for (int m = 0; m < nmat; ++m) {
     ChainFactor& f = b.f[m];
     f.X = a[m].X; f.PB = a[m].PB; f.piv = a[m].piv; f.ldet = a[m].ldet; f.pst = a[m].pst;
@@ -1454,40 +1458,41 @@ hipError_t launch_spd_chain(const ChainArgs* a, int nmat, int deriv, hipStream_t
     f.tu = a[m].tu; f.td = a[m].td; f.Bu = a[m].Bu; f.ldbu = a[m].ldbu; f.bu_t = a[m].bu_t;
     f.Ou = a[m].Ou; f.ldou = a[m].ldou; f.ou_t = a[m].ou_t; f.Od = a[m].Od; f.ldod = a[m].ldod;
     f.PBa = a[m].PBa; f.ldpba = a[m].ldpba;
-    f.gran = a[m].gran; f.piv_off = f.T * (f.T + f.tu + f.td); f.la = a[m].lookahead;
+    f.gran = a[m].gran; f.la = a[m].lookahead;
     f.PB2 = a[m].PB2; f.epoch = a[m].epoch;  // (both null: L^{-1} hand-off by flag + load)
-    if ((a[m].cid != nullptr) != gather || !f.gran || !f.PB2 != !f.epoch) return hipErrorInvalidValue;
-    Tmax = std::max(Tmax, f.T * (f.T + f.tu + f.td) + 1);  // + the pivot chain's workgroup
+    f.piv_off = f.T * (f.T + f.tu + f.td);
+    if ((f.cid != nullptr) != (a[0].cid != nullptr) || !f.gran) return false;
   }
-  dim3 grid(Tmax, nmat + (prep ? 1 : 0));
-  if (!gather)
-    hipLaunchKernelGGL((chain_kernel<0, false>), grid, dim3(256), 0, s, b);
-  else if (deriv == 1)
-    hipLaunchKernelGGL((chain_kernel<1, true>), grid, dim3(256), 0, s, b);
-  else
-    hipLaunchKernelGGL((chain_kernel<2, true>), grid, dim3(256), 0, s, b);
+  return true;
+}
+static hipError_t chain_launch(bool multi, const ChainBatch& b, int width, int deriv, bool prep,
+                               hipStream_t s) {
+  const dim3 grid(width, b.nmat + (prep ? 1 : 0));
+  hipLaunchKernelGGL(chain_instance(multi, deriv, b.f[0].cid != nullptr), grid, dim3(256), 0, s, b);
   return hipGetLastError();
+}
+
+hipError_t launch_spd_chain(const ChainArgs* a, int nmat, int deriv, hipStream_t s,
+                            const PrepArgs* prep, int q) {
+  ChainBatch b{};
+  if (!chain_batch(b, a, nmat, prep, q)) return hipErrorInvalidValue;
+  int Tmax = 0;
+  for (int m = 0; m < nmat; ++m) {
+    const ChainFactor& f = b.f[m];
+    if (!f.PB2 != !f.epoch) return hipErrorInvalidValue;
+    Tmax = std::max(Tmax, f.piv_off + 1);  // + the pivot chain's workgroup
+  }
+  return chain_launch(false, b, Tmax, deriv, prep != nullptr, s);
 }
 
 hipError_t launch_spd_chain_multi(const ChainArgs* a, int nmat, int deriv, hipStream_t s,
                                   const PrepArgs* prep, int q) {
   ChainBatch b{};
-  b.nmat = nmat;
-  if (prep) {
-    b.prep = *prep;
-    b.q = q;
-  }
+  if (!chain_batch(b, a, nmat, prep, q)) return hipErrorInvalidValue;
   int wmax = 0;
-  const bool gather = a[0].cid != nullptr;
   for (int m = 0; m < nmat; ++m) {
-    ChainFactor& f = b.f[m];
-    f.X = a[m].X; f.PB = a[m].PB; f.piv = a[m].piv; f.ldet = a[m].ldet; f.pst = a[m].pst;
-    f.status = a[m].status; f.flags = a[m].flags; f.p = a[m].p; f.n = a[m].n; f.T = a[m].p / 32;
-    f.cid = a[m].cid; f.kval = a[m].kval; f.dval = a[m].dval; f.x = a[m].x; f.jitter = a[m].jitter;
-    f.Kc = a[m].Kc; f.D = a[m].D;
-    f.gran = a[m].gran; f.piv_off = f.T * f.T; f.PB2 = a[m].PB2; f.epoch = a[m].epoch;
-    if ((a[m].cid != nullptr) != gather || a[m].tu || a[m].td || !f.gran || !f.PB2 || !f.epoch)
-      return hipErrorInvalidValue;
+    const ChainFactor& f = b.f[m];
+    if (f.tu || f.td || !f.PB2 || !f.epoch) return hipErrorInvalidValue;
     wmax = std::max(wmax, multi_workgroups(f.T));
   }
   // one factor: the pivot chain in the middle of the CUs that hold a single workgroup (the
@@ -1499,26 +1504,26 @@ hipError_t launch_spd_chain_multi(const ChainArgs* a, int nmat, int deriv, hipSt
       hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess &&
       wmax > cus && wmax < 2 * cus)
     b.mpos = wmax - cus + (2 * cus - wmax) / 2;
-  dim3 grid(wmax, nmat + (prep ? 1 : 0));
-  if (!gather)
-    hipLaunchKernelGGL((chain_multi_kernel<0, false>), grid, dim3(256), 0, s, b);
-  else if (deriv == 1)
-    hipLaunchKernelGGL((chain_multi_kernel<1, true>), grid, dim3(256), 0, s, b);
-  else
-    hipLaunchKernelGGL((chain_multi_kernel<2, true>), grid, dim3(256), 0, s, b);
-  return hipGetLastError();
+  return chain_launch(true, b, wmax, deriv, prep != nullptr, s);
 }
 
-// One launch of the inverse: stage -1 = pivot_init, stage k >= 0 = sweep k (bench/profiling).
-hipError_t launch_spd_stage(SpdArgs* a, int nmat, int stage, hipStream_t s) {
+// The sweep form's batch; Tmax: the largest factor's tiles per dimension
+static SpdBatch spd_batch(const SpdArgs* a, int nmat, int& Tmax) {
   SpdBatch b{};
-  int Tmax = 0;
+  Tmax = 0;
   for (int m = 0; m < nmat; ++m) {
     b.X[m] = a[m].X; b.Y[m] = a[m].Y; b.p[m] = a[m].p; b.T[m] = a[m].p / 32;
     b.piv[m] = a[m].piv; b.ldet[m] = a[m].ldet; b.status[m] = a[m].status;
     b.pst[m] = a[m].pst; b.n[m] = a[m].n;
-    if (b.T[m] > Tmax) Tmax = b.T[m];
+    Tmax = std::max(Tmax, b.T[m]);
   }
+  return b;
+}
+
+// One launch of the inverse: stage -1 = pivot_init, stage k >= 0 = sweep k (bench/profiling).
+hipError_t launch_spd_stage(SpdArgs* a, int nmat, int stage, hipStream_t s) {
+  int Tmax;
+  const SpdBatch b = spd_batch(a, nmat, Tmax);
   if (stage < 0)
     hipLaunchKernelGGL(pivot_init_kernel, dim3(nmat), dim3(256), 0, s, b);
   else
@@ -1528,22 +1533,10 @@ hipError_t launch_spd_stage(SpdArgs* a, int nmat, int stage, hipStream_t s) {
 
 hipError_t launch_spd_inverse(SpdArgs* a, int nmat, double** final_out, hipStream_t s,
                               bool pivot0_done) {
-  SpdBatch b{};
-  int Tmax = 0;
-  for (int m = 0; m < nmat; ++m) {
-    b.X[m] = a[m].X;
-    b.Y[m] = a[m].Y;
-    b.p[m] = a[m].p;
-    b.T[m] = a[m].p / 32;
-    b.piv[m] = a[m].piv;
-    b.ldet[m] = a[m].ldet;
-    b.pst[m] = a[m].pst;
-    b.n[m] = a[m].n;
-    b.status[m] = a[m].status;
-    if (b.T[m] > Tmax) Tmax = b.T[m];
-    // sweep k reads (k even ? X : Y) and writes the other; T sweeps end in:
-    final_out[m] = (b.T[m] & 1) ? a[m].Y : a[m].X;
-  }
+  int Tmax;
+  const SpdBatch b = spd_batch(a, nmat, Tmax);
+  // sweep k reads (k even ? X : Y) and writes the other; T sweeps end in:
+  for (int m = 0; m < nmat; ++m) final_out[m] = (b.T[m] & 1) ? a[m].Y : a[m].X;
   if (!pivot0_done) hipLaunchKernelGGL(pivot_init_kernel, dim3(nmat), dim3(256), 0, s, b);
   for (int k = 0; k < Tmax; ++k)
     hipLaunchKernelGGL(sweep_kernel, dim3(nmat, Tmax * Tmax), dim3(256), 0, s, b, k);
