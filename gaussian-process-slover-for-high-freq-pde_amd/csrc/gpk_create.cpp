@@ -209,10 +209,10 @@ static int allocate_buffers(gpk_handle* h, const gpk_problem* p) {
     A_(h->pst[a], 2);
     A_(h->aflag[a], 4 + P / 32);  // + the 128-wide update's per-sweep panel tickets
     if (h->bigspd) A_(h->Zp[a], (size_t)3 * 128 * P);
-    if (h->bigspd && h->bigwide && !(p->flags & GPK_FLAG_ONE_SWEEP_UPDATE)) {
+    if (h->bigspd && h->bigwide) {  // (fill_spd: SpdArgs::sched_paired names the same table)
       const int T2 = (int)((P + 127) / 128);
       std::vector<unsigned> tab;
-      wide_schedule(T2, true, tab);
+      wide_schedule(T2, !(p->flags & GPK_FLAG_ONE_SWEEP_UPDATE), tab);
       A_(h->wsched[a], tab.size());
       if (hipMemcpyAsync(h->wsched[a], tab.data(), tab.size() * sizeof(unsigned), hipMemcpyHostToDevice, h->s) != hipSuccess ||
           hipStreamSynchronize(h->s) != hipSuccess)

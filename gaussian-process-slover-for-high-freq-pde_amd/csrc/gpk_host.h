@@ -131,7 +131,7 @@ struct gpk_handle {
   // (GemvDesc::cid), so the inverse launch's gather writes neither matrix (64 MB at C2)
   bool cls_gemv = false;
   double* Zp[2] = {};                 // ... its panel buffers [3][128][P] (by sweep mod 3)
-  unsigned* wsched[2] = {};           // ... its two-sweep update schedule (wide_schedule)
+  unsigned* wsched[2] = {};           // ... its update schedule (wide_schedule; unpaired under GPK_FLAG_ONE_SWEEP_UPDATE)
   bool chain = false;                 // small factors: persistent one-launch inverse (chain_kernel)
   bool chain_aug = false;             // ... which also solves A, Bt^T and K^{-1} D^T (2D, unsharded)
   unsigned int* cflags[2] = {};       // its hand-off flags [T*(T+taug) + 2T + 1] per factor

@@ -226,9 +226,10 @@ struct SpdArgs {
   int no_quarters; // 128-wide update: keep the last round in whole tiles (tests, GPK_FLAG_NO_QUARTER_TILES)
   int qfirst;      // 128-wide update: quarter items before whole tiles (GPK_FLAG_NO_QUARTER_FIRST: after)
   double* Z;       // large path: panel buffers [3][128][p] by sweep mod 3 (nullable: Y)
-  // 128-wide update schedule (wide_schedule): per sweep, the tiles the launch updates and the
-  // sweeps (1 or 2) each applies; null: every tile every sweep (the one-sweep form)
+  // 128-wide update schedule (wide_schedule's table on the device): per sweep, the tiles the
+  // launch updates and the sweeps (1 or 2) each applies.  Never null for a wide factor; unused at 64.
   const unsigned* sched;
+  int sched_paired;  // which table sched is: wide_schedule(T2, paired); 0 = GPK_FLAG_ONE_SWEEP_UPDATE
 };
 // Two-sweep schedule of the 128-wide update (spdinv_big.hip): per sweep k of a factor with T2
 // 128-tiles per dimension, row k of tab (stride wide_sched_stride(T2)) holds [0] the tile count,

@@ -75,6 +75,7 @@ void fill_spd(gpk_handle* h, SpdArgs* sa) {
     sa[a].qfirst = (h->prob.flags & GPK_FLAG_NO_QUARTER_FIRST) ? 0 : 1;
     sa[a].Z = h->Zp[a];
     sa[a].sched = h->wsched[a];
+    sa[a].sched_paired = (h->prob.flags & GPK_FLAG_ONE_SWEEP_UPDATE) ? 0 : 1;
   }
 }
 

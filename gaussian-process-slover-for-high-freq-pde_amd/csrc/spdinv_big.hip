@@ -415,31 +415,18 @@ __device__ __forceinline__ void tile_of(int lin, int& I, int& J) {
   J = lin - i * (i + 1) / 2;
 }
 
-// The tile list of one update launch: the nh tiles of the next pivot block (hand-off tiles) sit
-// at the first position of the runs of workgroups 0, 1, 2 (done first, by different workgroups),
-// every other lower tile follows in row-major order.
+// The tile list of one 64-wide update launch: the next pivot's tile (k + 1, k + 1) -- the hand-off
+// tile -- sits at position 0 (workgroup 0 does it first), every other lower tile follows in
+// row-major order.
 struct TileList {
-  int nt, nh;
-  int hlin[3];  // hand-off tiles' row-major lower indices, ascending
-  int hpos[3];  // their positions in the list
+  int nt;
+  int hlin;  // the hand-off tile's row-major lower index; -1: none (the last sweep)
   __device__ void at(int pos, int& I, int& J) const {
-    for (int h = 0; h < nh; ++h)
-      if (pos == hpos[h]) {
-        tile_of(hlin[h], I, J);
-        return;
-      }
     int lin = pos;
-    for (int h = 0; h < nh; ++h)
-      if (hpos[h] < pos) --lin;
-    for (int h = 0; h < nh; ++h)
-      if (lin >= hlin[h]) ++lin;
+    if (hlin >= 0) lin = pos == 0 ? hlin : pos - 1 < hlin ? pos - 1 : pos;
     tile_of(lin, I, J);
   }
-  __device__ bool handoff(int pos) const {
-    for (int h = 0; h < nh; ++h)
-      if (pos == hpos[h]) return true;
-    return false;
-  }
+  __device__ bool handoff(int pos) const { return hlin >= 0 && pos == 0; }
 };
 
 // Z panel block in LDS: 64 rows (k) x 64 columns (i), XOR-swizzled instead of padded: element
@@ -466,55 +453,46 @@ __device__ __forceinline__ void zblock_store(const double (&v)[16], double* sZ, 
 constexpr int UPD_LDS = 2 * 64 * 64;  // sZI, sZJ (doubles); the last sweep's mirror stage reuses them
 constexpr int BIG_LDS = UPD_LDS > PIVOT_LDS ? UPD_LDS : PIVOT_LDS;
 
-// One sweep's update of every lower tile (+ the next pivot block, + the final sign flip / mirror).
-// Persistent: G tile workgroups per factor each take a contiguous run of the tile list; a tile
-// is R units (one per 64 rows of the panel): Z_I and Z_J of the unit sit in LDS, the next unit's
-// (and the next tile's X values) are fetched into registers while the current unit's MFMAs run.
-// At R = 1 a run stays within a block row mostly and Z_I is staged once per row.
-// blockIdx.x: 0 = tile workgroup 0, 1 = the pivot workgroup, 2.. = tile workgroups 1..  The pivot
-// workgroup waits for the hand-off tiles only; their workgroups never wait (no deadlock whatever
-// the residency).  LDS 67 KB and <= 256 VGPRs: two workgroups per CU.
-template <int R>
+// One 64-wide sweep's update of every lower tile (+ the next pivot block, + the final sign flip /
+// mirror).  Persistent: G tile workgroups per factor each take a contiguous run of the tile list,
+// one tile per iteration: Z_I and Z_J of the tile sit in LDS, the next tile's Z_J and X values
+// are fetched into registers while the current tile's MFMAs run.  A run stays within a block row
+// mostly, so Z_I is staged once per row (and per tile in the last sweep, whose mirror stage
+// overwrites it).
+// blockIdx.x: 0 = tile workgroup 0, 1 = the pivot workgroup, 2.. = tile workgroups 1.., then the
+// next sweep's panel workgroups.  The pivot workgroup waits for the hand-off tile only; its
+// workgroup never waits (no deadlock whatever the residency).  LDS 64 KB and <= 256 VGPRs: two
+// workgroups per CU.
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void big_update_kernel(BigSpdBatch b, int k, int skip_pivot) {
   const int m = blockIdx.y;
   const int p = b.p[m], T = b.T[m];
-  const int P0 = R * k;
-  if (P0 >= T) return;
-  const int nsw = (T + R - 1) / R;
-  const bool has_next = k + 1 < nsw;
+  if (k >= T) return;
+  const bool has_next = k + 1 < T;
   const bool last = !has_next;
+  const int Q = k + 1;
   TileList tl;
   tl.nt = T * (T + 1) / 2;
+  tl.hlin = has_next ? Q * (Q + 1) / 2 + Q : -1;
   const int G = min(tl.nt, b.G);
   const int chunk = (tl.nt + G - 1) / G;
-  tl.nh = 0;
-  if (has_next) {
-    const int Q0 = R * (k + 1);
-    tl.hlin[tl.nh++] = Q0 * (Q0 + 1) / 2 + Q0;
-    if (R == 2 && Q0 + 1 < T) {
-      tl.hlin[tl.nh++] = (Q0 + 1) * (Q0 + 2) / 2 + Q0;
-      tl.hlin[tl.nh++] = (Q0 + 1) * (Q0 + 2) / 2 + Q0 + 1;
-    }
-    for (int h = 0; h < tl.nh; ++h) tl.hpos[h] = h * chunk;
-  }
   const int x = blockIdx.x;
   __shared__ double sm[BIG_LDS];
   if (x > G) {  // the next sweep's panel (fused_panel); T - 1 panel-row tiles per sweep
     const int pj = x - G - 1;
-    if (!has_next || skip_pivot || pj >= T * R) return;
-    fused_panel<R>(b, m, k, pj, (unsigned)(T - 1), sm);
+    if (!has_next || skip_pivot || pj >= T) return;
+    fused_panel<1>(b, m, k, pj, (unsigned)(T - 1), sm);
     return;
   }
   if (x == 1) {
     if (!has_next || skip_pivot) return;
     if (threadIdx.x == 0) {  // pivot workgroup for block k+1
-      (void)spin_until_ge<2>(b.flag[m], (unsigned)tl.nh, b.status[m]);  // bounded (status bit 2)
+      (void)spin_until_ge<2>(b.flag[m], 1u, b.status[m]);  // bounded (status bit 2)
       *b.flag[m] = 0u;  // re-arm (next user: the next sweep's update launch)
       __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     }
     __syncthreads();
-    pivot_block<R>(b, m, k + 1, sm);
+    pivot_block<1>(b, m, Q, sm);
     release_add(b.flag[m] + 1, 1u);  // L^{-1} of pivot k + 1 ready (fused_panel)
     return;
   }
@@ -523,23 +501,21 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   const int pos0 = g * chunk, pos1 = min(tl.nt, pos0 + chunk);
   if (pos0 >= pos1) return;
   double* X = b.X[m];
-  const double* Z = zbuf<R>(b, m, k);
+  const double* Z = zbuf<1>(b, m, k);
   const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
   const int wr = wv >> 1, wc = wv & 1;
   const int li = lane & 15, lk = lane >> 4;
-  const int wK = min(BW * R, p - BW * P0);  // sweep width
-  const int nhalf = (wK + BW - 1) / BW;     // units per tile (<= R)
+  const int wK = min(BW, p - BW * k);  // sweep width (32 or 64)
   double* sZI = sm;
   double* sZJ = sm + 64 * 64;
   double* sT = sm;  // [64][SS] transpose stage of the last sweep's mirror (after a barrier)
   const double fin = last ? -1.0 : 1.0;
-  auto inP = [&](int I_) { return I_ >= P0 && I_ < P0 + R; };
 
-  // X tile (I, J) in this wave's MFMA layout; zero base for the swept row / column blocks.
+  // X tile (I, J) in this wave's MFMA layout; zero base for the swept row / column block.
   // Unconditional clamped loads times a 0/1 factor (a guarded load would become an exec-mask
   // branch); rows / columns past p are never stored.
   auto xo_fetch = [&](double (&xv)[2][2][4], int I_, int J_) {
-    const double f = (inP(I_) || inP(J_)) ? 0.0 : 1.0;
+    const double f = (I_ == k || J_ == k) ? 0.0 : 1.0;
 #pragma unroll
     for (int bi = 0; bi < 2; ++bi)
 #pragma unroll
@@ -551,7 +527,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
           xv[bi][bj][r] = X[(size_t)gi * p + gj] * f;
         }
   };
-  int I, J, h = 0, pos = pos0;
+  int I, J, pos = pos0;
   tl.at(pos0, I, J);
   double xo[2][2][4], xn[2][2][4];
   xo_fetch(xn, I, J);
@@ -573,28 +549,20 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
       for (int r = 0; r < 4; ++r) xo[bi][bj][r] = xn[bi][bj][r];
     }
   for (;;) {
-    // the next unit: its panel blocks (and, on a tile change, its X values) in flight under
-    // this unit's MFMAs
-    int hn = h + 1, posn = pos, In = I, Jn = J;
-    if (hn >= nhalf) {
-      hn = 0;
-      posn = pos + 1;
-    }
-    const bool more = posn < pos1;
-    const bool newtile = hn == 0;
+    // the next tile: its Z_J, its X values and -- on a row change, or in the last sweep, whose
+    // mirror stage overwrites it -- its Z_I, in flight under this tile's MFMAs
+    const bool more = pos + 1 < pos1;
+    int In = I, Jn = J;
     double vj[16], vi[16];
     bool ldI = false;
     if (more) {
-      if (newtile) tl.at(posn, In, Jn);
-      // Z_I stays staged along a block row (R = 1), except in the last sweep, whose mirror
-      // stage overwrites it
-      ldI = R > 1 || In != I || last;
-      zblock_fetch(vj, Z, p, BW * hn, BW * Jn, wK, t);
-      if (ldI) zblock_fetch(vi, Z, p, BW * hn, BW * In, wK, t);
-      if (newtile) xo_fetch(xn, In, Jn);
+      tl.at(pos + 1, In, Jn);
+      ldI = In != I || last;
+      zblock_fetch(vj, Z, p, 0, BW * Jn, wK, t);
+      if (ldI) zblock_fetch(vi, Z, p, 0, BW * In, wK, t);
+      xo_fetch(xn, In, Jn);
     }
-    const int kw = min(BW, wK - BW * h);
-    for (int k0 = 0; k0 < kw; k0 += 32) {
+    for (int k0 = 0; k0 < wK; k0 += 32) {
 #pragma unroll
       for (int kk = 0; kk < 8; ++kk) {
         const int kr = k0 + 4 * kk + lk;
@@ -611,14 +579,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
             acc[bi][bj] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[bi], bb[bj], acc[bi][bj], 0, 0, 0);
       }
     }
-    if (h == nhalf - 1) {  // the tile is complete: epilogue
+    {  // the tile's epilogue
       const int I0 = BW * I, J0 = BW * J;
-      const bool inPi = inP(I), inPj = inP(J);
-      const double sgn = ((inPi != inPj) ? -1.0 : 1.0) * fin;
-      // the next pivot block's tiles go to the pivot workgroup: stored write-through (sc1), so
+      const double sgn = (((I == k) != (J == k)) ? -1.0 : 1.0) * fin;
+      // the next pivot block's tile goes to the pivot workgroup: stored write-through (sc1), so
       // the hand-off needs no L2 write-back (release fence) -- drain, barrier, one counter add
       // (MI355X_MICROARCH §inter-workgroup visibility, "publish-large")
-      const bool handoff = has_next && tl.handoff(pos);
+      const bool handoff = tl.handoff(pos);
       double mx = 0.0;
       double vals[2][2][4];
 #pragma unroll
@@ -643,7 +610,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
         if (t == 0) atomicAdd(b.flag[m], 1u);
-      } else if (has_next && (I == R * (k + 1) || J == R * (k + 1))) {  // (R = 1) next panel row
+      } else if (has_next && (I == Q || J == Q)) {  // next panel row
         release_add(b.flag[m] + 2, 1u);
       }
       if (last && I == J) {  // refinement gate: max_i (K^{-1})_ii
@@ -680,18 +647,15 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     if (!more) break;
     zblock_store(vj, sZJ, t);
     if (ldI) zblock_store(vi, sZI, t);
-    if (newtile) {
 #pragma unroll
-      for (int bi = 0; bi < 2; ++bi)
+    for (int bi = 0; bi < 2; ++bi)
 #pragma unroll
-        for (int bj = 0; bj < 2; ++bj)
+      for (int bj = 0; bj < 2; ++bj)
 #pragma unroll
-          for (int r = 0; r < 4; ++r) xo[bi][bj][r] = xn[bi][bj][r];
-    }
+        for (int r = 0; r < 4; ++r) xo[bi][bj][r] = xn[bi][bj][r];
     I = In;
     J = Jn;
-    h = hn;
-    pos = posn;
+    ++pos;
     __syncthreads();
   }
 }
@@ -706,43 +670,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 // others, then factors it in place (pivot_blk: blocked Cholesky) while the other tiles are
 // updated -- no hand-off, no workgroup waits on another.  The last sweep flips the sign and
 // publishes max diag K^{-1}; big_mirror_kernel then fills the upper triangle.
+// Which tiles a launch updates, in which order, and with which coefficients comes from the
+// factor's schedule table alone (b.sched: wide_schedule, paired or not; never null here).
 constexpr int WT = 128;
 // the product loops' staging buffers (whole tiles: gemm_tile_dev.h; quarter tiles: [k][64] rows at
 // gemm_huge_dev.h's stride)
 constexpr int WIDE_LDS = tile::LDS_DOUBLES > 2 * 2 * huge::KS * huge::S ? tile::LDS_DOUBLES : 2 * 2 * huge::KS * huge::S;
 static_assert(WIDE_LDS >= PIVOT_LDS, "the pivot reuses the staging LDS");
-
-// position pos of sweep k's tile list of a factor with T2 128-tiles per dimension, with a next
-// pivot Q = k + 1: the T2 - 1 tiles the next panel reads first -- row Q left of the diagonal,
-// then column Q below it (round 0 of the factor's first XCD slot run: the panel's wait for its
-// row ends after one tile time instead of the last round) -- then every other lower tile in
-// row-major order; (Q, Q) is the pivot workgroup's, not listed.
-__device__ __forceinline__ void wide_tile_at(int pos, int T2, int Q, bool has_next, int& I, int& J) {
-  if (!has_next) {
-    tile_of(pos, I, J);
-    return;
-  }
-  if (pos < Q) {
-    I = Q;
-    J = pos;
-    return;
-  }
-  if (pos < T2 - 1) {
-    I = pos + 1;
-    J = Q;
-    return;
-  }
-  const int r = pos - (T2 - 1);
-  int i, j;
-  tile_of(r, i, j);
-  if (r < Q * (Q + 1) / 2) {  // rows above Q: row-major as they are
-    I = i;
-    J = j;
-    return;
-  }
-  I = i + 1;  // rows below Q hold I tiles each once column Q is taken out
-  J = j < Q ? j : j + 1;
-}
 
 __global__ __launch_bounds__(256, 2) void wide_update_kernel(BigSpdBatch b, int k, int skip_pivot, int gx,
                                                           int per_xcd, int nx, int first) {
@@ -809,7 +743,7 @@ __global__ __launch_bounds__(256, 2) void wide_update_kernel(BigSpdBatch b, int 
       const int T2 = (b.p[m] + WT - 1) / WT;
       if (k + 1 >= T2 || skip_pivot) return false;
       ti = tj = k + 1;
-      if (b.sched[m]) ent = b.sched[m][(size_t)k * b.sstride[m] + 1];
+      ent = b.sched[m][(size_t)k * b.sstride[m] + 1];
       return true;
     }
     int loc;
@@ -827,25 +761,12 @@ __global__ __launch_bounds__(256, 2) void wide_update_kernel(BigSpdBatch b, int 
     m = wi / gx;
     const int T2 = (b.p[m] + WT - 1) / WT;
     if (k >= T2) return false;
-    const bool has_next = k + 1 < T2;
-    const int nt = T2 * (T2 + 1) / 2;
-    const int Q = k + 1, qlin = Q * (Q + 1) / 2 + Q;
-    int lin = wi % gx;
-    if (b.sched[m]) {  // the two-sweep schedule's list of this sweep
-      const unsigned* row = b.sched[m] + (size_t)k * b.sstride[m];
-      if (lin >= (int)row[0]) return false;
-      ent = row[2 + lin];
-      ti = (int)((ent >> 8) & 0xffu);
-      tj = (int)(ent & 0xffu);
-      return true;
-    }
-    if (lin >= nt - (has_next ? 1 : 0)) return false;
-    if (has_next && !skip_pivot) {  // the next panel row's tiles first (wide_tile_at)
-      wide_tile_at(lin, T2, Q, true, ti, tj);
-      return true;
-    }
-    if (has_next && lin >= qlin) ++lin;  // (k+1, k+1) belongs to the pivot workgroup
-    tile_of(lin, ti, tj);
+    const int lin = wi % gx;
+    const unsigned* row = b.sched[m] + (size_t)k * b.sstride[m];  // the schedule's list of this sweep
+    if (lin >= (int)row[0]) return false;
+    ent = row[2 + lin];
+    ti = (int)((ent >> 8) & 0xffu);
+    tj = (int)(ent & 0xffu);
     return true;
   };
   constexpr int SZ = KS * S;
@@ -868,18 +789,15 @@ __global__ __launch_bounds__(256, 2) void wide_update_kernel(BigSpdBatch b, int 
     const double* Z = zbuf<2>(b, m, k);
     const int i0 = WT * ti + 64 * (qq >> 1), j0 = WT * tj + 64 * (qq & 1);
     const int wK = min(WT, p - WT * k);
-    const bool inPi = ti == k, inPj = tj == k;
-    const double sgn = ((inPi != inPj) ? -1.0 : 1.0) * (LAST ? -1.0 : 1.0);
     const int li = lane & 15, lk = lane >> 4;
     // schedule (as the whole tiles): v = c0 X + c1 Z_{k-1}^T Z_{k-1} + c2 Z_k^T Z_k
-    const bool sch = b.sched[m] != nullptr;
-    const bool two = sch && ((ent >> 16) & 1u);
+    const bool two = (ent >> 16) & 1u;
     auto cf = [](unsigned c) { return c == 0u ? 0.0 : c == 1u ? 1.0 : -1.0; };
     const double c0 = cf((ent >> 18) & 3u), c1 = cf((ent >> 20) & 3u), c2 = cf((ent >> 22) & 3u);
     const double* Zp = two ? zbuf<2>(b, m, k - 1) : Z;
     d4 acc[2][2];
     {
-      const double f = sch ? -c0 : ((inPi || inPj) ? 0.0 : 1.0);
+      const double f = -c0;
 #pragma unroll
       for (int bx = 0; bx < 2; ++bx)
 #pragma unroll
@@ -896,7 +814,7 @@ __global__ __launch_bounds__(256, 2) void wide_update_kernel(BigSpdBatch b, int 
     // K-step's loads in flight under the current one's MFMAs.  (All K-steps' loads up front --
     // one round trip per item -- measured slower: 121 vs 113 us per update launch.)
     // (two sweeps: K-steps [0, WT / KS) read panel k - 1 scaled by c1, the rest panel k by c2;
-    // the A operand is staged negated: acc = -(c0 X + ...), stored negated back by sgn below)
+    // the A operand is staged negated: acc = -(c0 X + ...), stored negated back below)
     const int nk1 = two ? WT / KS : 0;
     auto qfetch = [&](double2 (&ra)[2], double2 (&rb)[2], int kt) {
       const double* Zs = kt < nk1 ? Zp : Z;
@@ -909,7 +827,7 @@ __global__ __launch_bounds__(256, 2) void wide_update_kernel(BigSpdBatch b, int 
       }
     };
     auto qstore = [&](const double2 (&ra)[2], const double2 (&rb)[2], double* sA, double* sB, int kt) {
-      const double sa = sch ? (kt < nk1 ? -c1 : -c2) : -1.0;
+      const double sa = kt < nk1 ? -c1 : -c2;
 #pragma unroll
       for (int q = 0; q < 2; ++q) {
         const int e = t + 256 * q, kr = e >> 5, c = 2 * (e & 31);
@@ -957,7 +875,7 @@ __global__ __launch_bounds__(256, 2) void wide_update_kernel(BigSpdBatch b, int 
           const int row = i0 + 32 * wr + 16 * bx + lk + 4 * r;
           const int col = j0 + 32 * wc + 16 * by + li;
           if (row < p && col < p) {
-            const double v = sch ? -acc[bx][by][r] : sgn * acc[bx][by][r];
+            const double v = -acc[bx][by][r];
             X[(size_t)row * p + col] = v;
             if (LAST && row == col && row < b.n[m]) mx = fmax(mx, v);
           }
@@ -1006,29 +924,22 @@ __global__ __launch_bounds__(256, 2) void wide_update_kernel(BigSpdBatch b, int 
     const double* Z = zbuf<2>(b, m, k);
     const int i0 = WT * ti, j0 = WT * tj;
     const int wK = min(WT, p - WT * k);  // sweep width (a multiple of 32)
-    const bool inPi = ti == k, inPj = tj == k;
-    const double sgn = ((inPi != inPj) ? -1.0 : 1.0) * (LAST ? -1.0 : 1.0);
     // the workgroup's next item
     int m2 = 0, ti2 = 0, tj2 = 0, q2 = -1;
     unsigned ent2 = 0u;
     const bool next = tile_at(j + 1, m2, ti2, tj2, q2, ent2);
-    // The accumulators start at the tile's current values NEGATED (zero base in the swept blocks;
-    // clamped addresses: rows / columns past p are never stored) and the product is added; the
-    // store negates back: base - Z_I^T Z_J with the rounding of a subtraction (round-to-nearest
-    // commutes with negation), and no separate base registers.  The base loads are issued ahead
-    // of the product loop's first K-step.
-    // Two-sweep schedule (b.sched): new = c0 X + c1 Z_{k-1}^T Z_{k-1} + c2 Z_k^T Z_k, the
-    // coefficients (0, +-1) composing the sweeps' rules (wide_schedule); the products scale the
-    // A operand by c1 / c2 (exact).  One sweep (c1 = 0): the same operations as the form below,
-    // negated throughout -- bitwise the same values.  Without a schedule: the accumulators start
-    // at the tile NEGATED (zero base in the swept blocks) and the store negates back.
-    const bool sch = b.sched[m] != nullptr;
-    const bool two = sch && ((ent >> 16) & 1u);
+    // The schedule entry (b.sched): new = c0 X + c1 Z_{k-1}^T Z_{k-1} + c2 Z_k^T Z_k, the
+    // coefficients (0, +-1) composing the sweeps' rules (wide_schedule).  The accumulators start at
+    // c0 times the tile's current values (c0 = 0: zero base in the swept blocks; clamped addresses:
+    // rows / columns past p are never stored) and the products, their A operand scaled by c1 / c2
+    // (exact), are added: base - Z_I^T Z_J with the rounding of a subtraction, and no separate
+    // base registers.  The base loads are issued ahead of the product loop's first K-step.
+    const bool two = (ent >> 16) & 1u;
     auto cf = [](unsigned c) { return c == 0u ? 0.0 : c == 1u ? 1.0 : -1.0; };
     const double c0 = cf((ent >> 18) & 3u), c1 = cf((ent >> 20) & 3u), c2 = cf((ent >> 22) & 3u);
     d4 acc[4][4];
     {
-      const double f = sch ? c0 : ((inPi || inPj) ? -0.0 : -1.0);
+      const double f = c0;
 #pragma unroll
       for (int bx = 0; bx < 4; ++bx)
 #pragma unroll
@@ -1046,7 +957,7 @@ __global__ __launch_bounds__(256, 2) void wide_update_kernel(BigSpdBatch b, int 
     // sweeps read panel k - 1, always 128 deep since it is not the last sweep, then panel k)
     {
       const double* Zp = two ? zbuf<2>(b, m, k - 1) : Z;
-      tile::product2<1, 0>(Zp, Zp, two ? WT : 0, c1, Z, Z, wK, sch ? c2 : 1.0, p, p, p, p, i0, j0, sm, t,
+      tile::product2<1, 0>(Zp, Zp, two ? WT : 0, c1, Z, Z, wK, c2, p, p, p, p, i0, j0, sm, t,
                            wr, wc, lane, acc);
     }
     if (probe && !pivot && j < 2) TR_HI(SLOT_BIG_R0START + 3 * j + 2);
@@ -1060,7 +971,7 @@ __global__ __launch_bounds__(256, 2) void wide_update_kernel(BigSpdBatch b, int 
           const int row = i0 + 64 * wr + 16 * bx + (lane >> 4) + 4 * r;
           const int col = j0 + 64 * wc + 16 * by + (lane & 15);
           if (row < p && col < p) {
-            const double v = sch ? acc[bx][by][r] : -sgn * acc[bx][by][r];
+            const double v = acc[bx][by][r];
             X[(size_t)row * p + col] = v;
             if (LAST && row == col && row < b.n[m]) mx = fmax(mx, v);
           }
@@ -1179,7 +1090,9 @@ void wide_schedule(int T2, bool paired, std::vector<unsigned>& tab) {
              (code(t2 ? c1 : 0) << 20) | (code(c2) << 22);
     };
     int n = 0;
-    if (Q < T2) {  // the next panel's tiles first: row Q left of the diagonal, column Q below it
+    // the next panel's tiles first: row Q left of the diagonal, column Q below it (round 0 of the
+    // factor's first XCD slot run: the panel's wait for its row ends after one tile time)
+    if (Q < T2) {
       for (int J = 0; J < Q; ++J) row[2 + n++] = entry(Q, J);
       for (int I = Q + 1; I < T2; ++I) row[2 + n++] = entry(I, Q);
       row[1] = entry(Q, Q);
@@ -1196,12 +1109,13 @@ void wide_schedule(int T2, bool paired, std::vector<unsigned>& tab) {
 namespace {
 
 // the host copy of wide_schedule(T2, paired) -- the table gpk_create uploads per factor -- cached
-// per T2 (per host thread: handles of an in-process group launch from several threads)
-const std::vector<unsigned>& host_wide_schedule(int T2) {
-  static thread_local std::vector<std::vector<unsigned>> cache;
-  if ((int)cache.size() <= T2) cache.resize(T2 + 1);
-  if (cache[T2].empty()) wide_schedule(T2, true, cache[T2]);
-  return cache[T2];
+// per (T2, paired) (per host thread: handles of an in-process group launch from several threads)
+const std::vector<unsigned>& host_wide_schedule(int T2, bool paired) {
+  static thread_local std::vector<std::vector<unsigned>> cache[2];
+  std::vector<std::vector<unsigned>>& c = cache[paired ? 1 : 0];
+  if ((int)c.size() <= T2) c.resize(T2 + 1);
+  if (c[T2].empty()) wide_schedule(T2, paired, c[T2]);
+  return c[T2];
 }
 
 BigSpdBatch make_batch(SpdArgs* a, int nmat, int& Tmax, int& tiles_max) {
@@ -1217,7 +1131,7 @@ BigSpdBatch make_batch(SpdArgs* a, int nmat, int& Tmax, int& tiles_max) {
   for (int m = 0; m < nmat; ++m) {
     // every factor keeps its own schedule (built for its own T2 = ceil(p / 128)); the update
     // launch's per-factor item count covers the longest list (launch_stage_r)
-    b.sched[m] = a[m].wide ? a[m].sched : nullptr;
+    b.sched[m] = a[m].sched;
     b.sstride[m] = wide_sched_stride((a[m].p + 127) / 128);
     b.X[m] = a[m].X; b.Z[m] = a[m].Z ? a[m].Z : a[m].Y; b.Li[m] = a[m].piv;
     b.ldet[m] = a[m].ldet; b.pst[m] = a[m].pst; b.status[m] = a[m].status; b.flag[m] = a[m].flag;
@@ -1241,31 +1155,25 @@ int wide_cus() {
 }
 
 template <int R>
-void launch_stage_r(const BigSpdBatch& b, int nmat, int Tmax, int tiles, int stage, hipStream_t s,
-                    int skip_pivot = 0, bool mirror = true) {
+void launch_stage_r(const SpdArgs* a, const BigSpdBatch& b, int nmat, int Tmax, int tiles, int stage,
+                    hipStream_t s, int skip_pivot, bool mirror) {
   if (stage < 0) {
     hipLaunchKernelGGL(big_pivot_init_kernel<R>, dim3(nmat), dim3(256), 0, s, b);
   } else if ((stage & 1) == 0) {
     hipLaunchKernelGGL(big_panel_kernel<R>, dim3(Tmax, nmat), dim3(256), 0, s, b, stage >> 1);
   } else if (R == 1) {  // + the next sweep's panel workgroups (Tmax per factor)
-    hipLaunchKernelGGL(big_update_kernel<1>, dim3(tiles + Tmax, nmat), dim3(256), 0, s, b, stage >> 1,
+    hipLaunchKernelGGL(big_update_kernel, dim3(tiles + Tmax, nmat), dim3(256), 0, s, b, stage >> 1,
                        skip_pivot);
   } else {
     const int k = stage >> 1, nsw = (Tmax + 1) / 2;
-    // gx = item slots per factor: the longest list of sweep k over the batch's factors (a factor
-    // with a schedule: its row's length; without one: every lower tile but the pivot's)
+    // gx = item slots per factor: the longest list of sweep k (its schedule row's length) over
+    // the batch's factors
     int gx = 1;
     for (int m = 0; m < nmat; ++m) {
       const int T2 = (b.p[m] + WT - 1) / WT;
       if (k >= T2) continue;
-      int items;
-      if (b.sched[m]) {
-        const std::vector<unsigned>& tab = host_wide_schedule(T2);
-        items = (int)tab[(size_t)k * wide_sched_stride(T2)];
-      } else {
-        items = T2 * (T2 + 1) / 2 - (k + 1 < T2 ? 1 : 0);
-      }
-      gx = std::max(gx, items);
+      const std::vector<unsigned>& tab = host_wide_schedule(T2, a[m].sched_paired != 0);
+      gx = std::max(gx, (int)tab[(size_t)k * wide_sched_stride(T2)]);
     }
     const int per_xcd = (nmat * gx + 7) / 8;
     // persistent tile workgroups: two per CU on all but the 8 CUs whose first-pass workgroup is a
@@ -1283,6 +1191,13 @@ void launch_stage_r(const BigSpdBatch& b, int nmat, int Tmax, int tiles, int sta
   }
 }
 
+// one stage of the batch at its sweep width
+void launch_stage(const SpdArgs* a, const BigSpdBatch& b, int nmat, int Tmax, int tiles, int stage,
+                  hipStream_t s, int skip_pivot = 0, bool mirror = true) {
+  if (batch_R(a) == 2) launch_stage_r<2>(a, b, nmat, Tmax, tiles, stage, s, skip_pivot, mirror);
+  else launch_stage_r<1>(a, b, nmat, Tmax, tiles, stage, s, skip_pivot, mirror);
+}
+
 }  // namespace
 
 int spd_big_sweeps(int p, int wide) { return (p + BW * (wide ? 2 : 1) - 1) / (BW * (wide ? 2 : 1)); }
@@ -1295,8 +1210,7 @@ size_t spd_big_piv_doubles(int p) { return std::max<size_t>((size_t)p * 32, 2 * 
 hipError_t launch_spd_big_stage(SpdArgs* a, int nmat, int stage, hipStream_t s, bool mirror) {
   int Tmax, tiles;
   BigSpdBatch b = make_batch(a, nmat, Tmax, tiles);
-  if (batch_R(a) == 2) launch_stage_r<2>(b, nmat, Tmax, tiles, stage, s, 0, mirror);
-  else launch_stage_r<1>(b, nmat, Tmax, tiles, stage, s, 0, mirror);
+  launch_stage(a, b, nmat, Tmax, tiles, stage, s, 0, mirror);
   return hipGetLastError();
 }
 
@@ -1304,9 +1218,9 @@ hipError_t launch_spd_big_stage(SpdArgs* a, int nmat, int stage, hipStream_t s, 
 // accounting, gpk_bench_kernel): every listed tile's products, 2 w_I w_J (w_k [+ w_{k-1} for a
 // tile that takes sweeps k - 1 and k]) -- a diagonal tile whole (the kernel keeps both triangles
 // of its block) -- plus, with the pivot workgroup, the next pivot's tile, its blocked Cholesky
-// (W^3 / 3) and the fused next panel (forward substitution, W^2 p).  One-sweep forms: every lower
-// tile of the sweep.  Summed over the launches of one inverse the tile products are p^3 for the
-// one-sweep form (the Gauss-Jordan count).
+// (W^3 / 3) and the fused next panel (forward substitution, W^2 p).  W = 128: the handle's
+// schedule table; W = 64: every lower tile of the sweep.  Summed over the launches of one inverse
+// the tile products are p^3 where every tile takes every sweep (the Gauss-Jordan count).
 double spd_big_update_flops(const SpdArgs* a, int nmat, int k, bool with_pivot) {
   const int W = batch_R(a) == 2 ? 128 : 64;
   double fl = 0.0;
@@ -1315,8 +1229,8 @@ double spd_big_update_flops(const SpdArgs* a, int nmat, int k, bool with_pivot) 
     if (k >= T) continue;
     auto w = [&](int I) { return (double)std::min(W, p - W * I); };
     const bool has_next = k + 1 < T;
-    if (W == 128 && a[m].sched) {
-      const std::vector<unsigned>& tab = host_wide_schedule(T);
+    if (W == 128) {
+      const std::vector<unsigned>& tab = host_wide_schedule(T, a[m].sched_paired != 0);
       const unsigned* row = tab.data() + (size_t)k * wide_sched_stride(T);
       auto item = [&](unsigned ent) {
         const int I = (int)((ent >> 8) & 0xffu), J = (int)(ent & 0xffu);
@@ -1341,8 +1255,7 @@ double spd_big_update_flops(const SpdArgs* a, int nmat, int k, bool with_pivot) 
 hipError_t launch_spd_big_tiles(SpdArgs* a, int nmat, int k, hipStream_t s) {
   int Tmax, tiles;
   BigSpdBatch b = make_batch(a, nmat, Tmax, tiles);
-  if (batch_R(a) == 2) launch_stage_r<2>(b, nmat, Tmax, tiles, 2 * k + 1, s, 1);
-  else launch_stage_r<1>(b, nmat, Tmax, tiles, 2 * k + 1, s, 1);
+  launch_stage(a, b, nmat, Tmax, tiles, 2 * k + 1, s, 1);
   return hipGetLastError();
 }
 
@@ -1355,8 +1268,7 @@ hipError_t launch_spd_inverse_big(SpdArgs* a, int nmat, double** final_out, hipS
   // pivot 0, panel 0, then one update launch per sweep (each also forms the next sweep's panel)
   for (int st = -1; st < 2 * nsw; ++st) {
     if (st > 0 && (st & 1) == 0) continue;
-    if (R == 2) launch_stage_r<2>(b, nmat, Tmax, tiles, st, s);
-    else launch_stage_r<1>(b, nmat, Tmax, tiles, st, s);
+    launch_stage(a, b, nmat, Tmax, tiles, st, s);
   }
   return hipGetLastError();
 }

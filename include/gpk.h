@@ -134,8 +134,10 @@ typedef struct gpk_problem {
  * never (NO_DD_CONTRACTION). */
 #define GPK_FLAG_DD_CONTRACTION 131072
 #define GPK_FLAG_NO_DD_CONTRACTION 262144
-/* 128-wide SPD inverse (factors >= 3072): every lower tile takes every sweep in its own pass
- * (default: tiles take sweeps in pairs, K = 256 per pass, half the tiles per launch). */
+/* 128-wide SPD inverse (factors >= 3072): the handle uploads the unpaired update schedule
+ * (gpk_wide_schedule with paired = 0), so every lower tile takes every sweep in its own pass
+ * (default: the paired one -- tiles take sweeps in pairs, K = 256 per pass, half the tiles per
+ * launch).  Same update kernel either way. */
 #define GPK_FLAG_ONE_SWEEP_UPDATE 524288
 /* 128-wide SPD inverse: a tile workgroup with a quarter item works it after its whole tiles
  * (default: first, unless its first whole tile is in the next panel's row / column; A/B only).

@@ -252,12 +252,31 @@ def test_loss_grad_big_spd_path(dim, eq, kind, n1, n2, wide):
         _cmp_lossgrad(prob, params, 5, fs, flags=flags, path="big_wide" if wide else "big")
 
 
+@pytest.mark.parametrize("dim,eq,kind,n1,n2", [(2, "poisson", "Matern52_Cos_1d", 96, 80),
+                                               (1, "poisson", "SE_Cos_1d", 330, 0),
+                                               (2, "poisson", "Matern52_Cos_1d", 300, 600)])
+def test_loss_grad_wide_one_sweep(dim, eq, kind, n1, n2):
+    """GPK_FLAG_ONE_SWEEP_UPDATE on the 128-wide inverse (the unpaired wide_schedule table: every
+    tile takes one sweep per update launch), three cases of test_loss_grad_big_spd_path:
+    single-sweep factors with no next pivot (96 x 80), several sweeps with a ragged last pivot
+    (n = 330), and T2 = 3 and 5 -- two tables of different lengths in one launch (300 x 600)."""
+    from gpk._lib import GPK_FLAG_FORCE_BIG_SPD, GPK_FLAG_FORCE_WIDE_SPD, GPK_FLAG_ONE_SWEEP_UPDATE
+    flags = GPK_FLAG_FORCE_BIG_SPD | GPK_FLAG_FORCE_WIDE_SPD | GPK_FLAG_ONE_SWEEP_UPDATE
+    if dim == 1:
+        prob, params, _ = problem_1d(eq=eq, kind=kind, n=n1, Q=6, seed=3)
+        _cmp_lossgrad(prob, params, 6, 20.0, flags=flags, path="big_wide")
+    else:
+        prob, params, _, fs = problem_2d(eq=eq, kind=kind, n1=n1, n2=n2, Q=5, seed=8)
+        _cmp_lossgrad(prob, params, 5, fs, flags=flags, path="big_wide")
+
+
 @pytest.mark.parametrize("wide", [False, True])
 def test_big_spd_long_tile_runs(wide):
     """The update launch with 3 tile workgroups per factor: every workgroup walks a run of
-    tiles across block rows (panel blocks staged per unit and reused along a row at 64-wide,
-    the next unit prefetched under the current one's MFMAs, hand-off tiles at the start of
-    three runs, the last sweep's mirror stage reusing the panel LDS)."""
+    tiles across block rows (64-wide: Z_I stays staged along a block row, the next tile's Z_J
+    and X values are prefetched under the current tile's MFMAs, the next pivot's one hand-off
+    tile is the first of workgroup 0's run, the last sweep's mirror stage reuses the panel LDS;
+    128-wide: the persistent tile workgroups' rounds over the sweep's schedule row)."""
     from gpk._lib import GPK_FLAG_FORCE_BIG_SPD, GPK_FLAG_FORCE_WIDE_SPD, GPK_FLAG_FORCE_NARROW_SPD
     from gpk.core import set_spd_big_workgroups
     flags = GPK_FLAG_FORCE_BIG_SPD | (GPK_FLAG_FORCE_WIDE_SPD if wide else GPK_FLAG_FORCE_NARROW_SPD)
