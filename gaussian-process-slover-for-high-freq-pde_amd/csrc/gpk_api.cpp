@@ -209,7 +209,7 @@ int gpk_predict(gpk_handle* h, const double* xte1, int32_t m1, const double* xte
   // K^{-1} at the current params
   bool prof = h->profiling;
   h->profiling = false;
-  int rc = enqueue_assemble_inverse(h, 0);
+  int rc = enqueue_assemble_inverse(h, StepCtx{0});  // (apply = 0)
   h->profiling = prof;
   TRY(rc);
   const int M1p = pad_up(m1), P1 = L.p1;

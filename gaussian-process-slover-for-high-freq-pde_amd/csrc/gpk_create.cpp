@@ -172,7 +172,7 @@ static void choose_inverse_path(gpk_handle* h, const gpk_problem* p, bool local_
   }
 }
 
-#define A_(ptr, n) TRY(h->alloc(&(ptr), (n)))  // zero-filled, freed by gpk_destroy
+#define A_(ptr, n) TRY(dev_alloc(h->allocs, h->s, &(ptr), (n)))  // zero-filled, freed by gpk_destroy
 
 // phase 3: problem, parameter, factor and work buffers
 static int allocate_buffers(gpk_handle* h, const gpk_problem* p) {
@@ -453,17 +453,7 @@ int gpk_destroy(gpk_handle* h) {
   if (!h) return GPK_OK;
   DevSwitch ds(h->dev);
   if (h->s) (void)hipStreamSynchronize(h->s);
-  for (int k = 0; k < 2; ++k) {
-    if (h->g_exec[k]) (void)hipGraphExecDestroy(h->g_exec[k]);
-    if (h->g_fast[k]) (void)hipGraphExecDestroy(h->g_fast[k]);
-    if (h->g_multi[k]) (void)hipGraphExecDestroy(h->g_multi[k]);
-    for (auto& kv : h->g_batch[k])
-      if (kv.second) (void)hipGraphExecDestroy(kv.second);
-    if (k == 0)
-      for (auto& kv : h->g_calln)
-        if (kv.second) (void)hipGraphExecDestroy(kv.second);
-    if (h->g_call[k]) (void)hipGraphExecDestroy(h->g_call[k]);
-  }
+  for (auto& kv : h->graphs) (void)hipGraphExecDestroy(kv.second);
   for (int k = 0; k <= kMaxStages; ++k)
     if (h->ev[k]) (void)hipEventDestroy(h->ev[k]);
   if (h->rep_host) (void)hipHostFree(h->rep_host);

@@ -135,7 +135,7 @@ int gpk_profile_stages(gpk_handle* h, int32_t iters, double* out_us, int32_t cap
   h->profiling = true;
   for (int it = 0; it < iters; ++it) {
     HIPCHK(hipMemsetAsync(h->loss_slot, 0, sizeof(int), h->s));
-    int rc = enqueue_step(h, 1);
+    int rc = enqueue_step(h, StepCtx{});  // (a full step with apply = 1 that folds nothing)
     if (rc) { h->profiling = false; return rc; }
     HIPCHK(hipStreamSynchronize(h->s));
     for (int k = 0; k < h->nstage; ++k) {

@@ -2,7 +2,10 @@
 // the solver handle, the error helpers, and the functions that cross translation units.
 //   gpk_api.cpp     errors, device check, standalone kernels, predict, getters and setters
 //   gpk_create.cpp  handle construction (validate, choose path, allocate, classes, upload), state
-//   gpk_step.cpp    the step: plan (build_descs), enqueue, graph capture, batch protocol, gpk_step
+//   gpk_plan.cpp    the 2D step's GEMM plan (build_descs) and the GEMM descriptor helpers
+//   gpk_step.cpp    one step in stream order: argument fillers, the inverse, enqueue_step
+//   gpk_batch.cpp   graph cache and capture, batch begin / report / rollback, status handling,
+//                   gpk_step, gpk_prepare, gpk_loss_grad
 //   gpk_shard.cpp   the row-sharded step and its collective backends (the only user of RCCL)
 //   gpk_diag.cpp    measurement and diagnostic entry points (reached from no solver entry point)
 //   gpk_kron3.cpp   the 3-axis solver (step, predictions, criterion, Adam state) and gpk_mode_gemm
@@ -15,6 +18,7 @@
 #include <functional>
 #include <map>
 #include <string>
+#include <tuple>
 #include <vector>
 
 #include "../../include/gpk.h"
@@ -73,6 +77,32 @@ struct ShardGather {
   size_t chunk;     // doubles per rank (a block of rows), rank r's block at buf + r * chunk
 };
 
+// A captured graph of the step: `reps` steps back to back with (refine, apply) -- or, whole, a
+// call of its own: batch begin (snapshot, counters) + those steps + the pinned-memory report.
+// Ordered so that the graphs of one (whole, refine, apply) are neighbours in ascending reps.
+struct GraphKey {
+  bool whole, refine;
+  int apply, reps;
+  bool operator<(const GraphKey& o) const {
+    return std::tie(whole, refine, apply, reps) < std::tie(o.whole, o.refine, o.apply, o.reps);
+  }
+};
+
+// What one enqueued step is asked to do beyond the step itself, and (StepDone) what it did.
+struct StepCtx {
+  int apply = 1;
+  bool refine = true;     // false: the fast step (refinement stages left out, gates watched)
+  // pipelined class values (TailArgs::nce_flag, cls_pipe_ok): the parameter-gradient launch of
+  // step s of a captured batch evaluates step s + 1's class values after the kernel-parameter Adam
+  bool have_cls = false;  // the previous enqueued step evaluated this one's: no class-value launch
+  bool next_cls = false;  // this step evaluates the next one's
+  const StepBegin* begin = nullptr;    // batch begin to fold into the chain launch (chain + classes)
+  const StepReport* report = nullptr;  // batch report to fold into the loss workgroup
+};
+struct StepDone {
+  bool next_cls = false, begin = false, report = false;
+};
+
 struct gpk_handle {
   gpk_problem prob{};
   double freq_scale = 0.0;
@@ -88,10 +118,6 @@ struct gpk_handle {
   AxisConst* kc = nullptr;
   StepScalars* sc = nullptr;
   int *count = nullptr, *loss_slot = nullptr, *status = nullptr;
-  // batch begin / report folded into the next enqueued step (capture_call, capture_calln): the
-  // step that takes one clears its pointer
-  const StepBegin* fold_begin = nullptr;
-  const StepReport* fold_report = nullptr;
   double *losses = nullptr, *diag = nullptr;
   double* stat_x = nullptr;  // [2] status bits as doubles (split-factor group all-reduce)
 
@@ -158,55 +184,25 @@ struct gpk_handle {
   double* sred = nullptr;
   std::string splan;                  // the step's shard plan (gpk_shard_plan; gpk/shard.py)
 
-  hipGraphExec_t g_exec[2] = {nullptr, nullptr};  // [apply] full step graph
-  hipGraphExec_t g_fast[2] = {nullptr, nullptr};  // [apply] without the refinement stages
-  // STEP_GRAPH_REPS training steps back to back in one graph ([0] fast, [1] full): one host
-  // launch per group of steps (a graph launch boundary costs ~5-9 us of idle GPU)
-  hipGraphExec_t g_multi[2] = {nullptr, nullptr};
-  // batch graphs of exactly `reps` steps ([0] fast, [1] full), captured by gpk_prepare for the
-  // chunk sizes a call of its step count runs (FAST_CHUNK and the remainder): a prepared call is
-  // one graph launch per chunk
-  std::map<int, hipGraphExec_t> g_batch[2];
-  // fast chunks of a prepared step(n) call as whole-call graphs: batch begin (the rollback
-  // snapshot) + `reps` steps + the pinned-memory report -- one launch and one synchronisation
-  // per chunk (capture_call's form for step(1))
-  std::map<int, hipGraphExec_t> g_calln;
-  // one step(1) call as one graph ([0] fast, [1] full): batch begin (snapshot, counters), the
-  // step, and the pinned-memory report -- the reference's one-call-per-iteration loop shape
-  hipGraphExec_t g_call[2] = {nullptr, nullptr};
+  // every captured graph of this handle (gpk_batch.cpp step_graph: captured on first use, or by
+  // gpk_prepare).  Plain graphs exist at reps 1, at STEP_GRAPH_REPS (one host launch per group of
+  // steps: a graph launch boundary costs ~5-9 us of idle GPU) and at the chunk sizes of a prepared
+  // call; whole-call graphs at reps 1 (one step(1) call as one launch and one wait: the
+  // reference's one-call-per-iteration loop shape) and, fast only, at the prepared chunk sizes.
+  std::map<GraphKey, hipGraphExec_t> graphs;
   bool fast_ok = false;    // the fast graph exists for this handle (not row-sharded)
   int fast_mode = 0;       // next step(s) run the fast graph (gate closed with margin last time)
   long long rollbacks = 0;
   double* snap = nullptr;  // [3 * nparams] params, m, v at the start of a fast batch
   int* snap_count = nullptr;
   unsigned int* viol = nullptr;  // the fast graph met an open refinement gate
-  // pipelined class values (TailArgs::nce_flag): the parameter-gradient launch of step s of a
-  // captured batch evaluates step s + 1's class values after the kernel-parameter Adam.
-  // cls_next: the step being enqueued does that; cls_have: the previous enqueued step did, so
-  // this one needs no class-value launch.  Both false outside a multi-step capture.
   unsigned int* nce_flag = nullptr;  // raised by the Adam block, reset by the next publish_prep
   double* nce_kp = nullptr;          // [nsmall] the kernel parameters it hands over (sc1)
-  bool cls_next = false, cls_have = false;
   double* rep_host = nullptr;    // [8 + LOSS_CAP] pinned: status, viol, gates, losses (step_report)
-  double* pend_losses = nullptr; // caller's buffer for the last batch's losses (finish_batch)
-  int pend_n = 0;
   hipEvent_t ev[kMaxStages + 1] = {};
   bool profiling = false;
   int nstage = 0;
   const char* sname[kMaxStages] = {};  // name of each launched (profiled) stage
-
-  template <class T>
-  int alloc(T** p, size_t count_) {
-    void* q = nullptr;
-    size_t bytes = std::max<size_t>(count_ * sizeof(T), 16);
-    hipError_t e = hipMalloc(&q, bytes);
-    if (e != hipSuccess) return fail(GPK_ENOMEM, std::string("hipMalloc failed: ") + hipGetErrorString(e));
-    e = hipMemsetAsync(q, 0, bytes, s);
-    if (e != hipSuccess) return fail(GPK_EHIP, hipGetErrorString(e));
-    allocs.push_back(q);
-    *p = static_cast<T*>(q);
-    return GPK_OK;
-  }
 };
 
 #define TRY(x)                  \
@@ -214,6 +210,20 @@ struct gpk_handle {
     int r_ = (x);               \
     if (r_ != GPK_OK) return r_; \
   } while (0)
+
+// zero-filled device memory, freed with its handle (every pointer in `allocs`)
+template <class T>
+int dev_alloc(std::vector<void*>& allocs, hipStream_t s, T** p, size_t count) {
+  void* q = nullptr;
+  const size_t bytes = std::max<size_t>(count * sizeof(T), 16);
+  hipError_t e = hipMalloc(&q, bytes);
+  if (e != hipSuccess) return fail(GPK_ENOMEM, std::string("hipMalloc failed: ") + hipGetErrorString(e));
+  e = hipMemsetAsync(q, 0, bytes, s);
+  if (e != hipSuccess) return fail(GPK_EHIP, hipGetErrorString(e));
+  allocs.push_back(q);
+  *p = static_cast<T*>(q);
+  return GPK_OK;
+}
 
 // padded size, size and coordinates of axis a (0 or 1)
 inline int axis_p(const Layout& L, int a) { return a ? L.p2 : L.p1; }
@@ -227,7 +237,13 @@ bool build_classes(const double* x, int n, int P, std::vector<double>& dist, std
                    std::vector<int>& cbase, int& vmax);
 int create_impl(const gpk_problem* p, double freq_scale, int rank, int nranks, bool shard,
                 gpk_handle** out, bool local_group = false);
-// gpk_step.cpp: argument fillers, the enqueue, and the batch protocol
+// gpk_plan.cpp
+GemmDesc gemm_desc(const double* A, int lda, int ta, const double* B, int ldb, int tb, double* C,
+                   int ldc, int M, int N, int K);  // C = op(A) op(B), stored
+GemmDesc with_side(GemmDesc g, double* Y, const double* Ys, int ldy);  // + Y = Ys / 2 + v C
+int gemm_force(int flags);
+int build_descs(gpk_handle* h);
+// gpk_step.cpp: argument fillers and the enqueue of one step
 PrepArgs make_prep(gpk_handle* h, int apply);
 bool cls_pipe_ok(const gpk_handle* h);
 void fill_spd(gpk_handle* h, SpdArgs* sa);
@@ -237,16 +253,15 @@ hipError_t launch_chain(gpk_handle* h, bool gather, double** fin, bool aug = tru
                         const PrepArgs* prep = nullptr);
 hipError_t launch_inverse(gpk_handle* h, SpdArgs* sa, double** fin, bool pivot0_done);
 hipError_t launch_gemm_stage(gpk_handle* h, int k);  // stage k of the unsharded 2D plan
-int enqueue_assemble_inverse(gpk_handle* h, int apply, bool have_cls = false);
-TailArgs make_tail(gpk_handle* h, int apply, bool refine = true);
+int enqueue_assemble_inverse(gpk_handle* h, const StepCtx& c, StepDone* done = nullptr);
+TailArgs make_tail(gpk_handle* h, const StepCtx& c);
 void gemv_operand(const gpk_handle* h, GemvDesc& g);
-int enqueue_step(gpk_handle* h, int apply, bool refine = true);
-int gemm_force(int flags);
-int build_descs(gpk_handle* h);
+int enqueue_step(gpk_handle* h, const StepCtx& c, StepDone* done = nullptr);
+// gpk_batch.cpp: capture, the batch protocol, device status
 int capture_graph(hipStream_t s, hipGraphExec_t* slot, const std::function<int()>& body);
 StepBegin make_begin(gpk_handle* h, bool fast);
-int reset_handoffs(gpk_handle* h);
-int restore_snapshot(gpk_handle* h);
+std::string status_message(int st, bool handoffs, int rank = -1);
+int status_recover(int st, int* status, hipStream_t s, gpk_handle* h, bool undo_batch, bool handoffs);
 int status_error(int st, int* status, hipStream_t s, gpk_handle* h, bool undo_batch, bool handoffs);
 int read_status(gpk_handle* h);
 // gpk_shard.cpp

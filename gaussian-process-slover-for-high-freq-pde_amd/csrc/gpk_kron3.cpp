@@ -53,39 +53,9 @@ struct gpk_handle3 {
   int bpa = 0;
   std::vector<std::vector<GemmDesc>> stages;  // GEMM launches in stream order
   hipGraphExec_t exec[2] = {nullptr, nullptr};
-
-  template <class T>
-  int alloc(T** p, size_t count_) {
-    void* q_ = nullptr;
-    const size_t bytes = std::max<size_t>(count_ * sizeof(T), 16);
-    hipError_t e = hipMalloc(&q_, bytes);
-    if (e != hipSuccess) return fail(GPK_ENOMEM, std::string("hipMalloc failed: ") + hipGetErrorString(e));
-    e = hipMemsetAsync(q_, 0, bytes, s);
-    if (e != hipSuccess) return fail(GPK_EHIP, hipGetErrorString(e));
-    allocs.push_back(q_);
-    *p = static_cast<T*>(q_);
-    return GPK_OK;
-  }
 };
 
 namespace {
-
-GemmDesc mk(const double* A, int lda, int ta, const double* B, int ldb, int tb, double* C, int ldc,
-            int M, int N, int K) {
-  GemmDesc d{};
-  d.A = A; d.lda = lda; d.ta = ta;
-  d.B = B; d.ldb = ldb; d.tb = tb;
-  d.C = C; d.ldc = ldc;
-  d.M = M; d.N = N; d.K = K;
-  d.alpha = 1.0;
-  d.epi = EPI_STORE;
-  return d;
-}
-
-GemmDesc side(GemmDesc d, double* Y, const double* Ys, int ldy) {  // Y = Ys / 2 + v C
-  d.Y = Y; d.Ys = Ys; d.ldy = ldy;
-  return d;
-}
 
 // the step's GEMM launches (stream order; independent products of one launch batched)
 void build_stages(gpk_handle3* h) {
@@ -97,41 +67,41 @@ void build_stages(gpk_handle3* h) {
   auto& st = h->stages;
   st.clear();
   // forward: A1 = K1^{-1} x1 U, A3 = K3^{-1} x3 U
-  st.push_back({mk(Ki[0], P1, 0, h->Up, M1, 0, h->A1, M1, P1, M1, P1),
-                mk(h->Up, P3, 0, Ki[2], P3, 0, h->A3, P3, M3, P3, P3)});
+  st.push_back({gemm_desc(Ki[0], P1, 0, h->Up, M1, 0, h->A1, M1, P1, M1, P1),
+                gemm_desc(h->Up, P3, 0, Ki[2], P3, 0, h->A3, P3, M3, P3, P3)});
   // (U permuted) A2 = K2^{-1} x2 U;  T = A1 x3 K3^{-1}
-  st.push_back({mk(Ki[1], P2, 0, h->Upp, M2, 0, h->A2p, M2, P2, M2, P2),
-                mk(h->A1, P3, 0, Ki[2], P3, 0, h->Tm, P3, M3, P3, P3)});
+  st.push_back({gemm_desc(Ki[1], P2, 0, h->Upp, M2, 0, h->A2p, M2, P2, M2, P2),
+                gemm_desc(h->A1, P3, 0, Ki[2], P3, 0, h->Tm, P3, M3, P3, P3)});
   // (T permuted) S = K2^{-1} x2 T;  U_xx = D1 x1 A1, U_yy = D2 x2 A2, U_zz = D3 x3 A3
-  st.push_back({mk(Ki[1], P2, 0, h->Tp, M2, 0, h->Sp, M2, P2, M2, P2),
-                mk(D[0], P1, 0, h->A1, M1, 0, h->Rx, M1, P1, M1, P1),
-                mk(D[1], P2, 0, h->A2p, M2, 0, h->Ryp, M2, P2, M2, P2),
-                mk(h->A3, P3, 0, D[2], P3, 1, h->Rz, P3, M3, P3, P3)});
+  st.push_back({gemm_desc(Ki[1], P2, 0, h->Tp, M2, 0, h->Sp, M2, P2, M2, P2),
+                gemm_desc(D[0], P1, 0, h->A1, M1, 0, h->Rx, M1, P1, M1, P1),
+                gemm_desc(D[1], P2, 0, h->A2p, M2, 0, h->Ryp, M2, P2, M2, P2),
+                gemm_desc(h->A3, P3, 0, D[2], P3, 1, h->Rz, P3, M3, P3, P3)});
   // (R, S combined) reverse: D_k^T x_k R;  G_D1 = v R_(1) A1_(1)^T
   {
-    GemmDesc gd = mk(h->R, M1, 0, h->A1, M1, 1, h->GD[0], P1, P1, P1, M1);
+    GemmDesc gd = gemm_desc(h->R, M1, 0, h->A1, M1, 1, h->GD[0], P1, P1, P1, M1);
     gd.vscale = 1;
-    st.push_back({mk(D[0], P1, 1, h->R, M1, 0, h->T1, M1, P1, M1, P1),
-                  mk(D[1], P2, 1, h->Rp, M2, 0, h->T2p, M2, P2, M2, P2),
-                  mk(h->R, P3, 0, D[2], P3, 0, h->T3, P3, M3, P3, P3), gd});
+    st.push_back({gemm_desc(D[0], P1, 1, h->R, M1, 0, h->T1, M1, P1, M1, P1),
+                  gemm_desc(D[1], P2, 1, h->Rp, M2, 0, h->T2p, M2, P2, M2, P2),
+                  gemm_desc(h->R, P3, 0, D[2], P3, 0, h->T3, P3, M3, P3, P3), gd});
   }
   // X_k = K_k^{-1} x_k (D_k^T x_k R) with the side outputs Y_k = S/2 + v X_k;  G_D2
   {
-    GemmDesc gd = mk(h->Rp, M2, 0, h->A2p, M2, 1, h->GD[1], P2, P2, P2, M2);
+    GemmDesc gd = gemm_desc(h->Rp, M2, 0, h->A2p, M2, 1, h->GD[1], P2, P2, P2, M2);
     gd.vscale = 1;
-    st.push_back({side(mk(Ki[0], P1, 0, h->T1, M1, 0, h->X1, M1, P1, M1, P1), h->Y1, h->S, M1),
-                  side(mk(Ki[1], P2, 0, h->T2p, M2, 0, h->X2p, M2, P2, M2, P2), h->Y2p, h->Sp, M2),
-                  side(mk(h->T3, P3, 0, Ki[2], P3, 0, h->X3, P3, M3, P3, P3), h->Y3, h->S, P3), gd});
+    st.push_back({with_side(gemm_desc(Ki[0], P1, 0, h->T1, M1, 0, h->X1, M1, P1, M1, P1), h->Y1, h->S, M1),
+                  with_side(gemm_desc(Ki[1], P2, 0, h->T2p, M2, 0, h->X2p, M2, P2, M2, P2), h->Y2p, h->Sp, M2),
+                  with_side(gemm_desc(h->T3, P3, 0, Ki[2], P3, 0, h->X3, P3, M3, P3, P3), h->Y3, h->S, P3), gd});
   }
   // G_K_k = c/2 (N / N_k) K_k^{-1} - Y_k,(k) A_k,(k)^T;  G_D3
   {
-    GemmDesc g1 = mk(h->Y1, M1, 0, h->A1, M1, 1, h->GK[0], P1, P1, P1, M1);
+    GemmDesc g1 = gemm_desc(h->Y1, M1, 0, h->A1, M1, 1, h->GK[0], P1, P1, P1, M1);
     g1.alpha = -1.0; g1.beta = 0.5 * c * n2 * n3; g1.C0 = Ki[0]; g1.ldc0 = P1;
-    GemmDesc g2 = mk(h->Y2p, M2, 0, h->A2p, M2, 1, h->GK[1], P2, P2, P2, M2);
+    GemmDesc g2 = gemm_desc(h->Y2p, M2, 0, h->A2p, M2, 1, h->GK[1], P2, P2, P2, M2);
     g2.alpha = -1.0; g2.beta = 0.5 * c * n1 * n3; g2.C0 = Ki[1]; g2.ldc0 = P2;
-    GemmDesc g3 = mk(h->Y3, P3, 1, h->A3, P3, 0, h->GK[2], P3, P3, P3, M3);
+    GemmDesc g3 = gemm_desc(h->Y3, P3, 1, h->A3, P3, 0, h->GK[2], P3, P3, P3, M3);
     g3.alpha = -1.0; g3.beta = 0.5 * c * n1 * n2; g3.C0 = Ki[2]; g3.ldc0 = P3;
-    GemmDesc gd = mk(h->R, P3, 1, h->A3, P3, 0, h->GD[2], P3, P3, P3, M3);
+    GemmDesc gd = gemm_desc(h->R, P3, 1, h->A3, P3, 0, h->GD[2], P3, P3, P3, M3);
     gd.vscale = 1;
     st.push_back({g1, g2, g3, gd});
   }
@@ -301,7 +271,7 @@ int gpk_create3(const gpk_problem3* p, double freq_scale, gpk_handle3** out) {
   const long nb = 2 * ((long)ns[1] * ns[2] + (long)ns[0] * ns[2] + (long)ns[0] * ns[1]);
   int rc = GPK_OK;
 #define A3_(ptr, n) \
-  if ((rc = h->alloc(&(ptr), (n))) != GPK_OK) return bail(rc)
+  if ((rc = dev_alloc(h->allocs, h->s, &(ptr), (n))) != GPK_OK) return bail(rc)
   for (int a = 0; a < 3; ++a) {
     const int P = g.p[a];
     A3_(h->x[a], P);
@@ -524,18 +494,18 @@ int gpk_predict3(gpk_handle3* h, const double* xte1, int32_t m1, const double* x
     return check_launch(launch_gemm_slab(sg, h->s), "gemm_slab");
   };
   const int n1 = (int)N1, r3 = (int)R3;
-  if ((rc = gemm(mk(Ki[0], P1, 0, h->Up, n1, 0, W[0], n1, P1, n1, P1), 1.0, 0.0, nullptr)) ||
-      (rc = gemm(mk(Kc[0], P1, 0, W[0], n1, 0, W[1], n1, P1, n1, P1), -1.0, 1.0, h->Up)) ||
-      (rc = gemm(mk(Ki[0], P1, 0, W[1], n1, 0, W[0], n1, P1, n1, P1), 1.0, 1.0, W[0])) ||
-      (rc = gemm(mk(Kmn[0], P1, 0, W[0], n1, 0, W[1], n1, M1p, n1, P1), 1.0, 0.0, nullptr)) ||  // [M1p][P2][P3]
+  if ((rc = gemm(gemm_desc(Ki[0], P1, 0, h->Up, n1, 0, W[0], n1, P1, n1, P1), 1.0, 0.0, nullptr)) ||
+      (rc = gemm(gemm_desc(Kc[0], P1, 0, W[0], n1, 0, W[1], n1, P1, n1, P1), -1.0, 1.0, h->Up)) ||
+      (rc = gemm(gemm_desc(Ki[0], P1, 0, W[1], n1, 0, W[0], n1, P1, n1, P1), 1.0, 1.0, W[0])) ||
+      (rc = gemm(gemm_desc(Kmn[0], P1, 0, W[0], n1, 0, W[1], n1, M1p, n1, P1), 1.0, 0.0, nullptr)) ||  // [M1p][P2][P3]
       (rc = slab(Ki[1], P2, W[1], W[0], 1.0, 0.0, nullptr)) ||
       (rc = slab(Kc[1], P2, W[0], W[2], -1.0, 1.0, W[1])) ||
       (rc = slab(Ki[1], P2, W[2], W[0], 1.0, 1.0, W[0])) ||
       (rc = slab(Kmn[1], M2p, W[0], W[1], 1.0, 0.0, nullptr)) ||                               // [M1p][M2p][P3]
-      (rc = gemm(mk(W[1], P3, 0, Ki[2], P3, 0, W[0], P3, r3, P3, P3), 1.0, 0.0, nullptr)) ||
-      (rc = gemm(mk(W[0], P3, 0, Kc[2], P3, 0, W[2], P3, r3, P3, P3), -1.0, 1.0, W[1])) ||
-      (rc = gemm(mk(W[2], P3, 0, Ki[2], P3, 0, W[0], P3, r3, P3, P3), 1.0, 1.0, W[0])) ||
-      (rc = gemm(mk(W[0], P3, 0, Kmn[2], P3, 1, W[2], M3p, r3, M3p, P3), 1.0, 0.0, nullptr)))   // [M1p][M2p][M3p]
+      (rc = gemm(gemm_desc(W[1], P3, 0, Ki[2], P3, 0, W[0], P3, r3, P3, P3), 1.0, 0.0, nullptr)) ||
+      (rc = gemm(gemm_desc(W[0], P3, 0, Kc[2], P3, 0, W[2], P3, r3, P3, P3), -1.0, 1.0, W[1])) ||
+      (rc = gemm(gemm_desc(W[2], P3, 0, Ki[2], P3, 0, W[0], P3, r3, P3, P3), 1.0, 1.0, W[0])) ||
+      (rc = gemm(gemm_desc(W[0], P3, 0, Kmn[2], P3, 1, W[2], M3p, r3, M3p, P3), 1.0, 0.0, nullptr)))   // [M1p][M2p][M3p]
     return done(rc);
   for (int i1 = 0; i1 < m1; ++i1)
     if (hipMemcpy2DAsync(out + (size_t)i1 * m2 * m3, m3 * sizeof(double), W[2] + (size_t)i1 * M2p * M3p,
@@ -590,8 +560,8 @@ int gpk_mode_gemm(int32_t variant, int32_t k, int32_t d1, int32_t d2, int32_t d3
   };
   const int n23 = d2 * d3, n13 = d1 * d3, n12 = d1 * d2;
   auto launch = [&]() -> hipError_t {
-    if (k == 1) return one(mk(dM, d1, 0, dT, n23, 0, dC, n23, m, n23, d1), c0);
-    if (k == 3) return one(mk(dT, d3, 0, dM, d3, 1, dC, m, n12, m, d3), c0);
+    if (k == 1) return one(gemm_desc(dM, d1, 0, dT, n23, 0, dC, n23, m, n23, d1), c0);
+    if (k == 3) return one(gemm_desc(dT, d3, 0, dM, d3, 1, dC, m, n12, m, d3), c0);
     if (!permute) {  // the slab kernel (variant 2 / 3: its 32 / 64 tile forced)
       SlabGemm sg{};
       sg.A = dM; sg.B = dT; sg.sB = (size_t)n23; sg.C = dC; sg.sC = (size_t)m * d3; sg.C0 = c0; sg.sC0 = sg.sC;
@@ -606,7 +576,7 @@ int gpk_mode_gemm(int32_t variant, int32_t k, int32_t d1, int32_t d2, int32_t d3
     gc.p[0] = gc.n[0] = d1; gc.p[1] = gc.n[1] = m;                             // [d1][m][d3] -> [m][d1][d3]
     hipError_t r = k3_launch_permute(dT, dTp, gi, 0);
     if (r == hipSuccess && c0) r = k3_launch_permute(c0, dC0p, gc, 0);
-    if (r == hipSuccess) r = one(mk(dM, d2, 0, dTp, n13, 0, dCp, n13, m, n13, d2), c0 ? dC0p : nullptr);
+    if (r == hipSuccess) r = one(gemm_desc(dM, d2, 0, dTp, n13, 0, dCp, n13, m, n13, d2), c0 ? dC0p : nullptr);
     if (r == hipSuccess) r = k3_launch_permute(dCp, dC, go, 0);
     return r;
   };

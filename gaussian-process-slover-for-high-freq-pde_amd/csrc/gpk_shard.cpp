@@ -289,7 +289,9 @@ int build_shard(gpk_handle* h) {
 
 int enqueue_step_shard(gpk_handle* h, int apply) {
   const Layout& L = h->L;
-  TRY(enqueue_assemble_inverse(h, apply));  // replicated: K, D, K^{-1}, log det, step constants
+  StepCtx ctx;  // (a full step that folds nothing: the batch begin and report are launches)
+  ctx.apply = apply;
+  TRY(enqueue_assemble_inverse(h, ctx));  // replicated: K, D, K^{-1}, log det, step constants
   for (int k = 0; k < kGemmStages; ++k) {
     if (h->sst[k].n)  // (empty: a refinement stage of a path without refinement)
       TRY(check_launch(launch_gemm_auto(h->sdescs.data() + h->sst[k].off, h->sst[k].n, h->sc, h->s,
@@ -309,7 +311,7 @@ int enqueue_step_shard(gpk_handle* h, int apply) {
   TRY(check_launch(launch_status_f64(h->status, h->stat_x, 0, h->s), "status_pack"));
   TRY(h->comm->allreduce(h, h->sred, (size_t)(h->red_quad + h->nquad - h->sred)));
   TRY(check_launch(launch_status_f64(h->status, h->stat_x, 1, h->s), "status_unpack"));
-  TailArgs T = make_tail(h, apply);
+  TailArgs T = make_tail(h, ctx);
   T.fin.gpart = T.fin.gpart_lo = nullptr;  // (pg all-reduced above)
   T.fin.pg_out = nullptr;
   TRY(check_launch(launch_finalize(T.fin, h->s), "finalize"));
@@ -418,21 +420,14 @@ static int group_run(gpk_handle** hs, int nranks, int apply, int n_steps) {
   if (!any) return GPK_OK;
   for (int r = 0; r < nranks; ++r) {  // every rank undoes the batch (gpk.h: failed batches are undone)
     DevSwitch ds(hs[r]->dev);
-    HIPCHK(hipMemsetAsync(hs[r]->status, 0, sizeof(int), hs[r]->s));
-    if (any & 2) TRY(reset_handoffs(hs[r]));
-    TRY(restore_snapshot(hs[r]));
-    HIPCHK(hipStreamSynchronize(hs[r]->s));
+    TRY(status_recover(any, hs[r]->status, hs[r]->s, hs[r], true, true));
   }
-  if (any & 2) {
-    int r0 = 0;
-    while (!(st[r0] & 2)) ++r0;
-    return fail(GPK_ENOTPD, "SPD inverse: a pivot-chain hand-off timed out (device status 2, rank " +
-                                std::to_string(r0) + ")");
-  }
-  if (bad != nranks)
+  int r0 = 0;  // the first rank whose wait gave up
+  while ((any & 2) && !(st[r0] & 2)) ++r0;
+  if (!(any & 2) && bad != nranks)
     return fail(GPK_EINVAL, "internal: device status differs across the ranks of the group (" +
                                 std::to_string(bad) + " of " + std::to_string(nranks) + ")");
-  return fail(GPK_ENOTPD, "covariance factor is not positive definite (non-positive pivot in SPD inverse)");
+  return fail(GPK_ENOTPD, status_message(any, true, r0));
 }
 
 int gpk_group_step(gpk_handle** hs, int32_t nranks, int32_t n_steps, double* losses) {

@@ -6,7 +6,7 @@ all-gathered after which stage, the one all-reduce, the U gather after Adam), wi
 partition of `shard_rows` -- in NumPy fp64 on this process's share, exchanging over the
 torch.distributed (gloo) group of the caller.  Every output row a rank did not compute and did
 not receive is NaN, so a plan that omits an all-gather a later product needs poisons the loss.
-The stage formulas are those of csrc/gpk_step.cpp build_descs (the 2D step: forward solves,
+The stage formulas are those of csrc/gpk_plan.cpp build_descs (the 2D step: forward solves,
 residual, reverse pass, G_K / G_D); the kernel fields and the parameter
 contraction are the oracle's (oracle/gp_oracle.py, itself pinned to the reference).
 It has the solver interface bench.py's `sharded_section` drives (prepare / step / sync / close).

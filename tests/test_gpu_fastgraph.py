@@ -136,6 +136,28 @@ def test_prepared_batch_graphs_bitwise_single(name):
     b.close()
 
 
+@pytest.mark.parametrize("name", ["2d_closed", "2d_open", "1d_closed"])
+def test_call_longer_than_a_prepared_size_bitwise_single(name):
+    """gpk_prepare(100) captures graphs of 64 and 36 steps.  A later step(50) is neither: it runs
+    the largest prepared size below it (36), then an 8-step graph and six single steps; step(65)
+    is a chunk of 64 and a chunk of one step (which keeps the plain path: the call has more than
+    one step).  Bitwise one graph launch per step, rollbacks included."""
+    prob, params, Q, fs = _case(name)
+    a = device_solver(prob, Q, fs)
+    b = device_solver(prob, Q, fs)
+    for s in (a, b):
+        s.set_params(params)
+    a.prepare(100)
+    la = np.concatenate([a.step(100), a.step(50), a.step(65)])
+    lb = np.concatenate([b.step(1) for _ in range(215)])
+    assert np.array_equal(la, lb)
+    for x, y in zip(_state(a), _state(b)):
+        assert np.array_equal(x, y)
+    assert a.graph_mode()[1] == b.graph_mode()[1]  # same rollbacks
+    a.close()
+    b.close()
+
+
 @pytest.mark.parametrize("name", ["2d_open", "1d_open"])
 def test_single_step_call_graph_rollback(name):
     """step(1) runs one captured call graph (batch begin + step + pinned-memory report); a fast
