@@ -107,10 +107,15 @@ void build_stages(gpk_handle3* h) {
   }
 }
 
+// the GEMM kernel stage k launches with (what gpk_stage_variants3 reports)
+int stage_variant(const gpk_handle3* h, int k) {
+  const auto& d = h->stages[k];
+  return gemm_variant(d.data(), (int)d.size(), 0);
+}
+
 int launch_stage(gpk_handle3* h, int k) {
   const auto& d = h->stages[k];
-  const int variant = gemm_variant(d.data(), (int)d.size(), 0);
-  return check_launch(launch_gemm_auto(d.data(), (int)d.size(), h->sc, h->s, variant), "gemm");
+  return check_launch(launch_gemm_auto(d.data(), (int)d.size(), h->sc, h->s, stage_variant(h, k)), "gemm");
 }
 
 // Step constants, K_k and D_k, then K_k^{-1} and log det K_k at the current params: the front of
@@ -214,6 +219,12 @@ int read_status3(gpk_handle3* h) {
   HIPCHK(hipStreamSynchronize(h->s));
   // (no hand-off waits and no batches here: any status is a non-positive pivot)
   return st ? status_error(st, h->status, h->s, nullptr, false, false) : GPK_OK;
+}
+
+// K3Final::diag as the last step or gpk_loss_grad3 left it
+int read_diag3(gpk_handle3* h, double diag[8]) {
+  HIPCHK(hipMemcpy(diag, h->diag, 8 * sizeof(double), hipMemcpyDeviceToHost));
+  return GPK_OK;
 }
 
 }  // namespace
@@ -413,10 +424,27 @@ int gpk_criterion3(gpk_handle3* h, double* out) {
   TRY(gpk_loss_grad3(h, &loss, nullptr));
   DevSwitch ds(h->dev);
   double diag[8];
-  HIPCHK(hipMemcpy(diag, h->diag, sizeof(diag), hipMemcpyDeviceToHost));
+  TRY(read_diag3(h, diag));
   const double n1 = h->g.n[0], n2 = h->g.n[1], n3 = h->g.n[2];
   const double Nb = 2.0 * (n2 * n3 + n1 * n3 + n1 * n2), Nc = n1 * n2 * n3;
   *out = diag[6] / Nb + diag[5] / Nc;  // boundary_gap/Nb + eq_gap/Nc (K3Final::diag)
+  return GPK_OK;
+}
+
+int gpk_stage_variants3(gpk_handle3* h, int32_t* out, int32_t cap, int32_t* n) {
+  if (!h || !n || cap < 0 || (cap && !out)) return fail(GPK_EINVAL, "NULL argument");
+  *n = (int32_t)h->stages.size();
+  for (int k = 0; k < *n && k < cap; ++k) out[k] = stage_variant(h, k);
+  return GPK_OK;
+}
+
+int gpk_loss_terms3(gpk_handle3* h, double out[7]) {
+  if (!h || !out) return fail(GPK_EINVAL, "NULL argument");
+  DevSwitch ds(h->dev);
+  HIPCHK(hipStreamSynchronize(h->s));
+  double diag[8];
+  TRY(read_diag3(h, diag));
+  std::copy(diag, diag + 7, out);
   return GPK_OK;
 }
 

@@ -147,6 +147,8 @@ EXPORTS = {
     "gpk_predict3": ([ctypes.c_void_p, _dp, ctypes.c_int32, _dp, ctypes.c_int32, _dp, ctypes.c_int32,
                       _dp], ctypes.c_int),
     "gpk_criterion3": ([ctypes.c_void_p, _dp], ctypes.c_int),
+    "gpk_stage_variants3": ([ctypes.c_void_p, _ip, ctypes.c_int32, _ip], ctypes.c_int),
+    "gpk_loss_terms3": ([ctypes.c_void_p, _dp], ctypes.c_int),
     "gpk_mode_gemm": ([ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
                        ctypes.c_int32, ctypes.c_double, _dp, _dp, ctypes.c_double, _dp, _dp,
                        ctypes.c_int32, _dp], ctypes.c_int),

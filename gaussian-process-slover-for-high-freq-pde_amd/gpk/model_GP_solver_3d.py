@@ -147,6 +147,24 @@ class DeviceSolver3:
         check(_lib.load().gpk_criterion3(self._h, ctypes.byref(c)))
         return c.value
 
+    def stage_variants(self):
+        """The GEMM kernel of each of the step's GEMM launches, in stream order
+        (_lib.GEMM_SMALL / GEMM_BIG / GEMM_TILE128; gpk_stage_variants3)."""
+        out = np.zeros(16, np.int32)
+        n = ctypes.c_int32()
+        check(_lib.load().gpk_stage_variants3(self._h, out.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
+                                              out.size, ctypes.byref(n)))
+        assert n.value <= out.size
+        return [int(v) for v in out[:n.value]]
+
+    LOSS_TERMS = ("loss", "logdet_1", "logdet_2", "logdet_3", "quad", "egap", "bgap")
+
+    def loss_terms(self):
+        """The terms of the last loss_grad()'s loss (gpk_loss_terms3), keyed by LOSS_TERMS."""
+        out = np.empty(7)
+        check(_lib.load().gpk_loss_terms3(self._h, dptr(out)))
+        return dict(zip(self.LOSS_TERMS, out.tolist()))
+
 
 class GP_solver_3d_single(SolverBase):
     """GP_solver_2d_single's interface (model_GP_solver_2d.py:31-352) on three axes: SolverBase's

@@ -435,6 +435,13 @@ int gpk_predict3(gpk_handle3* h, const double* xte1, int32_t m1, const double* x
 /* compute_early_stopping (model_GP_solver_2d.py:222-233) on three axes: boundary_gap / Nb +
  * eq_gap / Nc at the current params, Nb = 2 (n2 n3 + n1 n3 + n1 n2), Nc = n1 n2 n3. */
 int gpk_criterion3(gpk_handle3* h, double* out);
+/* The GEMM kernel each of the step's GEMM launches takes, in stream order (gpk_dgemm's variant
+ * numbers: 1 the 16x16, 2 the 64x64, 3 the 128x128 kernel): *n launches, the first
+ * min(*n, cap) of them in out.  Fixed by the grid; nothing is launched. */
+int gpk_stage_variants3(gpk_handle3* h, int32_t* out, int32_t cap, int32_t* n);
+/* The terms of the last gpk_loss_grad3's loss: out = {loss, log det K1, log det K2, log det K3,
+ * <U, K^{-1} U>, eq_gap, boundary_gap} (read back; nothing is launched). */
+int gpk_loss_terms3(gpk_handle3* h, double out[7]);
 
 /* One mode-k product on host operands (tests, A/B timing; the counterpart of gpk_dgemm):
  *   C = alpha (Mat x_k T) + beta C0,   T [d1][d2][d3] row-major, Mat m x d_k row-major,

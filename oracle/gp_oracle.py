@@ -1165,12 +1165,13 @@ def _boundary_scatter_3d(shape, r):
     return g
 
 
-def loss_grad_3d(prob, params, want_grad=True):
+def loss_grad_3d(prob, params, want_grad=True, terms=None):
     """Negative log-joint and gradient of the 3-axis Kronecker solver.
 
     prob keys: kind, x1, x2, x3, src [N1,N2,N3], bvals [6 faces], jitter, llk_weight, logdet,
     eq ('poisson'|'allencahn').  params: {'U': [N1,N2,N3], 'kernel_paras_1..3', 'log_tau',
-    'log_v'} (flat order = sorted keys, as the 2-axis pytree)."""
+    'log_v'} (flat order = sorted keys, as the 2-axis pytree).  terms: a dict that receives the
+    loss's terms (loss, logdet_1..3, quad, egap, bgap)."""
     kind, eq = prob["kind"], prob["eq"]
     xs = [np.asarray(prob[f"x{a}"], np.float64).reshape(-1) for a in (1, 2, 3)]
     Ns = tuple(x.size for x in xs)
@@ -1199,6 +1200,9 @@ def loss_grad_3d(prob, params, want_grad=True):
     log_b = 0.5 * Nb * log_tau - 0.5 * tau * bgap
     eq_ll = 0.5 * Nc * log_v - 0.5 * v * egap
     loss = -(log_prior + log_b * wb + eq_ll)
+    if terms is not None:
+        terms.update(loss=loss, logdet_1=lds[0], logdet_2=lds[1], logdet_3=lds[2], quad=quad,
+                     egap=egap, bgap=bgap)
     if not want_grad:
         return loss, None
     X = [_mode_solve(lus[k], mode_product(KD[k][1].T, R, k), k) for k in range(3)]

@@ -31,7 +31,8 @@ def _tol(prob, params):
 @pytest.mark.parametrize("kind", KINDS)
 @pytest.mark.parametrize("eq", ["poisson", "allencahn"])
 def test_loss_grad_3d_vs_oracle(eq, kind):
-    """Loss and every gradient block at seeded params, unequal axes (padding per axis)."""
+    """Loss and every gradient block at seeded params, unequal n per axis; all three pad to 32
+    (grids with unequal padded sizes: tests/test_gpu_kron3_shapes.py)."""
     prob, params, fs = problem_3d(eq=eq, kind=kind, ns=(20, 14, 9), Q=4, seed=3)
     s = _solver(prob, 4, fs)
     try:

@@ -10,7 +10,7 @@ from tests.conftest import PKG_DIR
 from tests.test_abi import header_functions
 
 NEW_ENTRY_POINTS = ["gpk_mode_gemm", "gpk_predict3", "gpk_criterion3", "gpk_get_opt_state3",
-                    "gpk_set_opt_state3"]
+                    "gpk_set_opt_state3", "gpk_stage_variants3", "gpk_loss_terms3"]
 EQS = ["poisson_3d-mix_sin", "allencahn_3d-sin"]
 
 
@@ -21,6 +21,16 @@ def test_header_declares_the_3d_entry_points():
     from gpk import _lib
     for must in NEW_ENTRY_POINTS:
         assert must in _lib.EXPORTS, must
+
+
+def test_read_only_entry_points_reject_null():
+    import ctypes
+    from gpk import _lib
+    lib = _lib.load()
+    n = ctypes.c_int32()
+    out = (ctypes.c_int32 * 8)()
+    assert lib.gpk_stage_variants3(None, out, 8, ctypes.byref(n)) == _lib.GPK_EINVAL
+    assert lib.gpk_loss_terms3(None, (ctypes.c_double * 7)()) == _lib.GPK_EINVAL
 
 
 def test_config3d_files():
@@ -78,7 +88,8 @@ def test_solver_class_surface():
                  "save_checkpoint", "load_checkpoint", "init_params", "_make_device", "_err",
                  "_kernel_lists", "_finish_log"):
         assert callable(getattr(cls, meth)), meth
-    for meth in ("predict", "criterion", "get_opt_state", "set_opt_state", "sync"):
+    for meth in ("predict", "criterion", "get_opt_state", "set_opt_state", "sync", "stage_variants",
+                 "loss_terms"):
         assert callable(getattr(m3d.DeviceSolver3, meth)), meth
     for fn in ("test", "evals", "main", "load_config", "build_config", "boundary_3d"):
         assert callable(getattr(m3d, fn)), fn

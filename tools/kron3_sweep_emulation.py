@@ -1,0 +1,84 @@
+"""Is the 3-axis step's distance from the yardstick its algorithm's, or a layout's?  (CPU)
+
+NumPy fp64 emulation of the 3-axis step's solves at the cases of tests/test_gpu_kron3_shapes.py:
+the oracle's loss_grad_3d with every K_k^{-1} application a product with an explicit inverse,
+formed either as the device forms it -- 32-wide Cholesky-Gauss-Jordan sweeps over the identity-
+padded factor (spdinv.hip sweep_kernel), log det from the pivots -- or ("--inverse potri") from
+one Cholesky factorisation of the whole factor.  No refinement step, as the 3-axis step has none.
+Prints, per key, the emulation's distance from the long-double yardstick beside the fp64 LU
+oracle's.  The emulation has no layout to get wrong: where the device's ratio to the LU oracle
+matches the sweep emulation's, the excess is the algorithm's.
+
+usage: python tools/kron3_sweep_emulation.py [--inverse sweep|potri] [case ...]
+"""
+import argparse
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "gaussian-process-slover-for-high-freq-pde_amd")]
+import numpy as np
+import scipy.linalg as sla
+
+from oracle import gp_oracle as O
+import tests.test_gpu_kron3_shapes as T
+
+
+def sweep_inverse(K):
+    """(K^{-1}, log det K) by the sweep operator with 32-wide Cholesky pivots."""
+    n = K.shape[0]
+    p = -(-n // 32) * 32
+    X = np.eye(p)
+    X[:n, :n] = K
+    ld = 0.0
+    for k in range(p // 32):
+        s = slice(32 * k, 32 * k + 32)
+        L = np.linalg.cholesky(X[s, s])
+        ld += 2.0 * float(np.sum(np.log(np.diag(L))))
+        Li = sla.solve_triangular(L, np.eye(32), lower=True)
+        V = Li @ X[s, :]      # V_J = L^{-1} X_PJ
+        Y = X - V.T @ V       # X_IJ - V_I^T V_J
+        Y[s, :] = Li.T @ V    # L^{-T} V_J
+        Y[:, s] = V.T @ Li    # V_I^T L^{-1}
+        Y[s, s] = -(Li.T @ Li)
+        X = Y
+    return -X[:n, :n], ld
+
+
+def potri_inverse(K):
+    L = np.linalg.cholesky(K)
+    Li = sla.solve_triangular(L, np.eye(K.shape[0]), lower=True)
+    return Li.T @ Li, 2.0 * float(np.sum(np.log(np.diag(L))))
+
+
+def emulate(prob, params, inverse):
+    saved = O._lu, O._solve, O._slogdet_from_lu
+    O._lu = lambda K: ("inv", inverse(K))
+    O._solve = lambda f, B: f[1][0] @ B
+    O._slogdet_from_lu = lambda f: f[1][1]
+    try:
+        terms = {}
+        loss, grad = O.loss_grad_3d(prob, params, terms=terms)
+    finally:
+        O._lu, O._solve, O._slogdet_from_lu = saved
+    return loss, grad, terms
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--inverse", default="sweep", choices=["sweep", "potri"])
+    ap.add_argument("cases", nargs="*", default=list(T.ALL_CASES))
+    a = ap.parse_args()
+    inverse = sweep_inverse if a.inverse == "sweep" else potri_inverse
+    for case in a.cases:
+        (eq, kind, ns, Q), P, _ = T.ALL_CASES[case]
+        ref = T._reference(eq, kind, ns, Q)
+        d = T._distances(emulate(ref["prob"], ref["params"], inverse), ref["ext"])
+        print(f"== {case} ns={ns} padded={P} fp64 tol {ref['tol']:.2e}")
+        for k in d:
+            lu = ref["lu_err"][k]
+            print(f"   {k:16s} {a.inverse} {d[k]:.3e}  lu {lu:.3e}  ratio {d[k] / lu if lu else float('inf'):8.2f}")
+
+
+if __name__ == "__main__":
+    main()
