@@ -446,6 +446,30 @@ int slab_gemm_tile(const SlabGemm& g);
 // tile: 0 = by the tile count (slab_gemm_tile), 32 or 64 forced
 hipError_t launch_gemm_slab(const SlabGemm& g, hipStream_t s, int tile = 0);
 
+// Fused refinement step of one solve (refine_panel.hip): X += K^{-1} (B - Kc X) along the mode
+// index p < P, one workgroup per panel of 16 unfolding columns with the X and W panels in LDS
+// (three tensor passes instead of the two-GEMM route's six).  Element (p, column c) of X, B, Y and
+// Ys lies at p * sp + c * sc: the left form (X is P x M row-major, K applied to rows) has sp = M,
+// sc = 1; the right form (X is M x P, X K^{-1}) has sp = 1, sc = P and reads the matrices
+// transposed (right = 1).  P a multiple of 32, at most REFINE_PANEL_MAX_P (both panels in LDS);
+// M a multiple of 16.  A closed gate ends every workgroup before any load.
+constexpr int REFINE_PANEL_MAX_P = 512;
+struct RefinePanel {
+  const double* Kinv; const double* Kc;  // [P][P]
+  const double* B; double* X;
+  int P, M, right;
+  size_t sp, sc;
+  const double* gate;                    // nullable: always refine
+  double* Y; const double* Ys;           // side output Y = Ys / 2 + v X (nullable), X's addressing
+};
+constexpr int REFINE_MAX_BATCH = 3;
+struct RefinePanelBatch {  // passed by value (kernarg); blockIdx.y picks the solve
+  RefinePanel d[REFINE_MAX_BATCH];
+};
+hipError_t refine_panel_prepare();       // once per process, outside any stream capture
+// n <= REFINE_MAX_BATCH independent solves in one launch (r: HOST array)
+hipError_t launch_refine_panel(const RefinePanel* r, int n, const StepScalars* sc, hipStream_t s);
+
 __device__ __forceinline__ bool gate_open(const double* gate) {
   if (!gate) return true;
   const double k00 = gate[0];

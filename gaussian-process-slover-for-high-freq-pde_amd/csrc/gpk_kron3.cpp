@@ -11,6 +11,9 @@
 //     S = K^{-1} U,  R = sum_k D_k x_k A_k - F,  dL/dU = S + v sum_k X_k  (+ AC, boundary)
 //     G_Kk = c/2 (N / N_k) K_k^{-1} - (S/2 + v X_k)_(k) A_k,(k)^T,   G_Dk = v R_(k) A_k,(k)^T
 // (the 2-axis adjoints of SURVEY.md Appendix A, one per axis).
+// GPK_FLAG3_REFINE: every one of the eight solves (A1, A2, A3, T, S, X1, X2, X3) is followed by
+// one refinement step X += K_k^{-1} (B - K_k X) gated on the axis's pst: one fused panel launch
+// (refine_panel.hip), or two GEMMs where its panels do not fit LDS (build_refine).
 //
 // Beyond the step: gpk_predict3 (test-grid predictions, T <- Kmn_k x_k solve(K_k, T) axis after
 // axis; its mode-2 products are slab-batched launches, gemm.hip, with no permuted copy),
@@ -40,6 +43,7 @@ struct gpk_handle3 {
   int *count = nullptr, *loss_slot = nullptr, *status = nullptr;
   double *losses = nullptr, *diag = nullptr, *bgap = nullptr;
   double *K[3] = {}, *Kb[3] = {}, *D[3] = {}, *piv[3] = {}, *ldet[3] = {}, *pst[3] = {}, *Kinv[3] = {};
+  double* Kc[3] = {};  // kept copy of K_k (GPK_FLAG3_REFINE: the refinement residuals), else null
   unsigned int* aflag[3] = {};
   // grid tensors (natural [p1][p2][p3] or, suffix p, mode-2 permuted [p2][p1][p3])
   double *Upp = nullptr, *A1 = nullptr, *A2p = nullptr, *A3 = nullptr, *Tm = nullptr, *Tp = nullptr,
@@ -52,6 +56,12 @@ struct gpk_handle3 {
   double *pgpart = nullptr, *pg = nullptr;
   int bpa = 0;
   std::vector<std::vector<GemmDesc>> stages;  // GEMM launches in stream order
+  // GPK_FLAG3_REFINE: the refinement launches, [2 j] the residuals and [2 j + 1] the corrections
+  // that follow stage kRefineAfter[j] (empty without the flag)
+  std::vector<std::vector<GemmDesc>> rstages;
+  // route 1: one fused panel launch per solve instead (refine_panel.hip), [j] after kRefineAfter[j]
+  std::vector<std::vector<RefinePanel>> rpanels;
+  int route = 0;
   hipGraphExec_t exec[2] = {nullptr, nullptr};
 };
 
@@ -107,15 +117,82 @@ void build_stages(gpk_handle3* h) {
   }
 }
 
+// Refinement of the solves stage kRefineAfter[j] forms: W = B - Kc_k x_k X, then X += K_k^{-1} x_k W
+// in place, both gated on axis k's pst (a closed gate ends every workgroup before any load, so X
+// and the scratch keep their values).  W lives in tensors that are free at that point: T1 / T2p /
+// T3 until stage 3 writes them, Rx / Ryp / Rz once k3_combine has read them.  Mode 2 stays in
+// the permuted layout.  The corrections of X_k rewrite the side output Y_k from the refined X_k.
+// Route 1 does each solve's two GEMMs in one fused panel launch (no W tensor).  It measured faster
+// at every size it can run, so it is the handle's route whenever every
+// padded size is <= REFINE_PANEL_MAX_P (the panels fit LDS); GPK_FLAG3_REFINE_GEMM forces route 0.
+constexpr int kRefineAfter[4] = {0, 1, 2, 4};
+
+void build_refine(gpk_handle3* h) {
+  const int P1 = h->g.p[0], P2 = h->g.p[1], P3 = h->g.p[2];
+  const int M1 = P2 * P3, M2 = P1 * P3, M3 = P1 * P2;
+  const int Ps[3] = {P1, P2, P3}, Ms[3] = {M1, M2, M3};
+  auto& rs = h->rstages;
+  rs.assign(8, {});
+  h->rpanels.assign(4, {});
+  h->route = !(h->prob.flags & GPK_FLAG3_REFINE_GEMM) && std::max(P1, std::max(P2, P3)) <= REFINE_PANEL_MAX_P;
+  // solve X = K_a^{-1} x_a B of axis a (a = 1: permuted operands), scratch W
+  auto add = [&](int j, int a, const double* B, double* X, double* W) {
+    const int P = Ps[a], M = Ms[a];
+    GemmDesc r = a == 2 ? gemm_desc(X, P, 0, h->Kc[a], P, 0, W, P, M, P, P)
+                        : gemm_desc(h->Kc[a], P, 0, X, M, 0, W, M, P, M, P);
+    r.alpha = -1.0; r.beta = 1.0; r.C0 = B; r.ldc0 = r.ldc; r.gate = h->pst[a];
+    GemmDesc c = a == 2 ? gemm_desc(W, P, 0, h->Kinv[a], P, 0, X, P, M, P, P)
+                        : gemm_desc(h->Kinv[a], P, 0, W, M, 0, X, M, P, M, P);
+    c.beta = 1.0; c.C0 = X; c.ldc0 = c.ldc; c.gate = h->pst[a];
+    rs[2 * j].push_back(r);
+    rs[2 * j + 1].push_back(c);
+    RefinePanel f{};
+    f.Kinv = h->Kinv[a]; f.Kc = h->Kc[a]; f.B = B; f.X = X; f.P = P; f.M = M; f.right = a == 2;
+    f.sp = a == 2 ? 1 : (size_t)M; f.sc = a == 2 ? (size_t)P : 1; f.gate = h->pst[a];
+    h->rpanels[j].push_back(f);
+  };
+  add(0, 0, h->Up, h->A1, h->T1);      // A1
+  add(0, 2, h->Up, h->A3, h->T3);      // A3
+  add(1, 1, h->Upp, h->A2p, h->T2p);   // A2
+  add(1, 2, h->A1, h->Tm, h->T3);      // T = A1 x3 K3^{-1}
+  add(2, 1, h->Tp, h->Sp, h->T2p);     // S = K2^{-1} x2 T
+  add(3, 0, h->T1, h->X1, h->Rx);      // X_k
+  add(3, 1, h->T2p, h->X2p, h->Ryp);
+  add(3, 2, h->T3, h->X3, h->Rz);
+  double* const Y[3] = {h->Y1, h->Y2p, h->Y3};
+  const double* const Ys[3] = {h->S, h->Sp, h->S};
+  const int ldy[3] = {M1, M2, P3};
+  for (int a = 0; a < 3; ++a) {
+    rs[7][a] = with_side(rs[7][a], Y[a], Ys[a], ldy[a]);
+    h->rpanels[3][a].Y = Y[a]; h->rpanels[3][a].Ys = Ys[a];  // (ldy is X's leading dimension)
+  }
+}
+
+int launch_descs(gpk_handle3* h, const std::vector<GemmDesc>& d) {
+  return check_launch(launch_gemm_auto(d.data(), (int)d.size(), h->sc, h->s, gemm_variant(d.data(), (int)d.size(), 0)),
+                      "gemm");
+}
+
 // the GEMM kernel stage k launches with (what gpk_stage_variants3 reports)
 int stage_variant(const gpk_handle3* h, int k) {
   const auto& d = h->stages[k];
   return gemm_variant(d.data(), (int)d.size(), 0);
 }
 
+// stage k, then the refinement of its solves when the handle refines
 int launch_stage(gpk_handle3* h, int k) {
-  const auto& d = h->stages[k];
-  return check_launch(launch_gemm_auto(d.data(), (int)d.size(), h->sc, h->s, stage_variant(h, k)), "gemm");
+  TRY(launch_descs(h, h->stages[k]));
+  for (int j = 0; j < 4 && !h->rstages.empty(); ++j)
+    if (kRefineAfter[j] == k) {
+      if (h->route) {
+        const auto& f = h->rpanels[j];
+        TRY(check_launch(launch_refine_panel(f.data(), (int)f.size(), h->sc, h->s), "refine_panel"));
+        continue;
+      }
+      TRY(launch_descs(h, h->rstages[2 * j]));
+      TRY(launch_descs(h, h->rstages[2 * j + 1]));
+    }
+  return GPK_OK;
 }
 
 // Step constants, K_k and D_k, then K_k^{-1} and log det K_k at the current params: the front of
@@ -136,7 +213,7 @@ int enqueue_inverse3(gpk_handle3* h, int apply) {
   AssembleArgs aa[3] = {};
   for (int a = 0; a < 3; ++a) {
     aa[a].x = h->x[a]; aa[a].n = g.n[a]; aa[a].p = g.p[a]; aa[a].kc = h->kc + a;
-    aa[a].jitter = h->prob.jitter; aa[a].K = h->K[a]; aa[a].D = h->D[a]; aa[a].deriv = 2;
+    aa[a].jitter = h->prob.jitter; aa[a].K = h->K[a]; aa[a].Kc = h->Kc[a]; aa[a].D = h->D[a]; aa[a].deriv = 2;
   }
   // (skip = 1: the constants are published by k3_prep; each workgroup derives its axis's own)
   PrepArgs p12{};
@@ -295,6 +372,7 @@ int gpk_create3(const gpk_problem3* p, double freq_scale, gpk_handle3** out) {
     A3_(h->aflag[a], 1);
     A3_(h->GK[a], (size_t)P * P);
     A3_(h->GD[a], (size_t)P * P);
+    if (p->flags & GPK_FLAG3_REFINE) A3_(h->Kc[a], (size_t)P * P);
     const int T = P / 32;  // sweep k reads (k even ? K : Kb): T sweeps end in
     h->Kinv[a] = (T & 1) ? h->Kb[a] : h->K[a];
   }
@@ -338,6 +416,10 @@ int gpk_create3(const gpk_problem3* p, double freq_scale, gpk_handle3** out) {
       return bail(fail(GPK_EHIP, "upload failed"));
   }
   build_stages(h);
+  if (p->flags & GPK_FLAG3_REFINE) {
+    build_refine(h);
+    if (h->route && refine_panel_prepare() != hipSuccess) return bail(fail(GPK_EHIP, "refine_panel_prepare failed"));
+  }
   *out = h;
   return GPK_OK;
 }
@@ -435,6 +517,22 @@ int gpk_stage_variants3(gpk_handle3* h, int32_t* out, int32_t cap, int32_t* n) {
   if (!h || !n || cap < 0 || (cap && !out)) return fail(GPK_EINVAL, "NULL argument");
   *n = (int32_t)h->stages.size();
   for (int k = 0; k < *n && k < cap; ++k) out[k] = stage_variant(h, k);
+  return GPK_OK;
+}
+
+int gpk_refine_info3(gpk_handle3* h, double bound[3], int32_t open[3], int32_t* route) {
+  if (!h || !bound || !open || !route) return fail(GPK_EINVAL, "NULL argument");
+  if (h->rstages.empty())
+    return fail(GPK_EINVAL, "gpk_refine_info3: the handle was created without GPK_FLAG3_REFINE");
+  DevSwitch ds(h->dev);
+  HIPCHK(hipStreamSynchronize(h->s));
+  for (int a = 0; a < 3; ++a) {
+    double pst[2];  // K_00, bits of max diag K^{-1} (gate_open)
+    HIPCHK(hipMemcpy(pst, h->pst[a], sizeof(pst), hipMemcpyDeviceToHost));
+    bound[a] = pst[0] * pst[1];
+    open[a] = bound[a] > REFINE_COND_LB;
+  }
+  *route = h->route;
   return GPK_OK;
 }
 
@@ -630,6 +728,75 @@ int gpk_mode_gemm(int32_t variant, int32_t k, int32_t d1, int32_t d2, int32_t d3
   }
   cleanup();
   if (e != hipSuccess) return fail(GPK_EHIP, std::string("gpk_mode_gemm: ") + hipGetErrorString(e));
+  return GPK_OK;
+}
+
+int gpk_refine_panel(int32_t route, int32_t side, int32_t P, int32_t M, const double* Kinv, const double* Kc,
+                     const double* B, double* X, int32_t iters, double* avg_us) {
+  if (route < 0 || route > 1 || side < 0 || side > 1 || P < 32 || (P & 31) || M < 32 || (M & 31) ||
+      P > K3_MAX_N || !Kinv || !Kc || !B || !X || iters < 0 || (iters && !avg_us))
+    return fail(GPK_EINVAL, "gpk_refine_panel: bad argument (route, side in 0..1, sizes multiples of 32)");
+  if (route == 1 && P > REFINE_PANEL_MAX_P)
+    return fail(GPK_EINVAL, "gpk_refine_panel: the fused route holds two P x 16 panels in LDS: P <= 512");
+  if ((size_t)P * M > 0x7fffffff / 2) return fail(GPK_EINVAL, "gpk_refine_panel: tensor too large");
+  TRY(check_device(0));
+  DevSwitch dsw(0);
+  const size_t nt = (size_t)P * M, nm = (size_t)P * P;
+  std::vector<void*> mem;
+  auto cleanup = [&]() { for (void* p : mem) (void)hipFree(p); };
+  auto up = [&](const double* src, size_t n, double** dst) -> hipError_t {
+    hipError_t e = hipMalloc(dst, n * 8);
+    if (e != hipSuccess) return e;
+    mem.push_back(*dst);
+    return src ? hipMemcpy(*dst, src, n * 8, hipMemcpyHostToDevice) : hipSuccess;
+  };
+  double *dKi = nullptr, *dKc = nullptr, *dB = nullptr, *dX = nullptr, *dW = nullptr;
+  hipError_t e = up(Kinv, nm, &dKi);
+  if (e == hipSuccess) e = up(Kc, nm, &dKc);
+  if (e == hipSuccess) e = up(B, nt, &dB);
+  if (e == hipSuccess) e = up(X, nt, &dX);
+  if (e == hipSuccess) e = up(nullptr, nt, &dW);
+  if (e == hipSuccess && route == 1) e = refine_panel_prepare();
+  if (e != hipSuccess) {
+    cleanup();
+    return fail(e == hipErrorOutOfMemory ? GPK_ENOMEM : GPK_EHIP, std::string("gpk_refine_panel: ") + hipGetErrorString(e));
+  }
+  auto launch = [&]() -> hipError_t {
+    if (route == 1) {
+      RefinePanel f{};
+      f.Kinv = dKi; f.Kc = dKc; f.B = dB; f.X = dX; f.P = P; f.M = M; f.right = side;
+      f.sp = side ? 1 : (size_t)M; f.sc = side ? (size_t)P : 1;
+      return launch_refine_panel(&f, 1, nullptr, 0);
+    }
+    // the step's two GEMMs (build_refine)
+    GemmDesc r = side ? gemm_desc(dX, P, 0, dKc, P, 0, dW, P, M, P, P) : gemm_desc(dKc, P, 0, dX, M, 0, dW, M, P, M, P);
+    r.alpha = -1.0; r.beta = 1.0; r.C0 = dB; r.ldc0 = r.ldc;
+    GemmDesc c = side ? gemm_desc(dW, P, 0, dKi, P, 0, dX, P, M, P, P) : gemm_desc(dKi, P, 0, dW, M, 0, dX, M, P, M, P);
+    c.beta = 1.0; c.C0 = dX; c.ldc0 = c.ldc;
+    hipError_t rc = launch_gemm_auto(&r, 1, nullptr, 0, gemm_variant(&r, 1, 0));
+    return rc == hipSuccess ? launch_gemm_auto(&c, 1, nullptr, 0, gemm_variant(&c, 1, 0)) : rc;
+  };
+  // (X receives the checked launch's result; the timed launches keep refining the device copy)
+  e = launch();
+  if (e == hipSuccess) e = hipDeviceSynchronize();
+  if (e == hipSuccess) e = hipMemcpy(X, dX, nt * 8, hipMemcpyDeviceToHost);
+  if (e == hipSuccess && iters) {
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    e = hipEventCreate(&e0);
+    if (e == hipSuccess) e = hipEventCreate(&e1);
+    if (e == hipSuccess) e = launch();  // one untimed launch, then `iters` back to back
+    if (e == hipSuccess) e = hipEventRecord(e0, 0);
+    for (int it = 0; it < iters && e == hipSuccess; ++it) e = launch();
+    if (e == hipSuccess) e = hipEventRecord(e1, 0);
+    if (e == hipSuccess) e = hipEventSynchronize(e1);
+    float ms = 0.f;
+    if (e == hipSuccess) e = hipEventElapsedTime(&ms, e0, e1);
+    if (e == hipSuccess) *avg_us = ms * 1000.0 / iters;
+    if (e0) (void)hipEventDestroy(e0);
+    if (e1) (void)hipEventDestroy(e1);
+  }
+  cleanup();
+  if (e != hipSuccess) return fail(GPK_EHIP, std::string("gpk_refine_panel: ") + hipGetErrorString(e));
   return GPK_OK;
 }
 

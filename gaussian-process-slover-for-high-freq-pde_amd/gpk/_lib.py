@@ -37,6 +37,9 @@ GPK_FLAG_REFINE_FWD1_ONLY = 2097152
 GPK_FLAG_NO_CLASS_BINS = 4194304
 GPK_FLAG_NO_CLASS_PIPE = 8388608
 GPK_FLAG_NO_CHAIN_LOOKAHEAD = 16777216
+GPK_FLAG3_REFINE, GPK_FLAG3_REFINE_GEMM = 1, 2  # gpk_problem3.flags (their own bit space)
+REFINE_GEMM, REFINE_FUSED = 0, 1  # refinement routes (gpk_refine_info3, gpk_refine_panel)
+REFINE_COND_LB = 100.0  # csrc/gpk_internal.h: a refinement gate opens above this bound
 GPK_INV_SWEEP, GPK_INV_CHAIN, GPK_INV_CHAIN_AUG, GPK_INV_BIG, GPK_INV_BIG_WIDE, GPK_INV_CHAIN_MULTI = range(6)
 INV_PATH_NAMES = {0: "sweep", 1: "chain", 2: "chain_aug", 3: "big", 4: "big_wide", 5: "chain_multi"}
 KIND_IDS = {"SE_Cos_1d": 0, "Matern52_Cos_1d": 1, "SE_1d": 2, "Matern52_1d": 3}
@@ -149,6 +152,9 @@ EXPORTS = {
     "gpk_criterion3": ([ctypes.c_void_p, _dp], ctypes.c_int),
     "gpk_stage_variants3": ([ctypes.c_void_p, _ip, ctypes.c_int32, _ip], ctypes.c_int),
     "gpk_loss_terms3": ([ctypes.c_void_p, _dp], ctypes.c_int),
+    "gpk_refine_info3": ([ctypes.c_void_p, _dp, _ip, _ip], ctypes.c_int),
+    "gpk_refine_panel": ([ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _dp, _dp, _dp, _dp,
+                          ctypes.c_int32, _dp], ctypes.c_int),
     "gpk_mode_gemm": ([ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
                        ctypes.c_int32, ctypes.c_double, _dp, _dp, ctypes.c_double, _dp, _dp,
                        ctypes.c_int32, _dp], ctypes.c_int),
@@ -247,3 +253,19 @@ def mode_gemm(Mat, T, k, alpha=1.0, beta=0.0, C0=None, inplace=False, variant=MO
                                float(beta), dptr(c0) if c0 is not None else None, dptr(C), int(iters),
                                ctypes.byref(us) if iters else None))
     return C, (us.value if iters else None)
+
+
+def refine_panel(Kinv, Kc, B, X, side=0, route=REFINE_FUSED, iters=0):
+    """One refinement step on host operands (gpk_refine_panel): (X + Kinv (B - Kc X), avg_us) for
+    side 0 (X, B: P x M), (X + (B - X Kc) Kinv, avg_us) for side 1 (X, B: M x P); route REFINE_GEMM
+    or REFINE_FUSED; avg_us is None when iters = 0."""
+    Kinv, Kc, B = f64(Kinv), f64(Kc), f64(B)
+    out = f64(X).copy()
+    P = Kinv.shape[0]
+    M = out.shape[1] if side == 0 else out.shape[0]
+    if Kinv.shape != (P, P) or Kc.shape != (P, P) or B.shape != out.shape or out.shape != ((P, M) if side == 0 else (M, P)):
+        raise ValueError("refine_panel: operand shapes do not match")
+    us = ctypes.c_double()
+    check(load().gpk_refine_panel(int(route), int(side), P, M, dptr(Kinv), dptr(Kc), dptr(B), dptr(out),
+                                  int(iters), ctypes.byref(us)))
+    return out, (us.value if iters else None)

@@ -28,6 +28,7 @@ class ExpConfig(Config):
     kernel = None
     nepoch = 1000000
     device = None   # HIP device ordinal (added; the reference ran wherever JAX placed it)
+    refine = None   # 3-axis solver only: -refine=1, the gated refinement of every solve
 
     def __init__(self):
         super(ExpConfig, self).__init__()

@@ -10,7 +10,8 @@ MI355X through gpk_create3 / gpk_step3 (include/gpk.h); there is no CPU fallback
 Same surface as the 2-axis module: GP_solver_3d_single (train with checkpoint / resume, preds,
 compute_early_stopping), test() / evals() and the CLI
 (`python -m gpk.model_GP_solver_3d -equation=poisson_3d-mix_sin -kernel=Matern52_Cos_1d
--nepoch=200`), with its configs in gpk/config3d/.
+-nepoch=200`; `-refine=1` turns the gated refinement of every solve on), with its configs in
+gpk/config3d/.
 """
 import ctypes
 import os
@@ -47,7 +48,9 @@ class DeviceSolver3:
     """One gpk_handle3: problem, params and Adam state resident on the device."""
 
     def __init__(self, eq, kind, xs, src, bvals, Q=30, jitter=1e-6, llk_weight=200.0, logdet=True,
-                 lr=0.01, freq_scale=20.0, device=0, b1=0.9, b2=0.999, eps=1e-8):
+                 lr=0.01, freq_scale=20.0, device=0, b1=0.9, b2=0.999, eps=1e-8, refine=False):
+        """refine: one gated refinement step after every solve of the step (GPK_FLAG3_REFINE);
+        'gemm' also forces its two-GEMM route (GPK_FLAG3_REFINE_GEMM; tests, A/B)."""
         lib = _lib.load()
         if len(xs) != 3:
             raise ValueError("three coordinate axes")
@@ -68,7 +71,10 @@ class DeviceSolver3:
         p.src, p.bvals = dptr(self._src), dptr(self._bvals)
         p.jitter, p.llk_weight, p.logdet = jitter, llk_weight, float(logdet)
         p.lr, p.b1, p.b2, p.eps = lr, b1, b2, eps
-        p.device, p.flags = device, 0
+        p.device, p.flags = device, _lib.GPK_FLAG3_REFINE if refine else 0
+        if refine == "gemm":
+            p.flags |= _lib.GPK_FLAG3_REFINE_GEMM
+        self.refine = bool(refine)
         self._prob = p
         h = ctypes.c_void_p()
         check(lib.gpk_create3(ctypes.byref(p), float(freq_scale), ctypes.byref(h)))
@@ -157,6 +163,18 @@ class DeviceSolver3:
         assert n.value <= out.size
         return [int(v) for v in out[:n.value]]
 
+    def refine_info(self):
+        """The refinement gates of a refine=True solver as the last loss_grad() / step() left
+        them (gpk_refine_info3): {'bound': K_00 max diag K_k^{-1} per axis, 'open': whether that
+        run refined the axis's solves, 'route': _lib.REFINE_GEMM (two gated GEMMs per solve) or _lib.REFINE_FUSED (the panel kernel)}."""
+        bound = np.empty(3)
+        gates = np.zeros(3, np.int32)
+        route = ctypes.c_int32()
+        check(_lib.load().gpk_refine_info3(self._h, dptr(bound),
+                                           gates.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
+                                           ctypes.byref(route)))
+        return {"bound": bound.tolist(), "open": [bool(g) for g in gates], "route": int(route.value)}
+
     LOSS_TERMS = ("loss", "logdet_1", "logdet_2", "logdet_3", "quad", "egap", "bgap")
 
     def loss_terms(self):
@@ -173,7 +191,8 @@ class GP_solver_3d_single(SolverBase):
 
     bvals: boundary_3d(U) of the solution; X_col = (x, y, z); src_vals: N1 x N2 x N3;
     trick_paras: {'kernel': class, 'equation': 'poisson_3d-...' | 'allencahn_3d-...',
-    'llk_weight', 'logdet', 'lr', 'Q', 'freq_scale'} (+ 'nepoch', 'tol' for train);
+    'llk_weight', 'logdet', 'lr', 'Q', 'freq_scale', 'refine'} (+ 'nepoch', 'tol' for train);
+    'refine' (default False): DeviceSolver3's gated refinement of every solve;
     X_test = (x, y, z) test axes and u_test: M1 x M2 x M3, needed by train() and preds()."""
 
     dim = 3
@@ -203,7 +222,8 @@ class GP_solver_3d_single(SolverBase):
         self.dev = DeviceSolver3(eq, self.cov_func.KIND, self.X_col, self.src_vals, self.bvals,
                                  Q=tp.get("Q", 30), jitter=self.jitter, llk_weight=tp["llk_weight"],
                                  logdet=tp.get("logdet", True), lr=tp.get("lr", 0.01),
-                                 freq_scale=tp.get("freq_scale", 20.0), device=int(tp.get("device", device)))
+                                 freq_scale=tp.get("freq_scale", 20.0), device=int(tp.get("device", device)),
+                                 refine=bool(tp.get("refine", False)))
         self._version = 0
 
     # the device holds the params: reading fetches them, train()'s final assignment is a no-op
@@ -347,6 +367,8 @@ def build_config(args, allowed=EQUATIONS_3D):
     config["kernel"] = kernel_class(args.kernel)
     if getattr(args, "device", None) is not None:
         config["device"] = int(args.device)
+    if getattr(args, "refine", None) is not None:
+        config["refine"] = bool(args.refine)
     print("equation: %s, kernel: %s, freq_scale: %d" % (config["equation"], config["kernel"].__name__,
                                                         config["freq_scale"]))
     config["other_paras"] = config["other_paras"] + "-Ncol-%d" % config["N_col"]

@@ -407,8 +407,22 @@ typedef struct gpk_problem3 {
   double jitter, llk_weight, logdet;
   double lr, b1, b2, eps;
   int32_t device;
-  int32_t flags;        /* reserved, 0 */
+  int32_t flags;        /* GPK_FLAG3_* bits, normally 0 */
 } gpk_problem3;
+/* One refinement step X += K_k^{-1} (B - K_k X) after each of the step's eight solves (A1, A2, A3,
+ * T = A1 x_3 K3^{-1}, S, X1, X2, X3), as the 2-axis step has: each is gated on the
+ * device on its own axis's bound K_00 max diag K_k^{-1} (> 100 opens it), placed directly after
+ * the launch that forms the solve, so every later product reads the corrected value.  The handle
+ * keeps a copy of each K_k (written by the assembly launch).  With the bit clear the handle
+ * allocates, captures and launches exactly the unrefined step.  With it set and every gate
+ * closed the results equal the unrefined step's bit for bit.  (Its own bit space: the 2-axis
+ * GPK_FLAG_* values mean nothing here.) */
+#define GPK_FLAG3_REFINE 1
+/* The refinement's kernels (with GPK_FLAG3_REFINE).  Default: the fused panel kernel (one launch
+ * per solve, the X and residual panels in LDS; it measured faster at every size it runs at)
+ * whenever every padded size is <= 512 (both panels fit LDS), else two gated GEMMs per solve.
+ * GPK_FLAG3_REFINE_GEMM forces the two GEMMs (tests, A/B). */
+#define GPK_FLAG3_REFINE_GEMM 2
 
 typedef struct gpk_handle3 gpk_handle3;
 int gpk_create3(const gpk_problem3* p, double freq_scale, gpk_handle3** out);
@@ -442,6 +456,12 @@ int gpk_stage_variants3(gpk_handle3* h, int32_t* out, int32_t cap, int32_t* n);
 /* The terms of the last gpk_loss_grad3's loss: out = {loss, log det K1, log det K2, log det K3,
  * <U, K^{-1} U>, eq_gap, boundary_gap} (read back; nothing is launched). */
 int gpk_loss_terms3(gpk_handle3* h, double out[7]);
+/* Refinement gates of a GPK_FLAG3_REFINE handle as the last graph run (gpk_loss_grad3 / gpk_step3)
+ * left them: bound[k] = K_00 max diag K_k^{-1} of axis k (a lower bound of cond K_k), open[k] = 1
+ * when that run refined axis k's solves (bound > 100), *route the refinement's kernels (0: two
+ * gated GEMMs per solve, 1: the fused panel kernel).  Read back; nothing is launched.  GPK_EINVAL on a handle created
+ * without the flag.  The step's GEMM launches proper stay the six of gpk_stage_variants3. */
+int gpk_refine_info3(gpk_handle3* h, double bound[3], int32_t open[3], int32_t* route);
 
 /* One mode-k product on host operands (tests, A/B timing; the counterpart of gpk_dgemm):
  *   C = alpha (Mat x_k T) + beta C0,   T [d1][d2][d3] row-major, Mat m x d_k row-major,
@@ -454,6 +474,15 @@ int gpk_loss_terms3(gpk_handle3* h, double out[7]);
 int gpk_mode_gemm(int32_t variant, int32_t k, int32_t d1, int32_t d2, int32_t d3, int32_t m, double alpha,
                   const double* Mat, const double* T, double beta, const double* C0, double* C,
                   int32_t iters, double* avg_us);
+
+/* One refinement step X <- X + Kinv (B - Kc X) on host operands, no gate (tests, A/B timing; the
+ * counterpart of gpk_mode_gemm).  side 0: X and B are P x M row-major and the matrices act on
+ * rows; side 1: X and B are M x P and the step is X + (B - X Kc) Kinv.  route 0: the step's two
+ * GEMMs; route 1: the fused panel kernel (P <= 512, else GPK_EINVAL).  P, M multiples of 32,
+ * P <= 1024; Kinv and Kc P x P, any values.  X is overwritten with the result.  iters as
+ * gpk_mode_gemm (the timed launches keep refining the device copy of X). */
+int gpk_refine_panel(int32_t route, int32_t side, int32_t P, int32_t M, const double* Kinv, const double* Kc,
+                     const double* B, double* X, int32_t iters, double* avg_us);
 
 #ifdef __cplusplus
 }

@@ -4,12 +4,15 @@ NumPy fp64 emulation of the 3-axis step's solves at the cases of tests/test_gpu_
 the oracle's loss_grad_3d with every K_k^{-1} application a product with an explicit inverse,
 formed either as the device forms it -- 32-wide Cholesky-Gauss-Jordan sweeps over the identity-
 padded factor (spdinv.hip sweep_kernel), log det from the pivots -- or ("--inverse potri") from
-one Cholesky factorisation of the whole factor.  No refinement step, as the 3-axis step has none.
+one Cholesky factorisation of the whole factor.  No refinement step, as the 3-axis step has none
+by default; "--refine" follows every mode solve (A_k, T, S, X_k) with one fp64 step
+X += K^{-1} (B - K X), ungated, as a GPK_FLAG3_REFINE handle does behind an open gate: the
+explicit K^{-1} inside G_K and the log-dets (from the pivots) stay as they are.
 Prints, per key, the emulation's distance from the long-double yardstick beside the fp64 LU
 oracle's.  The emulation has no layout to get wrong: where the device's ratio to the LU oracle
 matches the sweep emulation's, the excess is the algorithm's.
 
-usage: python tools/kron3_sweep_emulation.py [--inverse sweep|potri] [case ...]
+usage: python tools/kron3_sweep_emulation.py [--inverse sweep|potri] [--refine] [case ...]
 """
 import argparse
 import os
@@ -51,33 +54,41 @@ def potri_inverse(K):
     return Li.T @ Li, 2.0 * float(np.sum(np.log(np.diag(L))))
 
 
-def emulate(prob, params, inverse):
-    saved = O._lu, O._solve, O._slogdet_from_lu
-    O._lu = lambda K: ("inv", inverse(K))
+def emulate(prob, params, inverse, refine=False):
+    saved = O._lu, O._solve, O._slogdet_from_lu, O._mode_solve
+    O._lu = lambda K: ("inv", inverse(K), K)
     O._solve = lambda f, B: f[1][0] @ B
     O._slogdet_from_lu = lambda f: f[1][1]
+    if refine:
+        def mode_solve(f, T, k):
+            B = O._unfold(T, k)
+            X = f[1][0] @ B
+            X = X + f[1][0] @ (B - f[2] @ X)
+            return O._fold(X, k, T.shape)
+        O._mode_solve = mode_solve
     try:
         terms = {}
         loss, grad = O.loss_grad_3d(prob, params, terms=terms)
     finally:
-        O._lu, O._solve, O._slogdet_from_lu = saved
+        O._lu, O._solve, O._slogdet_from_lu, O._mode_solve = saved
     return loss, grad, terms
 
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--inverse", default="sweep", choices=["sweep", "potri"])
+    ap.add_argument("--refine", action="store_true")
     ap.add_argument("cases", nargs="*", default=list(T.ALL_CASES))
     a = ap.parse_args()
     inverse = sweep_inverse if a.inverse == "sweep" else potri_inverse
     for case in a.cases:
         (eq, kind, ns, Q), P, _ = T.ALL_CASES[case]
         ref = T._reference(eq, kind, ns, Q)
-        d = T._distances(emulate(ref["prob"], ref["params"], inverse), ref["ext"])
+        d = T._distances(emulate(ref["prob"], ref["params"], inverse, a.refine), ref["ext"])
         print(f"== {case} ns={ns} padded={P} fp64 tol {ref['tol']:.2e}")
         for k in d:
             lu = ref["lu_err"][k]
-            print(f"   {k:16s} {a.inverse} {d[k]:.3e}  lu {lu:.3e}  ratio {d[k] / lu if lu else float('inf'):8.2f}")
+            print(f"   {k:16s} {a.inverse}{'+refine' if a.refine else ''} {d[k]:.3e}  lu {lu:.3e}  ratio {d[k] / lu if lu else float('inf'):8.2f}")
 
 
 if __name__ == "__main__":
