@@ -74,22 +74,18 @@ int gpk_kernel_matrices(int32_t kind, int32_t deriv, const double* x1, int32_t n
   TRY(check_device(dev));
   AxisConst hk;
   host_axis_const(logw, logls, freq, q, &hk);
+  CallScratch tmp("gpk_kernel_matrices");
   double *dx1, *dx2, *dK, *dD = nullptr;
   AxisConst* dkc;
   size_t nn = (size_t)n1 * n2;
-  HIPCHK(hipMalloc(&dx1, n1 * sizeof(double)));
-  HIPCHK(hipMalloc(&dx2, n2 * sizeof(double)));
-  HIPCHK(hipMalloc(&dK, nn * sizeof(double)));
-  if (deriv) HIPCHK(hipMalloc(&dD, nn * sizeof(double)));
-  HIPCHK(hipMalloc(&dkc, sizeof(AxisConst)));
-  HIPCHK(hipMemcpy(dx1, x1, n1 * sizeof(double), hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(dx2, x2, n2 * sizeof(double), hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(dkc, &hk, sizeof(AxisConst), hipMemcpyHostToDevice));
+  TRY(tmp.upload(&dx1, x1, n1));
+  TRY(tmp.upload(&dx2, x2, n2));
+  TRY(tmp.alloc(&dK, nn));
+  if (deriv) TRY(tmp.alloc(&dD, nn));
+  TRY(tmp.upload(&dkc, &hk, 1));
   TRY(check_launch(launch_cross(kind, q, dx1, n1, dx2, n2, n2, dkc, jitter, deriv, dK, dD, 0), "cross"));
   HIPCHK(hipMemcpy(K_out, dK, nn * sizeof(double), hipMemcpyDeviceToHost));
   if (deriv) HIPCHK(hipMemcpy(D_out, dD, nn * sizeof(double), hipMemcpyDeviceToHost));
-  (void)hipFree(dx1); (void)hipFree(dx2); (void)hipFree(dK); (void)hipFree(dkc);
-  if (dD) (void)hipFree(dD);
   return GPK_OK;
 }
 
@@ -105,28 +101,15 @@ int gpk_kernel_pairs(int32_t kind, int32_t deriv, const double* x1, const double
   TRY(check_device(dev));
   AxisConst hk;
   host_axis_const(logw, logls, freq, q, &hk);
-  double *d1 = nullptr, *d2 = nullptr, *dout = nullptr;
-  AxisConst* dkc = nullptr;
-  auto cleanup = [&]() {
-    if (d1) (void)hipFree(d1);
-    if (d2) (void)hipFree(d2);
-    if (dout) (void)hipFree(dout);
-    if (dkc) (void)hipFree(dkc);
-  };
-  const size_t bytes = (size_t)n * sizeof(double);
-  if (hipMalloc(&d1, bytes) != hipSuccess || hipMalloc(&d2, bytes) != hipSuccess ||
-      hipMalloc(&dout, bytes) != hipSuccess || hipMalloc(&dkc, sizeof(AxisConst)) != hipSuccess) {
-    cleanup();
-    return fail(GPK_ENOMEM, "hipMalloc failed");
-  }
-  hipError_t e = hipMemcpy(d1, x1, bytes, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(d2, x2, bytes, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(dkc, &hk, sizeof(AxisConst), hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = launch_pairs(kind, q, d1, d2, n, dkc, deriv, dout, 0);
-  if (e == hipSuccess) e = hipMemcpy(out, dout, bytes, hipMemcpyDeviceToHost);
-  cleanup();
-  if (e != hipSuccess) return fail(GPK_EHIP, std::string("kernel_pairs: ") + hipGetErrorString(e));
-  return GPK_OK;
+  CallScratch tmp("kernel_pairs");
+  double *d1, *d2, *dout;
+  AxisConst* dkc;
+  TRY(tmp.upload(&d1, x1, (size_t)n));
+  TRY(tmp.upload(&d2, x2, (size_t)n));
+  TRY(tmp.alloc(&dout, (size_t)n));
+  TRY(tmp.upload(&dkc, &hk, 1));
+  TRY(check_launch(launch_pairs(kind, q, d1, d2, n, dkc, deriv, dout, 0), "kernel_pairs"));
+  return check_launch(hipMemcpy(out, dout, (size_t)n * sizeof(double), hipMemcpyDeviceToHost), "kernel_pairs");
 }
 
 int gpk_sync(gpk_handle* h) {
@@ -213,43 +196,32 @@ int gpk_predict(gpk_handle* h, const double* xte1, int32_t m1, const double* xte
   h->profiling = prof;
   TRY(rc);
   const int M1p = pad_up(m1), P1 = L.p1;
-  std::vector<void*> tmp;
-  auto dalloc = [&](double** p, size_t n) -> int {
-    HIPCHK(hipMalloc((void**)p, std::max<size_t>(n, 2) * sizeof(double)));
-    tmp.push_back(*p);
-    HIPCHK(hipMemsetAsync(*p, 0, std::max<size_t>(n, 2) * sizeof(double), h->s));
-    return GPK_OK;
-  };
-  auto cleanup = [&]() {
-    (void)hipStreamSynchronize(h->s);
-    for (void* p : tmp) (void)hipFree(p);
-  };
+  CallScratch tmp("predict", h->s);  // (zero-filled: the padding of Kmn and of every product)
   double *dx1, *Kmn1, *res;
-  int r = GPK_OK;
-  if ((r = dalloc(&dx1, m1)) || (r = dalloc(&Kmn1, (size_t)M1p * P1))) { cleanup(); return r; }
-  (void)hipMemcpyAsync(dx1, xte1, m1 * sizeof(double), hipMemcpyHostToDevice, h->s);
+  TRY(tmp.alloc(&dx1, m1, true));
+  TRY(tmp.alloc(&Kmn1, (size_t)M1p * P1, true));
+  HIPCHK(hipMemcpyAsync(dx1, xte1, m1 * sizeof(double), hipMemcpyHostToDevice, h->s));
   // Kmn = kappa(xte_i, x_j) (no jitter), zero-padded to M1p x P1   (model_GP_solver_2d.py:198-202)
-  r = check_launch(launch_cross(h->prob.kind, L.q, dx1, m1, h->x1, L.n1, P1, h->kc, 0.0, 0, Kmn1, nullptr, h->s), "cross");
-  if (r) { cleanup(); return r; }
+  TRY(check_launch(launch_cross(h->prob.kind, L.q, dx1, m1, h->x1, L.n1, P1, h->kc, 0.0, 0, Kmn1, nullptr, h->s), "cross"));
   if (L.dim == 1) {
-    double* alpha;
-    if ((r = dalloc(&alpha, P1)) || (r = dalloc(&res, M1p))) { cleanup(); return r; }
-    double* rv;
-    if ((r = dalloc(&rv, P1))) { cleanup(); return r; }
+    double *alpha, *rv;
+    TRY(tmp.alloc(&alpha, P1, true));
+    TRY(tmp.alloc(&res, M1p, true));
+    TRY(tmp.alloc(&rv, P1, true));
     auto gv = [&](const double* A, const double* x, double* y, int rows, double al, const double* C0,
                   double be) {
       GemvDesc g{};
       g.A = A; g.lda = P1; g.x = x; g.y = y; g.p = P1; g.rows = rows; g.alpha = al;
       g.C0 = C0; g.beta = be; g.epi = EPI_STORE;
       gemv_operand(h, g);
-      (void)launch_gemv(g, h->s);
+      return check_launch(launch_gemv(g, h->s), "gemv");
     };
     // alpha = K^{-1} u with one refinement step (matches solve() accuracy; 1d.py:176-179)
-    gv(h->Kinv[0], h->Up, alpha, P1, 1.0, nullptr, 0.0);
-    gv(h->Kc[0], alpha, rv, P1, -1.0, h->Up, 1.0);
-    gv(h->Kinv[0], rv, alpha, P1, 1.0, alpha, 1.0);
-    gv(Kmn1, alpha, res, m1, 1.0, nullptr, 0.0);  // preds = Kmn K^{-1} u
-    (void)hipMemcpyAsync(out, res, m1 * sizeof(double), hipMemcpyDeviceToHost, h->s);
+    TRY(gv(h->Kinv[0], h->Up, alpha, P1, 1.0, nullptr, 0.0));
+    TRY(gv(h->Kc[0], alpha, rv, P1, -1.0, h->Up, 1.0));
+    TRY(gv(h->Kinv[0], rv, alpha, P1, 1.0, alpha, 1.0));
+    TRY(gv(Kmn1, alpha, res, m1, 1.0, nullptr, 0.0));  // preds = Kmn K^{-1} u
+    HIPCHK(hipMemcpyAsync(out, res, m1 * sizeof(double), hipMemcpyDeviceToHost, h->s));
   } else {
     // U_pred = Kmn2 (K2^{-1} (Kmn1 K1^{-1} U)^T), associated exactly as the reference does
     // (model_GP_solver_2d.py:185-220: M1 = Kmn K1inv_U, M2 = solve(K2, M1^T), Kmn2 M2): every
@@ -258,40 +230,28 @@ int gpk_predict(gpk_handle* h, const double* xte1, int32_t m1, const double* xte
     // Kmn1 S Kmn2^T cost up to 0.37 relative L2 at C5 with a random field.)
     const int M2p = pad_up(m2), P2 = L.p2;
     double *dx2, *Kmn2, *Aw, *Rw, *Mw, *Nw, *Rm;
-    if ((r = dalloc(&dx2, m2)) || (r = dalloc(&Kmn2, (size_t)M2p * P2)) || (r = dalloc(&Aw, (size_t)P1 * P2)) ||
-        (r = dalloc(&Rw, (size_t)P1 * P2)) || (r = dalloc(&Mw, (size_t)M1p * P2)) ||
-        (r = dalloc(&Nw, (size_t)M1p * P2)) || (r = dalloc(&Rm, (size_t)M1p * P2)) ||
-        (r = dalloc(&res, (size_t)M1p * M2p))) { cleanup(); return r; }
-    (void)hipMemcpyAsync(dx2, xte2, m2 * sizeof(double), hipMemcpyHostToDevice, h->s);
-    (void)launch_cross(h->prob.kind, L.q, dx2, m2, h->x2, L.n2, P2, h->kc + 1, 0.0, 0, Kmn2, nullptr, h->s);
-    GemmDesc d[8] = {};
-    auto mk = [](GemmDesc& g, const double* A, int lda, int ta, const double* B, int ldb, int tb,
-                 double* C, int ldc, int M, int N, int K) {
-      g.A = A; g.lda = lda; g.ta = ta; g.B = B; g.ldb = ldb; g.tb = tb; g.C = C; g.ldc = ldc;
-      g.M = M; g.N = N; g.K = K; g.alpha = 1.0; g.epi = EPI_STORE;
-    };
-    // A = K1^{-1} U and N = M1 K2^{-1}, each with one refinement step (solve() accuracy)
-    mk(d[0], h->Kinv[0], P1, 0, h->Up, P2, 0, Aw, P2, P1, P2, P1);
-    mk(d[1], h->Kc[0], P1, 0, Aw, P2, 0, Rw, P2, P1, P2, P1);          // Rw = U - K1 A
-    d[1].alpha = -1.0; d[1].beta = 1.0; d[1].C0 = h->Up; d[1].ldc0 = P2;
-    mk(d[2], h->Kinv[0], P1, 0, Rw, P2, 0, Aw, P2, P1, P2, P1);        // A += K1^{-1} Rw
-    d[2].beta = 1.0; d[2].C0 = Aw; d[2].ldc0 = P2;
-    mk(d[3], Kmn1, P1, 0, Aw, P2, 0, Mw, P2, M1p, P2, P1);             // M1 = Kmn1 A
-    mk(d[4], Mw, P2, 0, h->Kinv[1], P2, 0, Nw, P2, M1p, P2, P2);       // N = M1 K2^{-1} = M2^T
-    mk(d[5], Nw, P2, 0, h->Kc[1], P2, 0, Rm, P2, M1p, P2, P2);         // Rm = M1 - N K2
-    d[5].alpha = -1.0; d[5].beta = 1.0; d[5].C0 = Mw; d[5].ldc0 = P2;
-    mk(d[6], Rm, P2, 0, h->Kinv[1], P2, 0, Nw, P2, M1p, P2, P2);       // N += Rm K2^{-1}
-    d[6].beta = 1.0; d[6].C0 = Nw; d[6].ldc0 = P2;
-    mk(d[7], Nw, P2, 0, Kmn2, P2, 1, res, M2p, M1p, M2p, P2);       // U_pred = N Kmn2^T
+    TRY(tmp.alloc(&dx2, m2, true));
+    TRY(tmp.alloc(&Kmn2, (size_t)M2p * P2, true));
+    for (double** w : {&Aw, &Rw}) TRY(tmp.alloc(w, (size_t)P1 * P2, true));
+    for (double** w : {&Mw, &Nw, &Rm}) TRY(tmp.alloc(w, (size_t)M1p * P2, true));
+    TRY(tmp.alloc(&res, (size_t)M1p * M2p, true));
+    HIPCHK(hipMemcpyAsync(dx2, xte2, m2 * sizeof(double), hipMemcpyHostToDevice, h->s));
+    TRY(check_launch(launch_cross(h->prob.kind, L.q, dx2, m2, h->x2, L.n2, P2, h->kc + 1, 0.0, 0, Kmn2, nullptr, h->s), "cross"));
+    // A = K1^{-1} U and N = M1 K2^{-1} = M2^T, each with one refinement step (solve() accuracy)
+    const RefinedSolve sA = refined_solve(false, h->Kc[0], h->Kinv[0], h->Up, Aw, Rw, P1, P2, nullptr),
+                       sN = refined_solve(true, h->Kc[1], h->Kinv[1], Mw, Nw, Rm, M1p, P2, nullptr);
+    const GemmDesc d[8] = {sA.solve, sA.resid, sA.fix,
+                           gemm_desc(Kmn1, P1, 0, Aw, P2, 0, Mw, P2, M1p, P2, P1),  // M1 = Kmn1 A
+                           sN.solve, sN.resid, sN.fix,
+                           gemm_desc(Nw, P2, 0, Kmn2, P2, 1, res, M2p, M1p, M2p, P2)};  // U_pred = N Kmn2^T
     const int force_big = gemm_force(h->prob.flags);
-    for (int k = 0; k < 8; ++k)
-      (void)launch_gemm_auto(d + k, 1, h->sc, h->s, gemm_variant(d + k, 1, force_big));
+    for (const GemmDesc& g : d)
+      TRY(check_launch(launch_gemm_auto(&g, 1, h->sc, h->s, gemm_variant(&g, 1, force_big)), "gemm"));
     for (int i = 0; i < m1; ++i)
-      (void)hipMemcpyAsync(out + (size_t)i * m2, res + (size_t)i * M2p, m2 * sizeof(double),
-                           hipMemcpyDeviceToHost, h->s);
+      HIPCHK(hipMemcpyAsync(out + (size_t)i * m2, res + (size_t)i * M2p, m2 * sizeof(double),
+                            hipMemcpyDeviceToHost, h->s));
   }
-  hipError_t e = hipStreamSynchronize(h->s);
-  cleanup();
+  const hipError_t e = hipStreamSynchronize(h->s);
   if (e != hipSuccess) return fail(GPK_EHIP, std::string("predict: ") + hipGetErrorString(e));
   return read_status(h);
 }

@@ -1,8 +1,9 @@
 // gpk_diag.cpp — measurement and diagnostic entry points: per-stage and per-kernel timing, the
-// forward fields, the standalone GEMM, the trace hooks.  No solver entry point (gpk_create,
-// gpk_step, gpk_prepare, gpk_loss_grad, gpk_predict) reaches this file, and it reaches the step
-// only through the functions gpk_host.h declares.
+// forward fields, the standalone GEMM, mode-k product and refinement step, the trace hooks.  No
+// solver entry point (gpk_create, gpk_step, gpk_prepare, gpk_loss_grad, gpk_predict, gpk_*3)
+// reaches this file, and it reaches the step only through the functions gpk_host.h declares.
 #include "gpk_host.h"
+#include "gpk_kron3.h"
 #include "gpk_trace.h"
 #include "fields_dd.h"
 
@@ -208,23 +209,20 @@ int gpk_forward_field(gpk_handle* h, int32_t what, double* out, int64_t n) {
   if (n != want) return fail(GPK_EINVAL, "output size mismatch");
   DevSwitch ds(h->dev);
   std::vector<double> host;
+  CallScratch scratch("gpk_forward_field", h->s);
   double* tmp = nullptr;
-  auto cleanup = [&]() {
-    if (tmp) (void)hipFree(tmp);
-  };
   if (what <= 1) {  // K factor: assemble at the current params (kappa + jitter I)
     const int a = what;
     const int na = axis_n(L, a);
     TRY(check_launch(launch_prep2(h->params, L, h->kc, h->sc, h->count, 0, h->hyper.b1, h->hyper.b2, h->s), "prep"));
-    HIPCHK(hipMalloc(&tmp, (size_t)na * na * sizeof(double)));
+    TRY(scratch.alloc(&tmp, (size_t)na * na));
     const double* xa = axis_x(h, a);
-    int rc = check_launch(launch_cross(h->prob.kind, L.q, xa, na, xa, na, na, h->kc + a, h->prob.jitter,
-                                       0, tmp, nullptr, h->s), "cross");
-    if (rc == GPK_OK && hipMemcpyAsync(out, tmp, n * sizeof(double), hipMemcpyDeviceToHost, h->s) != hipSuccess)
-      rc = fail(GPK_EHIP, "copy");
-    if (rc == GPK_OK && hipStreamSynchronize(h->s) != hipSuccess) rc = fail(GPK_EHIP, "sync");
-    cleanup();
-    return rc;
+    TRY(check_launch(launch_cross(h->prob.kind, L.q, xa, na, xa, na, na, h->kc + a, h->prob.jitter,
+                                  0, tmp, nullptr, h->s), "cross"));
+    if (hipMemcpyAsync(out, tmp, n * sizeof(double), hipMemcpyDeviceToHost, h->s) != hipSuccess)
+      return fail(GPK_EHIP, "copy");
+    if (hipStreamSynchronize(h->s) != hipSuccess) return fail(GPK_EHIP, "sync");
+    return GPK_OK;
   }
   double loss = 0.0;
   TRY(gpk_loss_grad(h, &loss, nullptr));  // device buffers now hold the forward quantities
@@ -256,18 +254,16 @@ int gpk_forward_field(gpk_handle* h, int32_t what, double* out, int64_t n) {
     const int P = L.p1;
     const double* src = h->alpha;
     if (what == 4) {  // u_xx = D alpha
-      HIPCHK(hipMalloc(&tmp, P * sizeof(double)));
+      TRY(scratch.alloc(&tmp, P));
       GemvDesc g{};
       g.A = h->D[0]; g.lda = P; g.x = h->alpha; g.y = tmp; g.p = P; g.rows = P; g.alpha = 1.0;
       g.epi = EPI_STORE;
       gemv_operand(h, g);
-      int rc = check_launch(launch_gemv(g, h->s), "gemv");
-      if (rc) { cleanup(); return rc; }
+      TRY(check_launch(launch_gemv(g, h->s), "gemv"));
       src = tmp;
     }
     hipError_t e = hipMemcpyAsync(out, src, n * sizeof(double), hipMemcpyDeviceToHost, h->s);
     if (e == hipSuccess) e = hipStreamSynchronize(h->s);
-    cleanup();
     if (e != hipSuccess) return fail(GPK_EHIP, hipGetErrorString(e));
     return GPK_OK;
   }
@@ -316,7 +312,7 @@ int gpk_forward_field(gpk_handle* h, int32_t what, double* out, int64_t n) {
   }
   const double* src = (what == 3) ? h->Bt : h->A;
   if (what >= 4) {  // U_xx = D1 A  /  U_yy = Bt D2^T
-    HIPCHK(hipMalloc(&tmp, (size_t)P1 * P2 * sizeof(double)));
+    TRY(scratch.alloc(&tmp, (size_t)P1 * P2));
     GemmDesc g{};
     if (what == 4) {
       g.A = h->D[0]; g.lda = P1; g.B = h->A; g.ldb = P2; g.K = P1;
@@ -326,13 +322,12 @@ int gpk_forward_field(gpk_handle* h, int32_t what, double* out, int64_t n) {
     g.C = tmp; g.ldc = P2; g.M = P1; g.N = P2; g.alpha = 1.0; g.epi = EPI_STORE;
     hipError_t e = launch_gemm_auto(&g, 1, h->sc, h->s,
                                     gemm_variant(&g, 1, gemm_force(h->prob.flags)));
-    if (e != hipSuccess) { cleanup(); return fail(GPK_EHIP, hipGetErrorString(e)); }
+    if (e != hipSuccess) return fail(GPK_EHIP, hipGetErrorString(e));
     src = tmp;
   }
   host.resize((size_t)P1 * P2);
   hipError_t e = hipMemcpyAsync(host.data(), src, host.size() * sizeof(double), hipMemcpyDeviceToHost, h->s);
   if (e == hipSuccess) e = hipStreamSynchronize(h->s);
-  cleanup();
   if (e != hipSuccess) return fail(GPK_EHIP, hipGetErrorString(e));
   for (int64_t i = 0; i < n1; ++i)
     for (int64_t j = 0; j < n2; ++j) {
@@ -357,28 +352,19 @@ int gpk_fields_dd(int32_t kind, int32_t deriv, const double* d, int32_t n, doubl
   TRY(check_device(dev));
   const double om = TWO_PI * freq, oml = om_low(freq, om);  // (gpk_api.cpp host_axis_const)
   const size_t nb = (size_t)n * sizeof(double);
-  double *dd_ = nullptr, *dh = nullptr, *dl = nullptr;
-  auto cleanup = [&]() {
-    if (dd_) (void)hipFree(dd_);
-    if (dh) (void)hipFree(dh);
-    if (dl) (void)hipFree(dl);
-  };
-  if (hipMalloc(&dd_, nb) != hipSuccess || hipMalloc(&dh, 6 * nb) != hipSuccess ||
-      hipMalloc(&dl, 6 * nb) != hipSuccess) {
-    cleanup();
-    return fail(GPK_ENOMEM, "hipMalloc failed");
-  }
-  hipError_t e = hipMemcpy(dd_, d, nb, hipMemcpyHostToDevice);
-  if (e == hipSuccess)
-    e = kind == SE_COS         ? launch_fields_dd<false, true>(deriv, dd_, n, a, om, oml, dh, dl)
+  CallScratch tmp("fields_dd");
+  double *dd_, *dh, *dl;
+  TRY(tmp.upload(&dd_, d, (size_t)n));
+  TRY(tmp.alloc(&dh, (size_t)6 * n));
+  TRY(tmp.alloc(&dl, (size_t)6 * n));
+  hipError_t e =
+      kind == SE_COS           ? launch_fields_dd<false, true>(deriv, dd_, n, a, om, oml, dh, dl)
         : kind == MATERN52_COS ? launch_fields_dd<true, true>(deriv, dd_, n, a, om, oml, dh, dl)
         : kind == SE           ? launch_fields_dd<false, false>(deriv, dd_, n, a, om, oml, dh, dl)
                                : launch_fields_dd<true, false>(deriv, dd_, n, a, om, oml, dh, dl);
   if (e == hipSuccess) e = hipMemcpy(hi, dh, 6 * nb, hipMemcpyDeviceToHost);
   if (e == hipSuccess) e = hipMemcpy(lo, dl, 6 * nb, hipMemcpyDeviceToHost);
-  cleanup();
-  if (e != hipSuccess) return fail(GPK_EHIP, std::string("fields_dd: ") + hipGetErrorString(e));
-  return GPK_OK;
+  return check_launch(e, "fields_dd");
 }
 
 // large path: a freshly assembled K with pivot block 0 factored and (panel) sweep 0's panel formed
@@ -616,26 +602,15 @@ int gpk_dgemm(int32_t variant, int32_t M, int32_t N, int32_t K, double alpha, co
     return fail(GPK_EINVAL, "gpk_dgemm: leading dimension shorter than a row");
   TRY(check_device(0));
   DevSwitch dsw(0);
-  std::vector<void*> mem;
-  auto cleanup = [&]() { for (void* p : mem) (void)hipFree(p); };
-  auto up = [&](const double* src, size_t n, double** dst) -> hipError_t {
-    hipError_t e = hipMalloc(dst, n * 8);
-    if (e != hipSuccess) return e;
-    mem.push_back(*dst);
-    return src ? hipMemcpy(*dst, src, n * 8, hipMemcpyHostToDevice) : hipSuccess;
-  };
+  CallScratch tmp("gpk_dgemm");
   GemmDesc d{};
   double *dA = nullptr, *dB = nullptr, *dA2 = nullptr, *dB2 = nullptr, *dC = nullptr, *dC0 = nullptr;
-  hipError_t e = up(A, na, &dA);
-  if (e == hipSuccess) e = up(B, nb, &dB);
-  if (e == hipSuccess && K2) e = up(A2, na2, &dA2);
-  if (e == hipSuccess && K2) e = up(B2, nb2, &dB2);
-  if (e == hipSuccess) e = up(C0 == C ? C : nullptr, nc, &dC);
-  if (e == hipSuccess && C0 && C0 != C) e = up(C0, nc, &dC0);
-  if (e != hipSuccess) {
-    cleanup();
-    return fail(e == hipErrorOutOfMemory ? GPK_ENOMEM : GPK_EHIP, std::string("gpk_dgemm: ") + hipGetErrorString(e));
-  }
+  TRY(tmp.upload(&dA, A, na));
+  TRY(tmp.upload(&dB, B, nb));
+  if (K2) TRY(tmp.upload(&dA2, A2, na2));
+  if (K2) TRY(tmp.upload(&dB2, B2, nb2));
+  TRY(C0 == C ? tmp.upload(&dC, C, nc) : tmp.alloc(&dC, nc));
+  if (C0 && C0 != C) TRY(tmp.upload(&dC0, C0, nc));
   d.A = dA; d.lda = lda; d.ta = ta ? 1 : 0; d.B = dB; d.ldb = ldb; d.tb = tb ? 1 : 0;
   d.A2 = dA2; d.lda2 = lda2; d.ta2 = ta2 ? 1 : 0; d.B2 = dB2; d.ldb2 = ldb2; d.tb2 = tb2 ? 1 : 0;
   d.alpha = alpha; d.alpha2 = alpha2; d.K2 = K2;
@@ -644,14 +619,110 @@ int gpk_dgemm(int32_t variant, int32_t M, int32_t N, int32_t K, double alpha, co
   const int v = variant ? variant : gemm_variant(&d, 1, 0);
   auto launch = [&]() { return launch_gemm_auto(&d, 1, nullptr, 0, v); };
   // (an in-place C0 == C update is checked once; timed launches then repeat it on their own output)
-  e = launch();
+  hipError_t e = launch();
   if (e == hipSuccess) e = hipDeviceSynchronize();
   if (e == hipSuccess) e = hipMemcpy(C, dC, nc * 8, hipMemcpyDeviceToHost);
   // (timing only: with C0 == C every timed launch updates dC in place, so each one reads the
   // previous launch's output as its C0 -- same shapes and work, different values; the result
   // copied back above is the first launch's)
   if (e == hipSuccess && iters) e = time_launches(0, iters, 1, launch, avg_us);
-  cleanup();
-  if (e != hipSuccess) return fail(GPK_EHIP, std::string("gpk_dgemm: ") + hipGetErrorString(e));
-  return GPK_OK;
+  return check_launch(e, "gpk_dgemm");
+}
+
+int gpk_mode_gemm(int32_t variant, int32_t k, int32_t d1, int32_t d2, int32_t d3, int32_t m, double alpha,
+                  const double* Mat, const double* T, double beta, const double* C0, double* C,
+                  int32_t iters, double* avg_us) {
+  if (variant < 0 || variant > 3 || k < 1 || k > 3 || d1 <= 0 || d2 <= 0 || d3 <= 0 || m <= 0 ||
+      ((d1 | d2 | d3 | m) & 31) || !Mat || !T || !C || iters < 0 || (iters && !avg_us))
+    return fail(GPK_EINVAL, "gpk_mode_gemm: bad argument (k in 1..3, sizes multiples of 32)");
+  if (k == 2 && d1 > 65535) return fail(GPK_EINVAL, "gpk_mode_gemm: mode 2 takes at most 65535 slabs");
+  const int dk = k == 1 ? d1 : k == 2 ? d2 : d3;
+  const size_t nt = (size_t)d1 * d2 * d3, nc = nt / dk * m, nm = (size_t)m * dk;
+  if (nt / dk > 0x7fffffff / 2) return fail(GPK_EINVAL, "gpk_mode_gemm: tensor too large");
+  TRY(check_device(0));
+  DevSwitch dsw(0);
+  CallScratch tmp("gpk_mode_gemm");
+  const bool permute = k == 2 && variant == 1;
+  double *dM = nullptr, *dT = nullptr, *dC = nullptr, *dC0 = nullptr, *dTp = nullptr, *dCp = nullptr,
+         *dC0p = nullptr;
+  TRY(tmp.upload(&dM, Mat, nm));
+  TRY(tmp.upload(&dT, T, nt));
+  TRY(C0 == C ? tmp.upload(&dC, C, nc) : tmp.alloc(&dC, nc));
+  if (C0 && C0 != C) TRY(tmp.upload(&dC0, C0, nc));
+  if (permute) TRY(tmp.alloc(&dTp, nt));
+  if (permute) TRY(tmp.alloc(&dCp, nc));
+  if (permute && C0) TRY(tmp.alloc(&dC0p, nc));
+  const double* c0 = C0 ? (C0 == C ? dC : dC0) : nullptr;
+  const double be = C0 ? beta : 0.0;
+  auto one = [&](GemmDesc d, const double* c0_) {
+    d.alpha = alpha;
+    if (c0_) { d.beta = be; d.C0 = c0_; d.ldc0 = d.ldc; }
+    return launch_gemm_auto(&d, 1, nullptr, 0, gemm_variant(&d, 1, 0));
+  };
+  const int n23 = d2 * d3, n13 = d1 * d3, n12 = d1 * d2;
+  auto launch = [&]() -> hipError_t {
+    if (k == 1) return one(gemm_desc(dM, d1, 0, dT, n23, 0, dC, n23, m, n23, d1), c0);
+    if (k == 3) return one(gemm_desc(dT, d3, 0, dM, d3, 1, dC, m, n12, m, d3), c0);
+    if (!permute) {  // the slab kernel (variant 2 / 3: its 32 / 64 tile forced)
+      SlabGemm sg{};
+      sg.A = dM; sg.B = dT; sg.sB = (size_t)n23; sg.C = dC; sg.sC = (size_t)m * d3; sg.C0 = c0; sg.sC0 = sg.sC;
+      sg.M = m; sg.N = d3; sg.K = d2; sg.nb = d1; sg.alpha = alpha; sg.beta = be;
+      return launch_gemm_slab(sg, 0, variant == 2 ? 32 : variant == 3 ? 64 : 0);
+    }
+    // the step's route: permuted copy [d2][d1][d3], one GEMM on its rows, permuted back
+    K3Geom gi{}, go{};
+    gi.p[0] = gi.n[0] = d1; gi.p[1] = gi.n[1] = d2; gi.p[2] = gi.n[2] = d3;
+    go.p[0] = go.n[0] = m; go.p[1] = go.n[1] = d1; go.p[2] = go.n[2] = d3;   // [m][d1][d3] -> [d1][m][d3]
+    K3Geom gc = go;
+    gc.p[0] = gc.n[0] = d1; gc.p[1] = gc.n[1] = m;                             // [d1][m][d3] -> [m][d1][d3]
+    hipError_t r = k3_launch_permute(dT, dTp, gi, 0);
+    if (r == hipSuccess && c0) r = k3_launch_permute(c0, dC0p, gc, 0);
+    if (r == hipSuccess) r = one(gemm_desc(dM, d2, 0, dTp, n13, 0, dCp, n13, m, n13, d2), c0 ? dC0p : nullptr);
+    if (r == hipSuccess) r = k3_launch_permute(dCp, dC, go, 0);
+    return r;
+  };
+  // (as gpk_dgemm: C receives the checked launch's result; with C0 == C the timed launches keep
+  // updating the device copy in place -- same work, each on the last one's output)
+  hipError_t e = launch();
+  if (e == hipSuccess) e = hipDeviceSynchronize();
+  if (e == hipSuccess) e = hipMemcpy(C, dC, nc * 8, hipMemcpyDeviceToHost);
+  if (e == hipSuccess && iters) e = time_launches(0, iters, 1, launch, avg_us);
+  return check_launch(e, "gpk_mode_gemm");
+}
+
+int gpk_refine_panel(int32_t route, int32_t side, int32_t P, int32_t M, const double* Kinv, const double* Kc,
+                     const double* B, double* X, int32_t iters, double* avg_us) {
+  if (route < 0 || route > 1 || side < 0 || side > 1 || P < 32 || (P & 31) || M < 32 || (M & 31) ||
+      P > K3_MAX_N || !Kinv || !Kc || !B || !X || iters < 0 || (iters && !avg_us))
+    return fail(GPK_EINVAL, "gpk_refine_panel: bad argument (route, side in 0..1, sizes multiples of 32)");
+  if (route == 1 && P > REFINE_PANEL_MAX_P)
+    return fail(GPK_EINVAL, "gpk_refine_panel: the fused route holds two P x 16 panels in LDS: P <= 512");
+  if ((size_t)P * M > 0x7fffffff / 2) return fail(GPK_EINVAL, "gpk_refine_panel: tensor too large");
+  TRY(check_device(0));
+  DevSwitch dsw(0);
+  const size_t nt = (size_t)P * M, nm = (size_t)P * P;
+  CallScratch tmp("gpk_refine_panel");
+  double *dKi = nullptr, *dKc = nullptr, *dB = nullptr, *dX = nullptr, *dW = nullptr;
+  TRY(tmp.upload(&dKi, Kinv, nm));
+  TRY(tmp.upload(&dKc, Kc, nm));
+  TRY(tmp.upload(&dB, B, nt));
+  TRY(tmp.upload(&dX, X, nt));
+  TRY(tmp.alloc(&dW, nt));
+  if (route == 1) TRY(check_launch(refine_panel_prepare(), "gpk_refine_panel"));
+  // the step's refinement of one solve (gpk_kron3.cpp build_refine), ungated: X is P x M (side 0,
+  // K on the left) or M x P (side 1)
+  const int rows = side ? M : P, cols = side ? P : M;
+  const RefinePanel f = refine_panel_desc(side, dKc, dKi, dB, dX, rows, cols, nullptr);
+  const RefinedSolve g = refined_solve(side, dKc, dKi, dB, dX, dW, rows, cols, nullptr);
+  auto launch = [&]() -> hipError_t {
+    if (route == 1) return launch_refine_panel(&f, 1, nullptr, 0);
+    hipError_t rc = launch_gemm_auto(&g.resid, 1, nullptr, 0, gemm_variant(&g.resid, 1, 0));
+    return rc == hipSuccess ? launch_gemm_auto(&g.fix, 1, nullptr, 0, gemm_variant(&g.fix, 1, 0)) : rc;
+  };
+  // (X receives the checked launch's result; the timed launches keep refining the device copy)
+  hipError_t e = launch();
+  if (e == hipSuccess) e = hipDeviceSynchronize();
+  if (e == hipSuccess) e = hipMemcpy(X, dX, nt * 8, hipMemcpyDeviceToHost);
+  if (e == hipSuccess && iters) e = time_launches(0, iters, 1, launch, avg_us);
+  return check_launch(e, "gpk_refine_panel");
 }

@@ -2,13 +2,15 @@
 // the solver handle, the error helpers, and the functions that cross translation units.
 //   gpk_api.cpp     errors, device check, standalone kernels, predict, getters and setters
 //   gpk_create.cpp  handle construction (validate, choose path, allocate, classes, upload), state
-//   gpk_plan.cpp    the 2D step's GEMM plan (build_descs) and the GEMM descriptor helpers
+//   gpk_plan.cpp    the 2D step's GEMM plan (build_descs) and the descriptor helpers every unit
+//                   shares: gemm_desc, with_side, refined_solve, refine_panel_desc
 //   gpk_step.cpp    one step in stream order: argument fillers, the inverse, enqueue_step
 //   gpk_batch.cpp   graph cache and capture, batch begin / report / rollback, status handling,
 //                   gpk_step, gpk_prepare, gpk_loss_grad
 //   gpk_shard.cpp   the row-sharded step and its collective backends (the only user of RCCL)
-//   gpk_diag.cpp    measurement and diagnostic entry points (reached from no solver entry point)
-//   gpk_kron3.cpp   the 3-axis solver (step, predictions, criterion, Adam state) and gpk_mode_gemm
+//   gpk_diag.cpp    measurement and diagnostic entry points (reached from no solver entry point),
+//                   gpk_mode_gemm and gpk_refine_panel among them
+//   gpk_kron3.cpp   the 3-axis solver (step, predictions, criterion, Adam state)
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -45,6 +47,7 @@ int check_device(int dev);
 constexpr int LOSS_CAP = 4096;
 constexpr int kMaxStages = 18;
 constexpr int kGemmStages = 11;  // A, A_res, A_fix, B, B_res, B_fix, C, D, D_res, D_fix, E
+constexpr int K3_MAX_N = 1024;   // 3-axis solver, per axis (the per-sweep inverse; 1024^3 is 8 GB)
 
 // restore the caller's current device on scope exit
 struct __attribute__((visibility("hidden"))) DevSwitch {
@@ -225,6 +228,47 @@ int dev_alloc(std::vector<void*>& allocs, hipStream_t s, T** p, size_t count) {
   return GPK_OK;
 }
 
+// Device scratch of one call (handle lifetime: dev_alloc).  Every block is freed on scope exit,
+// whichever return ends the scope -- after `s` has drained when the call enqueues work on a stream
+// (what it enqueued may still read the blocks).  Both methods return the library's status, with
+// gpk_last_error set and GPK_ENOMEM for an allocation the device cannot serve.
+class __attribute__((visibility("hidden"))) CallScratch {
+ public:
+  explicit CallScratch(const char* who, hipStream_t s = nullptr) : who_(who), s_(s) {}
+  CallScratch(const CallScratch&) = delete;
+  CallScratch& operator=(const CallScratch&) = delete;
+  ~CallScratch() {
+    if (s_) (void)hipStreamSynchronize(s_);
+    for (void* p : mem_) (void)hipFree(p);
+  }
+  // n elements (at least 16 bytes), zero-filled in the order of `s` when asked
+  template <class T>
+  int alloc(T** p, size_t n, bool zero = false) {
+    void* q = nullptr;
+    const size_t bytes = std::max<size_t>(n * sizeof(T), 16);
+    const hipError_t e = hipMalloc(&q, bytes);
+    if (e != hipSuccess) {
+      (void)hipGetLastError();
+      return fail(e == hipErrorOutOfMemory ? GPK_ENOMEM : GPK_EHIP,
+                  std::string(who_) + ": hipMalloc failed: " + hipGetErrorString(e));
+    }
+    mem_.push_back(q);
+    *p = static_cast<T*>(q);
+    return zero ? check_launch(hipMemsetAsync(q, 0, bytes, s_), who_) : GPK_OK;
+  }
+  // n elements copied from the host array before the call returns
+  template <class T>
+  int upload(T** p, const T* src, size_t n) {
+    TRY(alloc(p, n));
+    return check_launch(hipMemcpy(*p, src, n * sizeof(T), hipMemcpyHostToDevice), who_);
+  }
+
+ private:
+  const char* who_;
+  hipStream_t s_;
+  std::vector<void*> mem_;
+};
+
 // padded size, size and coordinates of axis a (0 or 1)
 inline int axis_p(const Layout& L, int a) { return a ? L.p2 : L.p1; }
 inline int axis_n(const Layout& L, int a) { return a ? L.n2 : L.n1; }
@@ -241,6 +285,18 @@ int create_impl(const gpk_problem* p, double freq_scale, int rank, int nranks, b
 GemmDesc gemm_desc(const double* A, int lda, int ta, const double* B, int ldb, int tb, double* C,
                    int ldc, int M, int N, int K);  // C = op(A) op(B), stored
 GemmDesc with_side(GemmDesc g, double* Y, const double* Ys, int ldy);  // + Y = Ys / 2 + v C
+// One solve against K with its refinement step, X and B rows x cols and K of order rows (K on the
+// left, right = 0: X = K^{-1} B) or cols (right = 1: X = B K^{-1}); every operand row-major and
+// contiguous.  solve: X = K^{-1} B;  resid: W = B - Kc X;  fix: X += K^{-1} W in place -- the
+// last two gated on `gate` (nullable: always run).
+struct RefinedSolve {
+  GemmDesc solve, resid, fix;
+};
+RefinedSolve refined_solve(bool right, const double* Kc, const double* Kinv, const double* B, double* X,
+                           double* W, int rows, int cols, const double* gate);
+// the same refinement step as one fused panel launch (refine_panel.hip; P <= REFINE_PANEL_MAX_P)
+RefinePanel refine_panel_desc(bool right, const double* Kc, const double* Kinv, const double* B, double* X,
+                              int rows, int cols, const double* gate);
 int gemm_force(int flags);
 int build_descs(gpk_handle* h);
 // gpk_step.cpp: argument fillers and the enqueue of one step

@@ -17,13 +17,13 @@
 //
 // Beyond the step: gpk_predict3 (test-grid predictions, T <- Kmn_k x_k solve(K_k, T) axis after
 // axis; its mode-2 products are slab-batched launches, gemm.hip, with no permuted copy),
-// gpk_criterion3, the Adam state, and gpk_mode_gemm (one mode-k product on host operands).
+// gpk_criterion3 and the Adam state.  (The standalone measurements of its pieces, gpk_mode_gemm
+// and gpk_refine_panel, are in gpk_diag.cpp.)
 #include "gpk_host.h"
 #include "gpk_kron3.h"
 
 namespace {
 constexpr int K3_LOSS_CAP = 4096;
-constexpr int K3_MAX_N = 1024;  // per axis (the per-sweep inverse; a 3-axis grid of 1024^3 is 8 GB)
 }  // namespace
 
 struct gpk_handle3 {
@@ -135,21 +135,14 @@ void build_refine(gpk_handle3* h) {
   rs.assign(8, {});
   h->rpanels.assign(4, {});
   h->route = !(h->prob.flags & GPK_FLAG3_REFINE_GEMM) && std::max(P1, std::max(P2, P3)) <= REFINE_PANEL_MAX_P;
-  // solve X = K_a^{-1} x_a B of axis a (a = 1: permuted operands), scratch W
+  // solve X = K_a^{-1} x_a B of axis a (a = 1: permuted operands; a = 2: K on the right), scratch W
   auto add = [&](int j, int a, const double* B, double* X, double* W) {
-    const int P = Ps[a], M = Ms[a];
-    GemmDesc r = a == 2 ? gemm_desc(X, P, 0, h->Kc[a], P, 0, W, P, M, P, P)
-                        : gemm_desc(h->Kc[a], P, 0, X, M, 0, W, M, P, M, P);
-    r.alpha = -1.0; r.beta = 1.0; r.C0 = B; r.ldc0 = r.ldc; r.gate = h->pst[a];
-    GemmDesc c = a == 2 ? gemm_desc(W, P, 0, h->Kinv[a], P, 0, X, P, M, P, P)
-                        : gemm_desc(h->Kinv[a], P, 0, W, M, 0, X, M, P, M, P);
-    c.beta = 1.0; c.C0 = X; c.ldc0 = c.ldc; c.gate = h->pst[a];
-    rs[2 * j].push_back(r);
-    rs[2 * j + 1].push_back(c);
-    RefinePanel f{};
-    f.Kinv = h->Kinv[a]; f.Kc = h->Kc[a]; f.B = B; f.X = X; f.P = P; f.M = M; f.right = a == 2;
-    f.sp = a == 2 ? 1 : (size_t)M; f.sc = a == 2 ? (size_t)P : 1; f.gate = h->pst[a];
-    h->rpanels[j].push_back(f);
+    const bool right = a == 2;
+    const int rows = right ? Ms[a] : Ps[a], cols = right ? Ps[a] : Ms[a];
+    const RefinedSolve s = refined_solve(right, h->Kc[a], h->Kinv[a], B, X, W, rows, cols, h->pst[a]);
+    rs[2 * j].push_back(s.resid);
+    rs[2 * j + 1].push_back(s.fix);
+    h->rpanels[j].push_back(refine_panel_desc(right, h->Kc[a], h->Kinv[a], B, X, rows, cols, h->pst[a]));
   };
   add(0, 0, h->Up, h->A1, h->T1);      // A1
   add(0, 2, h->Up, h->A3, h->T3);      // A3
@@ -456,7 +449,9 @@ int gpk_loss_grad3(gpk_handle3* h, double* loss, double* grad_flat) {
   HIPCHK(hipMemsetAsync(h->loss_slot, 0, sizeof(int), h->s));
   HIPCHK(hipGraphLaunch(h->exec[0], h->s));
   TRY(read_status3(h));
-  HIPCHK(hipMemcpy(loss, h->diag, sizeof(double), hipMemcpyDeviceToHost));
+  double diag[8];
+  TRY(read_diag3(h, diag));
+  *loss = diag[0];
   if (grad_flat) HIPCHK(hipMemcpy(grad_flat, h->grad, h->nparams * sizeof(double), hipMemcpyDeviceToHost));
   return GPK_OK;
 }
@@ -560,57 +555,40 @@ int gpk_predict3(gpk_handle3* h, const double* xte1, int32_t m1, const double* x
   const int Mp[3] = {M1p, M2p, M3p};
   // scratch, allocated per call: test coordinates, Kmn_k (zero-padded to Mp_k x P_k), K_k again
   // (the sweeps overwrote it) and three work tensors W that take every intermediate in turn
-  std::vector<void*> tmp;
-  auto dalloc = [&](double** p, size_t n) -> int {
-    const size_t bytes = std::max<size_t>(n, 2) * sizeof(double);
-    hipError_t e = hipMalloc((void**)p, bytes);
-    if (e != hipSuccess) {
-      (void)hipGetLastError();
-      return fail(GPK_ENOMEM, std::string("gpk_predict3: hipMalloc failed: ") + hipGetErrorString(e));
-    }
-    tmp.push_back(*p);
-    HIPCHK(hipMemsetAsync(*p, 0, bytes, h->s));
-    return GPK_OK;
-  };
-  auto done = [&](int rc) {
-    (void)hipStreamSynchronize(h->s);
-    for (void* p : tmp) (void)hipFree(p);
-    return rc;
-  };
+  CallScratch tmp("gpk_predict3", h->s);
   const size_t N1 = (size_t)P2 * P3, R3 = (size_t)M1p * M2p;
   const size_t big = std::max(std::max((size_t)P1 * N1, (size_t)M1p * N1),
                               std::max(R3 * P3, R3 * M3p));
   double *xt[3], *Kmn[3], *Kc[3], *W[3];
-  int rc = GPK_OK;
-  for (int a = 0; a < 3 && !rc; ++a) {
-    if ((rc = dalloc(&xt[a], ms[a])) || (rc = dalloc(&Kmn[a], (size_t)Mp[a] * g.p[a])) ||
-        (rc = dalloc(&Kc[a], (size_t)g.p[a] * g.p[a])) || (rc = dalloc(&W[a], big)))
-      break;
+  for (int a = 0; a < 3; ++a) {
+    TRY(tmp.alloc(&xt[a], ms[a], true));
+    TRY(tmp.alloc(&Kmn[a], (size_t)Mp[a] * g.p[a], true));
+    TRY(tmp.alloc(&Kc[a], (size_t)g.p[a] * g.p[a], true));
+    TRY(tmp.alloc(&W[a], big, true));
   }
-  if (rc) return done(rc);
   for (int a = 0; a < 3; ++a)
     if (hipMemcpyAsync(xt[a], xte[a], ms[a] * sizeof(double), hipMemcpyHostToDevice, h->s) != hipSuccess)
-      return done(fail(GPK_EHIP, "gpk_predict3: upload of the test coordinates failed"));
+      return fail(GPK_EHIP, "gpk_predict3: upload of the test coordinates failed");
   // K_k^{-1} at the current params (the step's own front), then Kmn_k = kappa(xte_k, x_k) without
   // jitter and K_k with it, for the refinement residuals
-  if ((rc = enqueue_inverse3(h, 0))) return done(rc);
+  TRY(enqueue_inverse3(h, 0));
   const int kind = h->prob.kind, q = h->q;
   for (int a = 0; a < 3; ++a) {
-    if ((rc = check_launch(launch_cross(kind, q, xt[a], ms[a], h->x[a], g.n[a], g.p[a], h->kc + a, 0.0, 0,
-                                        Kmn[a], nullptr, h->s), "cross")) ||
-        (rc = check_launch(launch_cross(kind, q, h->x[a], g.n[a], h->x[a], g.n[a], g.p[a], h->kc + a,
-                                        h->prob.jitter, 0, Kc[a], nullptr, h->s), "cross")))
-      return done(rc);
+    TRY(check_launch(launch_cross(kind, q, xt[a], ms[a], h->x[a], g.n[a], g.p[a], h->kc + a, 0.0, 0,
+                                  Kmn[a], nullptr, h->s), "cross"));
+    TRY(check_launch(launch_cross(kind, q, h->x[a], g.n[a], h->x[a], g.n[a], g.p[a], h->kc + a,
+                                  h->prob.jitter, 0, Kc[a], nullptr, h->s), "cross"));
   }
   // T <- Kmn_k x_k solve(K_k, T) for k = 1, 2, 3 from T = U (the reference's 2-axis association,
   // model_GP_solver_2d.py:185-220, axis after axis: every intermediate stays O(|U_pred|)); each
   // solve is A = K^{-1} T, A += K^{-1} (T - K A).  Modes 1 and 3 are GEMMs on the row-major
   // unfoldings; mode 2 of [B][P2][P3] is B slabs of P2 x P3 (launch_gemm_slab: no permuted copy).
   double* const* Ki = h->Kinv;
-  auto gemm = [&](GemmDesc d, double alpha, double beta, const double* C0) {
-    d.alpha = alpha;
-    if (C0) { d.beta = beta; d.C0 = C0; d.ldc0 = d.ldc; }
-    return check_launch(launch_gemm_auto(&d, 1, h->sc, h->s, gemm_variant(&d, 1, 0)), "gemm");
+  auto solve = [&](int a, const double* B, double* X, double* Wr, int rows, int cols) -> int {
+    const RefinedSolve s = refined_solve(a == 2, Kc[a], Ki[a], B, X, Wr, rows, cols, nullptr);
+    TRY(launch_descs(h, {s.solve}));
+    TRY(launch_descs(h, {s.resid}));
+    return launch_descs(h, {s.fix});
   };
   auto slab = [&](const double* A, int M, const double* B, double* C, double alpha, double beta,
                   const double* C0) {
@@ -619,185 +597,25 @@ int gpk_predict3(gpk_handle3* h, const double* xte1, int32_t m1, const double* x
     sg.M = M; sg.N = P3; sg.K = P2; sg.nb = M1p; sg.alpha = alpha; sg.beta = beta;
     return check_launch(launch_gemm_slab(sg, h->s), "gemm_slab");
   };
+  auto slab_solve = [&](const double* B, double* X, double* Wr) -> int {
+    TRY(slab(Ki[1], P2, B, X, 1.0, 0.0, nullptr));
+    TRY(slab(Kc[1], P2, X, Wr, -1.0, 1.0, B));
+    return slab(Ki[1], P2, Wr, X, 1.0, 1.0, X);
+  };
   const int n1 = (int)N1, r3 = (int)R3;
-  if ((rc = gemm(gemm_desc(Ki[0], P1, 0, h->Up, n1, 0, W[0], n1, P1, n1, P1), 1.0, 0.0, nullptr)) ||
-      (rc = gemm(gemm_desc(Kc[0], P1, 0, W[0], n1, 0, W[1], n1, P1, n1, P1), -1.0, 1.0, h->Up)) ||
-      (rc = gemm(gemm_desc(Ki[0], P1, 0, W[1], n1, 0, W[0], n1, P1, n1, P1), 1.0, 1.0, W[0])) ||
-      (rc = gemm(gemm_desc(Kmn[0], P1, 0, W[0], n1, 0, W[1], n1, M1p, n1, P1), 1.0, 0.0, nullptr)) ||  // [M1p][P2][P3]
-      (rc = slab(Ki[1], P2, W[1], W[0], 1.0, 0.0, nullptr)) ||
-      (rc = slab(Kc[1], P2, W[0], W[2], -1.0, 1.0, W[1])) ||
-      (rc = slab(Ki[1], P2, W[2], W[0], 1.0, 1.0, W[0])) ||
-      (rc = slab(Kmn[1], M2p, W[0], W[1], 1.0, 0.0, nullptr)) ||                               // [M1p][M2p][P3]
-      (rc = gemm(gemm_desc(W[1], P3, 0, Ki[2], P3, 0, W[0], P3, r3, P3, P3), 1.0, 0.0, nullptr)) ||
-      (rc = gemm(gemm_desc(W[0], P3, 0, Kc[2], P3, 0, W[2], P3, r3, P3, P3), -1.0, 1.0, W[1])) ||
-      (rc = gemm(gemm_desc(W[2], P3, 0, Ki[2], P3, 0, W[0], P3, r3, P3, P3), 1.0, 1.0, W[0])) ||
-      (rc = gemm(gemm_desc(W[0], P3, 0, Kmn[2], P3, 1, W[2], M3p, r3, M3p, P3), 1.0, 0.0, nullptr)))   // [M1p][M2p][M3p]
-    return done(rc);
+  TRY(solve(0, h->Up, W[0], W[1], P1, n1));
+  TRY(launch_descs(h, {gemm_desc(Kmn[0], P1, 0, W[0], n1, 0, W[1], n1, M1p, n1, P1)}));  // [M1p][P2][P3]
+  TRY(slab_solve(W[1], W[0], W[2]));
+  TRY(slab(Kmn[1], M2p, W[0], W[1], 1.0, 0.0, nullptr));                                 // [M1p][M2p][P3]
+  TRY(solve(2, W[1], W[0], W[2], r3, P3));
+  TRY(launch_descs(h, {gemm_desc(W[0], P3, 0, Kmn[2], P3, 1, W[2], M3p, r3, M3p, P3)}));  // [M1p][M2p][M3p]
   for (int i1 = 0; i1 < m1; ++i1)
     if (hipMemcpy2DAsync(out + (size_t)i1 * m2 * m3, m3 * sizeof(double), W[2] + (size_t)i1 * M2p * M3p,
                          M3p * sizeof(double), m3 * sizeof(double), m2, hipMemcpyDeviceToHost, h->s) != hipSuccess)
-      return done(fail(GPK_EHIP, "gpk_predict3: download failed"));
+      return fail(GPK_EHIP, "gpk_predict3: download failed");
   const hipError_t e = hipStreamSynchronize(h->s);
-  (void)done(GPK_OK);
   if (e != hipSuccess) return fail(GPK_EHIP, std::string("gpk_predict3: ") + hipGetErrorString(e));
   return read_status3(h);
-}
-
-int gpk_mode_gemm(int32_t variant, int32_t k, int32_t d1, int32_t d2, int32_t d3, int32_t m, double alpha,
-                  const double* Mat, const double* T, double beta, const double* C0, double* C,
-                  int32_t iters, double* avg_us) {
-  if (variant < 0 || variant > 3 || k < 1 || k > 3 || d1 <= 0 || d2 <= 0 || d3 <= 0 || m <= 0 ||
-      ((d1 | d2 | d3 | m) & 31) || !Mat || !T || !C || iters < 0 || (iters && !avg_us))
-    return fail(GPK_EINVAL, "gpk_mode_gemm: bad argument (k in 1..3, sizes multiples of 32)");
-  if (k == 2 && d1 > 65535) return fail(GPK_EINVAL, "gpk_mode_gemm: mode 2 takes at most 65535 slabs");
-  const int dk = k == 1 ? d1 : k == 2 ? d2 : d3;
-  const size_t nt = (size_t)d1 * d2 * d3, nc = nt / dk * m, nm = (size_t)m * dk;
-  if (nt / dk > 0x7fffffff / 2) return fail(GPK_EINVAL, "gpk_mode_gemm: tensor too large");
-  TRY(check_device(0));
-  DevSwitch dsw(0);
-  std::vector<void*> mem;
-  auto cleanup = [&]() { for (void* p : mem) (void)hipFree(p); };
-  auto up = [&](const double* src, size_t n, double** dst) -> hipError_t {
-    hipError_t e = hipMalloc(dst, n * 8);
-    if (e != hipSuccess) return e;
-    mem.push_back(*dst);
-    return src ? hipMemcpy(*dst, src, n * 8, hipMemcpyHostToDevice) : hipSuccess;
-  };
-  const bool permute = k == 2 && variant == 1;
-  double *dM = nullptr, *dT = nullptr, *dC = nullptr, *dC0 = nullptr, *dTp = nullptr, *dCp = nullptr,
-         *dC0p = nullptr;
-  hipError_t e = up(Mat, nm, &dM);
-  if (e == hipSuccess) e = up(T, nt, &dT);
-  if (e == hipSuccess) e = up(C0 == C ? C : nullptr, nc, &dC);
-  if (e == hipSuccess && C0 && C0 != C) e = up(C0, nc, &dC0);
-  if (e == hipSuccess && permute) e = up(nullptr, nt, &dTp);
-  if (e == hipSuccess && permute) e = up(nullptr, nc, &dCp);
-  if (e == hipSuccess && permute && C0) e = up(nullptr, nc, &dC0p);
-  if (e != hipSuccess) {
-    cleanup();
-    return fail(e == hipErrorOutOfMemory ? GPK_ENOMEM : GPK_EHIP, std::string("gpk_mode_gemm: ") + hipGetErrorString(e));
-  }
-  const double* c0 = C0 ? (C0 == C ? dC : dC0) : nullptr;
-  const double be = C0 ? beta : 0.0;
-  auto one = [&](GemmDesc d, const double* c0_) {
-    d.alpha = alpha;
-    if (c0_) { d.beta = be; d.C0 = c0_; d.ldc0 = d.ldc; }
-    return launch_gemm_auto(&d, 1, nullptr, 0, gemm_variant(&d, 1, 0));
-  };
-  const int n23 = d2 * d3, n13 = d1 * d3, n12 = d1 * d2;
-  auto launch = [&]() -> hipError_t {
-    if (k == 1) return one(gemm_desc(dM, d1, 0, dT, n23, 0, dC, n23, m, n23, d1), c0);
-    if (k == 3) return one(gemm_desc(dT, d3, 0, dM, d3, 1, dC, m, n12, m, d3), c0);
-    if (!permute) {  // the slab kernel (variant 2 / 3: its 32 / 64 tile forced)
-      SlabGemm sg{};
-      sg.A = dM; sg.B = dT; sg.sB = (size_t)n23; sg.C = dC; sg.sC = (size_t)m * d3; sg.C0 = c0; sg.sC0 = sg.sC;
-      sg.M = m; sg.N = d3; sg.K = d2; sg.nb = d1; sg.alpha = alpha; sg.beta = be;
-      return launch_gemm_slab(sg, 0, variant == 2 ? 32 : variant == 3 ? 64 : 0);
-    }
-    // the step's route: permuted copy [d2][d1][d3], one GEMM on its rows, permuted back
-    K3Geom gi{}, go{};
-    gi.p[0] = gi.n[0] = d1; gi.p[1] = gi.n[1] = d2; gi.p[2] = gi.n[2] = d3;
-    go.p[0] = go.n[0] = m; go.p[1] = go.n[1] = d1; go.p[2] = go.n[2] = d3;   // [m][d1][d3] -> [d1][m][d3]
-    K3Geom gc = go;
-    gc.p[0] = gc.n[0] = d1; gc.p[1] = gc.n[1] = m;                             // [d1][m][d3] -> [m][d1][d3]
-    hipError_t r = k3_launch_permute(dT, dTp, gi, 0);
-    if (r == hipSuccess && c0) r = k3_launch_permute(c0, dC0p, gc, 0);
-    if (r == hipSuccess) r = one(gemm_desc(dM, d2, 0, dTp, n13, 0, dCp, n13, m, n13, d2), c0 ? dC0p : nullptr);
-    if (r == hipSuccess) r = k3_launch_permute(dCp, dC, go, 0);
-    return r;
-  };
-  // (as gpk_dgemm: C receives the checked launch's result; with C0 == C the timed launches keep
-  // updating the device copy in place -- same work, each on the last one's output)
-  e = launch();
-  if (e == hipSuccess) e = hipDeviceSynchronize();
-  if (e == hipSuccess) e = hipMemcpy(C, dC, nc * 8, hipMemcpyDeviceToHost);
-  if (e == hipSuccess && iters) {
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    e = hipEventCreate(&e0);
-    if (e == hipSuccess) e = hipEventCreate(&e1);
-    if (e == hipSuccess) e = launch();  // one untimed launch, then `iters` back to back
-    if (e == hipSuccess) e = hipEventRecord(e0, 0);
-    for (int it = 0; it < iters && e == hipSuccess; ++it) e = launch();
-    if (e == hipSuccess) e = hipEventRecord(e1, 0);
-    if (e == hipSuccess) e = hipEventSynchronize(e1);
-    float ms = 0.f;
-    if (e == hipSuccess) e = hipEventElapsedTime(&ms, e0, e1);
-    if (e == hipSuccess) *avg_us = ms * 1000.0 / iters;
-    if (e0) (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
-  }
-  cleanup();
-  if (e != hipSuccess) return fail(GPK_EHIP, std::string("gpk_mode_gemm: ") + hipGetErrorString(e));
-  return GPK_OK;
-}
-
-int gpk_refine_panel(int32_t route, int32_t side, int32_t P, int32_t M, const double* Kinv, const double* Kc,
-                     const double* B, double* X, int32_t iters, double* avg_us) {
-  if (route < 0 || route > 1 || side < 0 || side > 1 || P < 32 || (P & 31) || M < 32 || (M & 31) ||
-      P > K3_MAX_N || !Kinv || !Kc || !B || !X || iters < 0 || (iters && !avg_us))
-    return fail(GPK_EINVAL, "gpk_refine_panel: bad argument (route, side in 0..1, sizes multiples of 32)");
-  if (route == 1 && P > REFINE_PANEL_MAX_P)
-    return fail(GPK_EINVAL, "gpk_refine_panel: the fused route holds two P x 16 panels in LDS: P <= 512");
-  if ((size_t)P * M > 0x7fffffff / 2) return fail(GPK_EINVAL, "gpk_refine_panel: tensor too large");
-  TRY(check_device(0));
-  DevSwitch dsw(0);
-  const size_t nt = (size_t)P * M, nm = (size_t)P * P;
-  std::vector<void*> mem;
-  auto cleanup = [&]() { for (void* p : mem) (void)hipFree(p); };
-  auto up = [&](const double* src, size_t n, double** dst) -> hipError_t {
-    hipError_t e = hipMalloc(dst, n * 8);
-    if (e != hipSuccess) return e;
-    mem.push_back(*dst);
-    return src ? hipMemcpy(*dst, src, n * 8, hipMemcpyHostToDevice) : hipSuccess;
-  };
-  double *dKi = nullptr, *dKc = nullptr, *dB = nullptr, *dX = nullptr, *dW = nullptr;
-  hipError_t e = up(Kinv, nm, &dKi);
-  if (e == hipSuccess) e = up(Kc, nm, &dKc);
-  if (e == hipSuccess) e = up(B, nt, &dB);
-  if (e == hipSuccess) e = up(X, nt, &dX);
-  if (e == hipSuccess) e = up(nullptr, nt, &dW);
-  if (e == hipSuccess && route == 1) e = refine_panel_prepare();
-  if (e != hipSuccess) {
-    cleanup();
-    return fail(e == hipErrorOutOfMemory ? GPK_ENOMEM : GPK_EHIP, std::string("gpk_refine_panel: ") + hipGetErrorString(e));
-  }
-  auto launch = [&]() -> hipError_t {
-    if (route == 1) {
-      RefinePanel f{};
-      f.Kinv = dKi; f.Kc = dKc; f.B = dB; f.X = dX; f.P = P; f.M = M; f.right = side;
-      f.sp = side ? 1 : (size_t)M; f.sc = side ? (size_t)P : 1;
-      return launch_refine_panel(&f, 1, nullptr, 0);
-    }
-    // the step's two GEMMs (build_refine)
-    GemmDesc r = side ? gemm_desc(dX, P, 0, dKc, P, 0, dW, P, M, P, P) : gemm_desc(dKc, P, 0, dX, M, 0, dW, M, P, M, P);
-    r.alpha = -1.0; r.beta = 1.0; r.C0 = dB; r.ldc0 = r.ldc;
-    GemmDesc c = side ? gemm_desc(dW, P, 0, dKi, P, 0, dX, P, M, P, P) : gemm_desc(dKi, P, 0, dW, M, 0, dX, M, P, M, P);
-    c.beta = 1.0; c.C0 = dX; c.ldc0 = c.ldc;
-    hipError_t rc = launch_gemm_auto(&r, 1, nullptr, 0, gemm_variant(&r, 1, 0));
-    return rc == hipSuccess ? launch_gemm_auto(&c, 1, nullptr, 0, gemm_variant(&c, 1, 0)) : rc;
-  };
-  // (X receives the checked launch's result; the timed launches keep refining the device copy)
-  e = launch();
-  if (e == hipSuccess) e = hipDeviceSynchronize();
-  if (e == hipSuccess) e = hipMemcpy(X, dX, nt * 8, hipMemcpyDeviceToHost);
-  if (e == hipSuccess && iters) {
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    e = hipEventCreate(&e0);
-    if (e == hipSuccess) e = hipEventCreate(&e1);
-    if (e == hipSuccess) e = launch();  // one untimed launch, then `iters` back to back
-    if (e == hipSuccess) e = hipEventRecord(e0, 0);
-    for (int it = 0; it < iters && e == hipSuccess; ++it) e = launch();
-    if (e == hipSuccess) e = hipEventRecord(e1, 0);
-    if (e == hipSuccess) e = hipEventSynchronize(e1);
-    float ms = 0.f;
-    if (e == hipSuccess) e = hipEventElapsedTime(&ms, e0, e1);
-    if (e == hipSuccess) *avg_us = ms * 1000.0 / iters;
-    if (e0) (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
-  }
-  cleanup();
-  if (e != hipSuccess) return fail(GPK_EHIP, std::string("gpk_refine_panel: ") + hipGetErrorString(e));
-  return GPK_OK;
 }
 
 }  // extern "C"

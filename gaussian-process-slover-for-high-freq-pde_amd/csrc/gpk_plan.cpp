@@ -16,6 +16,28 @@ GemmDesc with_side(GemmDesc g, double* Y, const double* Ys, int ldy) {  // Y = Y
   return g;
 }
 
+RefinedSolve refined_solve(bool right, const double* Kc, const double* Kinv, const double* B, double* X,
+                           double* W, int rows, int cols, const double* gate) {
+  const int P = right ? cols : rows;
+  auto prod = [&](const double* Km, const double* T, double* C) {
+    return right ? gemm_desc(T, cols, 0, Km, P, 0, C, cols, rows, cols, P)
+                 : gemm_desc(Km, P, 0, T, cols, 0, C, cols, rows, cols, P);
+  };
+  RefinedSolve s{prod(Kinv, B, X), prod(Kc, X, W), prod(Kinv, W, X)};
+  s.resid.alpha = -1.0; s.resid.beta = 1.0; s.resid.C0 = B; s.resid.ldc0 = cols; s.resid.gate = gate;
+  s.fix.beta = 1.0; s.fix.C0 = X; s.fix.ldc0 = cols; s.fix.gate = gate;
+  return s;
+}
+
+RefinePanel refine_panel_desc(bool right, const double* Kc, const double* Kinv, const double* B, double* X,
+                              int rows, int cols, const double* gate) {
+  RefinePanel f{};
+  f.Kinv = Kinv; f.Kc = Kc; f.B = B; f.X = X; f.right = right; f.gate = gate;
+  f.P = right ? cols : rows; f.M = right ? rows : cols;
+  f.sp = right ? 1 : (size_t)cols; f.sc = right ? (size_t)cols : 1;
+  return f;
+}
+
 int gemm_force(int flags) {
   return (flags & GPK_FLAG_FORCE_HUGE_GEMM) ? 2 : (flags & GPK_FLAG_FORCE_BIG_GEMM) ? 1 : 0;
 }
@@ -39,10 +61,6 @@ int build_descs(gpk_handle* h) {
   // pass) is X = K^{-1} B (MFMA) plus one refinement X += K^{-1}(B - K X), whose two GEMMs are
   // gated on a lower bound of cond(K) (refine_gate_open) (skipped when K is well conditioned, e.g. 256^2).
   const int n1 = L.n1, n2 = L.n2;
-  auto gate = [&](GemmDesc g, int axis) {
-    g.gate = h->pst[axis];
-    return g;
-  };
   // Refinement GEMMs (X += K^{-1}(B - K X)) are gated on device on a lower bound of cond(K): a
   // closed gate ends each of their workgroups before any load (a launch).  Small factors: every
   // solve is refined.  Large 2D factors (P >= 1600), where each refinement is two N^3 GEMMs
@@ -70,12 +88,19 @@ int build_descs(gpk_handle* h) {
   };
   // X1 / X2 producers also write Y = S/2 + v X (GemmDesc::Y): G_K's left operand
   auto side = [&](GemmDesc g, double* Y) { return with_side(g, Y, h->S, P2); };
+  // the step's five solves (refined_solve): K1 on the left, K2 on the right, P1 x P2 operands
+  auto solve = [&](int a, const double* B, double* X, double* W) {
+    return refined_solve(a == 1, h->Kc[a], h->Kinv[a], B, X, W, P1, P2, h->pst[a]);
+  };
+  const RefinedSolve sA = solve(0, h->Up, h->A, h->W1), sBt = solve(1, h->Up, h->Bt, h->W2),
+                     sS = solve(1, h->A, h->S, h->W1), sX1 = solve(0, h->T1, h->X1, h->W1),
+                     sX2 = solve(1, h->T2, h->X2, h->W2);
   // Stage A: A = K1^{-1} U, Bt = U K2^{-1}                       (2d.py:104-105)
   // (augmented chain: both come out of the inverse launch itself -- no stage)
   begin(0);
   if (!h->chain_aug) {
-    d.push_back(gemm_desc(h->Kinv[0], P1, 0, h->Up, P2, 0, h->A, P2, P1, P2, P1));
-    d.push_back(gemm_desc(h->Up, P2, 0, h->Kinv[1], P2, 0, h->Bt, P2, P1, P2, P2));
+    d.push_back(sA.solve);
+    d.push_back(sBt.solve);
   }
   end(0);
   // (Measured in C4's training regime, tools/train_regime_parity.py, profiles/r5_train_regime_
@@ -83,30 +108,18 @@ int build_descs(gpk_handle* h) {
   // within 0.45 of the parity bar on its own K and D after 200-2000 Adam steps; refining the
   // forward solves every step took that to 0.05-0.25 for ~12 us per step, so the gate stays.)
   begin(1);  // residuals W1 = U - K1 A, W2 = U - Bt K2
-  {
-    GemmDesc g = gemm_desc(h->Kc[0], P1, 0, h->A, P2, 0, h->W1, P2, P1, P2, P1);
-    g.alpha = -1.0; g.beta = 1.0; g.C0 = h->Up; g.ldc0 = P2;
-    pushg(gate(g, 0));
-    GemmDesc g2 = gemm_desc(h->Bt, P2, 0, h->Kc[1], P2, 0, h->W2, P2, P1, P2, P2);
-    g2.alpha = -1.0; g2.beta = 1.0; g2.C0 = h->Up; g2.ldc0 = P2;
-    if (ref_fwd2) pushg(gate(g2, 1));
-  }
+  pushg(sA.resid);
+  if (ref_fwd2) pushg(sBt.resid);
   end(1);
   begin(2);  // A += K1^{-1} W1, Bt += W2 K2^{-1}  (in place)
-  {
-    GemmDesc g = gemm_desc(h->Kinv[0], P1, 0, h->W1, P2, 0, h->A, P2, P1, P2, P1);
-    g.beta = 1.0; g.C0 = h->A; g.ldc0 = P2;
-    pushg(gate(g, 0));
-    GemmDesc g2 = gemm_desc(h->W2, P2, 0, h->Kinv[1], P2, 0, h->Bt, P2, P1, P2, P2);
-    g2.beta = 1.0; g2.C0 = h->Bt; g2.ldc0 = P2;
-    if (ref_fwd2) pushg(gate(g2, 1));
-  }
+  pushg(sA.fix);
+  if (ref_fwd2) pushg(sBt.fix);
   end(2);
   // Stage B: S = A K2^{-1};  R = beta D1 A + Bt D2^T - F (+AC), ||R||^2 and the prior's
   // quadratic term sum(A * Bt) (2d.py:112-143, :161) from the same tile loop
   begin(3);
   {
-    d.push_back(gemm_desc(h->A, P2, 0, h->Kinv[1], P2, 0, h->S, P2, P1, P2, P2));
+    d.push_back(sS.solve);
     GemmDesc r = gemm_desc(h->D[0], P1, 0, h->A, P2, 0, h->R, P2, P1, P2, P1);
     r.alpha = beta;
     r.A2 = h->Bt; r.lda2 = P2; r.ta2 = 0; r.B2 = h->D[1]; r.ldb2 = P2; r.tb2 = 1; r.K2 = P2;
@@ -118,18 +131,10 @@ int build_descs(gpk_handle* h) {
   end(3);
   ref_now = ref_rev;  // (the reverse-pass solves from here on)
   begin(4);  // W1 = A - S K2
-  {
-    GemmDesc g = gemm_desc(h->S, P2, 0, h->Kc[1], P2, 0, h->W1, P2, P1, P2, P2);
-    g.alpha = -1.0; g.beta = 1.0; g.C0 = h->A; g.ldc0 = P2;
-    pushg(gate(g, 1));
-  }
+  pushg(sS.resid);
   end(4);
   begin(5);  // S += W1 K2^{-1}
-  {
-    GemmDesc g = gemm_desc(h->W1, P2, 0, h->Kinv[1], P2, 0, h->S, P2, P1, P2, P2);
-    g.beta = 1.0; g.C0 = h->S; g.ldc0 = P2;
-    pushg(gate(g, 1));
-  }
+  pushg(sS.fix);
   end(5);
   // Stage C: T1 = beta D1^T R, T2 = R D2, G_D1 = v beta R A^T, G_D2 = v R^T Bt  (Appendix A)
   // (augmented chain: X1 = beta (K1^{-1} D1^T) R and X2 = R (K2^{-1} D2^T)^T directly, from the
@@ -158,37 +163,29 @@ int build_descs(gpk_handle* h) {
   // Stage D: X1 = K1^{-1} T1, X2 = T2 K2^{-1} (refined)
   begin(7);
   if (!h->chain_aug) {
-    d.push_back(side(gemm_desc(h->Kinv[0], P1, 0, h->T1, P2, 0, h->X1, P2, P1, P2, P1), h->Y1));
-    d.push_back(side(gemm_desc(h->T2, P2, 0, h->Kinv[1], P2, 0, h->X2, P2, P1, P2, P2), h->Y2));
+    d.push_back(side(sX1.solve, h->Y1));
+    d.push_back(side(sX2.solve, h->Y2));
   }
   end(7);
   begin(8);  // refinement residuals W1 = beta D1^T R - K1 X1, W2 = R D2 - X2 K2
-  if (h->chain_aug) {  // (T1, T2 never formed: dual products)
+  if (h->chain_aug) {  // (T1, T2 never formed: dual products, not the solves' own residual form)
     GemmDesc g = gemm_desc(h->D[0], P1, 1, h->R, P2, 0, h->W1, P2, P1, P2, P1);
     g.alpha = beta;
     g.A2 = h->Kc[0]; g.lda2 = P1; g.B2 = h->X1; g.ldb2 = P2; g.K2 = P1; g.alpha2 = -1.0;
-    pushg(gate(g, 0));
+    g.gate = h->pst[0];
+    pushg(g);
     GemmDesc g2 = gemm_desc(h->R, P2, 0, h->D[1], P2, 0, h->W2, P2, P1, P2, P2);
     g2.A2 = h->X2; g2.lda2 = P2; g2.B2 = h->Kc[1]; g2.ldb2 = P2; g2.K2 = P2; g2.alpha2 = -1.0;
-    pushg(gate(g2, 1));
+    g2.gate = h->pst[1];
+    pushg(g2);
   } else {
-    GemmDesc g = gemm_desc(h->Kc[0], P1, 0, h->X1, P2, 0, h->W1, P2, P1, P2, P1);
-    g.alpha = -1.0; g.beta = 1.0; g.C0 = h->T1; g.ldc0 = P2;
-    pushg(gate(g, 0));
-    GemmDesc g2 = gemm_desc(h->X2, P2, 0, h->Kc[1], P2, 0, h->W2, P2, P1, P2, P2);
-    g2.alpha = -1.0; g2.beta = 1.0; g2.C0 = h->T2; g2.ldc0 = P2;
-    pushg(gate(g2, 1));
+    pushg(sX1.resid);
+    pushg(sX2.resid);
   }
   end(8);
-  begin(9);
-  {
-    GemmDesc g = gemm_desc(h->Kinv[0], P1, 0, h->W1, P2, 0, h->X1, P2, P1, P2, P1);
-    g.beta = 1.0; g.C0 = h->X1; g.ldc0 = P2;
-    pushg(side(gate(g, 0), h->Y1));
-    GemmDesc g2 = gemm_desc(h->W2, P2, 0, h->Kinv[1], P2, 0, h->X2, P2, P1, P2, P2);
-    g2.beta = 1.0; g2.C0 = h->X2; g2.ldc0 = P2;
-    pushg(side(gate(g2, 1), h->Y2));
-  }
+  begin(9);  // X1 += K1^{-1} W1, X2 += W2 K2^{-1}, Y rewritten from the refined X
+  pushg(side(sX1.fix, h->Y1));
+  pushg(side(sX2.fix, h->Y2));
   end(9);
   // Stage E: G_K1 = c N2/2 K1^{-1} - Y1 A^T;  G_K2 = c N1/2 K2^{-1} - Y2^T Bt, with
   // Y = S/2 + v X written by the X producers above (one product each instead of two)
