@@ -26,17 +26,8 @@ GPK_WAIT_LIMIT_SETTER(wait_limit_assemble)  // gpk_set_wait_limit
 
 GPK_TRACE_TU(assemble)
 
-// (eval_kd_part, class_value_store: prep_dev.h, shared with the pipelined class values of the
-// parameter-gradient launch)
-
-template <bool MATERN, bool COS, int DERIV>
-__device__ __forceinline__ void eval_kd(double diff, const double* w, const double* a,
-                                        const double* om, const double* oml, int q, double& K,
-                                        double& D) {
-  eval_kd_part<MATERN, COS, DERIV>(diff, w, a, om, oml, 0, 1, q, K, D);
-  // JAX abs JVP: select(x >= 0, g, -g) -> sign(0) = +1
-  if (DERIV == 1 && !(diff >= 0.0)) D = -D;
-}
+// (eval_kd_part, eval_kd, class_value_store: prep_dev.h, shared with the pipelined class values of
+// the parameter-gradient launch and with point_eval.hip)
 
 constexpr int ASM_SUB = 16;  // workgroups per 32x32 tile: 64 elements (2 rows) each
 

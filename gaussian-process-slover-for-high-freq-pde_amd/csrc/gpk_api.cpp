@@ -10,8 +10,9 @@
 // A row-sharded handle (gpk_create_sharded / gpk_group_create) runs the 2D step across ranks:
 // see "row-sharded multi-GPU step" in gpk_shard.cpp.
 //
-// This file: the error state, the device check, the standalone kernels, predict and the small
-// getters and setters; gpk_host.h lists the other host translation units.
+// This file: the error state, the device check, the standalone kernels, predict with its
+// derivative and scattered-point forms, and the small getters and setters; gpk_host.h lists the
+// other host translation units.
 #include "gpk_host.h"
 
 static thread_local std::string g_err;
@@ -49,8 +50,8 @@ int check_device(int dev) {
   return GPK_OK;
 }
 
-static void host_axis_const(const double* logw, const double* logls, const double* freq, int q,
-                            AxisConst* kc) {
+void host_axis_const(const double* logw, const double* logls, const double* freq, int q,
+                     AxisConst* kc) {
   std::memset(kc, 0, sizeof(AxisConst));
   for (int c = 0; c < q; ++c) {
     kc->w[c] = std::exp(logw[c]);
@@ -183,18 +184,65 @@ int gpk_criterion(gpk_handle* h, double* out) {
   return GPK_OK;
 }
 
-int gpk_predict(gpk_handle* h, const double* xte1, int32_t m1, const double* xte2, int32_t m2,
-                double* out) {
+namespace {
+
+// K^{-1} at the current params: the step's own front (apply = 0), unprofiled
+int inverse_front(gpk_handle* h) {
+  const bool prof = h->profiling;
+  h->profiling = false;
+  const int rc = enqueue_assemble_inverse(h, StepCtx{0});
+  h->profiling = prof;
+  return rc;
+}
+
+// Kmn^(d) = the d-th derivative of kappa in its first argument at (xte_i, x_j) of `axis`, no
+// jitter, into the zero-filled mp x P block Kmn.  Order 0 is launch_cross's K output and nothing
+// else is launched or allocated; above it Kmn takes the D output and K goes to a block of `tmp`.
+int cross_deriv(gpk_handle* h, CallScratch& tmp, int axis, const double* dx, int m, int mp, int d,
+                double* Kmn) {
+  const Layout& L = h->L;
+  const int P = axis_p(L, axis);
+  double* Kd = nullptr;
+  if (d) TRY(tmp.alloc(&Kd, (size_t)mp * P));
+  return check_launch(launch_cross(h->prob.kind, L.q, dx, m, axis_x(h, axis), axis_n(L, axis), P, h->kc + axis,
+                                   0.0, d, d ? Kd : Kmn, d ? Kmn : nullptr, h->s), "cross");
+}
+
+// y = al A x + be C0 over the P1 x P1 factor (the operand as the step reads it: gemv_operand)
+int predict_gemv(gpk_handle* h, const double* A, const double* x, double* y, int rows, double al,
+                 const double* C0, double be) {
+  GemvDesc g{};
+  g.A = A; g.lda = h->L.p1; g.x = x; g.y = y; g.p = h->L.p1; g.rows = rows; g.alpha = al;
+  g.C0 = C0; g.beta = be; g.epi = EPI_STORE;
+  gemv_operand(h, g);
+  return check_launch(launch_gemv(g, h->s), "gemv");
+}
+
+// alpha = K^{-1} u with one refinement step (matches solve() accuracy; 1d.py:176-179)
+int solve_alpha(gpk_handle* h, double* alpha, double* rv) {
+  TRY(predict_gemv(h, h->Kinv[0], h->Up, alpha, h->L.p1, 1.0, nullptr, 0.0));
+  TRY(predict_gemv(h, h->Kc[0], alpha, rv, h->L.p1, -1.0, h->Up, 1.0));
+  return predict_gemv(h, h->Kinv[0], rv, alpha, h->L.p1, 1.0, alpha, 1.0);
+}
+
+int launch_gemms(gpk_handle* h, const GemmDesc* d, int n) {
+  const int force_big = gemm_force(h->prob.flags);
+  for (int i = 0; i < n; ++i)
+    TRY(check_launch(launch_gemm_auto(d + i, 1, h->sc, h->s, gemm_variant(d + i, 1, force_big)), "gemm"));
+  return GPK_OK;
+}
+
+bool order_ok(int d) { return d >= 0 && d <= 2; }
+
+// gpk_predict / gpk_predict_deriv: the (d1, d2) derivative of the interpolant on a test grid
+int predict_impl(gpk_handle* h, const double* xte1, int32_t m1, const double* xte2, int32_t m2,
+                 int d1, int d2, double* out) {
   if (!h || !xte1 || !out || m1 <= 0) return fail(GPK_EINVAL, "bad argument");
   const Layout& L = h->L;
   if (L.dim == 2 && (!xte2 || m2 <= 0)) return fail(GPK_EINVAL, "2D predict needs xte2");
+  if (!order_ok(d1) || (L.dim == 2 && !order_ok(d2))) return fail(GPK_EINVAL, "derivative order must be 0, 1 or 2");
   DevSwitch ds(h->dev);
-  // K^{-1} at the current params
-  bool prof = h->profiling;
-  h->profiling = false;
-  int rc = enqueue_assemble_inverse(h, StepCtx{0});  // (apply = 0)
-  h->profiling = prof;
-  TRY(rc);
+  TRY(inverse_front(h));
   const int M1p = pad_up(m1), P1 = L.p1;
   CallScratch tmp("predict", h->s);  // (zero-filled: the padding of Kmn and of every product)
   double *dx1, *Kmn1, *res;
@@ -202,25 +250,14 @@ int gpk_predict(gpk_handle* h, const double* xte1, int32_t m1, const double* xte
   TRY(tmp.alloc(&Kmn1, (size_t)M1p * P1, true));
   HIPCHK(hipMemcpyAsync(dx1, xte1, m1 * sizeof(double), hipMemcpyHostToDevice, h->s));
   // Kmn = kappa(xte_i, x_j) (no jitter), zero-padded to M1p x P1   (model_GP_solver_2d.py:198-202)
-  TRY(check_launch(launch_cross(h->prob.kind, L.q, dx1, m1, h->x1, L.n1, P1, h->kc, 0.0, 0, Kmn1, nullptr, h->s), "cross"));
+  TRY(cross_deriv(h, tmp, 0, dx1, m1, M1p, d1, Kmn1));
   if (L.dim == 1) {
     double *alpha, *rv;
     TRY(tmp.alloc(&alpha, P1, true));
     TRY(tmp.alloc(&res, M1p, true));
     TRY(tmp.alloc(&rv, P1, true));
-    auto gv = [&](const double* A, const double* x, double* y, int rows, double al, const double* C0,
-                  double be) {
-      GemvDesc g{};
-      g.A = A; g.lda = P1; g.x = x; g.y = y; g.p = P1; g.rows = rows; g.alpha = al;
-      g.C0 = C0; g.beta = be; g.epi = EPI_STORE;
-      gemv_operand(h, g);
-      return check_launch(launch_gemv(g, h->s), "gemv");
-    };
-    // alpha = K^{-1} u with one refinement step (matches solve() accuracy; 1d.py:176-179)
-    TRY(gv(h->Kinv[0], h->Up, alpha, P1, 1.0, nullptr, 0.0));
-    TRY(gv(h->Kc[0], alpha, rv, P1, -1.0, h->Up, 1.0));
-    TRY(gv(h->Kinv[0], rv, alpha, P1, 1.0, alpha, 1.0));
-    TRY(gv(Kmn1, alpha, res, m1, 1.0, nullptr, 0.0));  // preds = Kmn K^{-1} u
+    TRY(solve_alpha(h, alpha, rv));
+    TRY(predict_gemv(h, Kmn1, alpha, res, m1, 1.0, nullptr, 0.0));  // preds = Kmn K^{-1} u
     HIPCHK(hipMemcpyAsync(out, res, m1 * sizeof(double), hipMemcpyDeviceToHost, h->s));
   } else {
     // U_pred = Kmn2 (K2^{-1} (Kmn1 K1^{-1} U)^T), associated exactly as the reference does
@@ -236,7 +273,7 @@ int gpk_predict(gpk_handle* h, const double* xte1, int32_t m1, const double* xte
     for (double** w : {&Mw, &Nw, &Rm}) TRY(tmp.alloc(w, (size_t)M1p * P2, true));
     TRY(tmp.alloc(&res, (size_t)M1p * M2p, true));
     HIPCHK(hipMemcpyAsync(dx2, xte2, m2 * sizeof(double), hipMemcpyHostToDevice, h->s));
-    TRY(check_launch(launch_cross(h->prob.kind, L.q, dx2, m2, h->x2, L.n2, P2, h->kc + 1, 0.0, 0, Kmn2, nullptr, h->s), "cross"));
+    TRY(cross_deriv(h, tmp, 1, dx2, m2, M2p, d2, Kmn2));
     // A = K1^{-1} U and N = M1 K2^{-1} = M2^T, each with one refinement step (solve() accuracy)
     const RefinedSolve sA = refined_solve(false, h->Kc[0], h->Kinv[0], h->Up, Aw, Rw, P1, P2, nullptr),
                        sN = refined_solve(true, h->Kc[1], h->Kinv[1], Mw, Nw, Rm, M1p, P2, nullptr);
@@ -244,15 +281,93 @@ int gpk_predict(gpk_handle* h, const double* xte1, int32_t m1, const double* xte
                            gemm_desc(Kmn1, P1, 0, Aw, P2, 0, Mw, P2, M1p, P2, P1),  // M1 = Kmn1 A
                            sN.solve, sN.resid, sN.fix,
                            gemm_desc(Nw, P2, 0, Kmn2, P2, 1, res, M2p, M1p, M2p, P2)};  // U_pred = N Kmn2^T
-    const int force_big = gemm_force(h->prob.flags);
-    for (const GemmDesc& g : d)
-      TRY(check_launch(launch_gemm_auto(&g, 1, h->sc, h->s, gemm_variant(&g, 1, force_big)), "gemm"));
+    TRY(launch_gemms(h, d, 8));
     for (int i = 0; i < m1; ++i)
       HIPCHK(hipMemcpyAsync(out + (size_t)i * m2, res + (size_t)i * M2p, m2 * sizeof(double),
                             hipMemcpyDeviceToHost, h->s));
   }
   const hipError_t e = hipStreamSynchronize(h->s);
   if (e != hipSuccess) return fail(GPK_EHIP, std::string("predict: ") + hipGetErrorString(e));
+  return read_status(h);
+}
+
+}  // namespace
+
+int gpk_predict(gpk_handle* h, const double* xte1, int32_t m1, const double* xte2, int32_t m2,
+                double* out) {
+  return predict_impl(h, xte1, m1, xte2, m2, 0, 0, out);
+}
+
+int gpk_predict_deriv(gpk_handle* h, const double* xte1, int32_t m1, const double* xte2, int32_t m2,
+                      int32_t d1, int32_t d2, double* out) {
+  return predict_impl(h, xte1, m1, xte2, m2, d1, d2, out);
+}
+
+// The same quantity at scattered points, in the reference's association per point: 1D
+// sum_j kappa^(d)(x_p, x_j) alpha_j; 2D sum_j kappa2^(d2)(y_p, x2_j) N[p][j] with
+// N = (Kmn1^(d1) K1^{-1} U) K2^{-1} -- no Kmn2 and no M x M product.  alpha / A = K1^{-1} U are
+// formed once; the points go in chunks of EVAL_CHUNK (the scratch is bounded whatever m), each
+// ending in its download and a stream wait, so the host staging vectors can be refilled.
+int gpk_evaluate(gpk_handle* h, const double* pts, int64_t m, int32_t d1, int32_t d2, double* out) {
+  if (!h || !pts || !out || m <= 0) return fail(GPK_EINVAL, "bad argument");
+  const Layout& L = h->L;
+  if (!order_ok(d1) || (L.dim == 2 && !order_ok(d2))) return fail(GPK_EINVAL, "derivative order must be 0, 1 or 2");
+  DevSwitch ds(h->dev);
+  TRY(inverse_front(h));
+  const int P1 = L.p1, P2 = L.p2, kind = h->prob.kind;
+  const int chunk = (int)std::min<int64_t>(m, EVAL_CHUNK), Cp = pad_up(chunk);
+  CallScratch tmp("gpk_evaluate", h->s);
+  double *dxp, *dyp = nullptr, *res, *alpha = nullptr, *rv = nullptr, *Kmn1 = nullptr, *Kd = nullptr,
+         *Aw = nullptr, *Rw = nullptr, *Mw = nullptr, *Nw = nullptr, *Rm = nullptr;
+  TRY(tmp.alloc(&dxp, chunk));
+  TRY(tmp.alloc(&res, chunk));
+  std::vector<double> hx(chunk), hy(L.dim == 2 ? chunk : 0);
+  RefinedSolve sN{};
+  GemmDesc gM{};
+  if (L.dim == 1) {
+    TRY(tmp.alloc(&alpha, P1, true));
+    TRY(tmp.alloc(&rv, P1, true));
+    TRY(solve_alpha(h, alpha, rv));
+  } else {
+    TRY(tmp.alloc(&dyp, chunk));
+    TRY(tmp.alloc(&Kmn1, (size_t)Cp * P1));
+    if (d1) TRY(tmp.alloc(&Kd, (size_t)Cp * P1));
+    for (double** w : {&Aw, &Rw}) TRY(tmp.alloc(w, (size_t)P1 * P2, true));
+    for (double** w : {&Mw, &Nw, &Rm}) TRY(tmp.alloc(w, (size_t)Cp * P2, true));
+    const RefinedSolve sA = refined_solve(false, h->Kc[0], h->Kinv[0], h->Up, Aw, Rw, P1, P2, nullptr);
+    const GemmDesc d[3] = {sA.solve, sA.resid, sA.fix};
+    TRY(launch_gemms(h, d, 3));
+  }
+  for (int64_t k = 0; k < chunk_count(m, chunk); ++k) {
+    const int64_t p0 = chunk_begin(k, chunk);
+    const int mc = chunk_size(m, k, chunk), mcp = pad_up(mc);
+    for (int i = 0; i < mc; ++i) {
+      hx[i] = pts[(size_t)(p0 + i) * L.dim];
+      if (L.dim == 2) hy[i] = pts[(size_t)(p0 + i) * 2 + 1];
+    }
+    HIPCHK(hipMemcpyAsync(dxp, hx.data(), mc * sizeof(double), hipMemcpyHostToDevice, h->s));
+    PointContract pc{};
+    pc.m = mc; pc.kc = h->kc; pc.q = L.q; pc.sj = 1; pc.sc = 1; pc.C = 1; pc.out = res;
+    if (L.dim == 1) {
+      pc.t = dxp; pc.x = h->x1; pc.n = L.n1; pc.T = alpha; pc.sp = 0;
+      TRY(check_launch(launch_point_contract(kind, d1, pc, h->s), "point_contract"));
+    } else {
+      HIPCHK(hipMemcpyAsync(dyp, hy.data(), mc * sizeof(double), hipMemcpyHostToDevice, h->s));
+      // Kmn1^(d1) of the chunk, its padding rows zero (so are those of every product below)
+      HIPCHK(hipMemsetAsync(Kmn1, 0, (size_t)mcp * P1 * sizeof(double), h->s));
+      TRY(check_launch(launch_cross(kind, L.q, dxp, mc, h->x1, L.n1, P1, h->kc, 0.0, d1, d1 ? Kd : Kmn1,
+                                    d1 ? Kmn1 : nullptr, h->s), "cross"));
+      sN = refined_solve(true, h->Kc[1], h->Kinv[1], Mw, Nw, Rm, mcp, P2, nullptr);
+      gM = gemm_desc(Kmn1, P1, 0, Aw, P2, 0, Mw, P2, mcp, P2, P1);  // G = Kmn1 A
+      const GemmDesc d[4] = {gM, sN.solve, sN.resid, sN.fix};       // N = G K2^{-1}, refined
+      TRY(launch_gemms(h, d, 4));
+      pc.t = dyp; pc.x = h->x2; pc.n = L.n2; pc.kc = h->kc + 1; pc.T = Nw; pc.sp = (size_t)P2;
+      TRY(check_launch(launch_point_contract(kind, d2, pc, h->s), "point_contract"));
+    }
+    HIPCHK(hipMemcpyAsync(out + p0, res, mc * sizeof(double), hipMemcpyDeviceToHost, h->s));
+    const hipError_t e = hipStreamSynchronize(h->s);
+    if (e != hipSuccess) return fail(GPK_EHIP, std::string("gpk_evaluate: ") + hipGetErrorString(e));
+  }
   return read_status(h);
 }
 

@@ -726,3 +726,40 @@ int gpk_refine_panel(int32_t route, int32_t side, int32_t P, int32_t M, const do
   if (e == hipSuccess && iters) e = time_launches(0, iters, 1, launch, avg_us);
   return check_launch(e, "gpk_refine_panel");
 }
+
+int gpk_point_contract(int32_t kind, int32_t deriv, const double* t, int32_t m, const double* x, int32_t n,
+                       const double* logw, const double* logls, const double* freq, int32_t q,
+                       const double* T, int64_t sp, int64_t sj, int64_t sc, int32_t C,
+                       double* out, int32_t iters, double* avg_us) {
+  if (kind < 0 || kind > 3) return fail(GPK_EINVAL, "Invalid Kernel");
+  if (deriv < 0 || deriv > 2) return fail(GPK_EINVAL, "deriv must be 0, 1 or 2");
+  if (m <= 0 || n <= 0 || C <= 0 || q <= 0 || q > QMAX || iters < 0)
+    return fail(GPK_EINVAL, "gpk_point_contract: bad sizes (m, n, C >= 1, 0 < q <= 64)");
+  if (!t || !x || !logw || !logls || !freq || !T || !out || (iters && !avg_us))
+    return fail(GPK_EINVAL, "gpk_point_contract: NULL pointer argument");
+  if (C > 1 && n > POINT_MAX_N)
+    return fail(GPK_EINVAL, "gpk_point_contract: C > 1 holds a point's n field values in LDS: n <= 4096");
+  const size_t nT = point_contract_extent(m, n, C, sp, sj, sc);
+  if (!nT) return fail(GPK_EINVAL, "gpk_point_contract: strides need sp >= 0, sj >= 1, sc >= 1");
+  TRY(check_device(0));
+  DevSwitch dsw(0);
+  AxisConst hk;
+  host_axis_const(logw, logls, freq, q, &hk);
+  CallScratch tmp("gpk_point_contract");
+  double *dt = nullptr, *dx = nullptr, *dT = nullptr, *dout = nullptr;
+  AxisConst* dkc = nullptr;
+  TRY(tmp.upload(&dt, t, (size_t)m));
+  TRY(tmp.upload(&dx, x, (size_t)n));
+  TRY(tmp.upload(&dT, T, nT));
+  TRY(tmp.alloc(&dout, (size_t)m * C));
+  TRY(tmp.upload(&dkc, &hk, 1));
+  PointContract pc{};
+  pc.t = dt; pc.m = m; pc.x = dx; pc.n = n; pc.kc = dkc; pc.q = q;
+  pc.T = dT; pc.sp = (size_t)sp; pc.sj = (size_t)sj; pc.sc = (size_t)sc; pc.C = C; pc.out = dout;
+  auto launch = [&]() { return launch_point_contract(kind, deriv, pc, 0); };
+  hipError_t e = launch();
+  if (e == hipSuccess) e = hipDeviceSynchronize();
+  if (e == hipSuccess) e = hipMemcpy(out, dout, (size_t)m * C * 8, hipMemcpyDeviceToHost);
+  if (e == hipSuccess && iters) e = time_launches(0, iters, 1, launch, avg_us);
+  return check_launch(e, "gpk_point_contract");
+}

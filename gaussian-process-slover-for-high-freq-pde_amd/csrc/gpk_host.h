@@ -1,6 +1,7 @@
 // gpk_host.h — what the host translation units of libgpk share (never included by device code):
 // the solver handle, the error helpers, and the functions that cross translation units.
-//   gpk_api.cpp     errors, device check, standalone kernels, predict, getters and setters
+//   gpk_api.cpp     errors, device check, standalone kernels, predict / predict_deriv / evaluate,
+//                   getters and setters
 //   gpk_create.cpp  handle construction (validate, choose path, allocate, classes, upload), state
 //   gpk_plan.cpp    the 2D step's GEMM plan (build_descs) and the descriptor helpers every unit
 //                   shares: gemm_desc, with_side, refined_solve, refine_panel_desc
@@ -9,8 +10,8 @@
 //                   gpk_step, gpk_prepare, gpk_loss_grad
 //   gpk_shard.cpp   the row-sharded step and its collective backends (the only user of RCCL)
 //   gpk_diag.cpp    measurement and diagnostic entry points (reached from no solver entry point),
-//                   gpk_mode_gemm and gpk_refine_panel among them
-//   gpk_kron3.cpp   the 3-axis solver (step, predictions, criterion, Adam state)
+//                   gpk_mode_gemm, gpk_refine_panel and gpk_point_contract among them
+//   gpk_kron3.cpp   the 3-axis solver (step, predictions, scattered points, criterion, Adam state)
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -24,6 +25,7 @@
 #include <vector>
 
 #include "../../include/gpk.h"
+#include "eval_chunk.h"
 #include "gpk_internal.h"
 #include "stepk.h"
 
@@ -34,6 +36,8 @@ using namespace gpk;
 int fail(int code, const std::string& msg);  // sets gpk_last_error, returns code (gpk_api.cpp)
 int check_launch(hipError_t e, const char* what);
 int check_device(int dev);
+// the axis constants of host kernel parameters, as the device derives them (gpk_api.cpp)
+void host_axis_const(const double* logw, const double* logls, const double* freq, int q, AxisConst* kc);
 #pragma GCC visibility pop
 
 #define HIPCHK(x)                                                                      \

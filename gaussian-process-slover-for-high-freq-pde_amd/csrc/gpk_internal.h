@@ -211,6 +211,20 @@ hipError_t launch_cross(int kind, int q, const double* xr, int nr, const double*
                         int ld, const AxisConst* kc, double jitter, int deriv, double* K,
                         double* D, hipStream_t s);
 
+// Contraction with a field evaluated at scattered points (point_eval.hip):
+//   out[p * C + c] = sum_{j < n} field(t[p] - x[j]) * T[p * sp + j * sj + c * sc],  p < m, c < C,
+// field = kappa / D_x1_kappa / DD_x1_kappa for deriv 0 / 1 / 2 -- cross_kernel's values, never
+// stored.  sp = 0 broadcasts one T.  C > 1 keeps a point's n field values in LDS: n <= POINT_MAX_N.
+constexpr int POINT_MAX_N = 4096;
+struct PointContract {
+  const double* t; long m;
+  const double* x; int n;
+  const AxisConst* kc; int q;
+  const double* T; size_t sp, sj, sc; int C;
+  double* out;
+};
+hipError_t launch_point_contract(int kind, int deriv, const PointContract& a, hipStream_t s);
+
 // SPD inverse by blocked Cholesky-Gauss-Jordan sweeps (pivot blocks factored in LDS).
 struct SpdArgs {
   double* X;       // [p*p] input (assembled K), ping

@@ -17,8 +17,11 @@
 //
 // Beyond the step: gpk_predict3 (test-grid predictions, T <- Kmn_k x_k solve(K_k, T) axis after
 // axis; its mode-2 products are slab-batched launches, gemm.hip, with no permuted copy),
-// gpk_criterion3 and the Adam state.  (The standalone measurements of its pieces, gpk_mode_gemm
-// and gpk_refine_panel, are in gpk_diag.cpp.)
+// gpk_predict_deriv3 (the same with D_x1_kappa / DD_x1_kappa blocks as Kmn_k), gpk_evaluate3 (the
+// same quantity at scattered points, chunk by chunk, its axis-2 and axis-3 products contracted
+// against fields evaluated on the fly: point_eval.hip), gpk_criterion3 and the Adam state.  (The
+// standalone measurements of its pieces, gpk_mode_gemm, gpk_refine_panel and gpk_point_contract,
+// are in gpk_diag.cpp.)
 #include "gpk_host.h"
 #include "gpk_kron3.h"
 
@@ -541,13 +544,62 @@ int gpk_loss_terms3(gpk_handle3* h, double out[7]) {
   return GPK_OK;
 }
 
-int gpk_predict3(gpk_handle3* h, const double* xte1, int32_t m1, const double* xte2, int32_t m2,
-                 const double* xte3, int32_t m3, double* out) {
-  if (!h || !xte1 || !xte2 || !xte3 || !out) return fail(GPK_EINVAL, "NULL argument");
-  const int ms[3] = {m1, m2, m3};
-  const double* xte[3] = {xte1, xte2, xte3};
-  for (int a = 0; a < 3; ++a)
+}  // extern "C"
+
+namespace {
+
+// K_k with jitter into Kc (the sweeps overwrote the assembled one): the refinement residuals'
+// operand of gpk_predict3 and gpk_evaluate3
+int cross_kc(gpk_handle3* h, int a, double* Kc) {
+  const K3Geom& g = h->g;
+  return check_launch(launch_cross(h->prob.kind, h->q, h->x[a], g.n[a], h->x[a], g.n[a], g.p[a], h->kc + a,
+                                   h->prob.jitter, 0, Kc, nullptr, h->s), "cross");
+}
+
+// Kmn_a^(d) = the d-th derivative of kappa in its first argument at (xt_i, x_a,j), no jitter,
+// into the zero-filled block Kmn (leading dimension p_a).  Order 0 is launch_cross's K output;
+// above it Kmn takes the D output and K goes to Kd.
+int cross_kmn(gpk_handle3* h, int a, const double* xt, int m, int d, double* Kmn, double* Kd) {
+  const K3Geom& g = h->g;
+  return check_launch(launch_cross(h->prob.kind, h->q, xt, m, h->x[a], g.n[a], g.p[a], h->kc + a, 0.0, d,
+                                   d ? Kd : Kmn, d ? Kmn : nullptr, h->s), "cross");
+}
+
+struct Solver3 {  // the refined solves of the prediction routes against the call's Kc
+  gpk_handle3* h;
+  double* const* Kc;
+  // X = K_a^{-1} B (a = 0, K on the left) or B K_a^{-1} (a = 2), rows x cols, residual scratch Wr
+  int solve(int a, const double* B, double* X, double* Wr, int rows, int cols) const {
+    const RefinedSolve s = refined_solve(a == 2, Kc[a], h->Kinv[a], B, X, Wr, rows, cols, nullptr);
+    TRY(launch_descs(h, {s.solve}));
+    TRY(launch_descs(h, {s.resid}));
+    return launch_descs(h, {s.fix});
+  }
+  // C = alpha A x_2 B + beta C0 over nb slabs of [P2][P3] (A: M x P2)
+  int slab(const double* A, int M, const double* B, double* C, double alpha, double beta, const double* C0,
+           int nb) const {
+    const int P2 = h->g.p[1], P3 = h->g.p[2];
+    SlabGemm sg{};
+    sg.A = A; sg.B = B; sg.sB = (size_t)P2 * P3; sg.C = C; sg.sC = (size_t)M * P3; sg.C0 = C0; sg.sC0 = sg.sC;
+    sg.M = M; sg.N = P3; sg.K = P2; sg.nb = nb; sg.alpha = alpha; sg.beta = beta;
+    return check_launch(launch_gemm_slab(sg, h->s), "gemm_slab");
+  }
+  int slab_solve(const double* B, double* X, double* Wr, int nb) const {
+    const int P2 = h->g.p[1];
+    TRY(slab(h->Kinv[1], P2, B, X, 1.0, 0.0, nullptr, nb));
+    TRY(slab(Kc[1], P2, X, Wr, -1.0, 1.0, B, nb));
+    return slab(h->Kinv[1], P2, Wr, X, 1.0, 1.0, X, nb);
+  }
+};
+
+// gpk_predict3 / gpk_predict_deriv3: the d-th derivatives of the interpolant on a test grid
+int predict3_impl(gpk_handle3* h, const double* const xte[3], const int ms[3], const int d[3], double* out) {
+  if (!h || !xte[0] || !xte[1] || !xte[2] || !out) return fail(GPK_EINVAL, "NULL argument");
+  for (int a = 0; a < 3; ++a) {
     if (ms[a] < 1 || ms[a] > K3_MAX_N) return fail(GPK_EINVAL, "need 1..1024 test points per axis");
+    if (d[a] < 0 || d[a] > 2) return fail(GPK_EINVAL, "derivative order must be 0, 1 or 2");
+  }
+  const int m1 = ms[0], m2 = ms[1], m3 = ms[2];
   DevSwitch ds(h->dev);
   const K3Geom& g = h->g;
   const int P1 = g.p[0], P2 = g.p[1], P3 = g.p[2];
@@ -559,7 +611,7 @@ int gpk_predict3(gpk_handle3* h, const double* xte1, int32_t m1, const double* x
   const size_t N1 = (size_t)P2 * P3, R3 = (size_t)M1p * M2p;
   const size_t big = std::max(std::max((size_t)P1 * N1, (size_t)M1p * N1),
                               std::max(R3 * P3, R3 * M3p));
-  double *xt[3], *Kmn[3], *Kc[3], *W[3];
+  double *xt[3], *Kmn[3], *Kc[3], *W[3], *Kd[3] = {};
   for (int a = 0; a < 3; ++a) {
     TRY(tmp.alloc(&xt[a], ms[a], true));
     TRY(tmp.alloc(&Kmn[a], (size_t)Mp[a] * g.p[a], true));
@@ -567,47 +619,28 @@ int gpk_predict3(gpk_handle3* h, const double* xte1, int32_t m1, const double* x
     TRY(tmp.alloc(&W[a], big, true));
   }
   for (int a = 0; a < 3; ++a)
+    if (d[a]) TRY(tmp.alloc(&Kd[a], (size_t)Mp[a] * g.p[a]));
+  for (int a = 0; a < 3; ++a)
     if (hipMemcpyAsync(xt[a], xte[a], ms[a] * sizeof(double), hipMemcpyHostToDevice, h->s) != hipSuccess)
       return fail(GPK_EHIP, "gpk_predict3: upload of the test coordinates failed");
-  // K_k^{-1} at the current params (the step's own front), then Kmn_k = kappa(xte_k, x_k) without
-  // jitter and K_k with it, for the refinement residuals
+  // K_k^{-1} at the current params (the step's own front), then Kmn_k = kappa^(d_k)(xte_k, x_k)
+  // without jitter and K_k with it, for the refinement residuals
   TRY(enqueue_inverse3(h, 0));
-  const int kind = h->prob.kind, q = h->q;
   for (int a = 0; a < 3; ++a) {
-    TRY(check_launch(launch_cross(kind, q, xt[a], ms[a], h->x[a], g.n[a], g.p[a], h->kc + a, 0.0, 0,
-                                  Kmn[a], nullptr, h->s), "cross"));
-    TRY(check_launch(launch_cross(kind, q, h->x[a], g.n[a], h->x[a], g.n[a], g.p[a], h->kc + a,
-                                  h->prob.jitter, 0, Kc[a], nullptr, h->s), "cross"));
+    TRY(cross_kmn(h, a, xt[a], ms[a], d[a], Kmn[a], Kd[a]));
+    TRY(cross_kc(h, a, Kc[a]));
   }
   // T <- Kmn_k x_k solve(K_k, T) for k = 1, 2, 3 from T = U (the reference's 2-axis association,
   // model_GP_solver_2d.py:185-220, axis after axis: every intermediate stays O(|U_pred|)); each
   // solve is A = K^{-1} T, A += K^{-1} (T - K A).  Modes 1 and 3 are GEMMs on the row-major
   // unfoldings; mode 2 of [B][P2][P3] is B slabs of P2 x P3 (launch_gemm_slab: no permuted copy).
-  double* const* Ki = h->Kinv;
-  auto solve = [&](int a, const double* B, double* X, double* Wr, int rows, int cols) -> int {
-    const RefinedSolve s = refined_solve(a == 2, Kc[a], Ki[a], B, X, Wr, rows, cols, nullptr);
-    TRY(launch_descs(h, {s.solve}));
-    TRY(launch_descs(h, {s.resid}));
-    return launch_descs(h, {s.fix});
-  };
-  auto slab = [&](const double* A, int M, const double* B, double* C, double alpha, double beta,
-                  const double* C0) {
-    SlabGemm sg{};
-    sg.A = A; sg.B = B; sg.sB = N1; sg.C = C; sg.sC = (size_t)M * P3; sg.C0 = C0; sg.sC0 = sg.sC;
-    sg.M = M; sg.N = P3; sg.K = P2; sg.nb = M1p; sg.alpha = alpha; sg.beta = beta;
-    return check_launch(launch_gemm_slab(sg, h->s), "gemm_slab");
-  };
-  auto slab_solve = [&](const double* B, double* X, double* Wr) -> int {
-    TRY(slab(Ki[1], P2, B, X, 1.0, 0.0, nullptr));
-    TRY(slab(Kc[1], P2, X, Wr, -1.0, 1.0, B));
-    return slab(Ki[1], P2, Wr, X, 1.0, 1.0, X);
-  };
+  const Solver3 sv{h, Kc};
   const int n1 = (int)N1, r3 = (int)R3;
-  TRY(solve(0, h->Up, W[0], W[1], P1, n1));
+  TRY(sv.solve(0, h->Up, W[0], W[1], P1, n1));
   TRY(launch_descs(h, {gemm_desc(Kmn[0], P1, 0, W[0], n1, 0, W[1], n1, M1p, n1, P1)}));  // [M1p][P2][P3]
-  TRY(slab_solve(W[1], W[0], W[2]));
-  TRY(slab(Kmn[1], M2p, W[0], W[1], 1.0, 0.0, nullptr));                                 // [M1p][M2p][P3]
-  TRY(solve(2, W[1], W[0], W[2], r3, P3));
+  TRY(sv.slab_solve(W[1], W[0], W[2], M1p));
+  TRY(sv.slab(Kmn[1], M2p, W[0], W[1], 1.0, 0.0, nullptr, M1p));                         // [M1p][M2p][P3]
+  TRY(sv.solve(2, W[1], W[0], W[2], r3, P3));
   TRY(launch_descs(h, {gemm_desc(W[0], P3, 0, Kmn[2], P3, 1, W[2], M3p, r3, M3p, P3)}));  // [M1p][M2p][M3p]
   for (int i1 = 0; i1 < m1; ++i1)
     if (hipMemcpy2DAsync(out + (size_t)i1 * m2 * m3, m3 * sizeof(double), W[2] + (size_t)i1 * M2p * M3p,
@@ -618,4 +651,89 @@ int gpk_predict3(gpk_handle3* h, const double* xte1, int32_t m1, const double* x
   return read_status3(h);
 }
 
+}  // namespace
+
+extern "C" {
+
+int gpk_predict3(gpk_handle3* h, const double* xte1, int32_t m1, const double* xte2, int32_t m2,
+                 const double* xte3, int32_t m3, double* out) {
+  const double* const xte[3] = {xte1, xte2, xte3};
+  const int ms[3] = {m1, m2, m3}, d[3] = {0, 0, 0};
+  return predict3_impl(h, xte, ms, d, out);
+}
+
+int gpk_predict_deriv3(gpk_handle3* h, const double* xte1, int32_t m1, const double* xte2, int32_t m2,
+                       const double* xte3, int32_t m3, const int32_t d[3], double* out) {
+  if (!d) return fail(GPK_EINVAL, "NULL argument");
+  const double* const xte[3] = {xte1, xte2, xte3};
+  const int ms[3] = {m1, m2, m3}, dd[3] = {d[0], d[1], d[2]};
+  return predict3_impl(h, xte, ms, dd, out);
+}
+
+// The same quantity at m scattered points, per point in gpk_predict3's association: with
+// A1 = K1^{-1} x_1 U (once per call), per chunk of at most EVAL_CHUNK3 points
+//   B = Kmn1^(d1) x_1 A1 [M][P2][P3] -> slab solve with K2 -> point contraction over axis 2 with
+//   kappa2^(d2)(y_p, .) [M][P3] -> right solve with K3 -> point contraction with kappa3^(d3)(z_p, .)
+// No Kmn2 / Kmn3 and no M x M (x M) product.  Each chunk ends in its download and a stream wait,
+// so the host staging vectors can be refilled.
+int gpk_evaluate3(gpk_handle3* h, const double* pts, int64_t m, const int32_t d[3], double* out) {
+  if (!h || !pts || !d || !out) return fail(GPK_EINVAL, "NULL argument");
+  if (m < 1) return fail(GPK_EINVAL, "need at least one point");
+  for (int a = 0; a < 3; ++a)
+    if (d[a] < 0 || d[a] > 2) return fail(GPK_EINVAL, "derivative order must be 0, 1 or 2");
+  DevSwitch ds(h->dev);
+  const K3Geom& g = h->g;
+  const int P1 = g.p[0], P2 = g.p[1], P3 = g.p[2], kind = h->prob.kind;
+  const size_t N1 = (size_t)P2 * P3;
+  const int chunk = (int)std::min<int64_t>(m, eval3_chunk(N1)), Cp = pad_up(chunk);
+  CallScratch tmp("gpk_evaluate3", h->s);
+  double *dp[3], *Kc[3], *A1, *WA, *Kmn1, *Kd = nullptr, *W[3], *G, *Nw, *Rn, *res;
+  for (int a = 0; a < 3; ++a) {
+    TRY(tmp.alloc(&dp[a], chunk));
+    TRY(tmp.alloc(&Kc[a], (size_t)g.p[a] * g.p[a], true));
+  }
+  TRY(tmp.alloc(&A1, (size_t)P1 * N1, true));
+  TRY(tmp.alloc(&WA, (size_t)P1 * N1, true));
+  TRY(tmp.alloc(&Kmn1, (size_t)Cp * P1));
+  if (d[0]) TRY(tmp.alloc(&Kd, (size_t)Cp * P1));
+  for (int a = 0; a < 3; ++a) TRY(tmp.alloc(&W[a], (size_t)Cp * N1, true));
+  for (double** w : {&G, &Nw, &Rn}) TRY(tmp.alloc(w, (size_t)Cp * P3, true));
+  TRY(tmp.alloc(&res, chunk));
+  TRY(enqueue_inverse3(h, 0));
+  for (int a = 0; a < 3; ++a) TRY(cross_kc(h, a, Kc[a]));
+  const Solver3 sv{h, Kc};
+  const int n1 = (int)N1;
+  TRY(sv.solve(0, h->Up, A1, WA, P1, n1));
+  std::vector<double> hp[3];
+  for (auto& v : hp) v.resize(chunk);
+  for (int64_t k = 0; k < chunk_count(m, chunk); ++k) {
+    const int64_t p0 = chunk_begin(k, chunk);
+    const int mc = chunk_size(m, k, chunk), mcp = pad_up(mc);
+    for (int i = 0; i < mc; ++i)
+      for (int a = 0; a < 3; ++a) hp[a][i] = pts[(size_t)(p0 + i) * 3 + a];
+    for (int a = 0; a < 3; ++a)
+      HIPCHK(hipMemcpyAsync(dp[a], hp[a].data(), mc * sizeof(double), hipMemcpyHostToDevice, h->s));
+    // Kmn1^(d1) of the chunk, its padding rows zero (so are those of every product below); G's
+    // padding rows are not written by the contraction, so they are cleared as well
+    HIPCHK(hipMemsetAsync(Kmn1, 0, (size_t)mcp * P1 * sizeof(double), h->s));
+    HIPCHK(hipMemsetAsync(G, 0, (size_t)mcp * P3 * sizeof(double), h->s));
+    TRY(cross_kmn(h, 0, dp[0], mc, d[0], Kmn1, Kd));
+    TRY(launch_descs(h, {gemm_desc(Kmn1, P1, 0, A1, n1, 0, W[0], n1, mcp, n1, P1)}));  // [mcp][P2][P3]
+    TRY(sv.slab_solve(W[0], W[1], W[2], mcp));
+    PointContract pc{};
+    pc.t = dp[1]; pc.m = mc; pc.x = h->x[1]; pc.n = g.n[1]; pc.kc = h->kc + 1; pc.q = h->q;
+    pc.T = W[1]; pc.sp = N1; pc.sj = (size_t)P3; pc.sc = 1; pc.C = P3; pc.out = G;       // [mcp][P3]
+    TRY(check_launch(launch_point_contract(kind, d[1], pc, h->s), "point_contract"));
+    TRY(sv.solve(2, G, Nw, Rn, mcp, P3));
+    pc.t = dp[2]; pc.x = h->x[2]; pc.n = g.n[2]; pc.kc = h->kc + 2;
+    pc.T = Nw; pc.sp = (size_t)P3; pc.sj = 1; pc.C = 1; pc.out = res;
+    TRY(check_launch(launch_point_contract(kind, d[2], pc, h->s), "point_contract"));
+    HIPCHK(hipMemcpyAsync(out + p0, res, mc * sizeof(double), hipMemcpyDeviceToHost, h->s));
+    const hipError_t e = hipStreamSynchronize(h->s);
+    if (e != hipSuccess) return fail(GPK_EHIP, std::string("gpk_evaluate3: ") + hipGetErrorString(e));
+  }
+  return read_status3(h);
+}
+
 }  // extern "C"
+

@@ -50,6 +50,17 @@ __device__ __forceinline__ void eval_kd_part(double diff, const double* w, const
   D = dv;  // unsigned: the D_x1 sign s_ij is applied by the caller
 }
 
+// K and the signed derivative field at one pair (cross_kernel, pairs_kernel, point_eval.hip): all
+// q components in order, the D_x1 sign applied.
+template <bool MATERN, bool COS, int DERIV>
+__device__ __forceinline__ void eval_kd(double diff, const double* w, const double* a,
+                                        const double* om, const double* oml, int q, double& K,
+                                        double& D) {
+  eval_kd_part<MATERN, COS, DERIV>(diff, w, a, om, oml, 0, 1, q, K, D);
+  // JAX abs JVP: select(x >= 0, g, -g) -> sign(0) = +1
+  if (DERIV == 1 && !(diff >= 0.0)) D = -D;
+}
+
 // Class u's values (class_eval_kernel; pgrad.hip next_class_values): K and the derivative field
 // at the class distance d, one mixture component per lane of a 32-lane half-wave (component c
 // and c + 32, ...), the terms added by a fixed xor butterfly (deterministic); lane 0 stores.

@@ -107,6 +107,9 @@ EXPORTS = {
     "gpk_prepare": ([ctypes.c_void_p, ctypes.c_int32], ctypes.c_int),
     "gpk_sync": ([ctypes.c_void_p], ctypes.c_int),
     "gpk_predict": ([ctypes.c_void_p, _dp, ctypes.c_int32, _dp, ctypes.c_int32, _dp], ctypes.c_int),
+    "gpk_predict_deriv": ([ctypes.c_void_p, _dp, ctypes.c_int32, _dp, ctypes.c_int32, ctypes.c_int32,
+                           ctypes.c_int32, _dp], ctypes.c_int),
+    "gpk_evaluate": ([ctypes.c_void_p, _dp, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, _dp], ctypes.c_int),
     "gpk_criterion": ([ctypes.c_void_p, _dp], ctypes.c_int),
     "gpk_profile_stages": ([ctypes.c_void_p, ctypes.c_int32, _dp, ctypes.c_int32, _ip], ctypes.c_int),
     "gpk_stage_name": ([ctypes.c_void_p, ctypes.c_int32], ctypes.c_char_p),
@@ -149,6 +152,9 @@ EXPORTS = {
                             ctypes.c_int64], ctypes.c_int),
     "gpk_predict3": ([ctypes.c_void_p, _dp, ctypes.c_int32, _dp, ctypes.c_int32, _dp, ctypes.c_int32,
                       _dp], ctypes.c_int),
+    "gpk_predict_deriv3": ([ctypes.c_void_p, _dp, ctypes.c_int32, _dp, ctypes.c_int32, _dp, ctypes.c_int32,
+                            _ip, _dp], ctypes.c_int),
+    "gpk_evaluate3": ([ctypes.c_void_p, _dp, ctypes.c_int64, _ip, _dp], ctypes.c_int),
     "gpk_criterion3": ([ctypes.c_void_p, _dp], ctypes.c_int),
     "gpk_stage_variants3": ([ctypes.c_void_p, _ip, ctypes.c_int32, _ip], ctypes.c_int),
     "gpk_loss_terms3": ([ctypes.c_void_p, _dp], ctypes.c_int),
@@ -158,6 +164,9 @@ EXPORTS = {
     "gpk_mode_gemm": ([ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
                        ctypes.c_int32, ctypes.c_double, _dp, _dp, ctypes.c_double, _dp, _dp,
                        ctypes.c_int32, _dp], ctypes.c_int),
+    "gpk_point_contract": ([ctypes.c_int32, ctypes.c_int32, _dp, ctypes.c_int32, _dp, ctypes.c_int32, _dp, _dp,
+                            _dp, ctypes.c_int32, _dp, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
+                            ctypes.c_int32, _dp, ctypes.c_int32, _dp], ctypes.c_int),
     "gpk_dgemm": ([ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_double, _dp,
                    ctypes.c_int32, ctypes.c_int32, _dp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
                    ctypes.c_double, _dp, ctypes.c_int32, ctypes.c_int32, _dp, ctypes.c_int32, ctypes.c_int32,
@@ -268,4 +277,34 @@ def refine_panel(Kinv, Kc, B, X, side=0, route=REFINE_FUSED, iters=0):
     us = ctypes.c_double()
     check(load().gpk_refine_panel(int(route), int(side), P, M, dptr(Kinv), dptr(Kc), dptr(B), dptr(out),
                                   int(iters), ctypes.byref(us)))
+    return out, (us.value if iters else None)
+
+
+def deriv_orders(deriv, dim):
+    """`deriv` as a tuple of dim ints (an int is accepted for dim 1); the library checks the range."""
+    d = (deriv,) if isinstance(deriv, (int, np.integer)) else tuple(deriv)
+    if len(d) != dim:
+        raise ValueError("deriv needs one order per axis (%d)" % dim)
+    return tuple(int(v) for v in d)
+
+
+def point_contract(kind, t, x, paras, T, C=1, sp=None, sj=None, sc=1, deriv=0, iters=0):
+    """The scattered-point contraction on host operands (gpk_point_contract): (out, avg_us) with
+    out[p, c] = sum_{j < n} field(t[p], x[j]) T.flat[p sp + j sj + c sc], field = kappa / D_x1_kappa
+    / DD_x1_kappa for deriv 0 / 1 / 2 at the kernel parameters `paras`, out (m, C).  The default
+    strides read T as a contiguous [m][n][C] array (sj = C, sp = n C); sp = 0 broadcasts one [n][C]
+    block to every point.  avg_us is None when iters = 0."""
+    t, x, T = f64(t).reshape(-1), f64(x).reshape(-1), f64(T).reshape(-1)
+    lw, ll, fr = (f64(paras[k]).reshape(-1) for k in ("log-w", "log-ls", "freq"))
+    m, n, C = t.size, x.size, int(C)
+    sj = C if sj is None else int(sj)
+    sp = n * sj if sp is None else int(sp)
+    if min(m, n, C) > 0 and sp >= 0 and sj > 0 and sc > 0 and T.size < (m - 1) * sp + (n - 1) * sj + (C - 1) * sc + 1:
+        raise ValueError("point_contract: T is shorter than the strides address")
+    out = np.empty((max(m, 1), max(C, 1)))
+    us = ctypes.c_double()
+    k = KIND_IDS[kind] if isinstance(kind, str) else int(kind)
+    check(load().gpk_point_contract(k, int(deriv), dptr(t), m, dptr(x), n, dptr(lw), dptr(ll), dptr(fr),
+                                    lw.size, dptr(T), sp, sj, int(sc), C, dptr(out), int(iters),
+                                    ctypes.byref(us)))
     return out, (us.value if iters else None)

@@ -237,6 +237,37 @@ class DeviceSolver:
         check(_lib.load().gpk_predict(self._h, dptr(x1), x1.size, dptr(x2), x2.size, dptr(out)))
         return out.reshape(x1.size, x2.size)
 
+    def predict_deriv(self, xte1, xte2=None, deriv=(0, 0)):
+        """The deriv-th derivatives (per axis, each 0, 1 or 2) of the solution on the test grid, taken
+        in the test point (gpk_predict_deriv): (m1,) for a 1D handle (deriv an int or a 1-tuple),
+        (m1, m2) in 2D.  Order 0 is predict(), bit for bit."""
+        d = _lib.deriv_orders(deriv, self.dim)
+        x1 = f64(xte1).reshape(-1)
+        if self.dim == 1:
+            out = np.empty(max(x1.size, 1))
+            check(_lib.load().gpk_predict_deriv(self._h, dptr(x1), x1.size, None, 0, d[0], 0, dptr(out)))
+            return out[:x1.size]
+        x2 = None if xte2 is None else f64(xte2).reshape(-1)
+        m2 = 0 if x2 is None else x2.size
+        out = np.empty(max(x1.size * m2, 1))
+        check(_lib.load().gpk_predict_deriv(self._h, dptr(x1), x1.size, None if x2 is None else dptr(x2), m2,
+                                            d[0], d[1], dptr(out)))
+        return out[:x1.size * m2].reshape(x1.size, m2)
+
+    def evaluate(self, points, deriv=None):
+        """The same quantity at scattered points (gpk_evaluate): points (m,) or (m, 1) for a 1D
+        handle, (m, 2) in 2D; returns (m,).  deriv defaults to order 0 (the solution itself)."""
+        d = _lib.deriv_orders((0,) * self.dim if deriv is None else deriv, self.dim)
+        if points is None:
+            pts, m = None, 0
+        else:
+            pts = f64(points).reshape(-1, self.dim)
+            m = pts.shape[0]
+        out = np.empty(max(m, 1))
+        check(_lib.load().gpk_evaluate(self._h, None if pts is None else dptr(pts), m, d[0],
+                                       d[1] if self.dim == 2 else 0, dptr(out)))
+        return out[:m]
+
     def criterion(self):
         c = ctypes.c_double()
         check(_lib.load().gpk_criterion(self._h, ctypes.byref(c)))

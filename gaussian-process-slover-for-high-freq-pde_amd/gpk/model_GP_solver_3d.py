@@ -148,6 +148,31 @@ class DeviceSolver3:
                                        dptr(out)))
         return out[:ms[0] * ms[1] * ms[2]].reshape(ms)
 
+    def predict_deriv(self, xte1, xte2, xte3, deriv):
+        """The deriv[k]-th derivative (0, 1 or 2) along each axis of the solution on the test grid,
+        (m1, m2, m3), taken in the test point (gpk_predict_deriv3).  (0, 0, 0) is predict()."""
+        d = np.asarray(_lib.deriv_orders(deriv, 3), np.int32)
+        xs = [None if x is None else f64(x).reshape(-1) for x in (xte1, xte2, xte3)]
+        ms = [0 if x is None else x.size for x in xs]
+        out = np.empty(max(ms[0] * ms[1] * ms[2], 1))
+        check(_lib.load().gpk_predict_deriv3(self._h, *[a for x, m in zip(xs, ms)
+                                                         for a in (None if x is None else dptr(x), m)],
+                                             d.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), dptr(out)))
+        return out[:ms[0] * ms[1] * ms[2]].reshape(ms)
+
+    def evaluate(self, points, deriv=(0, 0, 0)):
+        """The same quantity at scattered points (m, 3), any m >= 1 (gpk_evaluate3); returns (m,)."""
+        d = np.asarray(_lib.deriv_orders(deriv, 3), np.int32)
+        if points is None:
+            pts, m = None, 0
+        else:
+            pts = f64(points).reshape(-1, 3)
+            m = pts.shape[0]
+        out = np.empty(max(m, 1))
+        check(_lib.load().gpk_evaluate3(self._h, None if pts is None else dptr(pts), m,
+                                        d.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), dptr(out)))
+        return out[:m]
+
     def criterion(self):
         c = ctypes.c_double()
         check(_lib.load().gpk_criterion3(self._h, ctypes.byref(c)))

@@ -141,6 +141,59 @@ class SolverBase(object):
         self._version += 1
         return losses
 
+    # -- beyond the reference: derivatives of the solution and values at scattered points ------
+    def _test_axes(self, X_test):
+        X = self.Xte if X_test is None else X_test
+        if X is None:
+            raise ValueError("a test grid is needed (X_test)")
+        if self.dim == 1:
+            return (np.asarray(X, np.float64).reshape(-1),)
+        if len(X) != self.dim:
+            raise ValueError("X_test needs one axis per dimension")
+        return tuple(np.asarray(x, np.float64).reshape(-1) for x in X)
+
+    def preds_deriv(self, params, deriv, X_test=None):
+        """The deriv-th derivatives of the solution (one order 0, 1 or 2 per axis; an int in 1D),
+        taken in the test point, on the test grid X_test (default: the solver's own Xte; 1D: the
+        test points, else one axis per dimension).  Returns (M,) in 1D, (M1, M2) / (M1, M2, M3)
+        on two / three axes.  Order 0 everywhere is preds()."""
+        self._sync(params)
+        return self.dev.predict_deriv(*self._test_axes(X_test), deriv=deriv)
+
+    def preds_at(self, params, points, deriv=None):
+        """The same quantity at scattered points: points (m,) in 1D, (m, dim) otherwise; returns
+        (m,).  deriv defaults to order 0, the solution itself."""
+        self._sync(params)
+        return self.dev.evaluate(points, deriv=(0,) * self.dim if deriv is None else deriv)
+
+    def eq_residual(self, params, X_test, src_test):
+        """The equation's residual on the test grid X_test from the derivative predictions and
+        the source values src_test there (the grid's shape) -- boundary_and_eq_gap's expression and
+        the step's R, between the collocation points: Poisson u_xx + u_yy [+ u_zz] - f, Allen-Cahn
+        ... + u (u^2 - 1) - f, advection beta u_x + u_y - f (x the first axis)."""
+        self._sync(params)
+        axes = self._test_axes(X_test)
+        dim = self.dim
+
+        def pd(k, order):
+            d = [0] * dim
+            d[k] = order
+            return self.dev.predict_deriv(*axes, deriv=tuple(d))
+
+        eq = self.eq_type.split("_")[0]
+        if eq == "advection":
+            r = self.beta * pd(0, 1) + pd(1, 1)
+        elif eq in ("poisson", "allencahn"):
+            r = pd(0, 2)
+            for k in range(1, dim):
+                r = r + pd(k, 2)
+            if eq == "allencahn":
+                u = pd(0, 0)
+                r = r + u * (u ** 2 - 1)
+        else:
+            raise NotImplementedError
+        return r - np.asarray(src_test, np.float64).reshape(r.shape)
+
     def compute_early_stopping(self, params, key=None):
         """boundary_gap/Nb + eq_gap/Nc (model_GP_solver_2d.py:222-233)."""
         self._sync(params)

@@ -294,6 +294,24 @@ int gpk_prepare(gpk_handle* h, int32_t n_steps);
 int gpk_predict(gpk_handle* h, const double* xte1, int32_t m1, const double* xte2, int32_t m2,
                 double* out);
 
+/* d^d1/dx^d1 d^d2/dy^d2 of the interpolant u(x*) = kappa(x*, X) K^{-1} u on the test grid
+ * xte1 x xte2 at the current params; d1, d2 in {0, 1, 2}; out as gpk_predict.  The derivative is
+ * taken in the test point (kappa's first argument): Kmn_k is D_x1_kappa / DD_x1_kappa in place of
+ * kappa, the D block of gpk_kernel_matrices(deriv = d_k, xte_k, x_k), with its sign and JAX's
+ * abs'(0) = +1; the solves are gpk_predict's.  1D handles: xte2 / m2 / d2 ignored.  (0, 0) is
+ * gpk_predict, bit for bit.  Handles, status codes and side effects (none on params or Adam state)
+ * as gpk_predict; GPK_EINVAL on an order outside 0..2. */
+int gpk_predict_deriv(gpk_handle* h, const double* xte1, int32_t m1, const double* xte2, int32_t m2,
+                      int32_t d1, int32_t d2, double* out);
+
+/* The same quantity at m >= 1 scattered points: pts [m][dim] row-major (dim = the handle's, 1 or
+ * 2), out [m].  Per point in the reference's association (model_GP_solver_2d.py:185-220): 1D
+ * sum_j kappa^(d1)(x_p, x_j) (K^{-1} u)_j; 2D sum_j kappa2^(d2)(y_p, x2_j) N[p][j] with
+ * N = (Kmn1^(d1) K1^{-1} U) K2^{-1}, the kernel fields evaluated on the fly -- O(m (P1 + P2)) memory
+ * instead of the m x m grid whose diagonal this is.  The points are walked in chunks of 4096, so
+ * the scratch (allocated for the call, freed on return) is bounded whatever m. */
+int gpk_evaluate(gpk_handle* h, const double* pts, int64_t m, int32_t d1, int32_t d2, double* out);
+
 /* compute_early_stopping (model_GP_solver_2d.py:222-233): bgap/Nb + egap/Nc */
 int gpk_criterion(gpk_handle* h, double* out);
 
@@ -446,6 +464,18 @@ int gpk_get_opt_state3(gpk_handle3* h, int64_t* count, double* mu, double* nu, i
  * state are untouched. */
 int gpk_predict3(gpk_handle3* h, const double* xte1, int32_t m1, const double* xte2, int32_t m2,
                  const double* xte3, int32_t m3, double* out);
+/* gpk_predict3 with the d[k]-th derivative (0, 1 or 2) along axis k, taken in the test point as
+ * in gpk_predict_deriv: Kmn_k is the D block of gpk_kernel_matrices(deriv = d[k], xte_k, x_k).
+ * d = {0, 0, 0} is gpk_predict3, bit for bit; sizes, status codes and side effects are its own. */
+int gpk_predict_deriv3(gpk_handle3* h, const double* xte1, int32_t m1, const double* xte2, int32_t m2,
+                       const double* xte3, int32_t m3, const int32_t d[3], double* out);
+/* The same quantity at m >= 1 scattered points, pts [m][3] row-major, out [m]: gpk_predict3's
+ * association per point, with the axis-2 and axis-3 products contracted against kernel fields
+ * evaluated on the fly (no m x m x m grid, and no limit of 1024 on m).  The points are walked in
+ * chunks of at most 1024 (fewer on grids whose chunk x P2 x P3 intermediate would pass 2 GiB); the
+ * solve K1^{-1} x_1 U is done once per call.  A point's result does not depend on the chunks
+ * before it.  Scratch, status codes and side effects as gpk_predict3. */
+int gpk_evaluate3(gpk_handle3* h, const double* pts, int64_t m, const int32_t d[3], double* out);
 /* compute_early_stopping (model_GP_solver_2d.py:222-233) on three axes: boundary_gap / Nb +
  * eq_gap / Nc at the current params, Nb = 2 (n2 n3 + n1 n3 + n1 n2), Nc = n1 n2 n3. */
 int gpk_criterion3(gpk_handle3* h, double* out);
@@ -483,6 +513,21 @@ int gpk_mode_gemm(int32_t variant, int32_t k, int32_t d1, int32_t d2, int32_t d3
  * gpk_mode_gemm (the timed launches keep refining the device copy of X). */
 int gpk_refine_panel(int32_t route, int32_t side, int32_t P, int32_t M, const double* Kinv, const double* Kc,
                      const double* B, double* X, int32_t iters, double* avg_us);
+
+/* The scattered-point contraction on host operands (tests, timing; the counterpart of
+ * gpk_mode_gemm / gpk_refine_panel):
+ *   out[p * C + c] = sum_{j < n} field(t[p], x[j]) * T[p * sp + j * sj + c * sc],  p < m, c < C,
+ * field = kappa / D_x1_kappa / DD_x1_kappa for deriv 0 / 1 / 2 (first argument = the point), the
+ * values of gpk_kernel_matrices(kind, deriv, t, x, ...), evaluated on the fly.  sp = 0 broadcasts
+ * one T to all points; sp >= 0, sj >= 1, sc >= 1, and T holds (m-1) sp + (n-1) sj + (C-1) sc + 1
+ * doubles, of which only the addressed ones are used (padding may hold anything).  C = 1: one
+ * wave per point; C > 1: the point's field values in LDS, n <= 4096 (else GPK_EINVAL).  The sum's
+ * order depends on (n, C) only.  iters > 0 times that many back-to-back launches with HIP events
+ * after the checked one; *avg_us as gpk_dgemm. */
+int gpk_point_contract(int32_t kind, int32_t deriv, const double* t, int32_t m, const double* x, int32_t n,
+                       const double* logw, const double* logls, const double* freq, int32_t q,
+                       const double* T, int64_t sp, int64_t sj, int64_t sc, int32_t C,
+                       double* out, int32_t iters, double* avg_us);
 
 #ifdef __cplusplus
 }
