@@ -131,7 +131,7 @@ static int reset_handoffs(gpk_handle* h) {
     const size_t nflags = T * (T + (L.p1 + L.p2) / 32) + 2 * T + 1;
     HIPCHK(hipMemsetD32Async(h->cgran[a], CHAIN_SENTINEL32, T * 6144, h->s));
     if (h->PB2[a]) HIPCHK(hipMemsetD32Async(h->PB2[a], CHAIN_SENTINEL32, 4 * chain_half((int)P, h->chain_multi), h->s));
-    if (h->cepoch[a]) HIPCHK(hipMemsetAsync(h->cepoch[a], 0, 4 * sizeof(unsigned int), h->s));
+    if (h->cepoch[a]) HIPCHK(hipMemsetAsync(h->cepoch[a], 0, CHAIN_EPOCH_WORDS * sizeof(unsigned int), h->s));
     HIPCHK(hipMemsetAsync(h->cflags[a], 0, nflags * sizeof(unsigned int), h->s));
     HIPCHK(hipMemsetAsync(h->aflag[a], 0, (4 + P / 32) * sizeof(unsigned int), h->s));
   }

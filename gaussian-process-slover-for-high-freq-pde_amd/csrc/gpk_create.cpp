@@ -225,7 +225,7 @@ static int allocate_buffers(gpk_handle* h, const gpk_problem* p) {
       return fail(GPK_EHIP, "initialise the pivot-chain input slots");
     if (h->chain) {  // chain_multi: panel + L^{-1} slots; chain_kernel: the L^{-1} slots
       A_(h->PB2[a], 2 * chain_half(P, h->chain_multi));
-      A_(h->cepoch[a], 4);
+      A_(h->cepoch[a], CHAIN_EPOCH_WORDS);  // launch counter, arrival count (each its own line)
       if (hipMemsetD32Async(h->PB2[a], CHAIN_SENTINEL32, 4 * chain_half(P, h->chain_multi), h->s) != hipSuccess)
         return fail(GPK_EHIP, "initialise the panel slots");
     }

@@ -170,7 +170,7 @@ struct gpk_handle {
   unsigned int* cflags[2] = {};       // its hand-off flags [T*(T+taug) + 2T + 1] per factor
   double* cgran[2] = {};              // its pivot-chain input slots [T][3][1024] per factor
   double* PB2[2] = {};                // chain_multi: panel slots [2][P*P] by launch parity
-  unsigned int* cepoch[2] = {};       // chain_multi: launch counter per factor
+  unsigned int* cepoch[2] = {};       // launch counter + arrival count per factor [CHAIN_EPOCH_WORDS]
   double *PD[2] = {}, *PBa[2] = {};   // K_a^{-1} D_a^T; augmented panel buffers
   ClassArgs cls[2] = {};              // distance classes per axis (ncls = 0: per-pair path)
   double* rvec = nullptr;            // 1D refinement residual

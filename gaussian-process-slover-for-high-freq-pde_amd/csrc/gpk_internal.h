@@ -270,7 +270,12 @@ hipError_t launch_spd_stage(SpdArgs* args, int nmat, int stage, hipStream_t s);
 constexpr int CHAIN_MAX_BLOCKS = 512;
 struct ChainArgs {
   double* X; double* PB; double* piv; double* ldet; double* pst; int* status;
-  unsigned int* flags;  // [T*(T+tu+td) + 2T + 1], zero-initialised
+  // [T*(T+tu+td) + 2T + 1], zero-initialised: the panel-ready flags [T*(T+tu+td)], each holding
+  // the tag (epoch + 1) of the launch that raised it and never cleared by a kernel; the 2T + 1
+  // words behind them (once the pivot-ready flags, a gap and the done counter) keep their place;
+  // chain_kernel uses none of them, chain_multi_kernel counts its exits on the last
+  // (spdinv.hip ChainFactor::flags)
+  unsigned int* flags;
   int p, n;
   const int* cid; const double* kval; const double* dval; const double* x; double jitter;
   double* Kc; double* D;
@@ -283,9 +288,17 @@ struct ChainArgs {
                                            // (plain protocol: [T][2][1024] of them)
   int lookahead;                           // chain_kernel: two-block look-ahead in the pivot chain
                                            // (spdinv.hip chain_master_la; chain_multi ignores it)
-  double* PB2; unsigned int* epoch;        // chain_multi: hand-off slots [2][multi_half(p)]
-                                           // (CHAIN_SENTINEL), launch counter (zeroed)
+  double* PB2; unsigned int* epoch;        // hand-off slots [2][chain_half(p, multi)]
+                                           // (CHAIN_SENTINEL); launch counter + arrival count
+                                           // [CHAIN_EPOCH_WORDS], zeroed.  Both required.
 };
+// ChainArgs::epoch: word 0 the factor's launch counter (its parity selects the PB2 half, counter
+// + 1 tags the launch's flags), word CHAIN_STARTED -- a 128-byte line of its own, so that a few
+// hundred arrivals do not queue in front of the epoch loads -- the count of workgroups that have
+// read it in the current chain_kernel launch; the pivot chain's workgroup zeroes the count and
+// advances the counter (spdinv.hip chain_advance; chain_multi_kernel advances it from its last
+// workgroup to exit).  All zero at create and after reset_handoffs.
+constexpr int CHAIN_STARTED = 32, CHAIN_EPOCH_WORDS = 64;
 // one launch-parity half of chain_multi's hand-off slots: the panel [p*p], then L_k^{-1} of every
 // pivot [p/32][1024]
 __host__ __device__ inline size_t multi_half(int p) { return (size_t)p * p + (size_t)32 * p; }

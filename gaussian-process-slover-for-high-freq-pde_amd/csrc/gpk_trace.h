@@ -25,9 +25,17 @@ enum TraceSlot {
   // dispatch spread (last workgroup start) and intermediate points
   SLOT_PG_START = 47, SLOT_PG_STAGED = 48, SLOT_CSUM_START = 49, SLOT_CEVAL_START = 50,
   SLOT_GATHER_START = 51, SLOT_CSUM_LOADED = 52, SLOT_CHAIN_END = 53, SLOT_CHAIN_M1 = 54,
-  // chain, last sweep, tile (T-1, T-1) of factor 0: L^{-1} flag seen, L^{-1} in LDS, products
-  // done, outputs stored + done-counter returned; 62: the same end point, last aug tile
+  // chain, last sweep, tile (T-1, T-1) of factor 0: L^{-1} word seen, L^{-1} in LDS, products
+  // done, thread 0's output stores drained (the workgroup's exit: nothing is counted there any
+  // more); 62: the same end point, last aug tile.
+  // SLOT_CHAIN_END (53): the latest exit among a SAMPLE of tile workgroups -- up to four per
+  // factor in tile row max(T-2, 0), among the heaviest of the last sweep -- each at the same end
+  // point.  It bounds the launch's last exit from below; no workgroup can tell that it is the
+  // last, and a probe in all ~390 would serialise on the slot like the arrival count it replaced.
+  // SLOT_CHAIN_BUMP (63): factor 0's pivot-chain workgroup has seen every arrival and advanced the
+  // epoch (chain_advance).
   SLOT_LAST_FLAG = 58, SLOT_LAST_LDS = 59, SLOT_LAST_MMA = 60, SLOT_LAST_OUT = 61, SLOT_LAST_AUG = 62,
+  SLOT_CHAIN_BUMP = 63,
   SLOT_GEMM = 64,  // + 4 * stage: first wg [start, end], + 1: first wg operands loaded,
                    // + 2: first wg MFMAs done, + 3: last wg [start, end]  (stages < 16)
   // chain_multi_kernel, factor 0, sweep k < 16, the workgroup owning tile (k+2, k+2) (the pivot
@@ -74,7 +82,8 @@ constexpr int BIG_PROBE_SWEEP = 8;
     (void)hipMemcpyToSymbol(HIP_SYMBOL(trace_hi), hi, sizeof(hi));                        \
   }
 // probes fire in thread 0 of ONE workgroup per slot (a first-block / last-block / critical
-// block); same-address atomics from every workgroup would serialise and distort the timeline
+// block; SLOT_CHAIN_END: a sample of at most eight); same-address atomics from every workgroup
+// would serialise and distort the timeline
 #define TR_FIRST (threadIdx.x == 0 && blockIdx.x == 0 && blockIdx.y == 0 && blockIdx.z == 0)
 #define TR_LAST                                                                       \
   (threadIdx.x == 0 && blockIdx.x == gridDim.x - 1 && blockIdx.y == gridDim.y - 1 && \

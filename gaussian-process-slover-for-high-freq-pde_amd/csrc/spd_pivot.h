@@ -45,6 +45,19 @@ __device__ __forceinline__ bool spin_until_ge(const unsigned int* c, unsigned in
   return true;
 }
 
+// ... until the word EQUALS target (the chain inverse's tagged flags and its arrival count:
+// words that are never cleared, so "not yet" is any other value)
+template <int SLEEP = 1>
+__device__ __forceinline__ bool spin_until_eq(const unsigned int* c, unsigned int target, int* status) {
+  for (unsigned spins = 0;
+       __hip_atomic_load(const_cast<unsigned int*>(c), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != target;
+       ++spins) {
+    if (spin_give_up(spins, status)) return false;
+    __builtin_amdgcn_s_sleep(SLEEP);
+  }
+  return true;
+}
+
 // v_rsq_f64 is 2^-24.2 relative (tools/probes/rsq_probe.hip): one Newton step leaves 4e-15,
 // two 1.4e-16.  One third-order step y (1 + e/2 + 3e^2/8), e = 1 - p y^2 (truncation ~e^3/3 =
 // 2^-70) reaches the same accuracy in 4 dependent operations after the rsq instead of 6: the

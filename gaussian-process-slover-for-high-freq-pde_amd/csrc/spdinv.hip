@@ -250,13 +250,30 @@ struct ChainFactor {
   double* ldet;         // [T]
   double* pst;          // refinement gate [2]
   int* status;
-  unsigned int* flags;  // [T*TC] panel ready, [T] pivot ready, a T-word gap (the ABI's
-                        // allocation), the done counter at T*TC + 2T (zero; re-armed by the last workgroup)
+  // [T*TC] panel ready (chain_kernel); the 2T + 1 words after them (once the pivot-ready flags, a
+  // gap and the done counter) keep their place in the ABI's allocation; chain_kernel uses none of
+  // them, chain_multi_kernel (no flags) still counts its exits on the last, at T*T + 2T.  A flag
+  // carries the TAG of the launch that raised it, epoch + 1 (chain_tag), and no kernel ever clears
+  // one: a waiter spins until the word EQUALS its own launch's tag, and a word left by any earlier
+  // launch of the factor differs from it -- also when that launch laid the buffer out for another
+  // TC (the step's augmented launch, TC = T + tu + td, and the K^{-1}-only launch, TC = T, share
+  // it: the tag is unique per launch of the factor, whatever its layout) and in the create-time /
+  // reset_handoffs state (all zero, epoch 0: the first tag is 1).  The epoch advances by exactly
+  // one per launch and wraps at 2^32 like the tag; equality needs no order, so the wrap itself is
+  // harmless.  A stale word could pass only if it was last written exactly 2^32 launches of the
+  // factor ago -- or never since the reset, at the one launch whose tag is 0 -- and every launch
+  // rewrites every word it waits on in its own layout.
+  unsigned int* flags;
   double* gran;              // the pivot chain's input slots [T][3][1024] (chain_master)
   int la;                    // chain_kernel: two-block look-ahead in the pivot chain (chain_master)
-  double* PB2;               // chain_multi: panel slots [2][p*p] by launch parity (self-validating)
-  unsigned int* epoch;       // chain_multi: launch counter (its parity selects the PB2 half)
-  int piv_off;               // offset of the pivot-ready flags (T * TC)
+  double* PB2;               // hand-off slots [2][chain_half] by launch parity (self-validating)
+  // [CHAIN_EPOCH_WORDS] launch counter: its parity selects the PB2 half, epoch + 1 tags the flags.
+  // One 128-byte line further (CHAIN_STARTED) chain_kernel's `started` count: every active
+  // workgroup of the factor adds one after its last read of the epoch (chain_arrive), and the pivot
+  // chain's workgroup, the first to finish, zeroes it and advances the epoch once all have
+  // (chain_advance).  chain_multi_kernel advances the epoch from its last workgroup to exit.
+  unsigned int* epoch;
+  int piv_off;               // T * TC (once the offset of the pivot-ready flags; unused)
   int p, n, T;
   // gather mode: K from the distance classes (+ jitter), kept copy Kc and D written on the way
   const int* cid; const double* kval; const double* dval; const double* x; double jitter;
@@ -283,15 +300,50 @@ __device__ __forceinline__ void st_sc1(double* p, double v) {
 __device__ __forceinline__ double ld_sc1(const double* p) {
   return __hip_atomic_load(const_cast<double*>(p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
-// bounded (spd_pivot.h spin_until_ge): a flag that never rises sets status bit 2
-__device__ __forceinline__ void wait_flag(unsigned int* f, int* status) {
-  (void)spin_until_ge<1>(f, 1u, status);
+// The launch's tag: what its flags hold once raised (ChainFactor::flags).  ep: the epoch word as
+// this workgroup loaded it at its start.
+__device__ __forceinline__ unsigned chain_tag(unsigned ep) { return ep + 1u; }
+// bounded (spd_pivot.h spin_until_eq): a flag that never takes this launch's tag sets status bit 2
+__device__ __forceinline__ void wait_flag(unsigned int* f, unsigned tag, int* status) {
+  (void)spin_until_eq<1>(f, tag, status);
 }
 // every wave drained its sc1 stores -> barrier -> one lane raises the flag
-__device__ __forceinline__ void signal_flag(unsigned int* f) {
+__device__ __forceinline__ void signal_flag(unsigned int* f, unsigned tag) {
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
-  if (threadIdx.x == 0) __hip_atomic_store(f, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  if (threadIdx.x == 0) __hip_atomic_store(f, tag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+// A workgroup's arrival on the factor's `started` count: ONE non-returning agent-scope add by one
+// thread, which nothing in the workgroup waits for.  The epoch may advance as soon as the count is
+// full, so NO THREAD OF THE WORKGROUP MAY READ THE EPOCH WORD AFTER THIS IS ISSUED -- and an add
+// is not ordered behind another wave's outstanding load.  chain_kernel's tile workgroups
+// therefore issue it in sweep 0 behind the barrier that
+// follows the LDS stores of L_0^{-1}: every thread loads those words through an address formed
+// from its own copy of the epoch (the PB2 half) and stores them to LDS before that barrier, so
+// every wave reaches it only with its epoch load returned.  The pivot chain's workgroup arrives
+// in chain_advance.
+__device__ __forceinline__ void chain_arrive(const ChainFactor& F) {
+  (void)__hip_atomic_fetch_add(F.epoch + CHAIN_STARTED, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+// The pivot chain's workgroup, after its last L^{-1} and ldet are stored (it is the first of the
+// factor to finish: the tiles' last sweep is still ahead, ~3 us at C4): its own arrival, then one
+// thread polls `started` until all `active` workgroups of the factor have arrived -- they did
+// tens of microseconds ago, so this is one load round trip under the tiles' last sweep -- zeroes
+// it and advances the epoch for the next launch.  Nothing waits at the launch's end any more:
+// a tile workgroup exits after its output stores.  The barrier: every thread of this workgroup
+// has stored L^{-1} words through its own copy of the epoch before it (chain_arrive's condition).
+// Bounded like every wait; a poll that gives up (status bit 2) leaves both words alone -- the
+// host resets them (reset_handoffs), and until then the later launches of a captured batch see a
+// count that never fits and give up within 64 polls.
+__device__ __forceinline__ void chain_advance(const ChainFactor& F, unsigned ep, unsigned active, bool tr) {
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  unsigned int* started = F.epoch + CHAIN_STARTED;
+  chain_arrive(F);
+  if (!spin_until_eq<1>(started, active, F.status)) return;
+  __hip_atomic_store(started, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  __hip_atomic_store(F.epoch, ep + 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  if (tr) TR_HI(SLOT_CHAIN_BUMP);
 }
 
 // The pivot chain's inputs travel as self-validating words (MI355X_MICROARCH.md hand-off row
@@ -422,7 +474,6 @@ __device__ __forceinline__ void chain_master_la(const ChainFactor& F, int T, d4 
     c = wq == 2 ? 1 : 0;
     nw = wq == 3 ? 24 : 20;
   };
-  unsigned int* piv_rdy = F.flags + F.piv_off;
   __builtin_amdgcn_s_setprio(3);
   const double snan = __longlong_as_double((long long)CHAIN_SENTINEL);
   // word i of this wave's look-ahead inputs, as an offset into the slot's three tiles (0: P2,
@@ -535,10 +586,9 @@ __device__ __forceinline__ void chain_master_la(const ChainFactor& F, int T, d4 
       }
     }
     const double ls = pivot_chol_inv_1w<double*, NoPivotHook>(sP, Mk, pv, t, F.status);
-    double* ldst = (lw ? lw : F.piv) + (size_t)kp * 1024;
+    double* ldst = lw + (size_t)kp * 1024;
     for (int e = t; e < 1024; e += 256) st_sc1(ldst + e, Mk[(e >> 5) * SP + (e & 31)]);
     if (t == 0) F.ldet[kp] = ls;
-    if (kp + 1 == T && !lw) signal_flag(piv_rdy + kp);
     if (trm && kp > 0 && kp < 17) TR_HI(SLOT_SWEEP_PIVOT + kp - 1);
     if (trm && kp == 0) TR_HI(SLOT_PIVOT0);
   };
@@ -547,7 +597,7 @@ __device__ __forceinline__ void chain_master_la(const ChainFactor& F, int T, d4 
     __hip_atomic_store(reinterpret_cast<unsigned long long*>(F.pst + 1), 0ull, __ATOMIC_RELAXED,
                        __HIP_MEMORY_SCOPE_AGENT);
   }
-  if (lw) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // (the zeroing, before any L^{-1} word: below)
   // ONE call site of factor(): the unrolled factorisation (~10 KB) is inlined once, so pivot 0
   // runs the loop's copy and leaves it warm in the instruction cache for pivot 1 (with a call
   // ahead of the loop, pivot 0 ran a copy used once per launch and pivot 1 the loop's copy cold)
@@ -563,9 +613,7 @@ __device__ __forceinline__ void chain_master_la(const ChainFactor& F, int T, d4 
       for (int r = 0; r < 4; ++r) acc[r] = sD[(16 * wr + lk + 4 * r) * SP + 16 * wc + li];
       d4 vj = {0.0, 0.0, 0.0, 0.0};
       vj = mma_t(Lh, SP, 1, sXh, SB, 1, wr, wc, lane, vj);  // V1 = L_h^{-1} X_{h,h+1}
-      if (!lw) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // L^{-1}_h's stores, before its flag
       __syncthreads();
-      if (t == 0 && !lw) __hip_atomic_store(piv_rdy + h, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       store_quad(sXh, SB, wr, wc, lane, vj);
       __syncthreads();
       d4 prod = {0.0, 0.0, 0.0, 0.0};
@@ -598,7 +646,6 @@ __device__ __forceinline__ void chain_master(const ChainFactor& F, int T, d4 acc
   const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
   const int wr = wv >> 1, wc = wv & 1;
   const int tx = t & 31, ty = t >> 5;
-  unsigned int* piv_rdy = F.flags + F.piv_off;
   __shared__ int s_pflag;  // pivot_chol_inv_1w's "wave 0 passed block step 5" flag
     // (issue priority over the tile workgroup that may share its CU: this one is the chain)
   __builtin_amdgcn_s_setprio(3);
@@ -631,9 +678,8 @@ __device__ __forceinline__ void chain_master(const ChainFactor& F, int T, d4 acc
       if (k + 1 < T) (*f)(k);
     }
   };
-  // L^{-1}_kp is stored right after its factorisation, but its flag is raised inside the next
-  // hop (after the first product, when the stores have drained): the chain does not stall on
-  // the write-back of every pivot (the last one is signalled at once)
+  // L^{-1}_kp is stored right after its factorisation, as self-validating words: no drain, no
+  // flag -- the chain does not stall on the write-back of any pivot
   auto factor = [&](int kp) {
     if (trm && kp > 0 && kp < 17) TR_HI(SLOT_SWEEP + kp - 1);  // (inputs in: the hop ends)
     store_quad(sP, SP, wr, wc, lane, acc);
@@ -650,38 +696,32 @@ __device__ __forceinline__ void chain_master(const ChainFactor& F, int T, d4 acc
       ls = pivot_chol_inv_1w<double*, PivotPrefetch>(sP, sM, pv, t, F.status, &s_pflag, hook);
     else
       ls = pivot_chol_inv_block<4, double*, PivotPrefetch>(sP, sM, pv, t, F.status, hook);
-    // lw (chain_multi): L^{-1}_kp as self-validating words in this launch's slots, no flag
-    double* ldst = (lw ? lw : F.piv) + (size_t)kp * 1024;
+    // L^{-1}_kp as self-validating words in this launch's slots (lw), no flag
+    double* ldst = lw + (size_t)kp * 1024;
     for (int e = t; e < 1024; e += 256) st_sc1(ldst + e, sM[(e >> 5) * SP + (e & 31)]);
     if (t == 0) F.ldet[kp] = ls;
-    if (kp + 1 == T && !lw) signal_flag(piv_rdy + kp);
     if (trm && kp > 0 && kp < 17) TR_HI(SLOT_SWEEP_PIVOT + kp - 1);
     if (trm && kp == 0) TR_HI(SLOT_PIVOT0);
   };
   // refinement gate: K_00 = max diag K (stationary kernel + jitter), and max diag K^{-1}
-  // zeroed here -- before piv_rdy[0] is raised (the vmcnt(0) ahead of that flag drains these
-  // stores), so it precedes every diagonal tile's atomicMax, which waits on all piv_rdy[k]
+  // zeroed here
   if (t == 0) {
     st_sc1(F.pst, acc[0]);
     __hip_atomic_store(reinterpret_cast<unsigned long long*>(F.pst + 1), 0ull, __ATOMIC_RELAXED,
                        __HIP_MEMORY_SCOPE_AGENT);
   }
   if (t == 0) s_pflag = 0;  // (the barrier inside factor(0) orders it before the pivot)
-  // lw: no pivot flags -- the zeroing above completes before any L^{-1} word is stored (every
-  // diagonal tile's atomicMax comes after it has read L^{-1}_0's words)
-  if (lw) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  // the zeroing above completes before any L^{-1} word is stored (every diagonal tile's atomicMax
+  // comes after it has read L^{-1}_0's words)
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   // ONE call site of factor() (one inlined copy of the factorisation, as in chain_master_la):
   // pivot 0 factors acc = tile (0, 0) of K, gathered above; pivot kp > 0 follows hop kp - 1
   for (int kp = 0; kp < T; ++kp) {
     if (kp > 0) {
       const int k = kp - 1;
-      // L_k's flag: raised inside the hop (below); with early_flag (chain_multi, whose inputs are
-      // usually late) at once -- its stores drain while the inputs are awaited, and the tile
-      // workgroups' sweep k (which produces pivot k+2's inputs) does not wait for this hop
-      if (early_flag) {
-        if (lw) __syncthreads();
-        else signal_flag(piv_rdy + k);
-      }
+      // (early_flag, chain_multi: the barrier of the pivot-ready flag this hop once raised; L_k^{-1}
+      // travels as self-validating words now, the barrier keeps the hop's schedule)
+      if (early_flag) __syncthreads();
       bool ok = true;
 #pragma unroll
       for (int r = 0; r < 4; ++r) ok = ok && gran_ok(gx[r]) && gran_ok(gd[r]);
@@ -711,7 +751,6 @@ __device__ __forceinline__ void chain_master(const ChainFactor& F, int T, d4 acc
       vj = mma_t(sM, SP, 1, sXJ, SB, 1, wr, wc, lane, vj);  // V = L_k^{-1} X_{k,k+1}
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // L^{-1}_k's stores (long drained)
       __syncthreads();
-      if (t == 0 && !early_flag && !lw) __hip_atomic_store(piv_rdy + k, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       store_quad(sXJ, SB, wr, wc, lane, vj);
       __syncthreads();
       d4 prod = {0.0, 0.0, 0.0, 0.0};
@@ -745,8 +784,6 @@ __global__ __launch_bounds__(256, 2) void chain_kernel(ChainBatch b) {
   const int wr = wv >> 1, wc = wv & 1;
   const int tx = t & 31, ty = t >> 5;
   unsigned int* panel_rdy = F.flags;
-  unsigned int* piv_rdy = F.flags + T * TC;
-  unsigned int* done = F.flags + T * TC + 2 * T;
   // panel tile (row k) of column J: K part in PB, augmented part in PBa
   auto panel_ptr = [&](int k, int row, int col) -> double* {
     return J < T ? F.PB + (size_t)(k * 32 + row) * p + J * 32 + col
@@ -756,13 +793,14 @@ __global__ __launch_bounds__(256, 2) void chain_kernel(ChainBatch b) {
   __shared__ double sXI[32 * SB], sXJ[32 * SB];
   __shared__ double sP[32 * SP], sM[32 * SP], pv[32];
   __shared__ double sD[32 * SP];  // the pivot chain's look-ahead: its next diagonal tile
-  __shared__ unsigned int s_last;
   // L_k^{-1} as self-validating words (chain_multi_kernel's form) in this launch's half of the
   // L^{-1} slots (PB2, launch parity; the other half is reset by the tile workgroups): the tile
-  // workgroups see L_k^{-1} as soon as its stores land instead of after the pivot chain's flag,
-  // which it raises only inside the next hop
-  const unsigned ep = F.PB2 ? __hip_atomic_load(F.epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0u;
-  double* PLc = F.PB2 ? F.PB2 + (size_t)(ep & 1u) * chain_half(p, false) : nullptr;
+  // workgroups see L_k^{-1} as soon as its stores land, with no flag of the pivot chain's.
+  // The epoch: read here by every thread and never again (chain_arrive); its parity selects the
+  // half, epoch + 1 tags this launch's panel flags.
+  const unsigned ep = __hip_atomic_load(F.epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  const unsigned tag = chain_tag(ep);
+  double* PLc = F.PB2 + (size_t)(ep & 1u) * chain_half(p, false);
 
   // own tile, this wave's quadrant
   d4 acc;
@@ -783,7 +821,7 @@ __global__ __launch_bounds__(256, 2) void chain_kernel(ChainBatch b) {
   auto publish_tile = [&](void) {  // panel tile (I, J) <- acc, then its flag
 #pragma unroll
     for (int r = 0; r < 4; ++r) st_sc1(panel_ptr(I, q_row(wr, lane, r), q_col(wc, lane)), acc[r]);
-    signal_flag(panel_rdy + I * TC + J);
+    signal_flag(panel_rdy + I * TC + J, tag);
   };
   // the pivot chain's inputs of hop kk (after sweep kk-1): panel tile (kk, kk+1) and diagonal
   // tile (kk+1, kk+1) as granules (chain_master), before any other store of the tile
@@ -810,19 +848,22 @@ __global__ __launch_bounds__(256, 2) void chain_kernel(ChainBatch b) {
     // (a tile workgroup's sL and sXI are free here: the second L^{-1} and panel buffers)
     const ChainWindow win{sXI, sL, sD, t == 64 && m == 0};
     chain_master<true, true>(F, T, acc, sXJ, sP, sM, pv, trm, false, PLc, win, k_at);
-  } else {
-    if (trm && tile == 0) TR_LO(SLOT_GATHER);
-    chain_inputs(0);                       // tiles (0, 1) and (1, 1) as they are before sweep 0
-    if (I == 0 && J != 0) publish_tile();  // row 0 is the panel of sweep 0
-    if (PLc) {  // this tile's share of the other half's L^{-1} slots (last launch's) -> sentinel
-      double* PLo = F.PB2 + (size_t)((ep & 1u) ^ 1u) * chain_half(p, false);
-      const int share = (T * 1024 + T * TC - 1) / (T * TC);
-      const int e1 = min(T * 1024, (tile + 1) * share);
-      for (int e = tile * share + t; e < e1; e += 256) PLo[e] = __longlong_as_double((long long)CHAIN_SENTINEL);
-    }
+    if (t == 0 && m == 1) TR_HI(SLOT_CHAIN_M1);
+    if (t == 0 && m == 1) TR_LO(SLOT_CHAIN_M1);
+    chain_advance(F, ep, (unsigned)(T * TC + 1), trm);  // T*TC tiles + this workgroup
+    return;
+  }
+  if (trm && tile == 0) TR_LO(SLOT_GATHER);
+  chain_inputs(0);                       // tiles (0, 1) and (1, 1) as they are before sweep 0
+  if (I == 0 && J != 0) publish_tile();  // row 0 is the panel of sweep 0
+  {  // this tile's share of the other half's L^{-1} slots (last launch's) -> sentinel
+    double* PLo = F.PB2 + (size_t)((ep & 1u) ^ 1u) * chain_half(p, false);
+    const int share = (T * 1024 + T * TC - 1) / (T * TC);
+    const int e1 = min(T * 1024, (tile + 1) * share);
+    for (int e = tile * share + t; e < e1; e += 256) PLo[e] = __longlong_as_double((long long)CHAIN_SENTINEL);
   }
 
-  for (int k = 0; k < T && !master; ++k) {
+  for (int k = 0; k < T; ++k) {
     const bool needI = I != k, needJ = J != k && J != I;
     // issue priority over the CU's other workgroup when this tile feeds sweep k+1's panel or
     // the pivot chain
@@ -831,8 +872,8 @@ __global__ __launch_bounds__(256, 2) void chain_kernel(ChainBatch b) {
     // the panel tiles are usually published long before the pivot: fetch them first, then
     // wait for L^{-1}_k
     if (t == 0) {
-      if (needI) wait_flag(panel_rdy + k * TC + I, F.status);
-      if (needJ) wait_flag(panel_rdy + k * TC + J, F.status);
+      if (needI) wait_flag(panel_rdy + k * TC + I, tag, F.status);
+      if (needJ) wait_flag(panel_rdy + k * TC + J, tag, F.status);
     }
     __syncthreads();
     double xi[4], xj[4];
@@ -844,7 +885,7 @@ __global__ __launch_bounds__(256, 2) void chain_kernel(ChainBatch b) {
     }
     const bool trl = t == 0 && m == 0 && k == T - 1 && I == T - 1 && J == T - 1;
     double lv[4];
-    if (PLc) {
+    {
       // one thread polls one word of L_k^{-1} (the polling traffic of a flag), then every thread
       // loads its words and re-loads those still holding the sentinel (bounded)
       const double* Lw = PLc + (size_t)k * 1024;
@@ -869,13 +910,6 @@ __global__ __launch_bounds__(256, 2) void chain_kernel(ChainBatch b) {
         for (int r = 0; r < 4; ++r)
           if (!gran_ok(lv[r])) lv[r] = ld_sc1(Lw + (ty + 8 * r) * 32 + tx);
       }
-    } else {
-      if (t == 0) wait_flag(piv_rdy + k, F.status);
-      __syncthreads();
-      if (trl) TR_HI(SLOT_LAST_FLAG);
-      const double* Li = F.piv + (size_t)k * 1024;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) lv[r] = ld_sc1(Li + (ty + 8 * r) * 32 + tx);
     }
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
@@ -885,6 +919,9 @@ __global__ __launch_bounds__(256, 2) void chain_kernel(ChainBatch b) {
       if (needJ) sXJ[row * SB + tx] = xj[r];
     }
     __syncthreads();
+    // (every thread's L_0^{-1} words came through its own copy of the epoch and are in LDS:
+    // chain_arrive's condition holds from here on)
+    if (k == 0 && t == 0) chain_arrive(F);
     if (trl) TR_HI(SLOT_LAST_LDS);
     const double* sVJ = (J == I) ? sXI : sXJ;
     d4 vi = {0.0, 0.0, 0.0, 0.0}, vj = {0.0, 0.0, 0.0, 0.0};
@@ -902,7 +939,7 @@ __global__ __launch_bounds__(256, 2) void chain_kernel(ChainBatch b) {
     if (trl) TR_HI(SLOT_LAST_MMA);
     __syncthreads();  // LDS is refilled next sweep
   }
-  if (aug && !master) {  // upper-right block: +K^{-1} B (B_u part possibly stored transposed)
+  if (aug) {  // upper-right block: +K^{-1} B (B_u part possibly stored transposed)
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       // (q_row / q_col written out: called here they cost chain_kernel 4 VGPRs, 250 -> 254, which
@@ -918,33 +955,35 @@ __global__ __launch_bounds__(256, 2) void chain_kernel(ChainBatch b) {
   }
   // K^{-1} = -X after the last sweep
 #pragma unroll
-  for (int r = 0; r < 4 && !aug && !master; ++r) {
+  for (int r = 0; r < 4 && !aug; ++r) {
     const int row = q_row(wr, lane, r), col = q_col(wc, lane);
     const double y = -acc[r];
     F.X[(size_t)(I * 32 + row) * p + J * 32 + col] = y;
     if (I == J && row == col) pv[row] = (I * 32 + row < F.n) ? y : 0.0;
   }
   __syncthreads();
-  if (I == J && t == 0 && !master) {  // refinement gate: max_i (K^{-1})_ii of this block
+  if (I == J && t == 0) {  // refinement gate: max_i (K^{-1})_ii of this block
     double mx = 0.0;
     for (int j = 0; j < 32; ++j) mx = fmax(mx, pv[j]);
     atomicMax(reinterpret_cast<unsigned long long*>(F.pst + 1), (unsigned long long)__double_as_longlong(mx));
   }
   if (trm && tile == 0) TR_HI(SLOT_GATHER);
-  // the last workgroup of this factor re-arms the flags for the next launch
-  if (t == 0 && master && m == 1) TR_HI(SLOT_CHAIN_M1);
-  if (t == 0 && master && m == 1) TR_LO(SLOT_CHAIN_M1);
-  if (t == 0) s_last = atomicAdd(done, 1u) == (unsigned)(T * TC);  // T*TC tiles + the chain
-  __syncthreads();
-  if (t == 0 && m == 0 && I == T - 1 && J == T - 1 && !master) TR_HI(SLOT_LAST_OUT);
-  if (t == 0 && m == 0 && I == T - 1 && J == TC - 1 && !master) TR_HI(SLOT_LAST_AUG);
-  if (s_last && t == 0) TR_HI(SLOT_CHAIN_END);
-  if (s_last) {
-    for (int e = t; e < T * TC + 2 * T; e += 256)
-      __hip_atomic_store(F.flags + e, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (t == 0) __hip_atomic_store(done, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (PLc && t == 0) __hip_atomic_store(F.epoch, ep + 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
+  // A tile workgroup ends here: nothing is counted at the exit and no flag is cleared (the flags
+  // are tagged, the epoch is advanced by the pivot chain's workgroup: chain_advance).
+#ifdef GPK_TRACE
+  // probes: thread 0's stores drained (wave 0's share of the outputs; its atomicMax returned) in
+  // tile (T-1, T-1) and the last augmented tile of factor 0, and -- SLOT_CHAIN_END, an estimate of
+  // the launch's last exit from a sample -- in up to four tiles per factor of row max(T-2, 0),
+  // which are among the heaviest of the last sweep (two panel products and the update; their
+  // augmented outputs possibly stored transposed)
+  const bool tr_out = t == 0 && m == 0 && I == T - 1 && J == T - 1;
+  const bool tr_aug = t == 0 && m == 0 && I == T - 1 && J == TC - 1;
+  const bool tr_end = t == 0 && I == (T > 1 ? T - 2 : 0) && J >= TC - 4;
+  if (tr_out || tr_aug || tr_end) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  if (tr_out) TR_HI(SLOT_LAST_OUT);
+  if (tr_aug) TR_HI(SLOT_LAST_AUG);
+  if (tr_end) TR_HI(SLOT_CHAIN_END);
+#endif
 }
 
 // ---- multi-tile chain: large factors (1D, p up to 2048) -------------------------------------
@@ -1027,12 +1066,12 @@ __global__ __launch_bounds__(256, 2) void chain_multi_kernel(ChainBatch b) {
   const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
   const int wr = wv >> 1, wc = wv & 1;
   const int tx = t & 31, ty = t >> 5;
-  unsigned int* done = F.flags + T * T + 2 * T;
   // panel hand-off: self-validating words (chain_master's inputs, above) in the PB2 half of this
   // launch's parity; the other half (last launch's) is reset to the sentinel meanwhile, a chunk
   // per tile workgroup and sweep, off the critical path.  No flags, no drains.
   // L_k^{-1} travels the same way (PLc, after the panel slots in each half; no pivot flags): it
   // is normally written before the panel row it goes with, so it arrives with the panel's loads
+  unsigned int* done = F.flags + T * T + 2 * T;
   const unsigned ep = __hip_atomic_load(F.epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   const size_t hs = multi_half(p);
   double* PBc = F.PB2 + (size_t)(ep & 1u) * hs;
@@ -1391,15 +1430,16 @@ __global__ __launch_bounds__(256, 2) void chain_multi_kernel(ChainBatch b) {
     if (lane == 0 && mx > 0.0)
       atomicMax(reinterpret_cast<unsigned long long*>(F.pst + 1), (unsigned long long)__double_as_longlong(mx));
   }
-  // the last workgroup of this factor re-arms the flags for the next launch
+  // The last workgroup of this factor advances the epoch.  This kernel keeps the arrival count at
+  // its exit: it raises no flags (nothing to tag or re-arm), the count is ~1 % of its launch, and
+  // with chain_kernel's start-side arrival (chain_arrive / chain_advance) the 1D step measured
+  // 0.9 % slower.  The count is the word behind chain_kernel's flag layout.
   __syncthreads();
   if (t == 0) s_last = atomicAdd(done, 1u) == (unsigned)(nwg - 1);
   __syncthreads();
-  if (s_last) {
-    for (int e = t; e < T * T + 2 * T; e += 256)
-      __hip_atomic_store(F.flags + e, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (t == 0) __hip_atomic_store(done, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (t == 0) __hip_atomic_store(F.epoch, ep + 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  if (s_last && t == 0) {
+    __hip_atomic_store(done, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_store(F.epoch, ep + 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
 }
 
@@ -1459,7 +1499,7 @@ static bool chain_batch(ChainBatch& b, const ChainArgs* a, int nmat, const PrepA
     f.Ou = a[m].Ou; f.ldou = a[m].ldou; f.ou_t = a[m].ou_t; f.Od = a[m].Od; f.ldod = a[m].ldod;
     f.PBa = a[m].PBa; f.ldpba = a[m].ldpba;
     f.gran = a[m].gran; f.la = a[m].lookahead;
-    f.PB2 = a[m].PB2; f.epoch = a[m].epoch;  // (both null: L^{-1} hand-off by flag + load)
+    f.PB2 = a[m].PB2; f.epoch = a[m].epoch;  // (both required by both launchers)
     f.piv_off = f.T * (f.T + f.tu + f.td);
     if ((f.cid != nullptr) != (a[0].cid != nullptr) || !f.gran) return false;
   }
@@ -1479,7 +1519,7 @@ hipError_t launch_spd_chain(const ChainArgs* a, int nmat, int deriv, hipStream_t
   int Tmax = 0;
   for (int m = 0; m < nmat; ++m) {
     const ChainFactor& f = b.f[m];
-    if (!f.PB2 != !f.epoch) return hipErrorInvalidValue;
+    if (!f.PB2 || !f.epoch) return hipErrorInvalidValue;  // (the tag, the parity, the L^{-1} slots)
     Tmax = std::max(Tmax, f.piv_off + 1);  // + the pivot chain's workgroup
   }
   return chain_launch(false, b, Tmax, deriv, prep != nullptr, s);
