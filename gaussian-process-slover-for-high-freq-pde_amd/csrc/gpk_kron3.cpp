@@ -11,6 +11,14 @@
 //     S = K^{-1} U,  R = sum_k D_k x_k A_k - F,  dL/dU = S + v sum_k X_k  (+ AC, boundary)
 //     G_Kk = c/2 (N / N_k) K_k^{-1} - (S/2 + v X_k)_(k) A_k,(k)^T,   G_Dk = v R_(k) A_k,(k)^T
 // (the 2-axis adjoints of SURVEY.md Appendix A, one per axis).
+// Operator handles (gpk_create3_op): D_k is the order-o_k derivative block (o_k = 1 or 2, the
+// assembly's and the contraction's `deriv`, one order per launch, so axes 1-2 share a launch only
+// at equal orders) and its weight c_k is the alpha of every product with D_k -- D_k x_k A_k,
+// D_k^T x_k R and G_Dk -- so that X_k, Y_k, G_Kk and dL/dU carry it with no further change:
+//     R = sum_k c_k D_k x_k A_k - F + r1 U + r2 U^2 + r3 U^3,
+//     dL/dU = S + v sum_k c_k X_k + v (r1 + 2 r2 U + 3 r3 U^2) R + w tau scatter over the active faces.
+// gpk_create3 fills in the legacy equivalent (orders 2, weights 1.0, six faces), which multiplies
+// by alpha = 1.0 exactly and runs the launches it always ran.
 // GPK_FLAG3_REFINE: every one of the eight solves (A1, A2, A3, T, S, X1, X2, X3) is followed by
 // one refinement step X += K_k^{-1} (B - K_k X) gated on the axis's pst: one fused panel launch
 // (refine_panel.hip), or two GEMMs where its panels do not fit LDS (build_refine).
@@ -31,6 +39,10 @@ constexpr int K3_LOSS_CAP = 4096;
 
 struct gpk_handle3 {
   gpk_problem3 prob{};
+  // what the handle solves: gpk_create3_op's operator, or the legacy equation's equivalent
+  // (orders 2, weights 1, six faces; legacy_ac keeps Allen-Cahn in its own expression u(u^2 - 1))
+  gpk_operator3 op{};
+  int legacy_ac = 0;
   K3Geom g{};
   int q = 0;
   long nu = 0, nparams = 0;
@@ -77,6 +89,8 @@ void build_stages(gpk_handle3* h) {
   const double n1 = h->g.n[0], n2 = h->g.n[1], n3 = h->g.n[2], c = h->prob.logdet;
   double* const* Ki = h->Kinv;
   double* const* D = h->D;
+  const double* w = h->op.coef;  // c_k rides on every product with D_k (exact at 1.0)
+  auto scaled = [](GemmDesc d, double alpha) { d.alpha = alpha; return d; };
   auto& st = h->stages;
   st.clear();
   // forward: A1 = K1^{-1} x1 U, A3 = K3^{-1} x3 U
@@ -87,20 +101,20 @@ void build_stages(gpk_handle3* h) {
                 gemm_desc(h->A1, P3, 0, Ki[2], P3, 0, h->Tm, P3, M3, P3, P3)});
   // (T permuted) S = K2^{-1} x2 T;  U_xx = D1 x1 A1, U_yy = D2 x2 A2, U_zz = D3 x3 A3
   st.push_back({gemm_desc(Ki[1], P2, 0, h->Tp, M2, 0, h->Sp, M2, P2, M2, P2),
-                gemm_desc(D[0], P1, 0, h->A1, M1, 0, h->Rx, M1, P1, M1, P1),
-                gemm_desc(D[1], P2, 0, h->A2p, M2, 0, h->Ryp, M2, P2, M2, P2),
-                gemm_desc(h->A3, P3, 0, D[2], P3, 1, h->Rz, P3, M3, P3, P3)});
-  // (R, S combined) reverse: D_k^T x_k R;  G_D1 = v R_(1) A1_(1)^T
+                scaled(gemm_desc(D[0], P1, 0, h->A1, M1, 0, h->Rx, M1, P1, M1, P1), w[0]),
+                scaled(gemm_desc(D[1], P2, 0, h->A2p, M2, 0, h->Ryp, M2, P2, M2, P2), w[1]),
+                scaled(gemm_desc(h->A3, P3, 0, D[2], P3, 1, h->Rz, P3, M3, P3, P3), w[2])});
+  // (R, S combined) reverse: c_k D_k^T x_k R;  G_D1 = v c_1 R_(1) A1_(1)^T
   {
-    GemmDesc gd = gemm_desc(h->R, M1, 0, h->A1, M1, 1, h->GD[0], P1, P1, P1, M1);
+    GemmDesc gd = scaled(gemm_desc(h->R, M1, 0, h->A1, M1, 1, h->GD[0], P1, P1, P1, M1), w[0]);
     gd.vscale = 1;
-    st.push_back({gemm_desc(D[0], P1, 1, h->R, M1, 0, h->T1, M1, P1, M1, P1),
-                  gemm_desc(D[1], P2, 1, h->Rp, M2, 0, h->T2p, M2, P2, M2, P2),
-                  gemm_desc(h->R, P3, 0, D[2], P3, 0, h->T3, P3, M3, P3, P3), gd});
+    st.push_back({scaled(gemm_desc(D[0], P1, 1, h->R, M1, 0, h->T1, M1, P1, M1, P1), w[0]),
+                  scaled(gemm_desc(D[1], P2, 1, h->Rp, M2, 0, h->T2p, M2, P2, M2, P2), w[1]),
+                  scaled(gemm_desc(h->R, P3, 0, D[2], P3, 0, h->T3, P3, M3, P3, P3), w[2]), gd});
   }
-  // X_k = K_k^{-1} x_k (D_k^T x_k R) with the side outputs Y_k = S/2 + v X_k;  G_D2
+  // X_k = K_k^{-1} x_k (c_k D_k^T x_k R) with the side outputs Y_k = S/2 + v X_k;  G_D2
   {
-    GemmDesc gd = gemm_desc(h->Rp, M2, 0, h->A2p, M2, 1, h->GD[1], P2, P2, P2, M2);
+    GemmDesc gd = scaled(gemm_desc(h->Rp, M2, 0, h->A2p, M2, 1, h->GD[1], P2, P2, P2, M2), w[1]);
     gd.vscale = 1;
     st.push_back({with_side(gemm_desc(Ki[0], P1, 0, h->T1, M1, 0, h->X1, M1, P1, M1, P1), h->Y1, h->S, M1),
                   with_side(gemm_desc(Ki[1], P2, 0, h->T2p, M2, 0, h->X2p, M2, P2, M2, P2), h->Y2p, h->Sp, M2),
@@ -114,7 +128,7 @@ void build_stages(gpk_handle3* h) {
     g2.alpha = -1.0; g2.beta = 0.5 * c * n1 * n3; g2.C0 = Ki[1]; g2.ldc0 = P2;
     GemmDesc g3 = gemm_desc(h->Y3, P3, 1, h->A3, P3, 0, h->GK[2], P3, P3, P3, M3);
     g3.alpha = -1.0; g3.beta = 0.5 * c * n1 * n2; g3.C0 = Ki[2]; g3.ldc0 = P3;
-    GemmDesc gd = gemm_desc(h->R, P3, 1, h->A3, P3, 0, h->GD[2], P3, P3, P3, M3);
+    GemmDesc gd = scaled(gemm_desc(h->R, P3, 1, h->A3, P3, 0, h->GD[2], P3, P3, P3, M3), w[2]);
     gd.vscale = 1;
     st.push_back({g1, g2, g3, gd});
   }
@@ -191,6 +205,16 @@ int launch_stage(gpk_handle3* h, int k) {
   return GPK_OK;
 }
 
+K3Eq eq_layer(const gpk_handle3* h) {
+  const double* r = h->op.react;
+  K3Eq e{};
+  e.ac = h->legacy_ac;
+  e.on = !e.ac && (r[0] != 0.0 || r[1] != 0.0 || r[2] != 0.0);
+  e.faces = h->op.faces;
+  e.r1 = r[0]; e.r2 = r[1]; e.r3 = r[2];
+  return e;
+}
+
 // Step constants, K_k and D_k, then K_k^{-1} and log det K_k at the current params: the front of
 // the step, and all gpk_predict3 needs of it (apply = 0 leaves the Adam count alone).
 int enqueue_inverse3(gpk_handle3* h, int apply) {
@@ -203,13 +227,14 @@ int enqueue_inverse3(gpk_handle3* h, int apply) {
   P.kc = h->kc; P.sc = h->sc; P.count = h->count; P.apply = apply;
   P.b1 = h->prob.b1; P.b2 = h->prob.b2;
   P.Up = h->Up; P.bvals = h->bvals; P.nb = (int)(2 * ((long)g.n[1] * g.n[2] + (long)g.n[0] * g.n[2] + (long)g.n[0] * g.n[1]));
-  P.bgap = h->bgap;
+  P.faces = h->op.faces; P.bgap = h->bgap;
   TRY(check_launch(k3_launch_prep(P, h->s), "k3_prep"));
   // K_k, D_k: the 2-axis assembly kernel (per-pair path), its axis constants from the params
   AssembleArgs aa[3] = {};
   for (int a = 0; a < 3; ++a) {
     aa[a].x = h->x[a]; aa[a].n = g.n[a]; aa[a].p = g.p[a]; aa[a].kc = h->kc + a;
-    aa[a].jitter = h->prob.jitter; aa[a].K = h->K[a]; aa[a].Kc = h->Kc[a]; aa[a].D = h->D[a]; aa[a].deriv = 2;
+    aa[a].jitter = h->prob.jitter; aa[a].K = h->K[a]; aa[a].Kc = h->Kc[a]; aa[a].D = h->D[a];
+    aa[a].deriv = h->op.order[a];
   }
   // (skip = 1: the constants are published by k3_prep; each workgroup derives its axis's own)
   PrepArgs p12{};
@@ -218,7 +243,16 @@ int enqueue_inverse3(gpk_handle3* h, int apply) {
   PrepArgs p3 = p12;
   p3.off_kp[0] = h->off_kp[2];
   p3.naxes = 1;
-  TRY(check_launch(launch_assemble(kind, q, aa, 2, p12, h->s), "assemble"));
+  // (one derivative order per launch: axes 1-2 share theirs only when their orders are equal)
+  if (h->op.order[0] == h->op.order[1]) {
+    TRY(check_launch(launch_assemble(kind, q, aa, 2, p12, h->s), "assemble"));
+  } else {
+    PrepArgs p1 = p12, p2 = p12;
+    p1.naxes = p2.naxes = 1;
+    p2.off_kp[0] = h->off_kp[1];
+    TRY(check_launch(launch_assemble(kind, q, aa, 1, p1, h->s), "assemble"));
+    TRY(check_launch(launch_assemble(kind, q, aa + 1, 1, p2, h->s), "assemble"));
+  }
   TRY(check_launch(launch_assemble(kind, q, aa + 2, 1, p3, h->s), "assemble"));
   // K_k^{-1} and log det K_k (per-sweep Cholesky-Gauss-Jordan inverse; the output buffer of
   // each factor is fixed by its sweep count)
@@ -246,7 +280,7 @@ int enqueue_step3(gpk_handle3* h, int apply) {
   TRY(launch_stage(h, 2));
   K3Combine C{};
   C.g = g; C.Rx = h->Rx; C.Rz = h->Rz; C.Ryp = h->Ryp; C.F = h->F; C.Up = h->Up; C.Sp = h->Sp;
-  C.ac = h->prob.eq == GPK_ALLENCAHN; C.R = h->R; C.Rp = h->Rp; C.S = h->S;
+  C.eq = eq_layer(h); C.R = h->R; C.Rp = h->Rp; C.S = h->S;
   C.red_egap = h->red_egap; C.red_quad = h->red_quad;
   TRY(check_launch(k3_launch_combine(C, h->s), "k3_combine"));
   // reverse products and G_K, G_D
@@ -255,17 +289,22 @@ int enqueue_step3(gpk_handle3* h, int apply) {
   PGradArgs pg[3] = {};
   for (int a = 0; a < 3; ++a) {
     pg[a].x = h->x[a]; pg[a].n = g.n[a]; pg[a].p = g.p[a]; pg[a].kc = h->kc + a;
-    pg[a].GK = h->GK[a]; pg[a].GD = h->GD[a]; pg[a].deriv = 2;
+    pg[a].GK = h->GK[a]; pg[a].GD = h->GD[a]; pg[a].deriv = h->op.order[a];
     pg[a].part = h->pgpart + (size_t)a * h->bpa * 3 * QMAX;
   }
-  TRY(check_launch(launch_pgrad(kind, q, 0, pg, 2, h->bpa, h->sc, h->s), "pgrad"));
+  if (h->op.order[0] == h->op.order[1]) {
+    TRY(check_launch(launch_pgrad(kind, q, 0, pg, 2, h->bpa, h->sc, h->s), "pgrad"));
+  } else {
+    TRY(check_launch(launch_pgrad(kind, q, 0, pg, 1, h->bpa, h->sc, h->s), "pgrad"));
+    TRY(check_launch(launch_pgrad(kind, q, 0, pg + 1, 1, h->bpa, h->sc, h->s), "pgrad"));
+  }
   TRY(check_launch(launch_pgrad(kind, q, 0, pg + 2, 1, h->bpa, h->sc, h->s), "pgrad"));
   TRY(check_launch(launch_reduce_parts(h->pgpart, h->bpa, 3, q, h->pg, h->s), "reduce_parts"));
   // loss + small-parameter Adam, then dL/dU + Adam on U (U is read by nothing after this)
   K3Final F{};
   F.g = g; F.hyper = AdamHyper{h->prob.lr, h->prob.b1, h->prob.b2, h->prob.eps};
   F.llk_weight = h->prob.llk_weight; F.logdet = h->prob.logdet; F.apply = apply;
-  F.has_cos = kind_cos(kind) ? 1 : 0; F.q = q;
+  F.has_cos = kind_cos(kind) ? 1 : 0; F.q = q; F.faces = h->op.faces;
   F.red_quad = h->red_quad; F.red_egap = h->red_egap; F.nred = h->nred;
   for (int a = 0; a < 3; ++a) { F.ldet[a] = h->ldet[a]; F.nldet[a] = g.p[a] / 32; F.off_kp[a] = h->off_kp[a]; }
   F.pg = h->pg; F.kc = h->kc; F.sc = h->sc; F.bgap = h->bgap;
@@ -274,7 +313,7 @@ int enqueue_step3(gpk_handle3* h, int apply) {
   F.losses = h->losses; F.loss_slot = h->loss_slot; F.diag = h->diag;
   TRY(check_launch(k3_launch_finalize(F, h->s), "k3_finalize"));
   K3AdamU A{};
-  A.g = g; A.hyper = F.hyper; A.llk_weight = h->prob.llk_weight; A.apply = apply; A.ac = C.ac;
+  A.g = g; A.hyper = F.hyper; A.llk_weight = h->prob.llk_weight; A.apply = apply; A.eq = C.eq;
   A.sc = h->sc; A.S = h->S; A.X1 = h->X1; A.X2p = h->X2p; A.X3 = h->X3; A.R = h->R; A.Up = h->Up;
   A.bvals = h->bvals; A.off_u = 0; A.params = h->params; A.grad = h->grad; A.m = h->m; A.v = h->v;
   TRY(check_launch(k3_launch_adam_u(A, h->s), "k3_adam_u"));
@@ -316,12 +355,13 @@ int gpk_destroy3(gpk_handle3* h) {
   return GPK_OK;
 }
 
-int gpk_create3(const gpk_problem3* p, double freq_scale, gpk_handle3** out) {
-  if (!p || !out) return fail(GPK_EINVAL, "NULL argument");
-  *out = nullptr;
+}  // extern "C"
+
+namespace {
+
+// gpk_create3 (op = nullptr: the legacy equation p->eq) and gpk_create3_op
+int create3(const gpk_problem3* p, const gpk_operator3* op, double freq_scale, gpk_handle3** out) {
   if (p->kind < 0 || p->kind > 3) return fail(GPK_EINVAL, "Invalid Kernel");
-  if (p->eq != GPK_POISSON && p->eq != GPK_ALLENCAHN)
-    return fail(GPK_EINVAL, "equation type not supported for the 3-axis solver");
   if (p->q <= 0 || p->q > QMAX) return fail(GPK_EINVAL, "Q must be in [1, 64]");
   const int ns[3] = {p->n1, p->n2, p->n3};
   for (int a = 0; a < 3; ++a)
@@ -332,6 +372,14 @@ int gpk_create3(const gpk_problem3* p, double freq_scale, gpk_handle3** out) {
   gpk_handle3* h = new gpk_handle3();
   h->prob = *p;
   h->prob.x1 = h->prob.x2 = h->prob.x3 = h->prob.src = h->prob.bvals = nullptr;
+  if (op) {
+    h->op = *op;
+  } else {
+    for (int a = 0; a < 3; ++a) { h->op.order[a] = 2; h->op.coef[a] = 1.0; h->op.react[a] = 0.0; }
+    h->op.faces = K3_ALL_FACES;
+    h->legacy_ac = p->eq == GPK_ALLENCAHN;
+    if (h->legacy_ac) { h->op.react[0] = -1.0; h->op.react[2] = 1.0; }  // what gpk_operator_info3 reports
+  }
   h->dev = p->device;
   h->q = p->q;
   for (int a = 0; a < 3; ++a) {
@@ -417,6 +465,40 @@ int gpk_create3(const gpk_problem3* p, double freq_scale, gpk_handle3** out) {
     if (h->route && refine_panel_prepare() != hipSuccess) return bail(fail(GPK_EHIP, "refine_panel_prepare failed"));
   }
   *out = h;
+  return GPK_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int gpk_create3(const gpk_problem3* p, double freq_scale, gpk_handle3** out) {
+  if (!p || !out) return fail(GPK_EINVAL, "NULL argument");
+  *out = nullptr;
+  if (p->eq != GPK_POISSON && p->eq != GPK_ALLENCAHN)
+    return fail(GPK_EINVAL, "equation type not supported for the 3-axis solver");
+  return create3(p, nullptr, freq_scale, out);
+}
+
+int gpk_create3_op(const gpk_problem3* p, const gpk_operator3* op, double freq_scale, gpk_handle3** out) {
+  if (!p || !op || !out) return fail(GPK_EINVAL, "NULL argument");
+  *out = nullptr;
+  if (p->eq != GPK_POISSON)
+    return fail(GPK_EINVAL, "gpk_create3_op: eq must be GPK_POISSON (the operator states the equation)");
+  for (int a = 0; a < 3; ++a) {
+    if (op->order[a] != 1 && op->order[a] != 2)
+      return fail(GPK_EINVAL, "gpk_create3_op: derivative order must be 1 or 2");
+    if (!std::isfinite(op->coef[a]) || !std::isfinite(op->react[a]))
+      return fail(GPK_EINVAL, "gpk_create3_op: coef and react must be finite");
+  }
+  if (op->faces < 1 || op->faces > K3_ALL_FACES)
+    return fail(GPK_EINVAL, "gpk_create3_op: faces must be in 1..63");
+  return create3(p, op, freq_scale, out);
+}
+
+int gpk_operator_info3(const gpk_handle3* h, gpk_operator3* out) {
+  if (!h || !out) return fail(GPK_EINVAL, "NULL argument");
+  *out = h->op;
   return GPK_OK;
 }
 
@@ -506,7 +588,10 @@ int gpk_criterion3(gpk_handle3* h, double* out) {
   double diag[8];
   TRY(read_diag3(h, diag));
   const double n1 = h->g.n[0], n2 = h->g.n[1], n3 = h->g.n[2];
-  const double Nb = 2.0 * (n2 * n3 + n1 * n3 + n1 * n2), Nc = n1 * n2 * n3;
+  const double fs[3] = {n2 * n3, n1 * n3, n1 * n2}, Nc = n1 * n2 * n3;
+  double Nb = 0.0;  // the active faces' entries
+  for (int f = 0; f < 6; ++f)
+    if ((h->op.faces >> f) & 1) Nb += fs[f / 2];
   *out = diag[6] / Nb + diag[5] / Nc;  // boundary_gap/Nb + eq_gap/Nc (K3Final::diag)
   return GPK_OK;
 }

@@ -19,6 +19,19 @@ struct K3Geom {
   __host__ __device__ long real() const { return (long)n[0] * n[1] * n[2]; }
 };
 
+// Boundary faces in gpk_problem3.bvals order (bit f of a face mask): 0: i1 = 0, 1: i1 = n1 - 1,
+// 2: i2 = 0, 3: i2 = n2 - 1, 4: i3 = 0, 5: i3 = n3 - 1.  K3_ALL_FACES is the legacy six-face set.
+constexpr int K3_ALL_FACES = 63;
+
+// The equation layer of an operator handle (gpk_operator3; the per-axis orders and weights live
+// in the assembly launches and the GEMM descriptors): the reaction polynomial r1 u + r2 u^2 +
+// r3 u^3 (on = 0 skips it) and the active faces.  ac = 1 is the legacy Allen-Cahn term u(u^2 - 1)
+// in its own expression (legacy handles stay bit-identical); it excludes on.
+struct K3Eq {
+  int ac, on, faces;
+  double r1, r2, r3;
+};
+
 struct K3Prep {
   K3Geom g;
   const double* params;
@@ -28,14 +41,15 @@ struct K3Prep {
   int* count;
   int apply;
   double b1, b2;
-  const double* Up; const double* bvals; int nb;
+  const double* Up; const double* bvals; int nb;  // nb: all six faces (the bvals layout)
+  int faces;            // entries of a face whose bit is clear are never read
   double* bgap;         // out [1]
 };
 
 struct K3Combine {
   K3Geom g;
   const double *Rx, *Rz, *Ryp, *F, *Up, *Sp;  // U_xx, U_zz (natural), U_yy, S (permuted)
-  int ac;
+  K3Eq eq;
   double *R, *Rp, *S;                         // out: R (natural and permuted), S (natural)
   double *red_egap, *red_quad;                // out: per-block partials
 };
@@ -45,6 +59,7 @@ struct K3Final {
   AdamHyper hyper;
   double llk_weight, logdet;
   int apply, has_cos, q;
+  int faces;                 // Nb = the entries of the active faces
   const double* red_quad; const double* red_egap; int nred;
   const double* ldet[3]; int nldet[3];
   const double* pg;          // [3][3*QMAX]
@@ -61,7 +76,8 @@ struct K3AdamU {
   K3Geom g;
   AdamHyper hyper;
   double llk_weight;
-  int apply, ac;
+  int apply;
+  K3Eq eq;
   const StepScalars* sc;
   const double *S, *X1, *X2p, *X3, *R;  // X2 in the permuted layout
   double* Up;

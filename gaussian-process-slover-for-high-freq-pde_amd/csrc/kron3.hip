@@ -12,6 +12,11 @@
 //                copy Rp of R, and per-block partials of ||R||^2 and <U, S>
 //   k3_finalize  loss, small-parameter gradients and Adam (one workgroup)
 //   k3_adam_u    dL/dU = S + v (X1 + X2 + X3) [+ v(3U^2-1)R] + w tau scatter(u_b - b), Adam on U
+// Operator handles (gpk_create3_op, K3Eq): the mode products arrive weighted (c_k folded into the
+// GEMM descriptors), so R is still Rx + Rz + Ryp - F; the reaction term is r1 U + r2 U^2 + r3 U^3
+// with the factor r1 + 2 r2 U + 3 r3 U^2 in dL/dU, and the boundary sums, the scatter and Nb run
+// over the faces whose mask bit is set.  Legacy handles (ac, six faces) keep their expressions on
+// uniform branches, bit for bit.
 // Grids are padded per axis to P_k (multiple of 32); pads of every tensor are zero.
 #include "gpk_internal.h"
 #include "gpk_kron3.h"
@@ -30,24 +35,27 @@ __device__ __forceinline__ double k3_block_sum(double v, double* sh) {
   return (sh[0] + sh[1]) + (sh[2] + sh[3]);
 }
 
-// the six faces' entry index of boundary value k (oracle boundary_3d order)
-__device__ __forceinline__ void k3_face(const K3Geom& g, int k, int& i1, int& i2, int& i3) {
+// the six faces' entry index of boundary value k (oracle boundary_3d order); returns its face
+__device__ __forceinline__ int k3_face(const K3Geom& g, int k, int& i1, int& i2, int& i3) {
   const int n1 = g.n[0], n2 = g.n[1], n3 = g.n[2];
   const int f0 = n2 * n3, f2 = n1 * n3, f4 = n1 * n2;
   if (k < 2 * f0) {
     i1 = k < f0 ? 0 : n1 - 1;
     const int r = k % f0;
     i2 = r / n3; i3 = r % n3;
+    return k < f0 ? 0 : 1;
   } else if (k < 2 * f0 + 2 * f2) {
     const int kk = k - 2 * f0;
     i2 = kk < f2 ? 0 : n2 - 1;
     const int r = kk % f2;
     i1 = r / n3; i3 = r % n3;
+    return kk < f2 ? 2 : 3;
   } else {
     const int kk = k - 2 * f0 - 2 * f2;
     i3 = kk < f4 ? 0 : n3 - 1;
     const int r = kk % f4;
     i1 = r / n2; i2 = r % n2;
+    return kk < f4 ? 4 : 5;
   }
 }
 
@@ -72,7 +80,8 @@ __global__ __launch_bounds__(256) void k3_prep_kernel(K3Prep P) {
   double acc = 0.0;
   for (int k = t; k < P.nb; k += 256) {
     int i1, i2, i3;
-    k3_face(P.g, k, i1, i2, i3);
+    const int f = k3_face(P.g, k, i1, i2, i3);
+    if (!((P.faces >> f) & 1)) continue;  // an open face: its bvals entries are never read
     const double d = P.Up[P.g.at(i1, i2, i3)] - P.bvals[k];
     acc += d * d;
   }
@@ -108,7 +117,8 @@ __global__ __launch_bounds__(256) void k3_combine_kernel(K3Combine C) {
     if (real) {
       R = C.Rx[e] + C.Rz[e] + C.Ryp[ep] - C.F[e];
       const double u = C.Up[e];
-      if (C.ac) R += u * (u * u - 1.0);
+      if (C.eq.ac) R += u * (u * u - 1.0);
+      else if (C.eq.on) R += u * (C.eq.r1 + u * (C.eq.r2 + u * C.eq.r3));
       S = C.Sp[ep];
       r2 = R * R;
       us = u * S;
@@ -148,7 +158,12 @@ __global__ __launch_bounds__(256) void k3_finalize_kernel(K3Final F) {
   const double wb = F.llk_weight, c = F.logdet;
   const double n1 = F.g.n[0], n2 = F.g.n[1], n3 = F.g.n[2];
   const double Nc = n1 * n2 * n3;
-  const double Nb = 2.0 * (n2 * n3 + n1 * n3 + n1 * n2);
+  double Nb = 2.0 * (n2 * n3 + n1 * n3 + n1 * n2);
+  if (F.faces != K3_ALL_FACES) {  // the active faces' entries
+    const int fm = F.faces;
+    Nb = ((fm & 1) + ((fm >> 1) & 1)) * (n2 * n3) + (((fm >> 2) & 1) + ((fm >> 3) & 1)) * (n1 * n3) +
+         (((fm >> 4) & 1) + ((fm >> 5) & 1)) * (n1 * n2);
+  }
   const double log_tau = F.params[F.off_tau], log_v = F.params[F.off_v];
   if (t == 0) {
     const double bgap = *F.bgap;
@@ -198,16 +213,27 @@ __global__ __launch_bounds__(256) void k3_adam_u_kernel(K3AdamU A) {
   const double tau = A.sc->tau, v = A.sc->v, wt = A.llk_weight * tau;
   const double u = A.Up[pi];
   double gr = A.S[pi] + v * (A.X1[pi] + A.X2p[pp] + A.X3[pi]);
-  if (A.ac) gr += v * (3.0 * u * u - 1.0) * A.R[pi];
+  if (A.eq.ac) gr += v * (3.0 * u * u - 1.0) * A.R[pi];
+  else if (A.eq.on) gr += v * (A.eq.r1 + u * (2.0 * A.eq.r2 + 3.0 * A.eq.r3 * u)) * A.R[pi];
   const int n1 = g.n[0], n2 = g.n[1], n3 = g.n[2];
   const int f0 = n2 * n3, f2 = n1 * n3, f4 = n1 * n2;
   const int b2 = 2 * f0, b4 = 2 * f0 + 2 * f2;
-  if (i1 == 0) gr += wt * (u - A.bvals[i2 * n3 + i3]);
-  if (i1 == n1 - 1) gr += wt * (u - A.bvals[f0 + i2 * n3 + i3]);
-  if (i2 == 0) gr += wt * (u - A.bvals[b2 + i1 * n3 + i3]);
-  if (i2 == n2 - 1) gr += wt * (u - A.bvals[b2 + f2 + i1 * n3 + i3]);
-  if (i3 == 0) gr += wt * (u - A.bvals[b4 + i1 * n2 + i2]);
-  if (i3 == n3 - 1) gr += wt * (u - A.bvals[b4 + f4 + i1 * n2 + i2]);
+  if (A.eq.faces == K3_ALL_FACES) {
+    if (i1 == 0) gr += wt * (u - A.bvals[i2 * n3 + i3]);
+    if (i1 == n1 - 1) gr += wt * (u - A.bvals[f0 + i2 * n3 + i3]);
+    if (i2 == 0) gr += wt * (u - A.bvals[b2 + i1 * n3 + i3]);
+    if (i2 == n2 - 1) gr += wt * (u - A.bvals[b2 + f2 + i1 * n3 + i3]);
+    if (i3 == 0) gr += wt * (u - A.bvals[b4 + i1 * n2 + i2]);
+    if (i3 == n3 - 1) gr += wt * (u - A.bvals[b4 + f4 + i1 * n2 + i2]);
+  } else {  // each face under its bit (an edge of two active faces counts twice, as above)
+    const int fm = A.eq.faces;
+    if ((fm & 1) && i1 == 0) gr += wt * (u - A.bvals[i2 * n3 + i3]);
+    if ((fm & 2) && i1 == n1 - 1) gr += wt * (u - A.bvals[f0 + i2 * n3 + i3]);
+    if ((fm & 4) && i2 == 0) gr += wt * (u - A.bvals[b2 + i1 * n3 + i3]);
+    if ((fm & 8) && i2 == n2 - 1) gr += wt * (u - A.bvals[b2 + f2 + i1 * n3 + i3]);
+    if ((fm & 16) && i3 == 0) gr += wt * (u - A.bvals[b4 + i1 * n2 + i2]);
+    if ((fm & 32) && i3 == n3 - 1) gr += wt * (u - A.bvals[b4 + f4 + i1 * n2 + i2]);
+  }
   const long idx = A.off_u + e;
   A.grad[idx] = gr;
   if (A.apply) {

@@ -86,6 +86,13 @@ class gpk_problem3(ctypes.Structure):
     ]
 
 
+class gpk_operator3(ctypes.Structure):
+    _fields_ = [
+        ("order", ctypes.c_int32 * 3), ("coef", ctypes.c_double * 3), ("react", ctypes.c_double * 3),
+        ("faces", ctypes.c_int32),
+    ]
+
+
 EXPORTS = {
     "gpk_abi_version": ([], ctypes.c_int),
     "gpk_last_error": ([], ctypes.c_char_p),
@@ -141,6 +148,9 @@ EXPORTS = {
     "gpk_class_pipe": ([ctypes.c_void_p, _ip], ctypes.c_int),
     "gpk_create3": ([ctypes.POINTER(gpk_problem3), ctypes.c_double,
                      ctypes.POINTER(ctypes.c_void_p)], ctypes.c_int),
+    "gpk_create3_op": ([ctypes.POINTER(gpk_problem3), ctypes.POINTER(gpk_operator3), ctypes.c_double,
+                        ctypes.POINTER(ctypes.c_void_p)], ctypes.c_int),
+    "gpk_operator_info3": ([ctypes.c_void_p, ctypes.POINTER(gpk_operator3)], ctypes.c_int),
     "gpk_destroy3": ([ctypes.c_void_p], ctypes.c_int),
     "gpk_num_params3": ([ctypes.c_void_p, ctypes.POINTER(ctypes.c_int64)], ctypes.c_int),
     "gpk_set_params3": ([ctypes.c_void_p, _dp, ctypes.c_int64], ctypes.c_int),

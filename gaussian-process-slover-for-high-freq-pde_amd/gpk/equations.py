@@ -95,6 +95,83 @@ def solution_3d(equation):
     raise KeyError(equation)
 
 
+class Operator3:
+    """What an operator handle solves on a 3-axis grid (include/gpk.h gpk_operator3):
+    sum_k coef[k] d^order[k] u / dx_k^order[k] + react[0] u + react[1] u^2 + react[2] u^3 = f, with
+    boundary data on the faces whose bit is set in `faces` (bit order of boundary_3d: i1 = 0,
+    i1 = n1 - 1, i2 = 0, i2 = n2 - 1, i3 = 0, i3 = n3 - 1)."""
+
+    __slots__ = ("order", "coef", "react", "faces")
+
+    def __init__(self, order, coef, react=(0.0, 0.0, 0.0), faces=63):
+        self.order = tuple(int(o) for o in order)
+        self.coef = tuple(float(c) for c in coef)
+        self.react = tuple(float(r) for r in react)
+        self.faces = int(faces)
+        if len(self.order) != 3 or len(self.coef) != 3 or len(self.react) != 3:
+            raise ValueError("order, coef and react have three entries each")
+
+    @classmethod
+    def of(cls, value):
+        """An Operator3 from an Operator3 or a dict of its fields."""
+        if isinstance(value, cls):
+            return value
+        return cls(value["order"], value["coef"], value.get("react", (0.0, 0.0, 0.0)), value.get("faces", 63))
+
+    def as_dict(self):
+        return {"order": self.order, "coef": self.coef, "react": self.react, "faces": self.faces}
+
+    def __eq__(self, other):
+        return isinstance(other, Operator3) and self.as_dict() == other.as_dict()
+
+    def __repr__(self):
+        return "Operator3(order=%r, coef=%r, react=%r, faces=%d)" % (self.order, self.coef, self.react, self.faces)
+
+
+ALL_FACES, NO_FINAL_FACE = 0b111111, 0b011111  # every face; the final-time face i3 = n3 - 1 open
+
+# The operator equations: third axis = time where one appears.  Each entry builds (u, src,
+# operator) from a manufactured solution with closed-form derivatives.
+_HEAT_NU, _ADV_BETA, _HELM_K, _ACT_EPS = 0.1, (1.0, 0.5), 4.0, 0.05
+
+
+def _heat_sin():
+    # u = e^{-t} sin(2x) sin(3y):  u_t - nu (u_xx + u_yy) = (13 nu - 1) u
+    u = lambda x, y, t: np.exp(-t) * s_(2 * x) * s_(3 * y)
+    return u, (lambda x, y, t: (13.0 * _HEAT_NU - 1.0) * u(x, y, t)), \
+        Operator3((2, 2, 1), (-_HEAT_NU, -_HEAT_NU, 1.0), faces=NO_FINAL_FACE)
+
+
+def _advection_sin():
+    b1, b2 = _ADV_BETA
+    return (lambda x, y, t: s_(x - b1 * t + y - b2 * t)), (lambda x, y, t: 0.0 * x * y * t), \
+        Operator3((1, 1, 1), (b1, b2, 1.0))
+
+
+def _helmholtz_sin():
+    # u = sin(2x) sin(3y) sin(z):  lap u + k^2 u = (k^2 - 14) u
+    u = lambda x, y, z: s_(2 * x) * s_(3 * y) * s_(z)
+    return u, (lambda x, y, z: (_HELM_K ** 2 - 14.0) * u(x, y, z)), \
+        Operator3((2, 2, 2), (1.0, 1.0, 1.0), react=(_HELM_K ** 2, 0.0, 0.0))
+
+
+def _allencahn_t_sin():
+    # u = e^{-t} sin(2x) sin(2y):  u_t - eps (u_xx + u_yy) + u^3 - u = (8 eps - 2) u + u^3
+    u = lambda x, y, t: np.exp(-t) * s_(2 * x) * s_(2 * y)
+    return u, (lambda x, y, t: (8.0 * _ACT_EPS - 2.0) * u(x, y, t) + u(x, y, t) ** 3), \
+        Operator3((2, 2, 1), (-_ACT_EPS, -_ACT_EPS, 1.0), react=(-1.0, 0.0, 1.0), faces=NO_FINAL_FACE)
+
+
+_OP3D = {"heat_3d-sin": _heat_sin, "advection_3d-sin": _advection_sin,
+         "helmholtz_3d-sin": _helmholtz_sin, "allencahn_t-sin": _allencahn_t_sin}
+EQUATIONS_3D_OP = list(_OP3D)
+
+
+def solution_3d_op(equation):
+    """(u, src, operator) of an EQUATIONS_3D_OP entry."""
+    return _OP3D[equation]()
+
+
 def boundary_2d(u_mesh):
     """get_boundary_vals: hstack(U[0,:], U[-1,:], U[:,0], U[:,-1]) (model_GP_solver_2d.py:377-379)."""
     return np.hstack((u_mesh[0, :], u_mesh[-1, :], u_mesh[:, 0], u_mesh[:, -1]))

@@ -12,6 +12,11 @@ compute_early_stopping), test() / evals() and the CLI
 (`python -m gpk.model_GP_solver_3d -equation=poisson_3d-mix_sin -kernel=Matern52_Cos_1d
 -nepoch=200`; `-refine=1` turns the gated refinement of every solve on), with its configs in
 gpk/config3d/.
+
+Operator equations (equations.EQUATIONS_3D_OP: heat, transport, Helmholtz, Allen-Cahn in time, the
+third axis as time where one appears) run through gpk_create3_op: DeviceSolver3(operator=...),
+GP_solver_3d_single with such an equation name, and the same CLI
+(`-equation=heat_3d-sin`), with their configs in gpk/config3d_op/.
 """
 import ctypes
 import os
@@ -25,7 +30,7 @@ from . import _lib, init_func, replicas, utils
 from ._lib import check, dptr, f64
 from .cli import parse_flags
 from .core import tree_flatten, tree_unflatten
-from .equations import EQUATIONS_3D, solution_3d
+from .equations import EQUATIONS_3D, EQUATIONS_3D_OP, Operator3, solution_3d, solution_3d_op
 from .infras.exp_config import ExpConfig
 from .kernel_matrix import kernel_class
 from .solver_common import SolverBase
@@ -37,20 +42,32 @@ def params_template_3d(n1, n2, n3, Q):
             "kernel_paras_3": kp(), "log_tau": 0.0, "log_v": 0.0}
 
 
-def boundary_3d(U):
-    """The six faces U[0], U[-1], U[:,0], U[:,-1], U[:,:,0], U[:,:,-1] (each row-major)."""
-    U = np.asarray(U)
-    return np.concatenate([U[0].ravel(), U[-1].ravel(), U[:, 0].ravel(), U[:, -1].ravel(),
-                           U[:, :, 0].ravel(), U[:, :, -1].ravel()])
+def boundary_3d(U, faces=63):
+    """The six faces U[0], U[-1], U[:,0], U[:,-1], U[:,:,0], U[:,:,-1] (each row-major).  The
+    layout and length do not depend on `faces`; the entries of a face whose bit is clear are NaN
+    (an operator handle never reads them)."""
+    U = np.asarray(U, np.float64)
+    fs = [U[0], U[-1], U[:, 0], U[:, -1], U[:, :, 0], U[:, :, -1]]
+    return np.concatenate([f.ravel() if (faces >> k) & 1 else np.full(f.size, np.nan)
+                           for k, f in enumerate(fs)])
+
+
+def boundary_count_3d(ns, faces=63):
+    """Nb: the entries of the active faces."""
+    n1, n2, n3 = ns
+    return sum(s for k, s in enumerate((n2 * n3, n2 * n3, n1 * n3, n1 * n3, n1 * n2, n1 * n2)) if (faces >> k) & 1)
 
 
 class DeviceSolver3:
     """One gpk_handle3: problem, params and Adam state resident on the device."""
 
     def __init__(self, eq, kind, xs, src, bvals, Q=30, jitter=1e-6, llk_weight=200.0, logdet=True,
-                 lr=0.01, freq_scale=20.0, device=0, b1=0.9, b2=0.999, eps=1e-8, refine=False):
+                 lr=0.01, freq_scale=20.0, device=0, b1=0.9, b2=0.999, eps=1e-8, refine=False,
+                 operator=None):
         """refine: one gated refinement step after every solve of the step (GPK_FLAG3_REFINE);
-        'gemm' also forces its two-GEMM route (GPK_FLAG3_REFINE_GEMM; tests, A/B)."""
+        'gemm' also forces its two-GEMM route (GPK_FLAG3_REFINE_GEMM; tests, A/B).
+        operator: an Operator3 (or a dict of its fields) -- the handle then solves that operator
+        (gpk_create3_op; eq must be 'poisson', the operator says everything else)."""
         lib = _lib.load()
         if len(xs) != 3:
             raise ValueError("three coordinate axes")
@@ -77,7 +94,13 @@ class DeviceSolver3:
         self.refine = bool(refine)
         self._prob = p
         h = ctypes.c_void_p()
-        check(lib.gpk_create3(ctypes.byref(p), float(freq_scale), ctypes.byref(h)))
+        if operator is None:
+            check(lib.gpk_create3(ctypes.byref(p), float(freq_scale), ctypes.byref(h)))
+        else:
+            op = Operator3.of(operator)
+            c = _lib.gpk_operator3()
+            c.order[:], c.coef[:], c.react[:], c.faces = op.order, op.coef, op.react, op.faces
+            check(lib.gpk_create3_op(ctypes.byref(p), ctypes.byref(c), float(freq_scale), ctypes.byref(h)))
         self._h = h
         n = ctypes.c_int64()
         check(lib.gpk_num_params3(h, ctypes.byref(n)))
@@ -200,6 +223,13 @@ class DeviceSolver3:
                                            ctypes.byref(route)))
         return {"bound": bound.tolist(), "open": [bool(g) for g in gates], "route": int(route.value)}
 
+    def operator_info(self):
+        """The Operator3 the handle runs (gpk_operator_info3); a handle created without
+        `operator` reports its equation's equivalent."""
+        c = _lib.gpk_operator3()
+        check(_lib.load().gpk_operator_info3(self._h, ctypes.byref(c)))
+        return Operator3(tuple(c.order), tuple(c.coef), tuple(c.react), c.faces)
+
     LOSS_TERMS = ("loss", "logdet_1", "logdet_2", "logdet_3", "quad", "egap", "bgap")
 
     def loss_terms(self):
@@ -215,25 +245,33 @@ class GP_solver_3d_single(SolverBase):
     compute_early_stopping.
 
     bvals: boundary_3d(U) of the solution; X_col = (x, y, z); src_vals: N1 x N2 x N3;
-    trick_paras: {'kernel': class, 'equation': 'poisson_3d-...' | 'allencahn_3d-...',
+    trick_paras: {'kernel': class, 'equation': 'poisson_3d-...' | 'allencahn_3d-...' or an
+    operator equation (equations.EQUATIONS_3D_OP: its Operator3 is looked up by name, or given as
+    trick_paras['operator']; bvals keeps the six-face layout, Nb counts the active faces),
     'llk_weight', 'logdet', 'lr', 'Q', 'freq_scale', 'refine'} (+ 'nepoch', 'tol' for train);
     'refine' (default False): DeviceSolver3's gated refinement of every solve;
     X_test = (x, y, z) test axes and u_test: M1 x M2 x M3, needed by train() and preds()."""
 
     dim = 3
     eq_types = ("poisson_3d", "allencahn_3d")
+    op_eq_types = tuple(sorted({e.split("-")[0] for e in EQUATIONS_3D_OP}))
     early_stop_enabled = True
 
     def __init__(self, bvals, X_col, src_vals, jitter, trick_paras, device=0, X_test=None, u_test=None):
         self.eq_type = trick_paras["equation"].split("-")[0]
-        assert self.eq_type in self.eq_types
+        assert self.eq_type in self.eq_types + self.op_eq_types
+        self.operator = None
+        if trick_paras.get("operator") is not None:
+            self.operator = Operator3.of(trick_paras["operator"])
+        elif self.eq_type in self.op_eq_types:
+            self.operator = solution_3d_op(trick_paras["equation"])[2]
         self.cov_func = trick_paras["kernel"]()
         self.trick_paras = trick_paras
         self.bvals = np.asarray(bvals, np.float64)
         self.X_col = X_col
         self.jitter = jitter
         self.N1, self.N2, self.N3 = (np.asarray(x).size for x in X_col)
-        self.Nb = self.bvals.size
+        self.Nb = boundary_count_3d((self.N1, self.N2, self.N3), self.operator.faces if self.operator else 63)
         self.Nc = self.N1 * self.N2 * self.N3
         self.src_vals = np.asarray(src_vals, np.float64)
         self.llk_weight = trick_paras["llk_weight"]
@@ -243,13 +281,32 @@ class GP_solver_3d_single(SolverBase):
 
     def _make_device(self, device=0):
         tp = self.trick_paras
-        eq = {"poisson_3d": "poisson", "allencahn_3d": "allencahn"}[self.eq_type]
+        eq = "poisson" if self.operator else {"poisson_3d": "poisson", "allencahn_3d": "allencahn"}[self.eq_type]
         self.dev = DeviceSolver3(eq, self.cov_func.KIND, self.X_col, self.src_vals, self.bvals,
                                  Q=tp.get("Q", 30), jitter=self.jitter, llk_weight=tp["llk_weight"],
                                  logdet=tp.get("logdet", True), lr=tp.get("lr", 0.01),
                                  freq_scale=tp.get("freq_scale", 20.0), device=int(tp.get("device", device)),
-                                 refine=bool(tp.get("refine", False)))
+                                 refine=bool(tp.get("refine", False)), operator=self.operator)
         self._version = 0
+
+    def eq_residual(self, params, X_test, src_test):
+        """SolverBase.eq_residual; on an operator equation sum_k c_k d^{o_k} u / dx_k^{o_k} +
+        r1 u + r2 u^2 + r3 u^3 - f from the derivative predictions."""
+        op = self.operator
+        if op is None:
+            return SolverBase.eq_residual(self, params, X_test, src_test)
+        self._sync(params)
+        axes = self._test_axes(X_test)
+        r = np.zeros(tuple(a.size for a in axes))
+        for k in range(3):
+            if op.coef[k] != 0.0:
+                d = [0, 0, 0]
+                d[k] = op.order[k]
+                r = r + op.coef[k] * self.dev.predict_deriv(*axes, deriv=tuple(d))
+        if any(op.react):
+            u = self.dev.predict_deriv(*axes, deriv=(0, 0, 0))
+            r = r + op.react[0] * u + op.react[1] * u ** 2 + op.react[2] * u ** 3
+        return r - np.asarray(src_test, np.float64).reshape(r.shape)
 
     # the device holds the params: reading fetches them, train()'s final assignment is a no-op
     @property
@@ -336,12 +393,16 @@ SOLVER = GP_solver_3d_single
 def test(trick_paras, solver_cls=None):
     """Run num_fold trainings of one equation and write result_log (2d.py:382-464)."""
     solver_cls = solver_cls or SOLVER
-    u, src = solution_3d(trick_paras["equation"])
+    op = None
+    if trick_paras["equation"] in EQUATIONS_3D_OP:
+        u, src, op = solution_3d_op(trick_paras["equation"])
+    else:
+        u, src = solution_3d(trick_paras["equation"])
     scale = trick_paras["scale"]
     M, N = trick_paras["M_test"], trick_paras["N_col"]
     X_test, u_test = get_mesh_data(u, (M, M, M), scale)
     X_col, u_mh = get_mesh_data(u, (N, N, N), scale)
-    bvals = boundary_3d(u_mh)
+    bvals = boundary_3d(u_mh, op.faces if op else 63)
     _, src_vals = get_mesh_data(src, (N, N, N), scale)
     ctx = replicas.init()
     if ctx.world > 1:
@@ -370,16 +431,18 @@ def test(trick_paras, solver_cls=None):
 
 
 def load_config(equation):
-    """./config3d/<equation>.yaml, falling back to the package's copy."""
+    """./config3d/<equation>.yaml (the operator equations: ./config3d_op/), falling back to the
+    package's copy."""
+    cdir = "config3d_op" if equation in EQUATIONS_3D_OP else "config3d"
     for base in (os.getcwd(), os.path.dirname(os.path.abspath(__file__))):
-        p = os.path.join(base, "config3d", equation + ".yaml")
+        p = os.path.join(base, cdir, equation + ".yaml")
         if os.path.exists(p):
             with open(p, "r") as f:
                 return yaml.safe_load(f)
-    raise FileNotFoundError("config3d/" + equation + ".yaml")
+    raise FileNotFoundError(cdir + "/" + equation + ".yaml")
 
 
-def build_config(args, allowed=EQUATIONS_3D):
+def build_config(args, allowed=EQUATIONS_3D + EQUATIONS_3D_OP):
     """The 2-axis build_config (scale, kernel class, other_paras) on the config3d files."""
     assert args.equation in allowed
     config = load_config(args.equation)

@@ -445,6 +445,42 @@ typedef struct gpk_problem3 {
 typedef struct gpk_handle3 gpk_handle3;
 int gpk_create3(const gpk_problem3* p, double freq_scale, gpk_handle3** out);
 int gpk_destroy3(gpk_handle3* h);
+
+/* The same solver for a stated operator instead of one of the two built-in equations: one
+ * derivative order and one weight per axis, a constant-coefficient reaction polynomial, and the
+ * set of faces that carry boundary data (an initial-value problem leaves its final-time face
+ * open).  Residual on the grid
+ *     R = sum_k c_k (D_k^(o_k) K_k^{-1}) x_k U - F + r1 U + r2 U^2 + r3 U^3,
+ * D_k^(1) = D_x1_kappa, D_k^(2) = DD_x1_kappa of axis k (gpk_kernel_matrices deriv 1 / 2); the log
+ * joint is gpk_create3's with this R, and its boundary term, Nb (in the loss, in d/d log_tau, in
+ * gpk_criterion3 and gpk_loss_terms3's boundary_gap) run over the active faces only.  An edge
+ * shared by two active faces counts twice, as on a legacy handle; an edge between an active and
+ * an open face counts once.  Examples with the third axis as time: heat u_t - nu (u_xx + u_yy):
+ * order (2,2,1), coef (-nu,-nu,1), faces 31; transport b1 u_x + b2 u_y + u_t: order (1,1,1), coef
+ * (b1,b2,1); Helmholtz: order (2,2,2), coef (1,1,1), react (k^2,0,0); Allen-Cahn in time:
+ * order (2,2,1), coef (-eps,-eps,1), react (-1,0,1), faces 31.
+ * Not expressible: two orders on one axis (a d^2 + b d), coefficients that vary over the grid,
+ * derivative (Neumann / initial-velocity) boundary data. */
+typedef struct gpk_operator3 {
+  int32_t order[3];  /* 1 or 2: the derivative taken along axis k (D_x1_kappa / DD_x1_kappa block) */
+  double  coef[3];   /* its weight c_k, any finite value (0 drops that axis's term)               */
+  double  react[3];  /* r1, r2, r3: + r1 u + r2 u^2 + r3 u^3 in the residual                      */
+  int32_t faces;     /* bit f set: face f carries boundary data; f in gpk_problem3.bvals order:
+                        0: i1=0, 1: i1=n1-1, 2: i2=0, 3: i2=n2-1, 4: i3=0, 5: i3=n3-1.  1..63    */
+} gpk_operator3;
+/* p->eq must be GPK_POISSON (the operator says everything else); p->flags as on gpk_create3, both
+ * GPK_FLAG3_REFINE bits included.  p->bvals keeps the six-face layout and length whatever the
+ * mask: entries of open faces are never read and may be NaN.  GPK_EINVAL on a NULL op, an order
+ * outside {1, 2}, a non-finite coef or react, faces outside 1..63, or eq != GPK_POISSON.  Every
+ * other gpk_*3 call works on such a handle unchanged (predictions, derivatives and scattered
+ * points depend on K_k only).  order (2,2,2), coef (1,1,1), react 0, faces 63 is gpk_create3's
+ * Poisson handle bit for bit; react (-1,0,1) is its Allen-Cahn handle up to rounding (the legacy
+ * handle evaluates u(u^2 - 1)). */
+int gpk_create3_op(const gpk_problem3* p, const gpk_operator3* op, double freq_scale, gpk_handle3** out);
+/* What the handle runs: gpk_create3_op's operator, or a gpk_create3 handle's equivalent (orders 2,
+ * weights 1, faces 63, react 0 for Poisson and (-1,0,1) for Allen-Cahn). */
+int gpk_operator_info3(const gpk_handle3* h, gpk_operator3* out);
+
 int gpk_num_params3(const gpk_handle3* h, int64_t* n);
 int gpk_set_params3(gpk_handle3* h, const double* flat, int64_t n);
 int gpk_get_params3(gpk_handle3* h, double* flat, int64_t n);
@@ -477,7 +513,8 @@ int gpk_predict_deriv3(gpk_handle3* h, const double* xte1, int32_t m1, const dou
  * before it.  Scratch, status codes and side effects as gpk_predict3. */
 int gpk_evaluate3(gpk_handle3* h, const double* pts, int64_t m, const int32_t d[3], double* out);
 /* compute_early_stopping (model_GP_solver_2d.py:222-233) on three axes: boundary_gap / Nb +
- * eq_gap / Nc at the current params, Nb = 2 (n2 n3 + n1 n3 + n1 n2), Nc = n1 n2 n3. */
+ * eq_gap / Nc at the current params, Nb = 2 (n2 n3 + n1 n3 + n1 n2), Nc = n1 n2 n3 (operator handles: boundary_gap
+ * and Nb over the active faces). */
 int gpk_criterion3(gpk_handle3* h, double* out);
 /* The GEMM kernel each of the step's GEMM launches takes, in stream order (gpk_dgemm's variant
  * numbers: 1 the 16x16, 2 the 64x64, 3 the 128x128 kernel): *n launches, the first
