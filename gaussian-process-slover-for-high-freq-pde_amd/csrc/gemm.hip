@@ -6,9 +6,17 @@
 // The dual-product form fuses R = D1 A + Bt D2^T - F into one tile loop; epilogues also
 // produce the reductions the loss needs (||R||^2, <U,S>) as deterministic per-tile partials.
 //
-// Tile: 32x32 per 256-thread workgroup; wave w owns the 16x16 quadrant (w>>1, w&1);
-// K-steps of 32 staged through LDS; v_mfma_f64_16x16x4_f64 with the measured gfx950 map
-// (A[i=l&15][k=l>>4], B[k=l>>4][j=l&15], C/D row=(l>>4)+4r, col=l&15).
+// Kernels, all 256 threads per workgroup on v_mfma_f64_16x16x4_f64 with the measured gfx950 map
+// (A[i=l&15][k=l>>4], B[k=l>>4][j=l&15], C/D row=(l>>4)+4r, col=l&15):
+//   gemm_small_kernel  16x16 tile, K split over the 4 waves, operands global -> registers
+//                      (latency: the 256^2 headline)                          GEMM_SMALL
+//   gemm_big_kernel    64x64 tile, 32-deep K-steps through double-buffered LDS  GEMM_BIG
+//   gemm_huge_kernel   128x128 tile, the pipelined loop of gemm_tile_dev.h      GEMM_HUGE
+//   gemm_slab_kernel   slab-batched C_b = alpha A B_b + beta C0_b, 32x32 or 64x64 tiles
+//   gemv_kernel        one wave per row (the 1D solver)
+// launch_gemm_auto runs a descriptor batch on the variant it is given (gemm_variant: the size
+// rule), a dual product on 128x128 tiles as two passes (launch_huge); launch_gemm_slab picks
+// the slab tile by the slab size; launch_gemv is the GEMV.
 #include "gpk_internal.h"
 #include "gpk_trace.h"
 #include "gemm_tile_dev.h"
@@ -23,6 +31,8 @@ typedef double d4 __attribute__((ext_vector_type(4)));
 constexpr int GSA = 34;  // A-role LDS stride (doubles)
 constexpr int GSB = 48;  // B-role LDS stride
 
+// 32x32 tile per workgroup, wave w the 16x16 quadrant (w>>1, w&1), K-steps of 32 staged through
+// LDS: gemm_slab_kernel<32>'s loop (its only user)
 __device__ __forceinline__ void stage_tiles(double* sA, double* sB, const double* A, int lda,
                                             int ta, const double* B, int ldb, int tb, int i0,
                                             int j0, int k0, int t) {
@@ -115,62 +125,54 @@ __device__ __forceinline__ double epi_apply(const GemmDesc& d, double c, const E
   return c;
 }
 
-__global__ __launch_bounds__(256) void gemm_kernel(GemmBatch batch,
-                                                   const StepScalars* __restrict__ sc) {
-  const GemmDesc& d = batch.d[blockIdx.y];
-  const int tn = d.N >> 5;
-  const int tiles = (d.M >> 5) * tn;
-  if ((int)blockIdx.x >= tiles) return;
-  if (!gate_open(d.gate)) return;  // refinement not needed (uniform)
-  const int ti = blockIdx.x / tn, tj = blockIdx.x % tn;
-  const int i0 = ti * 32, j0 = tj * 32;
-
-  __shared__ double sA[32 * GSA];
-  __shared__ double sB[32 * GSB];
-  __shared__ double sred[4], sred2[4];
-  const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
-  const int wr = wv >> 1, wc = wv & 1;
-  EpiIn ein[4];
-#pragma unroll
-  for (int r = 0; r < 4; ++r)
-    ein[r] = epi_fetch(d, i0 + 16 * wr + (lane >> 4) + 4 * r, j0 + 16 * wc + (lane & 15));
-
-  d4 acc1 = {0.0, 0.0, 0.0, 0.0}, acc2 = {0.0, 0.0, 0.0, 0.0};
-  for (int k0 = 0; k0 < d.K; k0 += 32) {
-    stage_tiles(sA, sB, d.A, d.lda, d.ta, d.B, d.ldb, d.tb, i0, j0, k0, t);
-    __syncthreads();
-    acc1 = mma32(sA, sB, wr, wc, lane, acc1);
-    __syncthreads();
-  }
-  for (int k0 = 0; k0 < d.K2; k0 += 32) {
-    stage_tiles(sA, sB, d.A2, d.lda2, d.ta2, d.B2, d.ldb2, d.tb2, i0, j0, k0, t);
-    __syncthreads();
-    acc2 = mma32(sA, sB, wr, wc, lane, acc2);
-    __syncthreads();
-  }
-
+// the epilogue's scalars: the products' factors (times v where the descriptor says so) and the
+// side output's v
+struct EpiScal {
+  double alpha, alpha2, vv;
+};
+__device__ __forceinline__ EpiScal epi_scalars(const GemmDesc& d, const StepScalars* sc) {
   double alpha = d.alpha, alpha2 = d.alpha2;
   if (d.vscale) alpha *= sc->v;
   if (d.vscale2) alpha2 *= sc->v;
-  const double vv = d.Y ? sc->v : 0.0;
-  double part = 0.0, part2 = 0.0;
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    const int row = i0 + 16 * wr + (lane >> 4) + 4 * r, col = j0 + 16 * wc + (lane & 15);
-    double c = alpha * acc1[r];
-    if (d.K2) c += alpha2 * acc2[r];
-    c = epi_apply(d, c, ein[r], part, part2);
-    d.C[(size_t)row * d.ldc + col] = c;
-    epi_side(d, row, col, c, ein[r], vv);
-  }
+  return {alpha, alpha2, d.Y ? sc->v : 0.0};
+}
+
+// the workgroup's loss partials into the tile's slots (every thread calls; sred, sred2: LDS [4])
+__device__ __forceinline__ void epi_partials(const GemmDesc& d, int tile, double part, double part2,
+                                             double* sred, double* sred2) {
   if (d.red) {
     double s = block_sum_256(part, sred);
-    if (t == 0) d.red[blockIdx.x] = s;
+    if (threadIdx.x == 0) d.red[tile] = s;
   }
   if (d.red2) {
     double s = block_sum_256(part2, sred2);
-    if (t == 0) d.red2[blockIdx.x] = s;
+    if (threadIdx.x == 0) d.red2[tile] = s;
   }
+}
+
+template <int X, int Y>
+__device__ __forceinline__ void acc_zero(d4 (&acc)[X][Y]) {
+#pragma unroll
+  for (int x = 0; x < X; ++x)
+#pragma unroll
+    for (int y = 0; y < Y; ++y) acc[x][y] = d4{0.0, 0.0, 0.0, 0.0};
+}
+
+// This lane's 16 elements of its wave's 32x32 quadrant (wr, wc) of the 64x64 tile at (i0, j0):
+// f(row, col, bi, bj, r) for accumulator element acc[bi][bj][r], inside M x N only.  Fully
+// unrolled, so the accumulator indices are static (gemm_huge_kernel's epilogue note).
+template <typename F>
+__device__ __forceinline__ void quad_each(int i0, int j0, int wr, int wc, int lane, int M, int N, F&& f) {
+#pragma unroll
+  for (int bi = 0; bi < 2; ++bi)
+#pragma unroll
+    for (int bj = 0; bj < 2; ++bj)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int row = i0 + 32 * wr + 16 * bi + (lane >> 4) + 4 * r;
+        const int col = j0 + 32 * wc + 16 * bj + (lane & 15);
+        if (row < M && col < N) f(row, col, bi, bj, r);
+      }
 }
 
 // ---------------------------------------------------------------------------------------
@@ -180,6 +182,23 @@ __global__ __launch_bounds__(256) void gemm_kernel(GemmBatch batch,
 // k-substeps of loads in flight per wave; the 4 partial accumulators are summed through LDS
 // in fixed order (deterministic) by wave 0, which runs the epilogue.
 // ---------------------------------------------------------------------------------------
+// S k-substeps (4 deep each) of this lane's fragments: every operand load in flight before the
+// first MFMA
+template <int S>
+__device__ __forceinline__ d4 mma_block(const double* __restrict__ A, int lda, int ta,
+                                        const double* __restrict__ B, int ldb, int tb, int i, int j,
+                                        int k0, int lk, d4 acc) {
+  double a[S], b[S];
+#pragma unroll
+  for (int s = 0; s < S; ++s) {
+    const int k = k0 + 4 * s + lk;
+    a[s] = ta ? A[(size_t)k * lda + i] : A[(size_t)i * lda + k];
+    b[s] = tb ? B[(size_t)j * ldb + k] : B[(size_t)k * ldb + j];
+  }
+#pragma unroll
+  for (int s = 0; s < S; ++s) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a[s], b[s], acc, 0, 0, 0);
+  return acc;
+}
 __device__ __forceinline__ d4 mma_chunk(const double* __restrict__ A, int lda, int ta,
                                         const double* __restrict__ B, int ldb, int tb, int i0,
                                         int j0, int kbeg, int kend, int lane, d4 acc) {
@@ -187,28 +206,9 @@ __device__ __forceinline__ d4 mma_chunk(const double* __restrict__ A, int lda, i
   const int i = i0 + li, j = j0 + li;
   int k0 = kbeg;
   // 64-deep blocks: all 16 k-substeps of operands in flight before the first MFMA
-  for (; k0 + 64 <= kend; k0 += 64) {
-    double a[16], b[16];
-#pragma unroll
-    for (int s = 0; s < 16; ++s) {
-      const int k = k0 + 4 * s + lk;
-      a[s] = ta ? A[(size_t)k * lda + i] : A[(size_t)i * lda + k];
-      b[s] = tb ? B[(size_t)j * ldb + k] : B[(size_t)k * ldb + j];
-    }
-#pragma unroll
-    for (int s = 0; s < 16; ++s) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a[s], b[s], acc, 0, 0, 0);
-  }
-  if (k0 < kend) {  // K ranges are multiples of 32: at most one 32-deep tail
-    double a[8], b[8];
-#pragma unroll
-    for (int s = 0; s < 8; ++s) {
-      const int k = k0 + 4 * s + lk;
-      a[s] = ta ? A[(size_t)k * lda + i] : A[(size_t)i * lda + k];
-      b[s] = tb ? B[(size_t)j * ldb + k] : B[(size_t)k * ldb + j];
-    }
-#pragma unroll
-    for (int s = 0; s < 8; ++s) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a[s], b[s], acc, 0, 0, 0);
-  }
+  for (; k0 + 64 <= kend; k0 += 64) acc = mma_block<16>(A, lda, ta, B, ldb, tb, i, j, k0, lk, acc);
+  // K ranges are multiples of 32: at most one 32-deep tail
+  if (k0 < kend) acc = mma_block<8>(A, lda, ta, B, ldb, tb, i, j, k0, lk, acc);
   return acc;
 }
 
@@ -272,43 +272,26 @@ __device__ __forceinline__ void blk64(const GemmDesc& d, int i0, int j0, int b0,
     for (int s = 0; s < 16; ++s) acc2 = __builtin_amdgcn_mfma_f64_16x16x4f64(a2[s], bb2[s], acc2, 0, 0, 0);
   }
 }
-// runtime transpose flags -> one of the 4 (single) / 16 (dual) instantiations (uniform branch)
+// runtime transpose flags -> one of the 4 (single) / 16 (dual) instantiations (uniform branch):
+// code C runs the instantiation whose template arguments are C's bits, the last one unconditionally
+template <bool DUAL, int C = 0>
+__device__ __forceinline__ void blk64_pick(int code, const GemmDesc& d, int i0, int j0, int b0, int c0,
+                                           int lane, double* bufA, double* bufB, d4& acc1, d4& acc2) {
+  if constexpr (C < (DUAL ? 15 : 3)) {
+    if (code != C) return blk64_pick<DUAL, C + 1>(code, d, i0, j0, b0, c0, lane, bufA, bufB, acc1, acc2);
+  }
+  blk64<(C & 1) != 0, (C & 2) != 0, (C & 4) != 0, (C & 8) != 0, DUAL>(d, i0, j0, b0, c0, lane, bufA, bufB,
+                                                                      acc1, acc2);
+}
 template <bool DUAL>
 __device__ __forceinline__ void blk64_dispatch(const GemmDesc& d, int i0, int j0, int b0, int c0,
                                                int lane, double* bufA, double* bufB, d4& acc1,
                                                d4& acc2) {
   const int code = (!d.ta) | (d.tb << 1) | ((!d.ta2) << 2) | (d.tb2 << 3);
-#define GPK_B64(c) blk64<((c) & 1) != 0, ((c) & 2) != 0, ((c) & 4) != 0, ((c) & 8) != 0, true>
-#define GPK_B64S(c) blk64<((c) & 1) != 0, ((c) & 2) != 0, false, false, false>
-  if (DUAL && d.K2) {
-    switch (code) {
-      case 0: GPK_B64(0)(d, i0, j0, b0, c0, lane, bufA, bufB, acc1, acc2); break;
-      case 1: GPK_B64(1)(d, i0, j0, b0, c0, lane, bufA, bufB, acc1, acc2); break;
-      case 2: GPK_B64(2)(d, i0, j0, b0, c0, lane, bufA, bufB, acc1, acc2); break;
-      case 3: GPK_B64(3)(d, i0, j0, b0, c0, lane, bufA, bufB, acc1, acc2); break;
-      case 4: GPK_B64(4)(d, i0, j0, b0, c0, lane, bufA, bufB, acc1, acc2); break;
-      case 5: GPK_B64(5)(d, i0, j0, b0, c0, lane, bufA, bufB, acc1, acc2); break;
-      case 6: GPK_B64(6)(d, i0, j0, b0, c0, lane, bufA, bufB, acc1, acc2); break;
-      case 7: GPK_B64(7)(d, i0, j0, b0, c0, lane, bufA, bufB, acc1, acc2); break;
-      case 8: GPK_B64(8)(d, i0, j0, b0, c0, lane, bufA, bufB, acc1, acc2); break;
-      case 9: GPK_B64(9)(d, i0, j0, b0, c0, lane, bufA, bufB, acc1, acc2); break;
-      case 10: GPK_B64(10)(d, i0, j0, b0, c0, lane, bufA, bufB, acc1, acc2); break;
-      case 11: GPK_B64(11)(d, i0, j0, b0, c0, lane, bufA, bufB, acc1, acc2); break;
-      case 12: GPK_B64(12)(d, i0, j0, b0, c0, lane, bufA, bufB, acc1, acc2); break;
-      case 13: GPK_B64(13)(d, i0, j0, b0, c0, lane, bufA, bufB, acc1, acc2); break;
-      case 14: GPK_B64(14)(d, i0, j0, b0, c0, lane, bufA, bufB, acc1, acc2); break;
-      default: GPK_B64(15)(d, i0, j0, b0, c0, lane, bufA, bufB, acc1, acc2); break;
-    }
-  } else {
-    switch (code & 3) {
-      case 0: GPK_B64S(0)(d, i0, j0, b0, c0, lane, bufA, bufB, acc1, acc2); break;
-      case 1: GPK_B64S(1)(d, i0, j0, b0, c0, lane, bufA, bufB, acc1, acc2); break;
-      case 2: GPK_B64S(2)(d, i0, j0, b0, c0, lane, bufA, bufB, acc1, acc2); break;
-      default: GPK_B64S(3)(d, i0, j0, b0, c0, lane, bufA, bufB, acc1, acc2); break;
-    }
-  }
-#undef GPK_B64
-#undef GPK_B64S
+  if (DUAL && d.K2)
+    blk64_pick<true>(code, d, i0, j0, b0, c0, lane, bufA, bufB, acc1, acc2);
+  else
+    blk64_pick<false>(code & 3, d, i0, j0, b0, c0, lane, bufA, bufB, acc1, acc2);
 }
 
 // DUAL (some descriptor has a second product): waves_per_eu(2) = 256 VGPRs per lane, enough for
@@ -392,17 +375,14 @@ void gemm_small_kernel(GemmBatch batch, const StepScalars* __restrict__ sc) {
   if (TR_LAST) TR_HI(tslot + 3);
   // the epilogue on all four waves (one output per lane each; wave 0 used to run all four rows
   // in turn): the K quarters summed in fixed order, then the stage's epilogue and stores
-  double alpha = d.alpha, alpha2 = d.alpha2;
-  if (d.vscale) alpha *= sc->v;
-  if (d.vscale2) alpha2 *= sc->v;
-  const double vv = d.Y ? sc->v : 0.0;
+  const EpiScal es = epi_scalars(d, sc);
   double red = 0.0, red2 = 0.0, c;
   const int row = i0 + (lane >> 4) + 4 * wv, col = j0 + (lane & 15);
   {
     const int q = lane * 4 + wv;
     const double s1 = (part[0][0][q] + part[0][1][q]) + (part[0][2][q] + part[0][3][q]);
-    c = alpha * s1;
-    if (DUAL && d.K2) c += alpha2 * ((part[1][0][q] + part[1][1][q]) + (part[1][2][q] + part[1][3][q]));
+    c = es.alpha * s1;
+    if (DUAL && d.K2) c += es.alpha2 * ((part[1][0][q] + part[1][1][q]) + (part[1][2][q] + part[1][3][q]));
     c = epi_apply(d, c, ein, red, red2);
   }
   // The tile's class sums (d.cpart) and loss partials (d.red / d.red2) go through LDS: their
@@ -429,7 +409,7 @@ void gemm_small_kernel(GemmBatch batch, const StepScalars* __restrict__ sc) {
   }
   if (d.cpart || d.red || d.red2) __syncthreads();  // (uniform)
   d.C[(size_t)row * d.ldc + col] = c;
-  epi_side(d, row, col, c, ein, vv);
+  epi_side(d, row, col, c, ein, es.vv);
   if (d.cpart) {  // (uniform) the tile's sums per (signed diagonal, variant), rows in order
     // this thread's slots: class (k, v) [and (k, v + 8)] at (sign, band group, tile row)
     const int dl = (t >> 3) - 15, v = t & 7;
@@ -496,18 +476,6 @@ static void launch_small(const GemmBatch& b, int ndesc, int tiles, const StepSca
     hipLaunchKernelGGL(gemm_small_kernel<true>, dim3(tiles, ndesc), dim3(256), 0, s, b, sc);
   else
     hipLaunchKernelGGL(gemm_small_kernel<false>, dim3(tiles, ndesc), dim3(256), 0, s, b, sc);
-}
-
-hipError_t launch_gemm_batch(const GemmDesc* descs, int ndesc, int max_tiles,
-                             const StepScalars* sc, hipStream_t s, int small) {
-  if (ndesc < 1 || ndesc > GEMM_MAX_BATCH) return hipErrorInvalidValue;
-  GemmBatch b{};
-  for (int i = 0; i < ndesc; ++i) b.d[i] = descs[i];
-  if (small)
-    launch_small(b, ndesc, max_tiles, sc, s);
-  else
-    hipLaunchKernelGGL(gemm_kernel, dim3(max_tiles, ndesc), dim3(256), 0, s, b, sc);
-  return hipGetLastError();
 }
 
 // ---------------------------------------------------------------------------------------
@@ -633,45 +601,21 @@ __global__ __launch_bounds__(256) void gemm_big_kernel(GemmBatch batch, const St
   const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
   const int wr = wv >> 1, wc = wv & 1;
   d4 acc1[2][2], acc2[2][2];
-#pragma unroll
-  for (int a = 0; a < 2; ++a)
-#pragma unroll
-    for (int b = 0; b < 2; ++b) {
-      acc1[a][b] = d4{0.0, 0.0, 0.0, 0.0};
-      acc2[a][b] = d4{0.0, 0.0, 0.0, 0.0};
-    }
+  acc_zero(acc1);
+  acc_zero(acc2);
   big_product(d.A, d.lda, d.ta, d.B, d.ldb, d.tb, d.K, d.M, d.N, i0, j0, sA, sB, t, wr, wc, lane, acc1);
   if (d.K2) big_product(d.A2, d.lda2, d.ta2, d.B2, d.ldb2, d.tb2, d.K2, d.M, d.N, i0, j0, sA, sB, t, wr, wc, lane, acc2);
-  double alpha = d.alpha, alpha2 = d.alpha2;
-  if (d.vscale) alpha *= sc->v;
-  if (d.vscale2) alpha2 *= sc->v;
-  const double vv = d.Y ? sc->v : 0.0;
+  const EpiScal es = epi_scalars(d, sc);
   double part = 0.0, part2 = 0.0;
-#pragma unroll
-  for (int bi = 0; bi < 2; ++bi)
-#pragma unroll
-    for (int bj = 0; bj < 2; ++bj)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int row = i0 + 32 * wr + 16 * bi + (lane >> 4) + 4 * r;
-        const int col = j0 + 32 * wc + 16 * bj + (lane & 15);
-        if (row < d.M && col < d.N) {
-          const EpiIn e = epi_fetch(d, row, col);
-          double c = alpha * acc1[bi][bj][r];
-          if (d.K2) c += alpha2 * acc2[bi][bj][r];
-          c = epi_apply(d, c, e, part, part2);
-          d.C[(size_t)row * d.ldc + col] = c;
-          epi_side(d, row, col, c, e, vv);
-        }
-      }
-  if (d.red) {
-    double s = block_sum_256(part, sred);
-    if (t == 0) d.red[tile] = s;
-  }
-  if (d.red2) {
-    double s = block_sum_256(part2, sred2);
-    if (t == 0) d.red2[tile] = s;
-  }
+  quad_each(i0, j0, wr, wc, lane, d.M, d.N, [&](int row, int col, int bi, int bj, int r) {
+    const EpiIn e = epi_fetch(d, row, col);
+    double c = es.alpha * acc1[bi][bj][r];
+    if (d.K2) c += es.alpha2 * acc2[bi][bj][r];
+    c = epi_apply(d, c, e, part, part2);
+    d.C[(size_t)row * d.ldc + col] = c;
+    epi_side(d, row, col, c, e, es.vv);
+  });
+  epi_partials(d, tile, part, part2, sred, sred2);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -679,7 +623,7 @@ __global__ __launch_bounds__(256) void gemm_big_kernel(GemmBatch batch, const St
 // row-major [nb][K][N] tensor is nb independent row-major K x N matrices, so
 //   C_b = alpha A B_b + beta C0_b,   B_b = B + b sB,  C_b = C + b sC,  C0_b = C0 + b sC0
 // needs no permuted copy: the slab index is the grid's y dimension and offsets B, C and C0, one
-// M x K operand A serves every slab.  TILE 32: gemm_kernel's 32x32 tile loop (stage_tiles /
+// M x K operand A serves every slab.  TILE 32: the 32x32 tile loop (stage_tiles /
 // mma32); TILE 64: gemm_big_kernel's double-buffered 64x64 loop (big_product; edge tiles of a
 // 32-padded matrix half empty).  Plain store epilogue; C0 == C is an in-place update (every
 // element is read and written by the same lane).
@@ -714,26 +658,14 @@ __global__ __launch_bounds__(256) void gemm_slab_kernel(SlabGemm g) {
   } else {
     __shared__ double sA[2 * 64 * BSA], sB[2 * 32 * BSB];
     d4 acc[2][2];
-#pragma unroll
-    for (int x = 0; x < 2; ++x)
-#pragma unroll
-      for (int y = 0; y < 2; ++y) acc[x][y] = d4{0.0, 0.0, 0.0, 0.0};
+    acc_zero(acc);
     big_product(g.A, g.K, 0, B, g.N, 0, g.K, g.M, g.N, i0, j0, sA, sB, t, wr, wc, lane, acc);
-#pragma unroll
-    for (int bi = 0; bi < 2; ++bi)
-#pragma unroll
-      for (int bj = 0; bj < 2; ++bj)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int row = i0 + 32 * wr + 16 * bi + (lane >> 4) + 4 * r;
-          const int col = j0 + 32 * wc + 16 * bj + (lane & 15);
-          if (row < g.M && col < g.N) {
-            const size_t o = (size_t)row * g.N + col;
-            double c = g.alpha * acc[bi][bj][r];
-            if (C0) c += g.beta * C0[o];
-            C[o] = c;
-          }
-        }
+    quad_each(i0, j0, wr, wc, lane, g.M, g.N, [&](int row, int col, int bi, int bj, int r) {
+      const size_t o = (size_t)row * g.N + col;
+      double c = g.alpha * acc[bi][bj][r];
+      if (C0) c += g.beta * C0[o];
+      C[o] = c;
+    });
   }
 }
 
@@ -798,13 +730,9 @@ void gemm_huge_kernel(GemmBatch batch, const StepScalars* __restrict__ sc, int p
   const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
   const int wr = wv >> 1, wc = wv & 1;
   d4 acc[4][4];
-#pragma unroll
-  for (int x = 0; x < 4; ++x)
-#pragma unroll
-    for (int y = 0; y < 4; ++y) acc[x][y] = d4{0.0, 0.0, 0.0, 0.0};
+  acc_zero(acc);
   product<TA, TB, false, 0>(d.A, d.lda, d.B, d.ldb, d.K, d.M, d.N, i0, j0, 1.0, lds, t, wr, wc, lane, acc);
-  const double alpha = d.vscale ? d.alpha * sc->v : d.alpha;
-  const double vv = d.Y ? sc->v : 0.0;
+  const EpiScal es = epi_scalars(d, sc);  // (one product per launch: alpha2 unused)
   // Epilogue through LDS, one half tile (64 rows) at a time: the two waves of that half store
   // their accumulators (static indices: a rolled epilogue over the accumulators put them in
   // scratch), then every thread finishes 16 rows x 2 adjacent columns -- whole-row (coalesced)
@@ -831,24 +759,17 @@ void gemm_huge_kernel(GemmBatch batch, const StepScalars* __restrict__ sc, int p
         const int col = col0 + e2;
         if (col < d.N) {
           const EpiIn e = epi_fetch(d, row, col);
-          double c = alpha * lds[lr * ES + 2 * (t & 63) + e2];
+          double c = es.alpha * lds[lr * ES + 2 * (t & 63) + e2];
           if (d.Cp) c += d.Cp[(size_t)row * d.ldcp + col];
           c = epi_apply(d, c, e, part, part2);
           d.C[(size_t)row * d.ldc + col] = c;
-          epi_side(d, row, col, c, e, vv);
+          epi_side(d, row, col, c, e, es.vv);
         }
       }
     }
     __syncthreads();
   }
-  if (d.red) {
-    double s = block_sum_256(part, sred);
-    if (t == 0) d.red[tile] = s;
-  }
-  if (d.red2) {
-    double s = block_sum_256(part2, sred2);
-    if (t == 0) d.red2[tile] = s;
-  }
+  epi_partials(d, tile, part, part2, sred, sred2);
 }
 
 typedef void (*HugeFn)(GemmBatch, const StepScalars*, int);
@@ -881,11 +802,11 @@ static hipError_t launch_huge(const GemmDesc* descs, int ndesc, const StepScalar
                      o.U == d.C || o.Q1 == d.C || o.Q2 == d.C || o.Ys == d.C))
         return hipErrorInvalidValue;
     }
-    GemmDesc a{};  // alpha op(A) op(B) [+ beta C0] -> C
-    a.A = d.A; a.lda = d.lda; a.ta = d.ta; a.B = d.B; a.ldb = d.ldb; a.tb = d.tb;
-    a.alpha = d.alpha; a.vscale = d.vscale; a.C = d.C; a.ldc = d.ldc;
-    a.M = d.M; a.N = d.N; a.K = d.K; a.epi = EPI_STORE; a.gate = d.gate; a.ngate = d.ngate; a.tag = d.tag;
-    if (d.epi != EPI_RESID && d.beta != 0.0) { a.beta = d.beta; a.C0 = d.C0; a.ldc0 = d.ldc0; }
+    GemmDesc a = d;  // alpha op(A) op(B) [+ beta C0] -> C and nothing else:
+    a.K2 = 0; a.A2 = a.B2 = nullptr;                  // no second product,
+    a.epi = EPI_STORE; a.ac = 0;                      // no epilogue beyond the store
+    if (d.epi == EPI_RESID) a.beta = 0.0;             // (beta C0 belongs to STORE and QUAD only),
+    a.red = a.red2 = nullptr; a.Y = nullptr;          // no partials, no side output
     pass[0][np[0]++] = a;
     GemmDesc b = d;  // alpha2 op(A2) op(B2) + C, then the descriptor's epilogue
     b.A = d.A2; b.lda = d.lda2; b.ta = d.ta2; b.B = d.B2; b.ldb = d.ldb2; b.tb = d.tb2; b.K = d.K2;
@@ -915,10 +836,8 @@ static hipError_t launch_huge(const GemmDesc* descs, int ndesc, const StepScalar
 }
 
 int gemm_tiles(const GemmDesc& d, int variant) {
-  if (variant == GEMM_SMALL) return (d.M / 16) * (d.N / 16);
-  if (variant == GEMM_HUGE) return ((d.M + 127) / 128) * ((d.N + 127) / 128);
-  if (variant == GEMM_BIG) return ((d.M + 63) / 64) * ((d.N + 63) / 64);
-  return (d.M / 32) * (d.N / 32);
+  const int t = gemm_tile_dim(variant);  // (M, N multiples of 32: only 64 and 128 leave edge tiles)
+  return ((d.M + t - 1) / t) * ((d.N + t - 1) / t);
 }
 
 int gemm_variant(const GemmDesc* descs, int ndesc, int force_big) {
@@ -926,8 +845,8 @@ int gemm_variant(const GemmDesc* descs, int ndesc, int force_big) {
   if (force_big) return GEMM_BIG;
   long tot16 = 0, tot128 = 0;
   for (int i = 0; i < ndesc; ++i) {
-    tot16 += (long)(descs[i].M / 16) * (descs[i].N / 16);
-    tot128 += (long)((descs[i].M + 127) / 128) * ((descs[i].N + 127) / 128);
+    tot16 += gemm_tiles(descs[i], GEMM_SMALL);
+    tot128 += gemm_tiles(descs[i], GEMM_HUGE);
   }
   if (gemm_use_small(tot16)) return GEMM_SMALL;
   return tot128 >= GEMM_HUGE_MIN_TILES ? GEMM_HUGE : GEMM_BIG;
@@ -950,7 +869,7 @@ hipError_t launch_gemm_auto(const GemmDesc* descs, int ndesc, const StepScalars*
   } else if (variant == GEMM_HUGE) {
     return launch_huge(descs, ndesc, sc, s);
   } else {
-    hipLaunchKernelGGL(gemm_kernel, dim3(mt, ndesc), dim3(256), 0, s, b, sc);
+    return hipErrorInvalidValue;
   }
   return hipGetLastError();
 }

@@ -1,5 +1,5 @@
-// gemm_huge_dev.h — the 128x128-tile fp64 MFMA product loop (gfx950), shared by the large GEMM
-// (gemm.hip gemm_huge_kernel) and the large-factor SPD inverse's update (spdinv_big.hip).
+// gemm_huge_dev.h — the 128x128-tile fp64 MFMA product loop (gfx950) of the large-factor SPD
+// inverse's update (spdinv_big.hip; gemm.hip's gemm_huge_kernel runs gemm_tile_dev.h's loop).
 // A 128x128 output tile per 256-thread workgroup, each wave a 64x64 quadrant = 4x4
 // v_mfma_f64_16x16x4 blocks (every LDS fragment feeds 4 MFMAs, 16 independent accumulation
 // chains per wave); 16-deep K-steps through double-buffered LDS ([k][m] / [k][n], rows S = 140

@@ -228,7 +228,7 @@ int solve_alpha(gpk_handle* h, double* alpha, double* rv) {
 int launch_gemms(gpk_handle* h, const GemmDesc* d, int n) {
   const int force_big = gemm_force(h->prob.flags);
   for (int i = 0; i < n; ++i)
-    TRY(check_launch(launch_gemm_auto(d + i, 1, h->sc, h->s, gemm_variant(d + i, 1, force_big)), "gemm"));
+    TRY(check_launch(launch_gemm_sized(d + i, 1, h->sc, h->s, force_big), "gemm"));
   return GPK_OK;
 }
 

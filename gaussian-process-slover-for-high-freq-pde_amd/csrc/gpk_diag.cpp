@@ -320,8 +320,7 @@ int gpk_forward_field(gpk_handle* h, int32_t what, double* out, int64_t n) {
       g.A = h->Bt; g.lda = P2; g.B = h->D[1]; g.ldb = P2; g.tb = 1; g.K = P2;
     }
     g.C = tmp; g.ldc = P2; g.M = P1; g.N = P2; g.alpha = 1.0; g.epi = EPI_STORE;
-    hipError_t e = launch_gemm_auto(&g, 1, h->sc, h->s,
-                                    gemm_variant(&g, 1, gemm_force(h->prob.flags)));
+    hipError_t e = launch_gemm_sized(&g, 1, h->sc, h->s, gemm_force(h->prob.flags));
     if (e != hipSuccess) return fail(GPK_EHIP, hipGetErrorString(e));
     src = tmp;
   }
@@ -657,7 +656,7 @@ int gpk_mode_gemm(int32_t variant, int32_t k, int32_t d1, int32_t d2, int32_t d3
   auto one = [&](GemmDesc d, const double* c0_) {
     d.alpha = alpha;
     if (c0_) { d.beta = be; d.C0 = c0_; d.ldc0 = d.ldc; }
-    return launch_gemm_auto(&d, 1, nullptr, 0, gemm_variant(&d, 1, 0));
+    return launch_gemm_sized(&d, 1, nullptr, 0);
   };
   const int n23 = d2 * d3, n13 = d1 * d3, n12 = d1 * d2;
   auto launch = [&]() -> hipError_t {
@@ -716,8 +715,8 @@ int gpk_refine_panel(int32_t route, int32_t side, int32_t P, int32_t M, const do
   const RefinedSolve g = refined_solve(side, dKc, dKi, dB, dX, dW, rows, cols, nullptr);
   auto launch = [&]() -> hipError_t {
     if (route == 1) return launch_refine_panel(&f, 1, nullptr, 0);
-    hipError_t rc = launch_gemm_auto(&g.resid, 1, nullptr, 0, gemm_variant(&g.resid, 1, 0));
-    return rc == hipSuccess ? launch_gemm_auto(&g.fix, 1, nullptr, 0, gemm_variant(&g.fix, 1, 0)) : rc;
+    hipError_t rc = launch_gemm_sized(&g.resid, 1, nullptr, 0);
+    return rc == hipSuccess ? launch_gemm_sized(&g.fix, 1, nullptr, 0) : rc;
   };
   // (X receives the checked launch's result; the timed launches keep refining the device copy)
   hipError_t e = launch();

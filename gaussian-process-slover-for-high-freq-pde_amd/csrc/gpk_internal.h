@@ -404,11 +404,11 @@ struct GemmDesc {
   int vscale, vscale2;      // multiply alpha / alpha2 by v (StepScalars) when 1
   double* red;              // per-tile partial sums, [tiles] (nullable)
   double* red2; const double* Q1; const double* Q2;  // EPI_RESID: sum Q1*Q2 (quad term)
-  const double* gate; int ngate;  // refinement gate (gate_open); nullptr = always store
+  const double* gate;       // refinement gate (gate_open); nullptr = always store
+  int tag;                  // step stage (timeline probes only, gpk_trace.h)
   // side output (EPI_STORE): Y = 0.5 Ys + v C, with C the stored value -- the G_K operand
   // (S/2 + v X) formed where X is produced, so the G_K stage is a single product
   double* Y; const double* Ys; int ldy;
-  int tag;                  // step stage (timeline probes only, gpk_trace.h)
   // 128x128-tile kernel only: a partial product added to alpha op(A) op(B) before the epilogue
   // (the first pass of a dual product, launch_gemm_auto's split)
   const double* Cp; int ldcp;
@@ -435,22 +435,27 @@ constexpr int GEMM_MAX_BATCH = 4;
 struct GemmBatch {  // passed by value (kernarg): no dependent descriptor load before the operands
   GemmDesc d[GEMM_MAX_BATCH];
 };
-// small = 1: 16x16-tile latency kernel (max_tiles counts 16x16 tiles); 0: 32x32 LDS-tiled.
-// descs: HOST array of ndesc <= GEMM_MAX_BATCH descriptors (copied into the kernel arguments).
-hipError_t launch_gemm_batch(const GemmDesc* descs, int ndesc, int max_tiles,
-                             const StepScalars* sc, hipStream_t s, int small);
 // heuristic: use the 16x16 latency kernel while the whole stage has few enough tiles
 inline bool gemm_use_small(long tiles16_total) { return tiles16_total <= 16384; }
-enum { GEMM_TILED32 = 0, GEMM_SMALL = 1, GEMM_BIG = 2, GEMM_HUGE = 3 };
+// the kernels of launch_gemm_auto (the C ABI's variant numbers, gpk/_lib.py; 0 there = by size)
+enum { GEMM_SMALL = 1, GEMM_BIG = 2, GEMM_HUGE = 3 };
+// side of a variant's square output tile
+constexpr int gemm_tile_dim(int variant) { return variant == GEMM_SMALL ? 16 : variant == GEMM_BIG ? 64 : 128; }
 // 128x128 tiles once a launch has this many of them (one round over the 256 CUs)
 constexpr long GEMM_HUGE_MIN_TILES = 256;
 // variant for a batch (force_big 1: the 64x64 throughput kernel, 2: the 128x128 one, regardless
-// of size), tiles of a
-// descriptor under a variant (= the entries its red/red2 partials fill), and the launcher
+// of size), tiles of a descriptor under a variant (= the entries its red/red2 partials fill),
+// and the launcher (descs: HOST array of ndesc <= GEMM_MAX_BATCH descriptors, copied into the
+// kernel arguments; an unknown variant is hipErrorInvalidValue)
 int gemm_variant(const GemmDesc* descs, int ndesc, int force_big);
 int gemm_tiles(const GemmDesc& d, int variant);
 hipError_t launch_gemm_auto(const GemmDesc* descs, int ndesc, const StepScalars* sc, hipStream_t s,
                             int variant);
+// ... at the variant gemm_variant picks for the batch
+inline hipError_t launch_gemm_sized(const GemmDesc* descs, int ndesc, const StepScalars* sc, hipStream_t s,
+                                    int force_big = 0) {
+  return launch_gemm_auto(descs, ndesc, sc, s, gemm_variant(descs, ndesc, force_big));
+}
 
 // Slab-batched product (gemm.hip gemm_slab_kernel): for every slab b < nb,
 // C_b = alpha A B_b + beta C0_b with A M x K shared by all slabs, B_b = B + b sB (K x N),
@@ -515,7 +520,7 @@ struct GemvDesc {
   const double* U0;  // Allen-Cahn offset: the term uses U + U0 (nullable)
   double* red;       // per-block partials
   double* red2; const double* Q1; const double* Q2;  // per-block partials of sum Q1*Q2
-  const double* gate; int ngate;
+  const double* gate;
   // class operand (cid != nullptr, A unused): A[i][j] = cv[cid[i*lda + j]], ident = 1 (K): + cdiag
   // (the jitter) on i == j and the identity on pads (cid < 0); ident = 0 (D): zero on pads --
   // bitwise the Kc / D matrices the inverse launch would have written, read as int32 ids (half

@@ -179,7 +179,7 @@ void build_refine(gpk_handle3* h) {
 }
 
 int launch_descs(gpk_handle3* h, const std::vector<GemmDesc>& d) {
-  return check_launch(launch_gemm_auto(d.data(), (int)d.size(), h->sc, h->s, gemm_variant(d.data(), (int)d.size(), 0)),
+  return check_launch(launch_gemm_sized(d.data(), (int)d.size(), h->sc, h->s),
                       "gemm");
 }
 

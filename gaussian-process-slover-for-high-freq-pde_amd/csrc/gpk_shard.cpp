@@ -131,9 +131,8 @@ struct LocalComm : ShardComm {
   bool capturable() const override { return false; }
 };
 
-int tile_rows(int variant) { return variant == GEMM_SMALL ? 16 : variant == GEMM_BIG ? 64 : variant == GEMM_HUGE ? 128 : 32; }
 int tile_cols_count(const GemmDesc& d, int variant) {
-  const int tc = tile_rows(variant);
+  const int tc = gemm_tile_dim(variant);
   return (d.N + tc - 1) / tc;
 }
 
@@ -153,7 +152,7 @@ GemmDesc slice_rows(const GemmDesc& d, int r0, int rows, int variant) {
     s.Y = d.Y + (size_t)r0 * d.ldy;
     s.Ys = d.Ys + (size_t)r0 * d.ldy;
   }
-  const size_t toff = (size_t)(r0 / tile_rows(variant)) * tile_cols_count(d, variant);
+  const size_t toff = (size_t)(r0 / gemm_tile_dim(variant)) * tile_cols_count(d, variant);
   if (d.red) s.red = d.red + toff;
   if (d.red2) s.red2 = d.red2 + toff;
   return s;
@@ -236,7 +235,7 @@ int build_shard(gpk_handle* h) {
     }
     int variant = gemm_variant(tmp.data(), n, force);
     for (int i = 0; i < n; ++i)
-      while (mode_of(k, full[i]) == 'r' && (full[i].M == P1 ? h->h1 : h->h2) % tile_rows(variant) != 0)
+      while (mode_of(k, full[i]) == 'r' && (full[i].M == P1 ? h->h1 : h->h2) % gemm_tile_dim(variant) != 0)
         variant = variant == GEMM_HUGE ? GEMM_BIG : GEMM_SMALL;
     h->sst[k].off = (int)h->sdescs.size();
     h->sst[k].n = n;

@@ -5,7 +5,8 @@ code/model_GP_solver_advection.py:104-119: the K^{-1}-applications, the D-produc
 residual and the gradient products of the reverse pass) is one of these GEMMs.  Checked here
 for each kernel (16x16 latency tiles, 64x64 tiles, the pipelined 128x128 tile of
 gemm_tile_dev.h), every transpose signature, edge tiles (M, N multiples of 32 but not of 128),
-the dual product (two passes on the 128x128 tile, in mixed signatures, alpha = 0 included),
+the dual product (two passes on the 128x128 tile, in mixed signatures, alpha = 0 included;
+every signature of the 16x16 kernel's one-block path),
 beta C0 and the in-place update C += op(A) op(B).
 
 Bar: max |C - C_ref| <= 64 K eps max(|A|)max(|B|) -- fp64 summation of K products of bounded
@@ -49,9 +50,10 @@ def test_single_product(variant, ta, tb, M, N, K):
 
 @pytest.mark.parametrize("sig", [(0, 0, 0, 1), (1, 0, 0, 0), (0, 1, 1, 1), (1, 1, 0, 0)])
 @pytest.mark.parametrize("alpha", [1.5, 0.0])
-def test_dual_product_tile128(sig, alpha):
-    """C = alpha op(A) op(B) + alpha2 op(A2) op(B2) + beta C0 on the 128x128 tile (two passes)
-    and on the 64x64 kernel (one pass), both against NumPy."""
+def test_dual_product_each_kernel(sig, alpha):
+    """C = alpha op(A) op(B) + alpha2 op(A2) op(B2) + beta C0 on the 128x128 tile (two passes),
+    on the 64x64 kernel (one pass) and on the 16x16 kernel (the waves' K quarters 32 and 64 deep:
+    both block depths of its general K loop), each against NumPy."""
     ta, tb, ta2, tb2 = sig
     M, N, K, K2 = 288, 416, 160, 224
     rng = np.random.default_rng(sum(sig) + int(alpha * 4))
@@ -61,10 +63,37 @@ def test_dual_product_tile128(sig, alpha):
     B2 = _mat(rng, *((N, K2) if tb2 else (K2, N)))
     C0 = _mat(rng, M, N)
     ref = alpha * (_op(A, ta) @ _op(B, tb)) - 0.5 * (_op(A2, ta2) @ _op(B2, tb2)) + 0.25 * C0
-    for variant in (GEMM_TILE128, GEMM_BIG):
+    for variant in (GEMM_TILE128, GEMM_BIG, GEMM_SMALL):
         C, _ = dgemm(A, B, ta=ta, tb=tb, alpha=alpha, A2=A2, B2=B2, ta2=ta2, tb2=tb2, alpha2=-0.5,
                      beta=0.25, C0=C0, variant=variant)
         assert np.abs(C - ref).max() <= _bar(K + K2, A, B) + _bar(K2, A2, B2)
+
+
+@pytest.mark.parametrize("dual", [True, False])
+def test_small_kernel_one_block_signatures(dual):
+    """The 16x16 kernel at K = K2 = 256, one 64-deep block per wave and product (its one-round-trip
+    path, one instantiation per transpose signature): all 16 dual signatures, and the 4 single
+    ones on the kernel built without a second product.  M = 32, N = 64: 8 tiles, dealt XCD-major."""
+    M, N, K = 32, 64, 256
+    rng = np.random.default_rng(17 + dual)
+    X = {(r, c): _mat(rng, r, c) for r, c in ((M, K), (K, M), (K, N), (N, K))}
+    X2 = {k: _mat(rng, *k) for k in X}
+    C0 = _mat(rng, M, N)
+    for code in range(16 if dual else 4):
+        ta, tb, ta2, tb2 = code & 1, (code >> 1) & 1, (code >> 2) & 1, (code >> 3) & 1
+        A, B = X[(K, M) if ta else (M, K)], X[(N, K) if tb else (K, N)]
+        ref = 1.5 * (_op(A, ta) @ _op(B, tb)) + 0.25 * C0
+        bar = _bar(K, A, B)
+        second = {}
+        if dual:
+            A2, B2 = X2[(K, M) if ta2 else (M, K)], X2[(N, K) if tb2 else (K, N)]
+            ref = ref - 0.5 * (_op(A2, ta2) @ _op(B2, tb2))
+            bar += _bar(K, A2, B2)
+            second = dict(A2=A2, B2=B2, ta2=ta2, tb2=tb2, alpha2=-0.5)
+        C, _ = dgemm(A, B, ta=ta, tb=tb, alpha=1.5, beta=0.25, C0=C0, variant=GEMM_SMALL, **second)
+        err = np.abs(C - ref).max()
+        print(f"sig {(ta, tb, ta2, tb2) if dual else (ta, tb)}: err {err:.3e} bar {bar:.3e}")
+        assert err <= bar, (ta, tb, ta2, tb2)
 
 
 @pytest.mark.parametrize("variant", [GEMM_BIG, GEMM_TILE128])

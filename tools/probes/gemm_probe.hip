@@ -105,7 +105,7 @@ int main() {
         GemmDesc d{};
         d.A = A; d.lda = n; d.B = src; d.ldb = n; d.C = dst; d.ldc = n; d.M = n; d.N = n; d.K = n;
         d.alpha = 1.0; d.epi = EPI_STORE;
-        CHK(launch_gemm_batch(&d, 1, (n / 16) * (n / 16), sc, s, 1));
+        CHK(launch_gemm_auto(&d, 1, sc, s, GEMM_SMALL));
       } else if (v == 1) {
         hipLaunchKernelGGL(gemm_lds16<256>, dim3((n / 16) * (n / 16)), dim3(256), 0, s, A, src, dst, n);
       } else if (v == 2) {
@@ -131,7 +131,7 @@ int main() {
     GemmDesc d{};
     d.A = A; d.lda = n; d.B = B; d.ldb = n; d.C = C0; d.ldc = n; d.M = n; d.N = n; d.K = n;
     d.alpha = 1.0; d.epi = EPI_STORE;
-    CHK(launch_gemm_batch(&d, 1, (n / 16) * (n / 16), sc, s, 1));
+    CHK(launch_gemm_auto(&d, 1, sc, s, GEMM_SMALL));
     hipLaunchKernelGGL(gemm_lds16<256>, dim3((n / 16) * (n / 16)), dim3(256), 0, s, A, B, C1, n);
     std::vector<double> r0(h.size()), r1(h.size());
     CHK(hipMemcpy(r0.data(), C0, 8 * h.size(), hipMemcpyDeviceToHost));
