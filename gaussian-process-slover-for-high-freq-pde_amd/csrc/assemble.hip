@@ -83,6 +83,8 @@ __global__ __launch_bounds__(256) void assemble_kernel(AssembleBatch b, int q) {
 
   __shared__ double sw[QMAX], sa[QMAX], so[QMAX], sol[QMAX];
   __shared__ double pk[4][64], pd[4][64];
+  constexpr bool BOTH = DERIV == DERIV_BOTH;  // pd: the order-2 field, pd1: the order-1 field
+  __shared__ double pd1[BOTH ? 4 : 1][64];    // (no reference in the other modes: not allocated)
   if (t < q) axis_component(b.prep, axis, q, t, sw[t], sa[t], so[t], sol[t]);
   if (blockIdx.x == 0 && axis == 0) publish_prep(b.prep, q);
   __syncthreads();
@@ -97,18 +99,21 @@ __global__ __launch_bounds__(256) void assemble_kernel(AssembleBatch b, int q) {
   const int e = t & 63, g = t >> 6;
   const int i = I * 32 + 2 * sub + (e >> 5), j = J * 32 + (e & 31);
   const bool real = i < A.n && j < A.n;
-  double diff = 0.0, kv = 0.0, dv = 0.0;
+  double diff = 0.0, kv = 0.0, dv = 0.0, dv1 = 0.0;
   if (real) {
     diff = A.x[i] - A.x[j];
-    eval_kd_part<MATERN, COS, DERIV>(diff, sw, sa, so, sol, g, 4, q, kv, dv);
+    if constexpr (BOTH) eval_kd_part<MATERN, COS>(diff, sw, sa, so, sol, g, 4, q, kv, dv, dv1);
+    else eval_kd_part<MATERN, COS, DERIV>(diff, sw, sa, so, sol, g, 4, q, kv, dv);
   }
   pk[g][e] = kv;
   pd[g][e] = dv;
+  if constexpr (BOTH) pd1[g][e] = dv1;
   __syncthreads();
   if (g != 0) return;
   if (real) {
     kv = (pk[0][e] + pk[1][e]) + (pk[2][e] + pk[3][e]);
     dv = (pd[0][e] + pd[1][e]) + (pd[2][e] + pd[3][e]);
+    if constexpr (BOTH) dv1 = (pd1[0][e] + pd1[1][e]) + (pd1[2][e] + pd1[3][e]);
     if (i == j) kv += A.jitter;
   } else {
     kv = (i == j) ? 1.0 : 0.0;  // padded block is the identity
@@ -120,11 +125,15 @@ __global__ __launch_bounds__(256) void assemble_kernel(AssembleBatch b, int q) {
   if (A.Kc) A.Kc[(size_t)i * A.p + j] = kv;
   if (DERIV == 2) A.D[(size_t)i * A.p + j] = dv;
   if (DERIV == 1) A.D[(size_t)i * A.p + j] = real ? s_ij * dv : 0.0;
+  // each field reduced on its own, then the weighted block: the symmetric part mirrors as it is,
+  // the antisymmetric part with its sign, so D is neither
+  if constexpr (BOTH) A.D[(size_t)i * A.p + j] = real ? A.c2 * dv + A.c1 * (s_ij * dv1) : 0.0;
   if (I != J) {
     A.K[(size_t)j * A.p + i] = kv;
     if (A.Kc) A.Kc[(size_t)j * A.p + i] = kv;
     if (DERIV == 2) A.D[(size_t)j * A.p + i] = dv;
     if (DERIV == 1) A.D[(size_t)j * A.p + i] = real ? s_ji * dv : 0.0;
+    if constexpr (BOTH) A.D[(size_t)j * A.p + i] = real ? A.c2 * dv + A.c1 * (s_ji * dv1) : 0.0;
   }
   if (tile == 0 && b.pivot_x >= 0) {  // release this sub-block of tile (0,0) to pivot0
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // (only wave 0 stored)
@@ -481,6 +490,8 @@ static void launch_assemble_t(const AssembleBatch& b, int naxes, int maxt, int q
     hipLaunchKernelGGL((assemble_kernel<MATERN, COS, 2>), grid, dim3(256), 0, s, b, q);
   else if (deriv == 1)
     hipLaunchKernelGGL((assemble_kernel<MATERN, COS, 1>), grid, dim3(256), 0, s, b, q);
+  else if (deriv == DERIV_BOTH)
+    hipLaunchKernelGGL((assemble_kernel<MATERN, COS, DERIV_BOTH>), grid, dim3(256), 0, s, b, q);
   else
     hipLaunchKernelGGL((assemble_kernel<MATERN, COS, 0>), grid, dim3(256), 0, s, b, q);
 }
@@ -501,6 +512,11 @@ hipError_t launch_assemble(int kind, int q, const AssembleArgs* a, int naxes, co
         (a[k].cls.ncls > 0) != (a[0].cls.ncls > 0))
       return hipErrorInvalidValue;
   int deriv = a[0].deriv;
+  // one mode per launch (DERIV_BOTH carries its weights per axis); the class path stores one dval
+  // per class, so it has no DERIV_BOTH
+  for (int k = 0; k < naxes; ++k)
+    if ((a[k].deriv == DERIV_BOTH) != (deriv == DERIV_BOTH) || (deriv == DERIV_BOTH && a[k].cls.ncls > 0))
+      return hipErrorInvalidValue;
   if (a[0].cls.ncls > 0) {  // class path: every 32x32 tile of the full matrix, one per workgroup
     int maxc = 0, maxtiles = 0;
     for (int k = 0; k < naxes; ++k) {

@@ -10,7 +10,7 @@
 //                   gpk_step, gpk_prepare, gpk_loss_grad
 //   gpk_shard.cpp   the row-sharded step and its collective backends (the only user of RCCL)
 //   gpk_diag.cpp    measurement and diagnostic entry points (reached from no solver entry point),
-//                   gpk_mode_gemm, gpk_refine_panel and gpk_point_contract among them
+//                   gpk_mode_gemm, gpk_refine_panel, gpk_point_contract and gpk_assemble_pairs among them
 //   gpk_kron3.cpp   the 3-axis solver (step, predictions, scattered points, criterion, Adam state)
 #pragma once
 #include <hip/hip_runtime.h>

@@ -184,6 +184,12 @@ struct ClassArgs {
   double* part;          // [2][nchunk][ncls]
 };
 
+// Derivative mode of an assembly or contraction launch: the order of its one derivative field
+// (1 or 2), or both fields from one exp / sincos set per mixture component, combined with the
+// axis's weights: D = c2 DD_x1_kappa + c1 D_x1_kappa (the 3-axis solver's mixed-order axes;
+// per-pair path only).
+constexpr int DERIV_BOTH = 3;
+
 struct AssembleArgs {
   const double* x;       // coords [n] (padded buffer ok)
   int n;                 // true size
@@ -193,7 +199,8 @@ struct AssembleArgs {
   double* K;             // [p*p]  (consumed in place by the SPD inverse)
   double* Kc;            // [p*p]  kept copy of K for iterative refinement (nullable)
   double* D;             // [p*p]
-  int deriv;             // 1 or 2 (0: K only)
+  int deriv;             // 1 or 2 (0: K only), or DERIV_BOTH
+  double c2, c1;         // DERIV_BOTH: D = c2 DD + c1 D1 (read in that mode only)
   // pivot block 0 of the SPD inverse, factored by one extra workgroup of the assembly launch
   // (nullable piv: not fused).  Same outputs as the sweep's pivot_init.
   double* piv; double* ldet; double* pst; int* status;
@@ -538,7 +545,8 @@ struct PGradArgs {
   const double* Kinv;                     // 1D mode
   const double* alpha; const double* beta; const double* R;  // 1D mode vectors
   double halfc;                           // 1D mode: 0.5*logdet flag
-  int deriv;
+  int deriv;                              // 1, 2 or DERIV_BOTH (2D per-pair path only)
+  double c2, c1;                          // DERIV_BOTH: G_D weighs c2 dDD + c1 dD1 (read in that mode only)
   double* part;                           // [nblocks * 3*QMAX]
   // DD (class path, 2D, fused tail): the derivative fields and every sum after them in
   // double-double; part holds the partials' high parts, part_lo their low parts (null: fp64)

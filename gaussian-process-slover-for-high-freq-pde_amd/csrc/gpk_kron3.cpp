@@ -19,6 +19,11 @@
 //     dL/dU = S + v sum_k c_k X_k + v (r1 + 2 r2 U + 3 r3 U^2) R + w tau scatter over the active faces.
 // gpk_create3 fills in the legacy equivalent (orders 2, weights 1.0, six faces), which multiplies
 // by alpha = 1.0 exactly and runs the launches it always ran.
+// Mixed-order axes (gpk_create3_opx, both c2_k and c1_k non-zero): the assembled block is
+// D_k = c2_k DD_k + c1_k D1_k (assembly and contraction in DERIV_BOTH, the weights in their
+// arguments) and the three GEMM weights of that axis are exactly 1.0, so every formula above holds
+// with c_k = 1 and this D_k.  Axes 1-2 share a launch when their modes are equal; two mixed axes
+// with different weights still do.  An axis with one non-zero weight is the path above, unchanged.
 // GPK_FLAG3_REFINE: every one of the eight solves (A1, A2, A3, T, S, X1, X2, X3) is followed by
 // one refinement step X += K_k^{-1} (B - K_k X) gated on the axis's pst: one fused panel launch
 // (refine_panel.hip), or two GEMMs where its panels do not fit LDS (build_refine).
@@ -43,6 +48,10 @@ struct gpk_handle3 {
   // (orders 2, weights 1, six faces; legacy_ac keeps Allen-Cahn in its own expression u(u^2 - 1))
   gpk_operator3 op{};
   int legacy_ac = 0;
+  // per axis: the assembly's / contraction's mode (op.order[k], or DERIV_BOTH on a mixed axis,
+  // where op.order[k] = 0 and op.coef[k] = 1.0, the GEMM weight) and the weights as stated
+  int mode[3] = {2, 2, 2};
+  double c2[3] = {}, c1[3] = {};
   K3Geom g{};
   int q = 0;
   long nu = 0, nparams = 0;
@@ -234,7 +243,7 @@ int enqueue_inverse3(gpk_handle3* h, int apply) {
   for (int a = 0; a < 3; ++a) {
     aa[a].x = h->x[a]; aa[a].n = g.n[a]; aa[a].p = g.p[a]; aa[a].kc = h->kc + a;
     aa[a].jitter = h->prob.jitter; aa[a].K = h->K[a]; aa[a].Kc = h->Kc[a]; aa[a].D = h->D[a];
-    aa[a].deriv = h->op.order[a];
+    aa[a].deriv = h->mode[a]; aa[a].c2 = h->c2[a]; aa[a].c1 = h->c1[a];
   }
   // (skip = 1: the constants are published by k3_prep; each workgroup derives its axis's own)
   PrepArgs p12{};
@@ -243,8 +252,8 @@ int enqueue_inverse3(gpk_handle3* h, int apply) {
   PrepArgs p3 = p12;
   p3.off_kp[0] = h->off_kp[2];
   p3.naxes = 1;
-  // (one derivative order per launch: axes 1-2 share theirs only when their orders are equal)
-  if (h->op.order[0] == h->op.order[1]) {
+  // (one derivative mode per launch: axes 1-2 share theirs only when their modes are equal)
+  if (h->mode[0] == h->mode[1]) {
     TRY(check_launch(launch_assemble(kind, q, aa, 2, p12, h->s), "assemble"));
   } else {
     PrepArgs p1 = p12, p2 = p12;
@@ -289,10 +298,11 @@ int enqueue_step3(gpk_handle3* h, int apply) {
   PGradArgs pg[3] = {};
   for (int a = 0; a < 3; ++a) {
     pg[a].x = h->x[a]; pg[a].n = g.n[a]; pg[a].p = g.p[a]; pg[a].kc = h->kc + a;
-    pg[a].GK = h->GK[a]; pg[a].GD = h->GD[a]; pg[a].deriv = h->op.order[a];
+    pg[a].GK = h->GK[a]; pg[a].GD = h->GD[a]; pg[a].deriv = h->mode[a];
+    pg[a].c2 = h->c2[a]; pg[a].c1 = h->c1[a];
     pg[a].part = h->pgpart + (size_t)a * h->bpa * 3 * QMAX;
   }
-  if (h->op.order[0] == h->op.order[1]) {
+  if (h->mode[0] == h->mode[1]) {
     TRY(check_launch(launch_pgrad(kind, q, 0, pg, 2, h->bpa, h->sc, h->s), "pgrad"));
   } else {
     TRY(check_launch(launch_pgrad(kind, q, 0, pg, 1, h->bpa, h->sc, h->s), "pgrad"));
@@ -359,8 +369,10 @@ int gpk_destroy3(gpk_handle3* h) {
 
 namespace {
 
-// gpk_create3 (op = nullptr: the legacy equation p->eq) and gpk_create3_op
-int create3(const gpk_problem3* p, const gpk_operator3* op, double freq_scale, gpk_handle3** out) {
+// gpk_create3 (op = nullptr: the legacy equation p->eq), gpk_create3_op, and gpk_create3_opx
+// (opx: op is its one-order-per-axis part, a mixed axis entered as order 0 with weight 1.0)
+int create3(const gpk_problem3* p, const gpk_operator3* op, double freq_scale, gpk_handle3** out,
+            const gpk_operator3x* opx = nullptr) {
   if (p->kind < 0 || p->kind > 3) return fail(GPK_EINVAL, "Invalid Kernel");
   if (p->q <= 0 || p->q > QMAX) return fail(GPK_EINVAL, "Q must be in [1, 64]");
   const int ns[3] = {p->n1, p->n2, p->n3};
@@ -379,6 +391,12 @@ int create3(const gpk_problem3* p, const gpk_operator3* op, double freq_scale, g
     h->op.faces = K3_ALL_FACES;
     h->legacy_ac = p->eq == GPK_ALLENCAHN;
     if (h->legacy_ac) { h->op.react[0] = -1.0; h->op.react[2] = 1.0; }  // what gpk_operator_info3 reports
+  }
+  for (int a = 0; a < 3; ++a) {
+    const bool mixed = h->op.order[a] == 0;
+    h->mode[a] = mixed ? DERIV_BOTH : h->op.order[a];
+    h->c2[a] = mixed ? opx->c2[a] : h->op.order[a] == 2 ? h->op.coef[a] : 0.0;
+    h->c1[a] = mixed ? opx->c1[a] : h->op.order[a] == 1 ? h->op.coef[a] : 0.0;
   }
   h->dev = p->device;
   h->q = p->q;
@@ -498,7 +516,44 @@ int gpk_create3_op(const gpk_problem3* p, const gpk_operator3* op, double freq_s
 
 int gpk_operator_info3(const gpk_handle3* h, gpk_operator3* out) {
   if (!h || !out) return fail(GPK_EINVAL, "NULL argument");
+  for (int a = 0; a < 3; ++a)
+    if (h->mode[a] == DERIV_BOTH)
+      return fail(GPK_EINVAL, "gpk_operator_info3: the handle has a mixed-order axis (gpk_operator_info3x states it)");
   *out = h->op;
+  return GPK_OK;
+}
+
+int gpk_create3_opx(const gpk_problem3* p, const gpk_operator3x* op, double freq_scale, gpk_handle3** out) {
+  if (!p || !op || !out) return fail(GPK_EINVAL, "NULL argument");
+  *out = nullptr;
+  if (p->eq != GPK_POISSON)
+    return fail(GPK_EINVAL, "gpk_create3_opx: eq must be GPK_POISSON (the operator states the equation)");
+  for (int a = 0; a < 3; ++a)
+    if (!std::isfinite(op->c2[a]) || !std::isfinite(op->c1[a]) || !std::isfinite(op->react[a]))
+      return fail(GPK_EINVAL, "gpk_create3_opx: c2, c1 and react must be finite");
+  if (op->faces < 1 || op->faces > K3_ALL_FACES)
+    return fail(GPK_EINVAL, "gpk_create3_opx: faces must be in 1..63");
+  // one non-zero weight: that order with that weight (gpk_create3_op's handle); none: order 2 with
+  // weight 0; both: a mixed axis, its weights in the assembled block and 1.0 on its GEMMs
+  gpk_operator3 o{};
+  for (int a = 0; a < 3; ++a) {
+    const bool has2 = op->c2[a] != 0.0, has1 = op->c1[a] != 0.0;
+    o.order[a] = has2 && has1 ? 0 : has1 ? 1 : 2;
+    o.coef[a] = has2 && has1 ? 1.0 : has1 ? op->c1[a] : op->c2[a];
+    o.react[a] = op->react[a];
+  }
+  o.faces = op->faces;
+  return create3(p, &o, freq_scale, out, op);
+}
+
+int gpk_operator_info3x(const gpk_handle3* h, gpk_operator3x* out) {
+  if (!h || !out) return fail(GPK_EINVAL, "NULL argument");
+  for (int a = 0; a < 3; ++a) {
+    out->c2[a] = h->c2[a];
+    out->c1[a] = h->c1[a];
+    out->react[a] = h->op.react[a];
+  }
+  out->faces = h->op.faces;
   return GPK_OK;
 }
 

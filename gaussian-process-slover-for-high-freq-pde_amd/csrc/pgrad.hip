@@ -416,6 +416,11 @@ __global__ __launch_bounds__(256) void pgrad_kernel(PGradBatch b, int q,
   if (b.shard_n > 1 && tile % b.shard_n != b.shard_rank) return;
 
   __shared__ double sd[PAIRS], swk[PAIRS], swd[PAIRS];
+  // DERIV_BOTH: swd weighs the order-2 field, swd1 the order-1 field (no reference in the other
+  // modes: not allocated)
+  constexpr bool BOTH = DERIV == DERIV_BOTH;
+  static_assert(!BOTH || (!MODE1D && !CLS && !DD), "DERIV_BOTH: the 2D per-pair contraction only");
+  __shared__ double swd1[BOTH ? PAIRS : 1];
   __shared__ double sw[QMAX], sa[QMAX], so[QMAX], sol[QMAX];
   __shared__ double sacc[8][3][32];
   const int t = threadIdx.x;
@@ -463,7 +468,7 @@ __global__ __launch_bounds__(256) void pgrad_kernel(PGradBatch b, int q,
     while (I * (I + 1) / 2 > tile) --I;
     const int J = tile - I * (I + 1) / 2;
     const int i = I * 32 + chunk * (PAIRS / 32) + (t >> 5), j = J * 32 + (t & 31);
-    double d = 0.0, wk = 0.0, wd = 0.0;
+    double d = 0.0, wk = 0.0, wd = 0.0, wd1 = 0.0;
     if (i < A.n && j < A.n) {
       const double diff = A.x[i] - A.x[j];
       d = fabs(diff);
@@ -494,10 +499,16 @@ __global__ __launch_bounds__(256) void pgrad_kernel(PGradBatch b, int q,
         wk = gkij + gkji;
         wd = gdij + gdji;
       }
+      // D = c2 DD + c1 s D1: the order-2 field takes c2 G_D as it is, the order-1 field c1 s G_D
+      if constexpr (BOTH) {
+        wd1 = A.c1 * (I == J ? sij * gdij : sij * gdij + sji * gdji);
+        wd = A.c2 * wd;
+      }
     }
     sd[t] = d;
     swk[t] = wk;
     swd[t] = wd;
+    if constexpr (BOTH) swd1[t] = wd1;
   }
   __syncthreads();
   if (TR_FIRST) TR_HI(SLOT_PG_STAGED);
@@ -513,7 +524,9 @@ __global__ __launch_bounds__(256) void pgrad_kernel(PGradBatch b, int q,
       const double a = sa[c], om = so[c], oml = sol[c];
       for (int e = g; e < NP; e += 8) {
         const double wk = swk[e], wd = swd[e];
-        if (wk == 0.0 && wd == 0.0) continue;
+        double wd1 = 0.0;
+        if constexpr (BOTH) wd1 = swd1[e];
+        if (wk == 0.0 && wd == 0.0 && wd1 == 0.0) continue;
         const double d = sd[e];
         if constexpr (DD) {
           dd::D fw, fl, ff, dw, dl, df;
@@ -534,6 +547,15 @@ __global__ __launch_bounds__(256) void pgrad_kernel(PGradBatch b, int q,
           const double c2f = -2.0 * TWO_PI * om * C + TWO_PI * om * om * d * S;
           double fw = m0 * c0, fl = m0l * c0, ff = m0 * c0f;
           double dw, dl, df;
+          if constexpr (BOTH) {  // both orders from the shared m*, c0..c2, c*f
+            const double dw2 = m2 * c0 + 2.0 * m1 * c1 + m0 * c2, dw1 = m1 * c0 + m0 * c1;
+            const double dl2 = m2l * c0 + 2.0 * m1l * c1 + m0l * c2, dl1 = m1l * c0 + m0l * c1;
+            const double df2 = m2 * c0f + 2.0 * m1 * c1f + m0 * c2f, df1 = m1 * c0f + m0 * c1f;
+            accw += wk * fw + wd * dw2 + wd1 * dw1;
+            accl += wk * fl + wd * dl2 + wd1 * dl1;
+            accf += wk * ff + wd * df2 + wd1 * df1;
+            continue;
+          }
           if (DERIV == 2) {
             dw = m2 * c0 + 2.0 * m1 * c1 + m0 * c2;
             dl = m2l * c0 + 2.0 * m1l * c1 + m0l * c2;
@@ -546,6 +568,9 @@ __global__ __launch_bounds__(256) void pgrad_kernel(PGradBatch b, int q,
           accw += wk * fw + wd * dw;
           accl += wk * fl + wd * dl;
           accf += wk * ff + wd * df;
+        } else if constexpr (BOTH) {
+          accw += wk * m0 + wd * m2 + wd1 * m1;
+          accl += wk * m0l + wd * m2l + wd1 * m1l;
         } else {
           const double dw = DERIV == 2 ? m2 : m1, dl = DERIV == 2 ? m2l : m1l;
           accw += wk * m0 + wd * dw;
@@ -648,6 +673,9 @@ static void launch_pg_c(const PGradBatch& b, int naxes, int bpa, int q, int deri
     hipLaunchKernelGGL((pgrad_kernel<MATERN, COS, 2, true, CLS>), grid, dim3(256), 0, s, b, q, sc);
   } else if (deriv == 2) {
     hipLaunchKernelGGL((pgrad_kernel<MATERN, COS, 2, false, CLS>), grid, dim3(256), 0, s, b, q, sc);
+  } else if (deriv == DERIV_BOTH) {  // (per-pair only: launch_pgrad refuses it on the class path)
+    if constexpr (!CLS)
+      hipLaunchKernelGGL((pgrad_kernel<MATERN, COS, DERIV_BOTH, false, false>), grid, dim3(256), 0, s, b, q, sc);
   } else {
     hipLaunchKernelGGL((pgrad_kernel<MATERN, COS, 1, false, CLS>), grid, dim3(256), 0, s, b, q, sc);
   }
@@ -703,6 +731,11 @@ hipError_t launch_pgrad(int kind, int q, int mode1d, const PGradArgs* a, int nax
                           shard_n > 1))
     return hipErrorInvalidValue;
   int deriv = a[0].deriv;
+  // one mode per launch (DERIV_BOTH carries its weights per axis): 2D per-pair contraction only
+  for (int k = 0; k < naxes; ++k)
+    if ((a[k].deriv == DERIV_BOTH) != (deriv == DERIV_BOTH) ||
+        (deriv == DERIV_BOTH && (a[k].cls.ncls > 0 || mode1d)))
+      return hipErrorInvalidValue;
   switch (kind) {
     case SE_COS: launch_pg_t<false, true>(b, naxes, blocks_per_axis, q, deriv, mode1d, sc, s); break;
     case MATERN52_COS: launch_pg_t<true, true>(b, naxes, blocks_per_axis, q, deriv, mode1d, sc, s); break;

@@ -50,6 +50,36 @@ __device__ __forceinline__ void eval_kd_part(double diff, const double* w, const
   D = dv;  // unsigned: the D_x1 sign s_ij is applied by the caller
 }
 
+// The two-output form (DERIV_BOTH): the order-2 and the order-1 partial sums from the same m0, m1,
+// m2, S, C per component -- one exp / sincos set for both fields.  Each sum is the expression the
+// one-output form adds at that order; both are unsigned.
+template <bool MATERN, bool COS>
+__device__ __forceinline__ void eval_kd_part(double diff, const double* w, const double* a,
+                                             const double* om, const double* oml, int c0, int cs,
+                                             int q, double& K, double& D2, double& D1) {
+  double d = fabs(diff);
+  double k = 0.0, dv2 = 0.0, dv1 = 0.0;
+  for (int c = c0; c < q; c += cs) {
+    double m0, m1, m2;
+    radial<MATERN>(d, a[c], m0, m1, m2);
+    if (COS) {
+      double S, C;
+      phase_sincos(om[c], oml[c], d, S, C);
+      double o = om[c];
+      k += w[c] * (m0 * C);
+      dv2 += w[c] * (m2 * C - 2.0 * m1 * (o * S) - m0 * (o * o * C));
+      dv1 += w[c] * (m1 * C - m0 * (o * S));
+    } else {
+      k += w[c] * m0;
+      dv2 += w[c] * m2;
+      dv1 += w[c] * m1;
+    }
+  }
+  K = k;
+  D2 = dv2;
+  D1 = dv1;
+}
+
 // K and the signed derivative field at one pair (cross_kernel, pairs_kernel, point_eval.hip): all
 // q components in order, the D_x1 sign applied.
 template <bool MATERN, bool COS, int DERIV>

@@ -93,6 +93,13 @@ class gpk_operator3(ctypes.Structure):
     ]
 
 
+class gpk_operator3x(ctypes.Structure):
+    _fields_ = [
+        ("c2", ctypes.c_double * 3), ("c1", ctypes.c_double * 3), ("react", ctypes.c_double * 3),
+        ("faces", ctypes.c_int32),
+    ]
+
+
 EXPORTS = {
     "gpk_abi_version": ([], ctypes.c_int),
     "gpk_last_error": ([], ctypes.c_char_p),
@@ -151,6 +158,9 @@ EXPORTS = {
     "gpk_create3_op": ([ctypes.POINTER(gpk_problem3), ctypes.POINTER(gpk_operator3), ctypes.c_double,
                         ctypes.POINTER(ctypes.c_void_p)], ctypes.c_int),
     "gpk_operator_info3": ([ctypes.c_void_p, ctypes.POINTER(gpk_operator3)], ctypes.c_int),
+    "gpk_create3_opx": ([ctypes.POINTER(gpk_problem3), ctypes.POINTER(gpk_operator3x), ctypes.c_double,
+                         ctypes.POINTER(ctypes.c_void_p)], ctypes.c_int),
+    "gpk_operator_info3x": ([ctypes.c_void_p, ctypes.POINTER(gpk_operator3x)], ctypes.c_int),
     "gpk_destroy3": ([ctypes.c_void_p], ctypes.c_int),
     "gpk_num_params3": ([ctypes.c_void_p, ctypes.POINTER(ctypes.c_int64)], ctypes.c_int),
     "gpk_set_params3": ([ctypes.c_void_p, _dp, ctypes.c_int64], ctypes.c_int),
@@ -177,6 +187,10 @@ EXPORTS = {
     "gpk_point_contract": ([ctypes.c_int32, ctypes.c_int32, _dp, ctypes.c_int32, _dp, ctypes.c_int32, _dp, _dp,
                             _dp, ctypes.c_int32, _dp, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
                             ctypes.c_int32, _dp, ctypes.c_int32, _dp], ctypes.c_int),
+    "gpk_assemble_pairs": ([ctypes.c_int32, _dp, ctypes.c_int32, _dp, _dp, _dp, ctypes.c_int32, ctypes.c_double,
+                            ctypes.c_double, ctypes.c_double, _dp, _dp], ctypes.c_int),
+    "gpk_assemble_pairs_time": ([ctypes.c_int32, _dp, ctypes.c_int32, _dp, _dp, _dp, ctypes.c_int32, ctypes.c_double,
+                                 ctypes.c_double, ctypes.c_int32, ctypes.c_int32, _dp], ctypes.c_int),
     "gpk_dgemm": ([ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_double, _dp,
                    ctypes.c_int32, ctypes.c_int32, _dp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
                    ctypes.c_double, _dp, ctypes.c_int32, ctypes.c_int32, _dp, ctypes.c_int32, ctypes.c_int32,
@@ -318,3 +332,29 @@ def point_contract(kind, t, x, paras, T, C=1, sp=None, sj=None, sc=1, deriv=0, i
                                     lw.size, dptr(T), sp, sj, int(sc), C, dptr(out), int(iters),
                                     ctypes.byref(us)))
     return out, (us.value if iters else None)
+
+
+def assemble_pairs(kind, x, paras, jitter=0.0, c2=1.0, c1=0.0):
+    """The step's per-pair assembly kernel on one axis (gpk_assemble_pairs): (K, D), both (n, n).
+    c1 == 0: D = DD_x1_kappa; c2 == 0: D = D_x1_kappa (both unweighted, as the step assembles them);
+    otherwise the mixed block c2 DD_x1_kappa + c1 D_x1_kappa."""
+    x = f64(x).reshape(-1)
+    lw, ll, fr = (f64(paras[k]).reshape(-1) for k in ("log-w", "log-ls", "freq"))
+    n = x.size
+    K, D = np.empty((max(n, 1), max(n, 1))), np.empty((max(n, 1), max(n, 1)))
+    k = KIND_IDS[kind] if isinstance(kind, str) else int(kind)
+    check(load().gpk_assemble_pairs(k, dptr(x), n, dptr(lw), dptr(ll), dptr(fr), lw.size, float(jitter),
+                                    float(c2), float(c1), dptr(K), dptr(D)))
+    return K, D
+
+
+def assemble_pairs_time(kind, x, paras, c2=1.0, c1=0.0, split=False, iters=200):
+    """Mean device time in us of the per-pair assembly launch (gpk_assemble_pairs_time): the mode
+    c2 and c1 select, or with split modes 2 and 1 as two launches."""
+    x = f64(x).reshape(-1)
+    lw, ll, fr = (f64(paras[k]).reshape(-1) for k in ("log-w", "log-ls", "freq"))
+    us = ctypes.c_double()
+    k = KIND_IDS[kind] if isinstance(kind, str) else int(kind)
+    check(load().gpk_assemble_pairs_time(k, dptr(x), x.size, dptr(lw), dptr(ll), dptr(fr), lw.size, float(c2),
+                                         float(c1), int(bool(split)), int(iters), ctypes.byref(us)))
+    return us.value

@@ -172,6 +172,76 @@ def solution_3d_op(equation):
     return _OP3D[equation]()
 
 
+class Operator3X:
+    """What a gpk_create3_opx handle solves (include/gpk.h gpk_operator3x): sum_k (c2[k] d^2 u /
+    dx_k^2 + c1[k] du / dx_k) + react[0] u + react[1] u^2 + react[2] u^3 = f, faces as Operator3.
+    An axis with both weights non-zero is a mixed axis; with one, Operator3's order 2 or 1."""
+
+    __slots__ = ("c2", "c1", "react", "faces")
+
+    def __init__(self, c2, c1, react=(0.0, 0.0, 0.0), faces=63):
+        self.c2 = tuple(float(c) for c in c2)
+        self.c1 = tuple(float(c) for c in c1)
+        self.react = tuple(float(r) for r in react)
+        self.faces = int(faces)
+        if len(self.c2) != 3 or len(self.c1) != 3 or len(self.react) != 3:
+            raise ValueError("c2, c1 and react have three entries each")
+
+    @classmethod
+    def of(cls, value):
+        """An Operator3X from an Operator3X or a dict of its fields."""
+        if isinstance(value, cls):
+            return value
+        return cls(value["c2"], value["c1"], value.get("react", (0.0, 0.0, 0.0)), value.get("faces", 63))
+
+    @property
+    def mixed(self):
+        """Per axis: both weights non-zero."""
+        return tuple(a != 0.0 and b != 0.0 for a, b in zip(self.c2, self.c1))
+
+    def as_dict(self):
+        return {"c2": self.c2, "c1": self.c1, "react": self.react, "faces": self.faces}
+
+    def __eq__(self, other):
+        return isinstance(other, Operator3X) and self.as_dict() == other.as_dict()
+
+    def __repr__(self):
+        return "Operator3X(c2=%r, c1=%r, react=%r, faces=%d)" % (self.c2, self.c1, self.react, self.faces)
+
+
+# Convection-diffusion, u_t + beta . grad u - nu lap u = f: second- and first-order terms on the
+# same axis (gpk_create3_opx).  nu and beta are fixed here, once, for both entries.
+_CD_NU, _CD_BETA = 0.05, (1.0, 0.5, 0.25)
+
+
+def _convdiff_t_sin():
+    # u = e^{-t} sin(2x) sin(3y):  u_t + b1 u_x + b2 u_y - nu (u_xx + u_yy)
+    #   = (13 nu - 1) u + e^{-t} (2 b1 cos(2x) sin(3y) + 3 b2 sin(2x) cos(3y))
+    b1, b2 = _CD_BETA[:2]
+    u = lambda x, y, t: np.exp(-t) * s_(2 * x) * s_(3 * y)
+    f = lambda x, y, t: ((13.0 * _CD_NU - 1.0) * u(x, y, t)
+                         + np.exp(-t) * (2.0 * b1 * c_(2 * x) * s_(3 * y) + 3.0 * b2 * s_(2 * x) * c_(3 * y)))
+    return u, f, Operator3X((-_CD_NU, -_CD_NU, 0.0), (b1, b2, 1.0), faces=NO_FINAL_FACE)
+
+
+def _convdiff_3d_sin():
+    # steady, u = sin(2x) sin(3y) sin(z):  beta . grad u - nu lap u = beta . grad u + 14 nu u
+    b1, b2, b3 = _CD_BETA
+    u = lambda x, y, z: s_(2 * x) * s_(3 * y) * s_(z)
+    f = lambda x, y, z: (2.0 * b1 * c_(2 * x) * s_(3 * y) * s_(z) + 3.0 * b2 * s_(2 * x) * c_(3 * y) * s_(z)
+                         + b3 * s_(2 * x) * s_(3 * y) * c_(z) + 14.0 * _CD_NU * u(x, y, z))
+    return u, f, Operator3X((-_CD_NU,) * 3, (b1, b2, b3))
+
+
+_OPX3D = {"convdiff_t-sin": _convdiff_t_sin, "convdiff_3d-sin": _convdiff_3d_sin}
+EQUATIONS_3D_OPX = list(_OPX3D)
+
+
+def solution_3d_opx(equation):
+    """(u, src, operator) of an EQUATIONS_3D_OPX entry (operator: an Operator3X)."""
+    return _OPX3D[equation]()
+
+
 def boundary_2d(u_mesh):
     """get_boundary_vals: hstack(U[0,:], U[-1,:], U[:,0], U[:,-1]) (model_GP_solver_2d.py:377-379)."""
     return np.hstack((u_mesh[0, :], u_mesh[-1, :], u_mesh[:, 0], u_mesh[:, -1]))

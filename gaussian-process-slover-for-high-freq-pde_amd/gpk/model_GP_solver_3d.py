@@ -17,6 +17,10 @@ Operator equations (equations.EQUATIONS_3D_OP: heat, transport, Helmholtz, Allen
 third axis as time where one appears) run through gpk_create3_op: DeviceSolver3(operator=...),
 GP_solver_3d_single with such an equation name, and the same CLI
 (`-equation=heat_3d-sin`), with their configs in gpk/config3d_op/.
+
+Mixed-order operator equations (equations.EQUATIONS_3D_OPX: convection-diffusion, a second- and a
+first-order term on the same axis) run through gpk_create3_opx the same way: an Operator3X as
+`operator`, `-equation=convdiff_t-sin`, configs in gpk/config3d_opx/.
 """
 import ctypes
 import os
@@ -30,7 +34,8 @@ from . import _lib, init_func, replicas, utils
 from ._lib import check, dptr, f64
 from .cli import parse_flags
 from .core import tree_flatten, tree_unflatten
-from .equations import EQUATIONS_3D, EQUATIONS_3D_OP, Operator3, solution_3d, solution_3d_op
+from .equations import (EQUATIONS_3D, EQUATIONS_3D_OP, EQUATIONS_3D_OPX, Operator3, Operator3X, solution_3d,
+                        solution_3d_op, solution_3d_opx)
 from .infras.exp_config import ExpConfig
 from .kernel_matrix import kernel_class
 from .solver_common import SolverBase
@@ -67,7 +72,8 @@ class DeviceSolver3:
         """refine: one gated refinement step after every solve of the step (GPK_FLAG3_REFINE);
         'gemm' also forces its two-GEMM route (GPK_FLAG3_REFINE_GEMM; tests, A/B).
         operator: an Operator3 (or a dict of its fields) -- the handle then solves that operator
-        (gpk_create3_op; eq must be 'poisson', the operator says everything else)."""
+        (gpk_create3_op; eq must be 'poisson', the operator says everything else); an Operator3X
+        (or a dict with 'c2' and 'c1') goes to gpk_create3_opx, which takes mixed-order axes."""
         lib = _lib.load()
         if len(xs) != 3:
             raise ValueError("three coordinate axes")
@@ -96,6 +102,11 @@ class DeviceSolver3:
         h = ctypes.c_void_p()
         if operator is None:
             check(lib.gpk_create3(ctypes.byref(p), float(freq_scale), ctypes.byref(h)))
+        elif isinstance(operator, Operator3X) or (isinstance(operator, dict) and "c2" in operator):
+            op = Operator3X.of(operator)
+            c = _lib.gpk_operator3x()
+            c.c2[:], c.c1[:], c.react[:], c.faces = op.c2, op.c1, op.react, op.faces
+            check(lib.gpk_create3_opx(ctypes.byref(p), ctypes.byref(c), float(freq_scale), ctypes.byref(h)))
         else:
             op = Operator3.of(operator)
             c = _lib.gpk_operator3()
@@ -230,6 +241,13 @@ class DeviceSolver3:
         check(_lib.load().gpk_operator_info3(self._h, ctypes.byref(c)))
         return Operator3(tuple(c.order), tuple(c.coef), tuple(c.react), c.faces)
 
+    def operator_info_x(self):
+        """The Operator3X the handle runs (gpk_operator_info3x): every 3-axis handle has one; a
+        handle with a mixed-order axis has only this form (operator_info() raises on it)."""
+        c = _lib.gpk_operator3x()
+        check(_lib.load().gpk_operator_info3x(self._h, ctypes.byref(c)))
+        return Operator3X(tuple(c.c2), tuple(c.c1), tuple(c.react), c.faces)
+
     LOSS_TERMS = ("loss", "logdet_1", "logdet_2", "logdet_3", "quad", "egap", "bgap")
 
     def loss_terms(self):
@@ -246,8 +264,9 @@ class GP_solver_3d_single(SolverBase):
 
     bvals: boundary_3d(U) of the solution; X_col = (x, y, z); src_vals: N1 x N2 x N3;
     trick_paras: {'kernel': class, 'equation': 'poisson_3d-...' | 'allencahn_3d-...' or an
-    operator equation (equations.EQUATIONS_3D_OP: its Operator3 is looked up by name, or given as
-    trick_paras['operator']; bvals keeps the six-face layout, Nb counts the active faces),
+    operator equation (equations.EQUATIONS_3D_OP / EQUATIONS_3D_OPX: its Operator3 / Operator3X is
+    looked up by name, or given as trick_paras['operator']; bvals keeps the six-face layout, Nb
+    counts the active faces),
     'llk_weight', 'logdet', 'lr', 'Q', 'freq_scale', 'refine'} (+ 'nepoch', 'tol' for train);
     'refine' (default False): DeviceSolver3's gated refinement of every solve;
     X_test = (x, y, z) test axes and u_test: M1 x M2 x M3, needed by train() and preds()."""
@@ -255,16 +274,22 @@ class GP_solver_3d_single(SolverBase):
     dim = 3
     eq_types = ("poisson_3d", "allencahn_3d")
     op_eq_types = tuple(sorted({e.split("-")[0] for e in EQUATIONS_3D_OP}))
+    opx_eq_types = tuple(sorted({e.split("-")[0] for e in EQUATIONS_3D_OPX}))
     early_stop_enabled = True
 
     def __init__(self, bvals, X_col, src_vals, jitter, trick_paras, device=0, X_test=None, u_test=None):
         self.eq_type = trick_paras["equation"].split("-")[0]
-        assert self.eq_type in self.eq_types + self.op_eq_types
+        assert self.eq_type in self.eq_types + self.op_eq_types + self.opx_eq_types
         self.operator = None
-        if trick_paras.get("operator") is not None:
-            self.operator = Operator3.of(trick_paras["operator"])
+        given = trick_paras.get("operator")
+        if isinstance(given, Operator3X) or (isinstance(given, dict) and "c2" in given):
+            self.operator = Operator3X.of(given)
+        elif given is not None:
+            self.operator = Operator3.of(given)
         elif self.eq_type in self.op_eq_types:
             self.operator = solution_3d_op(trick_paras["equation"])[2]
+        elif self.eq_type in self.opx_eq_types:
+            self.operator = solution_3d_opx(trick_paras["equation"])[2]
         self.cov_func = trick_paras["kernel"]()
         self.trick_paras = trick_paras
         self.bvals = np.asarray(bvals, np.float64)
@@ -291,18 +316,23 @@ class GP_solver_3d_single(SolverBase):
 
     def eq_residual(self, params, X_test, src_test):
         """SolverBase.eq_residual; on an operator equation sum_k c_k d^{o_k} u / dx_k^{o_k} +
-        r1 u + r2 u^2 + r3 u^3 - f from the derivative predictions."""
+        r1 u + r2 u^2 + r3 u^3 - f from the derivative predictions (an Operator3X: sum_k (c2_k d^2
+        + c1_k d) u / dx_k, zero weights skipped)."""
         op = self.operator
         if op is None:
             return SolverBase.eq_residual(self, params, X_test, src_test)
         self._sync(params)
         axes = self._test_axes(X_test)
         r = np.zeros(tuple(a.size for a in axes))
-        for k in range(3):
-            if op.coef[k] != 0.0:
+        if isinstance(op, Operator3X):
+            terms = [(k, o, w) for k in range(3) for o, w in ((2, op.c2[k]), (1, op.c1[k]))]
+        else:
+            terms = [(k, op.order[k], op.coef[k]) for k in range(3)]
+        for k, o, w in terms:
+            if w != 0.0:
                 d = [0, 0, 0]
-                d[k] = op.order[k]
-                r = r + op.coef[k] * self.dev.predict_deriv(*axes, deriv=tuple(d))
+                d[k] = o
+                r = r + w * self.dev.predict_deriv(*axes, deriv=tuple(d))
         if any(op.react):
             u = self.dev.predict_deriv(*axes, deriv=(0, 0, 0))
             r = r + op.react[0] * u + op.react[1] * u ** 2 + op.react[2] * u ** 3
@@ -396,6 +426,8 @@ def test(trick_paras, solver_cls=None):
     op = None
     if trick_paras["equation"] in EQUATIONS_3D_OP:
         u, src, op = solution_3d_op(trick_paras["equation"])
+    elif trick_paras["equation"] in EQUATIONS_3D_OPX:
+        u, src, op = solution_3d_opx(trick_paras["equation"])
     else:
         u, src = solution_3d(trick_paras["equation"])
     scale = trick_paras["scale"]
@@ -431,9 +463,9 @@ def test(trick_paras, solver_cls=None):
 
 
 def load_config(equation):
-    """./config3d/<equation>.yaml (the operator equations: ./config3d_op/), falling back to the
-    package's copy."""
-    cdir = "config3d_op" if equation in EQUATIONS_3D_OP else "config3d"
+    """./config3d/<equation>.yaml (the operator equations: ./config3d_op/, the mixed-order ones:
+    ./config3d_opx/), falling back to the package's copy."""
+    cdir = "config3d_op" if equation in EQUATIONS_3D_OP else "config3d_opx" if equation in EQUATIONS_3D_OPX else "config3d"
     for base in (os.getcwd(), os.path.dirname(os.path.abspath(__file__))):
         p = os.path.join(base, cdir, equation + ".yaml")
         if os.path.exists(p):
@@ -442,7 +474,7 @@ def load_config(equation):
     raise FileNotFoundError(cdir + "/" + equation + ".yaml")
 
 
-def build_config(args, allowed=EQUATIONS_3D + EQUATIONS_3D_OP):
+def build_config(args, allowed=EQUATIONS_3D + EQUATIONS_3D_OP + EQUATIONS_3D_OPX):
     """The 2-axis build_config (scale, kernel class, other_paras) on the config3d files."""
     assert args.equation in allowed
     config = load_config(args.equation)

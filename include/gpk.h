@@ -459,8 +459,9 @@ int gpk_destroy3(gpk_handle3* h);
  * order (2,2,1), coef (-nu,-nu,1), faces 31; transport b1 u_x + b2 u_y + u_t: order (1,1,1), coef
  * (b1,b2,1); Helmholtz: order (2,2,2), coef (1,1,1), react (k^2,0,0); Allen-Cahn in time:
  * order (2,2,1), coef (-eps,-eps,1), react (-1,0,1), faces 31.
- * Not expressible: two orders on one axis (a d^2 + b d), coefficients that vary over the grid,
- * derivative (Neumann / initial-velocity) boundary data. */
+ * Two orders on one axis (a d^2 + b d) are stated with gpk_operator3x / gpk_create3_opx below.
+ * Not expressible: coefficients that vary over the grid, derivative (Neumann / initial-velocity)
+ * boundary data. */
 typedef struct gpk_operator3 {
   int32_t order[3];  /* 1 or 2: the derivative taken along axis k (D_x1_kappa / DD_x1_kappa block) */
   double  coef[3];   /* its weight c_k, any finite value (0 drops that axis's term)               */
@@ -478,8 +479,35 @@ typedef struct gpk_operator3 {
  * handle evaluates u(u^2 - 1)). */
 int gpk_create3_op(const gpk_problem3* p, const gpk_operator3* op, double freq_scale, gpk_handle3** out);
 /* What the handle runs: gpk_create3_op's operator, or a gpk_create3 handle's equivalent (orders 2,
- * weights 1, faces 63, react 0 for Poisson and (-1,0,1) for Allen-Cahn). */
+ * weights 1, faces 63, react 0 for Poisson and (-1,0,1) for Allen-Cahn).  GPK_EINVAL on a
+ * gpk_create3_opx handle with a mixed-order axis: this struct cannot state it (gpk_operator_info3x
+ * works on every 3-axis handle). */
 int gpk_operator_info3(const gpk_handle3* h, gpk_operator3* out);
+
+/* Operators with a second- and a first-order term on the same axis (convection-diffusion,
+ * u_t + beta . grad u - nu lap u + r(u) = f).  Residual on the grid
+ *     R = sum_k (c2_k D_k^(2) + c1_k D_k^(1)) K_k^{-1} x_k U - F + r1 U + r2 U^2 + r3 U^3;
+ * the log joint, boundary term, Nb, criterion and loss terms as on a gpk_create3_op handle.  Per
+ * axis: exactly one non-zero weight is gpk_operator3's order 2 or 1 with that weight, both zero is
+ * order 2 with weight 0 -- a handle without a mixed axis equals the gpk_create3_op handle of the
+ * same operator bit for bit.  Both non-zero is a mixed axis: its assembled block is
+ * D_k = c2_k DD_x1_kappa + c1_k D_x1_kappa (neither symmetric nor antisymmetric; both fields from
+ * one evaluation per pair and mixture component) and every product with D_k has weight exactly 1.
+ * Example, third axis time: u_t + b1 u_x + b2 u_y - nu (u_xx + u_yy): c2 (-nu,-nu,0), c1 (b1,b2,1),
+ * faces 31.  Still not expressible: coefficients that vary over the grid, derivative boundary
+ * data; the 1- and 2-axis handles and sharded handles take no such operator. */
+typedef struct gpk_operator3x {
+  double  c2[3];    /* weight of d^2/dx_k^2 (DD_x1_kappa block) */
+  double  c1[3];    /* weight of d/dx_k     (D_x1_kappa block)  */
+  double  react[3]; /* r1, r2, r3 as in gpk_operator3           */
+  int32_t faces;    /* as in gpk_operator3, 1..63               */
+} gpk_operator3x;
+/* p as on gpk_create3_op.  GPK_EINVAL on a NULL op, a non-finite c2, c1 or react, faces outside
+ * 1..63, or eq != GPK_POISSON.  Every other gpk_*3 call works on such a handle unchanged. */
+int gpk_create3_opx(const gpk_problem3* p, const gpk_operator3x* op, double freq_scale, gpk_handle3** out);
+/* What any 3-axis handle runs, in this form: a gpk_create3 or gpk_create3_op handle reports its
+ * equivalent (the weight under c2 or c1 by its order, the other 0). */
+int gpk_operator_info3x(const gpk_handle3* h, gpk_operator3x* out);
 
 int gpk_num_params3(const gpk_handle3* h, int64_t* n);
 int gpk_set_params3(gpk_handle3* h, const double* flat, int64_t n);
@@ -565,6 +593,23 @@ int gpk_point_contract(int32_t kind, int32_t deriv, const double* t, int32_t m, 
                        const double* logw, const double* logls, const double* freq, int32_t q,
                        const double* T, int64_t sp, int64_t sj, int64_t sc, int32_t C,
                        double* out, int32_t iters, double* avg_us);
+
+/* The step's per-pair assembly kernel on one axis of host operands (tests; the counterpart of
+ * gpk_point_contract): K_out = kappa(x_i, x_j) + jitter on the diagonal and D_out, both n x n
+ * row-major, as the 3-axis step assembles them before the inverse.  c1 == 0: D_out = DD_x1_kappa
+ * (mode 2); c2 == 0 (and c1 != 0): D_out = D_x1_kappa (mode 1) -- both unweighted, as in the step,
+ * where the weight rides on the GEMMs; otherwise the mixed block c2 DD_x1_kappa + c1 D_x1_kappa.
+ * 1 <= n <= 1024, 1 <= q <= 64, c2 and c1 finite. */
+int gpk_assemble_pairs(int32_t kind, const double* x, int32_t n, const double* logw, const double* logls,
+                       const double* freq, int32_t q, double jitter, double c2, double c1,
+                       double* K_out, double* D_out);
+/* The same launch timed (A/B; no outputs): *avg_us is the mean over iters >= 1 back-to-back
+ * launches between two HIP events, after a checked and a warm-up one.  split != 0 runs mode 2 and
+ * mode 1 as two launches per iteration, each into a block of its own -- what forming the two
+ * fields of a mixed axis separately would cost -- whatever c2 and c1 are. */
+int gpk_assemble_pairs_time(int32_t kind, const double* x, int32_t n, const double* logw, const double* logls,
+                            const double* freq, int32_t q, double c2, double c1, int32_t split,
+                            int32_t iters, double* avg_us);
 
 #ifdef __cplusplus
 }
