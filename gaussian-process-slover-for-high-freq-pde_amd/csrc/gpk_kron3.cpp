@@ -24,6 +24,10 @@
 // arguments) and the three GEMM weights of that axis are exactly 1.0, so every formula above holds
 // with c_k = 1 and this D_k.  Axes 1-2 share a launch when their modes are equal; two mixed axes
 // with different weights still do.  An axis with one non-zero weight is the path above, unchanged.
+// Coefficient fields (gpk_create3_opv): R = sum_k a_k . (D_k x_k A_k) - F + (r1 + rho) . U + ...
+// (k3_combine_v), and the reverse pass reads W_k = a_k . R where it reads R above -- X_k, G_Dk --
+// so dL/dU and the G's hold with no further change; rho joins r1 in dL/dU's reaction factor
+// (k3_adam_u_v).  An axis without a field has no W_k: its operand stays R (Rp on axis 2).
 // GPK_FLAG3_REFINE: every one of the eight solves (A1, A2, A3, T, S, X1, X2, X3) is followed by
 // one refinement step X += K_k^{-1} (B - K_k X) gated on the axis's pst: one fused panel launch
 // (refine_panel.hip), or two GEMMs where its panels do not fit LDS (build_refine).
@@ -74,6 +78,10 @@ struct gpk_handle3 {
          *Sp = nullptr, *S = nullptr, *Rx = nullptr, *Rz = nullptr, *Ryp = nullptr, *R = nullptr,
          *Rp = nullptr, *T1 = nullptr, *X1 = nullptr, *T2p = nullptr, *X2p = nullptr, *T3 = nullptr,
          *X3 = nullptr, *Y1 = nullptr, *Y2p = nullptr, *Y3 = nullptr;
+  // gpk_create3_opv: the fields given (padded, natural layout; null: absent) and, per axis with a
+  // field, W_k = a_k R (W[1] permuted).  They are allocations of their own: Rx / Ryp / Rz are the
+  // refinement's residual scratch after k3_combine (build_refine).
+  double *cf[3] = {}, *rho = nullptr, *W[3] = {};
   double *GK[3] = {}, *GD[3] = {};
   double *red_egap = nullptr, *red_quad = nullptr;
   int nred = 0;
@@ -100,6 +108,10 @@ void build_stages(gpk_handle3* h) {
   double* const* D = h->D;
   const double* w = h->op.coef;  // c_k rides on every product with D_k (exact at 1.0)
   auto scaled = [](GemmDesc d, double alpha) { d.alpha = alpha; return d; };
+  // the reverse pass's operand of axis k: a_k R on an axis with a field, else R (Rp on axis 2)
+  const double* W1 = h->W[0] ? h->W[0] : h->R;
+  const double* W2p = h->W[1] ? h->W[1] : h->Rp;
+  const double* W3 = h->W[2] ? h->W[2] : h->R;
   auto& st = h->stages;
   st.clear();
   // forward: A1 = K1^{-1} x1 U, A3 = K3^{-1} x3 U
@@ -113,17 +125,17 @@ void build_stages(gpk_handle3* h) {
                 scaled(gemm_desc(D[0], P1, 0, h->A1, M1, 0, h->Rx, M1, P1, M1, P1), w[0]),
                 scaled(gemm_desc(D[1], P2, 0, h->A2p, M2, 0, h->Ryp, M2, P2, M2, P2), w[1]),
                 scaled(gemm_desc(h->A3, P3, 0, D[2], P3, 1, h->Rz, P3, M3, P3, P3), w[2])});
-  // (R, S combined) reverse: c_k D_k^T x_k R;  G_D1 = v c_1 R_(1) A1_(1)^T
+  // (R, S combined) reverse: c_k D_k^T x_k W_k;  G_D1 = v c_1 W1_(1) A1_(1)^T
   {
-    GemmDesc gd = scaled(gemm_desc(h->R, M1, 0, h->A1, M1, 1, h->GD[0], P1, P1, P1, M1), w[0]);
+    GemmDesc gd = scaled(gemm_desc(W1, M1, 0, h->A1, M1, 1, h->GD[0], P1, P1, P1, M1), w[0]);
     gd.vscale = 1;
-    st.push_back({scaled(gemm_desc(D[0], P1, 1, h->R, M1, 0, h->T1, M1, P1, M1, P1), w[0]),
-                  scaled(gemm_desc(D[1], P2, 1, h->Rp, M2, 0, h->T2p, M2, P2, M2, P2), w[1]),
-                  scaled(gemm_desc(h->R, P3, 0, D[2], P3, 0, h->T3, P3, M3, P3, P3), w[2]), gd});
+    st.push_back({scaled(gemm_desc(D[0], P1, 1, W1, M1, 0, h->T1, M1, P1, M1, P1), w[0]),
+                  scaled(gemm_desc(D[1], P2, 1, W2p, M2, 0, h->T2p, M2, P2, M2, P2), w[1]),
+                  scaled(gemm_desc(W3, P3, 0, D[2], P3, 0, h->T3, P3, M3, P3, P3), w[2]), gd});
   }
   // X_k = K_k^{-1} x_k (c_k D_k^T x_k R) with the side outputs Y_k = S/2 + v X_k;  G_D2
   {
-    GemmDesc gd = scaled(gemm_desc(h->Rp, M2, 0, h->A2p, M2, 1, h->GD[1], P2, P2, P2, M2), w[1]);
+    GemmDesc gd = scaled(gemm_desc(W2p, M2, 0, h->A2p, M2, 1, h->GD[1], P2, P2, P2, M2), w[1]);
     gd.vscale = 1;
     st.push_back({with_side(gemm_desc(Ki[0], P1, 0, h->T1, M1, 0, h->X1, M1, P1, M1, P1), h->Y1, h->S, M1),
                   with_side(gemm_desc(Ki[1], P2, 0, h->T2p, M2, 0, h->X2p, M2, P2, M2, P2), h->Y2p, h->Sp, M2),
@@ -137,7 +149,7 @@ void build_stages(gpk_handle3* h) {
     g2.alpha = -1.0; g2.beta = 0.5 * c * n1 * n3; g2.C0 = Ki[1]; g2.ldc0 = P2;
     GemmDesc g3 = gemm_desc(h->Y3, P3, 1, h->A3, P3, 0, h->GK[2], P3, P3, P3, M3);
     g3.alpha = -1.0; g3.beta = 0.5 * c * n1 * n2; g3.C0 = Ki[2]; g3.ldc0 = P3;
-    GemmDesc gd = scaled(gemm_desc(h->R, P3, 1, h->A3, P3, 0, h->GD[2], P3, P3, P3, M3), w[2]);
+    GemmDesc gd = scaled(gemm_desc(W3, P3, 1, h->A3, P3, 0, h->GD[2], P3, P3, P3, M3), w[2]);
     gd.vscale = 1;
     st.push_back({g1, g2, g3, gd});
   }
@@ -291,7 +303,14 @@ int enqueue_step3(gpk_handle3* h, int apply) {
   C.g = g; C.Rx = h->Rx; C.Rz = h->Rz; C.Ryp = h->Ryp; C.F = h->F; C.Up = h->Up; C.Sp = h->Sp;
   C.eq = eq_layer(h); C.R = h->R; C.Rp = h->Rp; C.S = h->S;
   C.red_egap = h->red_egap; C.red_quad = h->red_quad;
-  TRY(check_launch(k3_launch_combine(C, h->s), "k3_combine"));
+  if (h->cf[0] || h->cf[1] || h->cf[2] || h->rho) {
+    K3CombineV V{};
+    V.c = C; V.rho = h->rho;
+    for (int a = 0; a < 3; ++a) { V.a[a] = h->cf[a]; V.W[a] = h->W[a]; }
+    TRY(check_launch(k3_launch_combine_v(V, h->s), "k3_combine_v"));
+  } else {
+    TRY(check_launch(k3_launch_combine(C, h->s), "k3_combine"));
+  }
   // reverse products and G_K, G_D
   for (int k = 3; k < (int)h->stages.size(); ++k) TRY(launch_stage(h, k));
   // kernel-parameter contraction (the 2-axis kernels: axes 1-2, then axis 3)
@@ -326,7 +345,11 @@ int enqueue_step3(gpk_handle3* h, int apply) {
   A.g = g; A.hyper = F.hyper; A.llk_weight = h->prob.llk_weight; A.apply = apply; A.eq = C.eq;
   A.sc = h->sc; A.S = h->S; A.X1 = h->X1; A.X2p = h->X2p; A.X3 = h->X3; A.R = h->R; A.Up = h->Up;
   A.bvals = h->bvals; A.off_u = 0; A.params = h->params; A.grad = h->grad; A.m = h->m; A.v = h->v;
-  TRY(check_launch(k3_launch_adam_u(A, h->s), "k3_adam_u"));
+  if (h->rho) {
+    TRY(check_launch(k3_launch_adam_u_v(K3AdamUV{A, h->rho}, h->s), "k3_adam_u_v"));
+  } else {
+    TRY(check_launch(k3_launch_adam_u(A, h->s), "k3_adam_u"));
+  }
   return GPK_OK;
 }
 
@@ -369,16 +392,24 @@ int gpk_destroy3(gpk_handle3* h) {
 
 namespace {
 
-// gpk_create3 (op = nullptr: the legacy equation p->eq), gpk_create3_op, and gpk_create3_opx
-// (opx: op is its one-order-per-axis part, a mixed axis entered as order 0 with weight 1.0)
-int create3(const gpk_problem3* p, const gpk_operator3* op, double freq_scale, gpk_handle3** out,
-            const gpk_operator3x* opx = nullptr) {
+// what every create call checks of the problem itself, before any device work
+int check_problem3(const gpk_problem3* p) {
   if (p->kind < 0 || p->kind > 3) return fail(GPK_EINVAL, "Invalid Kernel");
   if (p->q <= 0 || p->q > QMAX) return fail(GPK_EINVAL, "Q must be in [1, 64]");
   const int ns[3] = {p->n1, p->n2, p->n3};
   for (int a = 0; a < 3; ++a)
     if (ns[a] < 2 || ns[a] > K3_MAX_N) return fail(GPK_EINVAL, "need 2..1024 collocation points per axis");
   if (!p->x1 || !p->x2 || !p->x3 || !p->src || !p->bvals) return fail(GPK_EINVAL, "NULL problem array");
+  return GPK_OK;
+}
+
+// gpk_create3 (op = nullptr: the legacy equation p->eq), gpk_create3_op, gpk_create3_opx (opx: op
+// is its one-order-per-axis part, a mixed axis entered as order 0 with weight 1.0) and
+// gpk_create3_opv (cf: the fields it was given, at least one of them)
+int create3(const gpk_problem3* p, const gpk_operator3* op, double freq_scale, gpk_handle3** out,
+            const gpk_operator3x* opx = nullptr, const gpk_coef3* cf = nullptr) {
+  TRY(check_problem3(p));
+  const int ns[3] = {p->n1, p->n2, p->n3};
   TRY(check_device(p->device));
   DevSwitch ds(p->device);
   gpk_handle3* h = new gpk_handle3();
@@ -452,6 +483,24 @@ int create3(const gpk_problem3* p, const gpk_operator3* op, double freq_scale, g
   h->bpa = std::max(pgrad_blocks(ns[0]), std::max(pgrad_blocks(ns[1]), pgrad_blocks(ns[2])));
   A3_(h->pgpart, (size_t)3 * h->bpa * 3 * QMAX);
   A3_(h->pg, (size_t)3 * 3 * QMAX);
+  // the fields: zero-padded natural-layout tensors, and W_k for each axis that has one
+  if (cf) {
+    std::vector<double> fp(np);
+    const double* given[4] = {cf->a[0], cf->a[1], cf->a[2], cf->rho};
+    double** dst[4] = {&h->cf[0], &h->cf[1], &h->cf[2], &h->rho};
+    for (int k = 0; k < 4; ++k) {
+      if (!given[k]) continue;
+      A3_(*dst[k], np);
+      if (k < 3) A3_(h->W[k], np);
+      std::fill(fp.begin(), fp.end(), 0.0);
+      for (int i1 = 0; i1 < ns[0]; ++i1)
+        for (int i2 = 0; i2 < ns[1]; ++i2)
+          std::memcpy(&fp[g.at(i1, i2, 0)], given[k] + ((size_t)i1 * ns[1] + i2) * ns[2], ns[2] * sizeof(double));
+      if (hipMemcpyAsync(*dst[k], fp.data(), np * sizeof(double), hipMemcpyHostToDevice, h->s) != hipSuccess ||
+          hipStreamSynchronize(h->s) != hipSuccess)
+        return bail(fail(GPK_EHIP, "upload of a coefficient field failed"));
+    }
+  }
 #undef A3_
   // upload: coordinates, the padded source, boundary values, the initial params
   // (model_GP_solver_2d.py:245-261: U = 0, freq = linspace(0,1,Q) freq_scale, log-ls = 0,
@@ -483,6 +532,35 @@ int create3(const gpk_problem3* p, const gpk_operator3* op, double freq_scale, g
     if (h->route && refine_panel_prepare() != hipSuccess) return bail(fail(GPK_EHIP, "refine_panel_prepare failed"));
   }
   *out = h;
+  return GPK_OK;
+}
+
+// gpk_operator3x as create3 takes it.  One non-zero weight: that order with that weight
+// (gpk_create3_op's handle); none: order 2 with weight 0; both: a mixed axis (order 0), its
+// weights in the assembled block and 1.0 on its GEMMs
+gpk_operator3 one_order_part(const gpk_operator3x* op) {
+  gpk_operator3 o{};
+  for (int a = 0; a < 3; ++a) {
+    const bool has2 = op->c2[a] != 0.0, has1 = op->c1[a] != 0.0;
+    o.order[a] = has2 && has1 ? 0 : has1 ? 1 : 2;
+    o.coef[a] = has2 && has1 ? 1.0 : has1 ? op->c1[a] : op->c2[a];
+    o.react[a] = op->react[a];
+  }
+  o.faces = op->faces;
+  return o;
+}
+
+// the arguments of gpk_create3_opx and gpk_create3_opv (`who`), up to the problem's own checks
+int check_operator3x(const gpk_problem3* p, const gpk_operator3x* op, gpk_handle3** out, const char* who) {
+  if (!p || !op || !out) return fail(GPK_EINVAL, "NULL argument");
+  *out = nullptr;
+  const std::string w(who);
+  if (p->eq != GPK_POISSON)
+    return fail(GPK_EINVAL, w + ": eq must be GPK_POISSON (the operator states the equation)");
+  for (int a = 0; a < 3; ++a)
+    if (!std::isfinite(op->c2[a]) || !std::isfinite(op->c1[a]) || !std::isfinite(op->react[a]))
+      return fail(GPK_EINVAL, w + ": c2, c1 and react must be finite");
+  if (op->faces < 1 || op->faces > K3_ALL_FACES) return fail(GPK_EINVAL, w + ": faces must be in 1..63");
   return GPK_OK;
 }
 
@@ -524,25 +602,8 @@ int gpk_operator_info3(const gpk_handle3* h, gpk_operator3* out) {
 }
 
 int gpk_create3_opx(const gpk_problem3* p, const gpk_operator3x* op, double freq_scale, gpk_handle3** out) {
-  if (!p || !op || !out) return fail(GPK_EINVAL, "NULL argument");
-  *out = nullptr;
-  if (p->eq != GPK_POISSON)
-    return fail(GPK_EINVAL, "gpk_create3_opx: eq must be GPK_POISSON (the operator states the equation)");
-  for (int a = 0; a < 3; ++a)
-    if (!std::isfinite(op->c2[a]) || !std::isfinite(op->c1[a]) || !std::isfinite(op->react[a]))
-      return fail(GPK_EINVAL, "gpk_create3_opx: c2, c1 and react must be finite");
-  if (op->faces < 1 || op->faces > K3_ALL_FACES)
-    return fail(GPK_EINVAL, "gpk_create3_opx: faces must be in 1..63");
-  // one non-zero weight: that order with that weight (gpk_create3_op's handle); none: order 2 with
-  // weight 0; both: a mixed axis, its weights in the assembled block and 1.0 on its GEMMs
-  gpk_operator3 o{};
-  for (int a = 0; a < 3; ++a) {
-    const bool has2 = op->c2[a] != 0.0, has1 = op->c1[a] != 0.0;
-    o.order[a] = has2 && has1 ? 0 : has1 ? 1 : 2;
-    o.coef[a] = has2 && has1 ? 1.0 : has1 ? op->c1[a] : op->c2[a];
-    o.react[a] = op->react[a];
-  }
-  o.faces = op->faces;
+  TRY(check_operator3x(p, op, out, "gpk_create3_opx"));
+  const gpk_operator3 o = one_order_part(op);
   return create3(p, &o, freq_scale, out, op);
 }
 
@@ -554,6 +615,28 @@ int gpk_operator_info3x(const gpk_handle3* h, gpk_operator3x* out) {
     out->react[a] = h->op.react[a];
   }
   out->faces = h->op.faces;
+  return GPK_OK;
+}
+
+int gpk_create3_opv(const gpk_problem3* p, const gpk_operator3x* op, const gpk_coef3* cf, double freq_scale,
+                    gpk_handle3** out) {
+  const double* given[4] = {cf ? cf->a[0] : nullptr, cf ? cf->a[1] : nullptr, cf ? cf->a[2] : nullptr,
+                            cf ? cf->rho : nullptr};
+  if (!given[0] && !given[1] && !given[2] && !given[3]) return gpk_create3_opx(p, op, freq_scale, out);
+  TRY(check_operator3x(p, op, out, "gpk_create3_opv"));
+  TRY(check_problem3(p));  // (the grid's size, before the fields are read)
+  const size_t n = (size_t)p->n1 * p->n2 * p->n3;
+  for (const double* f : given)
+    if (f && !std::all_of(f, f + n, [](double x) { return std::isfinite(x); }))
+      return fail(GPK_EINVAL, "gpk_create3_opv: a coefficient field has a non-finite value");
+  const gpk_operator3 o = one_order_part(op);
+  return create3(p, &o, freq_scale, out, op, cf);
+}
+
+int gpk_coef_info3(const gpk_handle3* h, int32_t has[4]) {
+  if (!h || !has) return fail(GPK_EINVAL, "NULL argument");
+  for (int a = 0; a < 3; ++a) has[a] = h->cf[a] != nullptr;
+  has[3] = h->rho != nullptr;
   return GPK_OK;
 }
 

@@ -54,6 +54,17 @@ struct K3Combine {
   double *red_egap, *red_quad;                // out: per-block partials
 };
 
+// k3_combine_v (gpk_create3_opv): k3_combine with a coefficient field per axis and on the linear
+// reaction term.  Fields are natural-layout padded tensors; a null one is absent (a_k = 1, rho = 0).
+// W[k] = a_k R is the reverse pass's operand of axis k (W[1] in the mode-2 permuted layout); an
+// absent field has no W[k] (null): its operand is R itself, or c.Rp, which is written only then.
+struct K3CombineV {
+  K3Combine c;
+  const double* a[3];
+  const double* rho;
+  double* W[3];
+};
+
 struct K3Final {
   K3Geom g;
   AdamHyper hyper;
@@ -86,12 +97,20 @@ struct K3AdamU {
   double *params, *grad, *m, *v;
 };
 
+// k3_adam_u_v: k3_adam_u of an operator handle with rho (natural padded layout) added to r1
+struct K3AdamUV {
+  K3AdamU a;
+  const double* rho;
+};
+
 hipError_t k3_launch_prep(const K3Prep& P, hipStream_t s);
 hipError_t k3_launch_permute(const double* src, double* dst, const K3Geom& g, hipStream_t s);
 int k3_combine_blocks(const K3Geom& g);
 hipError_t k3_launch_combine(const K3Combine& C, hipStream_t s);
+hipError_t k3_launch_combine_v(const K3CombineV& V, hipStream_t s);
 hipError_t k3_launch_finalize(const K3Final& F, hipStream_t s);
 hipError_t k3_launch_adam_u(const K3AdamU& A, hipStream_t s);
+hipError_t k3_launch_adam_u_v(const K3AdamUV& V, hipStream_t s);
 hipError_t k3_launch_sync_u(const double* params, long off_u, const K3Geom& g, double* Up, hipStream_t s);
 
 }  // namespace gpk

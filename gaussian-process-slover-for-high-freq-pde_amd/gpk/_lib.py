@@ -100,6 +100,10 @@ class gpk_operator3x(ctypes.Structure):
     ]
 
 
+class gpk_coef3(ctypes.Structure):
+    _fields_ = [("a", ctypes.POINTER(ctypes.c_double) * 3), ("rho", ctypes.POINTER(ctypes.c_double))]
+
+
 EXPORTS = {
     "gpk_abi_version": ([], ctypes.c_int),
     "gpk_last_error": ([], ctypes.c_char_p),
@@ -161,6 +165,9 @@ EXPORTS = {
     "gpk_create3_opx": ([ctypes.POINTER(gpk_problem3), ctypes.POINTER(gpk_operator3x), ctypes.c_double,
                          ctypes.POINTER(ctypes.c_void_p)], ctypes.c_int),
     "gpk_operator_info3x": ([ctypes.c_void_p, ctypes.POINTER(gpk_operator3x)], ctypes.c_int),
+    "gpk_create3_opv": ([ctypes.POINTER(gpk_problem3), ctypes.POINTER(gpk_operator3x), ctypes.POINTER(gpk_coef3),
+                         ctypes.c_double, ctypes.POINTER(ctypes.c_void_p)], ctypes.c_int),
+    "gpk_coef_info3": ([ctypes.c_void_p, ctypes.POINTER(ctypes.c_int32)], ctypes.c_int),
     "gpk_destroy3": ([ctypes.c_void_p], ctypes.c_int),
     "gpk_num_params3": ([ctypes.c_void_p, ctypes.POINTER(ctypes.c_int64)], ctypes.c_int),
     "gpk_set_params3": ([ctypes.c_void_p, _dp, ctypes.c_int64], ctypes.c_int),

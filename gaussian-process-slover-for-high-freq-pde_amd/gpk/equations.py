@@ -242,6 +242,98 @@ def solution_3d_opx(equation):
     return _OPX3D[equation]()
 
 
+class Operator3V:
+    """What a gpk_create3_opv handle solves (include/gpk.h gpk_coef3): Operator3X with a
+    coefficient field per axis and one on the linear reaction term,
+    sum_k a[k](x) (c2[k] d^2 u / dx_k^2 + c1[k] du / dx_k) + (react[0] + rho(x)) u + react[1] u^2
+    + react[2] u^3 = f.  Each of a[0..2] and rho is None (a = 1, rho = 0), an array of the grid's
+    shape, or a callable of the three coordinate meshes (x, y, z); fields(axes) evaluates them."""
+
+    __slots__ = ("c2", "c1", "react", "faces", "a", "rho")
+
+    def __init__(self, c2, c1, react=(0.0, 0.0, 0.0), faces=63, a=(None, None, None), rho=None):
+        x = Operator3X(c2, c1, react, faces)
+        self.c2, self.c1, self.react, self.faces = x.c2, x.c1, x.react, x.faces
+        self.a = tuple(a)
+        self.rho = rho
+        if len(self.a) != 3:
+            raise ValueError("a has three entries (None for an axis without a field)")
+
+    @property
+    def constant(self):
+        """The Operator3X of the constant part (what gpk_operator_info3x reports)."""
+        return Operator3X(self.c2, self.c1, self.react, self.faces)
+
+    @property
+    def has(self):
+        """(a1, a2, a3, rho) present, as DeviceSolver3.coef_info() reports."""
+        return tuple(f is not None for f in self.a + (self.rho,))
+
+    def fields(self, axes):
+        """[a1, a2, a3, rho] on the tensor grid of the three coordinate axes: float64 arrays of
+        shape (n1, n2, n3), None where absent.  Callables get the 'ij' meshes."""
+        axes = [np.asarray(x, np.float64).reshape(-1) for x in axes]
+        shape = tuple(x.size for x in axes)
+        mesh = None
+        out = []
+        for f in self.a + (self.rho,):
+            if f is None:
+                out.append(None)
+                continue
+            if callable(f):
+                mesh = np.meshgrid(*axes, indexing="ij") if mesh is None else mesh
+                v = np.asarray(f(*mesh), np.float64) * np.ones(shape)
+            else:
+                v = np.asarray(f, np.float64)
+                if v.shape != shape:
+                    raise ValueError("a coefficient field given as an array must have the grid's shape %r" % (shape,))
+            out.append(np.ascontiguousarray(v))
+        return out
+
+    def __repr__(self):
+        kind = lambda f: "None" if f is None else "<callable>" if callable(f) else "<array>"
+        return "Operator3V(c2=%r, c1=%r, react=%r, faces=%d, a=(%s), rho=%s)" % (
+            self.c2, self.c1, self.react, self.faces, ", ".join(kind(f) for f in self.a), kind(self.rho))
+
+
+# Coefficient-field equations on [0, 1]^3 (gpk_create3_opv); third axis = time where one appears.
+_HV_K2 = lambda x, y, z: 16.0 * (1.0 + 0.5 * x)                                # k(x)^2, max 24 < 3 pi^2
+_HEATV_A = lambda x, y, t: 1.0 + 0.5 * s_(2 * np.pi * x) * c_(2 * np.pi * y)    # nu(x, y) / _HEAT_NU
+_ROT_B1, _ROT_B2 = (lambda x, y, t: -(y - 0.5)), (lambda x, y, t: x - 0.5)      # the rotating flow
+
+
+def _helmholtz_var_sin():
+    # u = sin(2x) sin(3y) sin(z):  lap u + k(x)^2 u = (k(x)^2 - 14) u
+    u = lambda x, y, z: s_(2 * x) * s_(3 * y) * s_(z)
+    return u, (lambda x, y, z: (_HV_K2(x, y, z) - 14.0) * u(x, y, z)), \
+        Operator3V((1.0, 1.0, 1.0), (0.0, 0.0, 0.0), rho=_HV_K2)
+
+
+def _heat_var_sin():
+    # u = e^{-t} sin(2x) sin(3y):  u_t - nu(x,y) (u_xx + u_yy) = (13 nu(x,y) - 1) u, nu = _HEAT_NU a
+    u = lambda x, y, t: np.exp(-t) * s_(2 * x) * s_(3 * y)
+    return u, (lambda x, y, t: (13.0 * _HEAT_NU * _HEATV_A(x, y, t) - 1.0) * u(x, y, t)), \
+        Operator3V((-_HEAT_NU, -_HEAT_NU, 0.0), (0.0, 0.0, 1.0), faces=NO_FINAL_FACE, a=(_HEATV_A, _HEATV_A, None))
+
+
+def _transport_var_sin():
+    # the same u:  u_t + b1 u_x + b2 u_y = -u + e^{-t} (2 b1 cos(2x) sin(3y) + 3 b2 sin(2x) cos(3y))
+    u = lambda x, y, t: np.exp(-t) * s_(2 * x) * s_(3 * y)
+    f = lambda x, y, t: (-u(x, y, t) + np.exp(-t) * (2.0 * _ROT_B1(x, y, t) * c_(2 * x) * s_(3 * y)
+                                                     + 3.0 * _ROT_B2(x, y, t) * s_(2 * x) * c_(3 * y)))
+    return u, f, Operator3V((0.0, 0.0, 0.0), (1.0, 1.0, 1.0), faces=NO_FINAL_FACE, a=(_ROT_B1, _ROT_B2, None))
+
+
+_OPV3D = {"helmholtz_var-sin": _helmholtz_var_sin, "heat_var-sin": _heat_var_sin,
+          "transport_var-sin": _transport_var_sin}
+EQUATIONS_3D_OPV = list(_OPV3D)
+
+
+def solution_3d_opv(equation):
+    """(u, src, operator) of an EQUATIONS_3D_OPV entry (operator: an Operator3V of callables)."""
+    return _OPV3D[equation]()
+
+
 def boundary_2d(u_mesh):
     """get_boundary_vals: hstack(U[0,:], U[-1,:], U[:,0], U[:,-1]) (model_GP_solver_2d.py:377-379)."""
     return np.hstack((u_mesh[0, :], u_mesh[-1, :], u_mesh[:, 0], u_mesh[:, -1]))

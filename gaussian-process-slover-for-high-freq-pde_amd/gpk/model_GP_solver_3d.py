@@ -21,6 +21,11 @@ GP_solver_3d_single with such an equation name, and the same CLI
 Mixed-order operator equations (equations.EQUATIONS_3D_OPX: convection-diffusion, a second- and a
 first-order term on the same axis) run through gpk_create3_opx the same way: an Operator3X as
 `operator`, `-equation=convdiff_t-sin`, configs in gpk/config3d_opx/.
+
+Coefficient-field equations (equations.EQUATIONS_3D_OPV: Helmholtz in a medium, heat with a
+conductivity field, transport in a rotating flow) run through gpk_create3_opv: an Operator3V as
+`operator` (its fields evaluated on the collocation mesh), `-equation=heat_var-sin`, configs in
+gpk/config3d_opv/.
 """
 import ctypes
 import os
@@ -34,8 +39,8 @@ from . import _lib, init_func, replicas, utils
 from ._lib import check, dptr, f64
 from .cli import parse_flags
 from .core import tree_flatten, tree_unflatten
-from .equations import (EQUATIONS_3D, EQUATIONS_3D_OP, EQUATIONS_3D_OPX, Operator3, Operator3X, solution_3d,
-                        solution_3d_op, solution_3d_opx)
+from .equations import (EQUATIONS_3D, EQUATIONS_3D_OP, EQUATIONS_3D_OPV, EQUATIONS_3D_OPX, Operator3, Operator3V,
+                        Operator3X, solution_3d, solution_3d_op, solution_3d_opv, solution_3d_opx)
 from .infras.exp_config import ExpConfig
 from .kernel_matrix import kernel_class
 from .solver_common import SolverBase
@@ -73,7 +78,8 @@ class DeviceSolver3:
         'gemm' also forces its two-GEMM route (GPK_FLAG3_REFINE_GEMM; tests, A/B).
         operator: an Operator3 (or a dict of its fields) -- the handle then solves that operator
         (gpk_create3_op; eq must be 'poisson', the operator says everything else); an Operator3X
-        (or a dict with 'c2' and 'c1') goes to gpk_create3_opx, which takes mixed-order axes."""
+        (or a dict with 'c2' and 'c1') goes to gpk_create3_opx, which takes mixed-order axes; an
+        Operator3V goes to gpk_create3_opv with its fields evaluated on the collocation mesh."""
         lib = _lib.load()
         if len(xs) != 3:
             raise ValueError("three coordinate axes")
@@ -102,6 +108,18 @@ class DeviceSolver3:
         h = ctypes.c_void_p()
         if operator is None:
             check(lib.gpk_create3(ctypes.byref(p), float(freq_scale), ctypes.byref(h)))
+        elif isinstance(operator, Operator3V):
+            c = _lib.gpk_operator3x()
+            c.c2[:], c.c1[:], c.react[:], c.faces = operator.c2, operator.c1, operator.react, operator.faces
+            self._coef = operator.fields(self._x)  # (the library copies them; kept for the call)
+            cf = _lib.gpk_coef3()
+            for k, f in enumerate(self._coef[:3]):
+                if f is not None:
+                    cf.a[k] = dptr(f)
+            if self._coef[3] is not None:
+                cf.rho = dptr(self._coef[3])
+            check(lib.gpk_create3_opv(ctypes.byref(p), ctypes.byref(c), ctypes.byref(cf), float(freq_scale),
+                                      ctypes.byref(h)))
         elif isinstance(operator, Operator3X) or (isinstance(operator, dict) and "c2" in operator):
             op = Operator3X.of(operator)
             c = _lib.gpk_operator3x()
@@ -248,6 +266,13 @@ class DeviceSolver3:
         check(_lib.load().gpk_operator_info3x(self._h, ctypes.byref(c)))
         return Operator3X(tuple(c.c2), tuple(c.c1), tuple(c.react), c.faces)
 
+    def coef_info(self):
+        """Which coefficient fields the handle has (gpk_coef_info3): (a1, a2, a3, rho) as bools;
+        all False on every handle not made from an Operator3V with a field."""
+        has = np.zeros(4, np.int32)
+        check(_lib.load().gpk_coef_info3(self._h, has.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))))
+        return tuple(bool(v) for v in has)
+
     LOSS_TERMS = ("loss", "logdet_1", "logdet_2", "logdet_3", "quad", "egap", "bgap")
 
     def loss_terms(self):
@@ -264,8 +289,8 @@ class GP_solver_3d_single(SolverBase):
 
     bvals: boundary_3d(U) of the solution; X_col = (x, y, z); src_vals: N1 x N2 x N3;
     trick_paras: {'kernel': class, 'equation': 'poisson_3d-...' | 'allencahn_3d-...' or an
-    operator equation (equations.EQUATIONS_3D_OP / EQUATIONS_3D_OPX: its Operator3 / Operator3X is
-    looked up by name, or given as trick_paras['operator']; bvals keeps the six-face layout, Nb
+    operator equation (equations.EQUATIONS_3D_OP / EQUATIONS_3D_OPX / EQUATIONS_3D_OPV: its
+    Operator3 / Operator3X / Operator3V is looked up by name, or given as trick_paras['operator']; bvals keeps the six-face layout, Nb
     counts the active faces),
     'llk_weight', 'logdet', 'lr', 'Q', 'freq_scale', 'refine'} (+ 'nepoch', 'tol' for train);
     'refine' (default False): DeviceSolver3's gated refinement of every solve;
@@ -275,14 +300,17 @@ class GP_solver_3d_single(SolverBase):
     eq_types = ("poisson_3d", "allencahn_3d")
     op_eq_types = tuple(sorted({e.split("-")[0] for e in EQUATIONS_3D_OP}))
     opx_eq_types = tuple(sorted({e.split("-")[0] for e in EQUATIONS_3D_OPX}))
+    opv_eq_types = tuple(sorted({e.split("-")[0] for e in EQUATIONS_3D_OPV}))
     early_stop_enabled = True
 
     def __init__(self, bvals, X_col, src_vals, jitter, trick_paras, device=0, X_test=None, u_test=None):
         self.eq_type = trick_paras["equation"].split("-")[0]
-        assert self.eq_type in self.eq_types + self.op_eq_types + self.opx_eq_types
+        assert self.eq_type in self.eq_types + self.op_eq_types + self.opx_eq_types + self.opv_eq_types
         self.operator = None
         given = trick_paras.get("operator")
-        if isinstance(given, Operator3X) or (isinstance(given, dict) and "c2" in given):
+        if isinstance(given, Operator3V):
+            self.operator = given
+        elif isinstance(given, Operator3X) or (isinstance(given, dict) and "c2" in given):
             self.operator = Operator3X.of(given)
         elif given is not None:
             self.operator = Operator3.of(given)
@@ -290,6 +318,8 @@ class GP_solver_3d_single(SolverBase):
             self.operator = solution_3d_op(trick_paras["equation"])[2]
         elif self.eq_type in self.opx_eq_types:
             self.operator = solution_3d_opx(trick_paras["equation"])[2]
+        elif self.eq_type in self.opv_eq_types:  # (a resumed run rebuilds the fields the same way)
+            self.operator = solution_3d_opv(trick_paras["equation"])[2]
         self.cov_func = trick_paras["kernel"]()
         self.trick_paras = trick_paras
         self.bvals = np.asarray(bvals, np.float64)
@@ -317,14 +347,21 @@ class GP_solver_3d_single(SolverBase):
     def eq_residual(self, params, X_test, src_test):
         """SolverBase.eq_residual; on an operator equation sum_k c_k d^{o_k} u / dx_k^{o_k} +
         r1 u + r2 u^2 + r3 u^3 - f from the derivative predictions (an Operator3X: sum_k (c2_k d^2
-        + c1_k d) u / dx_k, zero weights skipped)."""
+        + c1_k d) u / dx_k, zero weights skipped; an Operator3V: each axis's terms times a_k and
+        rho added to r1, the fields -- callables only -- evaluated on the test mesh)."""
         op = self.operator
         if op is None:
             return SolverBase.eq_residual(self, params, X_test, src_test)
         self._sync(params)
         axes = self._test_axes(X_test)
         r = np.zeros(tuple(a.size for a in axes))
-        if isinstance(op, Operator3X):
+        a = [None, None, None]
+        rho = None
+        if isinstance(op, Operator3V):
+            if not all(f is None or callable(f) for f in op.a + (op.rho,)):
+                raise ValueError("eq_residual needs the coefficient fields as callables (to evaluate them on the test mesh)")
+            *a, rho = op.fields(axes)
+        if isinstance(op, (Operator3X, Operator3V)):
             terms = [(k, o, w) for k in range(3) for o, w in ((2, op.c2[k]), (1, op.c1[k]))]
         else:
             terms = [(k, op.order[k], op.coef[k]) for k in range(3)]
@@ -332,10 +369,13 @@ class GP_solver_3d_single(SolverBase):
             if w != 0.0:
                 d = [0, 0, 0]
                 d[k] = o
-                r = r + w * self.dev.predict_deriv(*axes, deriv=tuple(d))
-        if any(op.react):
+                t = w * self.dev.predict_deriv(*axes, deriv=tuple(d))
+                r = r + (t if a[k] is None else a[k] * t)
+        if any(op.react) or rho is not None:
             u = self.dev.predict_deriv(*axes, deriv=(0, 0, 0))
             r = r + op.react[0] * u + op.react[1] * u ** 2 + op.react[2] * u ** 3
+            if rho is not None:
+                r = r + rho * u
         return r - np.asarray(src_test, np.float64).reshape(r.shape)
 
     # the device holds the params: reading fetches them, train()'s final assignment is a no-op
@@ -428,6 +468,8 @@ def test(trick_paras, solver_cls=None):
         u, src, op = solution_3d_op(trick_paras["equation"])
     elif trick_paras["equation"] in EQUATIONS_3D_OPX:
         u, src, op = solution_3d_opx(trick_paras["equation"])
+    elif trick_paras["equation"] in EQUATIONS_3D_OPV:
+        u, src, op = solution_3d_opv(trick_paras["equation"])
     else:
         u, src = solution_3d(trick_paras["equation"])
     scale = trick_paras["scale"]
@@ -464,8 +506,9 @@ def test(trick_paras, solver_cls=None):
 
 def load_config(equation):
     """./config3d/<equation>.yaml (the operator equations: ./config3d_op/, the mixed-order ones:
-    ./config3d_opx/), falling back to the package's copy."""
-    cdir = "config3d_op" if equation in EQUATIONS_3D_OP else "config3d_opx" if equation in EQUATIONS_3D_OPX else "config3d"
+    ./config3d_opx/, the coefficient-field ones: ./config3d_opv/), falling back to the package's copy."""
+    cdir = ("config3d_op" if equation in EQUATIONS_3D_OP else "config3d_opx" if equation in EQUATIONS_3D_OPX
+            else "config3d_opv" if equation in EQUATIONS_3D_OPV else "config3d")
     for base in (os.getcwd(), os.path.dirname(os.path.abspath(__file__))):
         p = os.path.join(base, cdir, equation + ".yaml")
         if os.path.exists(p):
@@ -474,7 +517,7 @@ def load_config(equation):
     raise FileNotFoundError(cdir + "/" + equation + ".yaml")
 
 
-def build_config(args, allowed=EQUATIONS_3D + EQUATIONS_3D_OP + EQUATIONS_3D_OPX):
+def build_config(args, allowed=EQUATIONS_3D + EQUATIONS_3D_OP + EQUATIONS_3D_OPX + EQUATIONS_3D_OPV):
     """The 2-axis build_config (scale, kernel class, other_paras) on the config3d files."""
     assert args.equation in allowed
     config = load_config(args.equation)

@@ -460,8 +460,8 @@ int gpk_destroy3(gpk_handle3* h);
  * (b1,b2,1); Helmholtz: order (2,2,2), coef (1,1,1), react (k^2,0,0); Allen-Cahn in time:
  * order (2,2,1), coef (-eps,-eps,1), react (-1,0,1), faces 31.
  * Two orders on one axis (a d^2 + b d) are stated with gpk_operator3x / gpk_create3_opx below.
- * Not expressible: coefficients that vary over the grid, derivative (Neumann / initial-velocity)
- * boundary data. */
+ * Coefficients that vary over the grid are stated with gpk_coef3 / gpk_create3_opv below.
+ * Not expressible: derivative (Neumann / initial-velocity) boundary data. */
 typedef struct gpk_operator3 {
   int32_t order[3];  /* 1 or 2: the derivative taken along axis k (D_x1_kappa / DD_x1_kappa block) */
   double  coef[3];   /* its weight c_k, any finite value (0 drops that axis's term)               */
@@ -494,8 +494,8 @@ int gpk_operator_info3(const gpk_handle3* h, gpk_operator3* out);
  * D_k = c2_k DD_x1_kappa + c1_k D_x1_kappa (neither symmetric nor antisymmetric; both fields from
  * one evaluation per pair and mixture component) and every product with D_k has weight exactly 1.
  * Example, third axis time: u_t + b1 u_x + b2 u_y - nu (u_xx + u_yy): c2 (-nu,-nu,0), c1 (b1,b2,1),
- * faces 31.  Still not expressible: coefficients that vary over the grid, derivative boundary
- * data; the 1- and 2-axis handles and sharded handles take no such operator. */
+ * faces 31.  Still not expressible: derivative boundary data; the 1- and 2-axis handles and
+ * sharded handles take no such operator. */
 typedef struct gpk_operator3x {
   double  c2[3];    /* weight of d^2/dx_k^2 (DD_x1_kappa block) */
   double  c1[3];    /* weight of d/dx_k     (D_x1_kappa block)  */
@@ -508,6 +508,31 @@ int gpk_create3_opx(const gpk_problem3* p, const gpk_operator3x* op, double freq
 /* What any 3-axis handle runs, in this form: a gpk_create3 or gpk_create3_op handle reports its
  * equivalent (the weight under c2 or c1 by its order, the other 0). */
 int gpk_operator_info3x(const gpk_handle3* h, gpk_operator3x* out);
+
+/* Coefficients that vary over the grid: a field a_k(x) on axis k's term and a field rho(x) on the
+ * linear reaction term (Helmholtz in a medium, lap u + k(x)^2 u; heat in a heterogeneous
+ * conductor, u_t - nu(x,y) (u_xx + u_yy); transport in a non-uniform flow; a potential V(x) u).
+ * With T_k = (c2_k D_k^(2) + c1_k D_k^(1)) K_k^{-1} x_k U exactly as on the gpk_create3_opx handle
+ * of the same `op` (constant weights included), the residual on the grid is
+ *     R = a_1 . T_1 + a_2 . T_2 + a_3 . T_3 - F + (r1 + rho) . U + r2 U^2 + r3 U^3
+ * ( . elementwise); the log joint, boundary term, Nb, criterion and loss terms are those of the
+ * opx handle with this R.  The fields are problem data like src: given at the collocation points,
+ * copied at creation, never part of the parameter vector.  One field serves both terms of a
+ * mixed-order axis; r2 and r3 stay constants.  Not expressible: two different fields on the two
+ * terms of one axis (divergence form -div(a grad u)), derivative boundary data. */
+typedef struct gpk_coef3 {
+  const double* a[3]; /* per axis: NULL (identically 1) or n1*n2*n3 values, row-major [i1][i2][i3] like src */
+  const double* rho;  /* NULL (identically 0) or the same layout: + rho . u in the residual               */
+} gpk_coef3;
+/* p and op as on gpk_create3_opx, with its GPK_EINVAL cases; also GPK_EINVAL on a non-finite value
+ * in a given field.  cf == NULL, or all four pointers NULL, is gpk_create3_opx itself: the same
+ * handle, graph and kernels.  gpk_operator_info3x / gpk_operator_info3 report the constant part,
+ * as for the opx handle of the same op.  Every other gpk_*3 call works on such a handle unchanged. */
+int gpk_create3_opv(const gpk_problem3* p, const gpk_operator3x* op, const gpk_coef3* cf,
+                    double freq_scale, gpk_handle3** out);
+/* has[0..2]: axis k has a field; has[3]: rho is present.  Any 3-axis handle; all zeros on a handle
+ * of gpk_create3, gpk_create3_op or gpk_create3_opx. */
+int gpk_coef_info3(const gpk_handle3* h, int32_t has[4]);
 
 int gpk_num_params3(const gpk_handle3* h, int64_t* n);
 int gpk_set_params3(gpk_handle3* h, const double* flat, int64_t n);
