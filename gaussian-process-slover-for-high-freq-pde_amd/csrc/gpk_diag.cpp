@@ -1,5 +1,6 @@
 // gpk_diag.cpp — measurement and diagnostic entry points: per-stage and per-kernel timing, the
-// forward fields, the standalone GEMM, mode-k product and refinement step, the trace hooks.  No
+// forward fields, the standalone GEMM (plain and with the step's epilogues), GEMV, mode-k product
+// and refinement step, the trace hooks.  No
 // solver entry point (gpk_create, gpk_step, gpk_prepare, gpk_loss_grad, gpk_predict, gpk_*3)
 // reaches this file, and it reaches the step only through the functions gpk_host.h declares.
 #include "gpk_host.h"
@@ -626,6 +627,231 @@ int gpk_dgemm(int32_t variant, int32_t M, int32_t N, int32_t K, double alpha, co
   // copied back above is the first launch's)
   if (e == hipSuccess && iters) e = time_launches(0, iters, 1, launch, avg_us);
   return check_launch(e, "gpk_dgemm");
+}
+
+namespace {
+
+// elements a row-major rows x cols block with leading dimension ld spans; 0 when ld is shorter
+// than a row or odd (the kernels' 16-byte operand loads)
+size_t block_extent(int rows, int cols, int ld) {
+  return (ld >= cols && !(ld & 1)) ? (size_t)(rows - 1) * ld + cols : 0;
+}
+
+// the two gate words (gate_open: open when gate[0] * gate[1] > REFINE_COND_LB; a product equal to
+// the bound is closed) of a gate selector, uploaded; GPK_GATE_NONE leaves *gate null
+int upload_gate(CallScratch& tmp, int sel, const double** gate) {
+  *gate = nullptr;
+  if (sel == GPK_GATE_NONE) return GPK_OK;
+  const double w[2] = {1.0, sel == GPK_GATE_OPEN ? 2.0 * REFINE_COND_LB : REFINE_COND_LB};
+  double* d = nullptr;
+  TRY(tmp.upload(&d, w, 2));
+  *gate = d;
+  return GPK_OK;
+}
+
+// a host array (nullable) uploaded for a descriptor's const operand
+int upload_opt(CallScratch& tmp, const double* src, size_t n, const double** dst) {
+  *dst = nullptr;
+  if (!src) return GPK_OK;
+  double* d = nullptr;
+  TRY(tmp.upload(&d, src, n));
+  *dst = d;
+  return GPK_OK;
+}
+
+// no output of a call may be one of its inputs or another output; `inplace` lists the outputs
+// that one input each may equal (C0 == C)
+bool outputs_alias(const std::vector<const void*>& in, const std::vector<const void*>& out,
+                   const std::vector<const void*>& inplace) {
+  for (size_t o = 0; o < out.size(); ++o) {
+    for (size_t q = o + 1; q < out.size(); ++q)
+      if (out[o] == out[q]) return true;
+    size_t same = 0, allowed = 0;
+    for (const void* p : in) same += p == out[o];
+    for (const void* p : inplace) allowed += p == out[o];
+    if (same > allowed) return true;
+  }
+  return false;
+}
+
+}  // namespace
+
+int gpk_dgemm_epi(int32_t variant, int32_t ndesc, gpk_gemm_case* cases, double v) {
+  if (variant < GEMM_SMALL || variant > GEMM_HUGE || ndesc < 1 || ndesc > GEMM_MAX_BATCH || !cases ||
+      !std::isfinite(v))
+    return fail(GPK_EINVAL, "gpk_dgemm_epi: variant 1..3, 1..4 descriptors, finite v");
+  struct Ext { size_t a, b, a2, b2, c, c0, f, y; };
+  Ext ex[GEMM_MAX_BATCH] = {};
+  std::vector<const void*> in, out, inplace;
+  for (int i = 0; i < ndesc; ++i) {
+    gpk_gemm_case& g = cases[i];
+    Ext& e = ex[i];
+    if (g.M <= 0 || g.N <= 0 || g.K <= 0 || g.K2 < 0 || ((g.M | g.N | g.K | g.K2) & 31))
+      return fail(GPK_EINVAL, "gpk_dgemm_epi: M, N, K, K2 must be multiples of 32");
+    GemmDesc shape{};
+    shape.M = g.M; shape.N = g.N;
+    g.tiles = gemm_tiles(shape, variant);
+    if (!g.A || !g.B || !g.C || (g.K2 && (!g.A2 || !g.B2)))
+      return fail(GPK_EINVAL, "gpk_dgemm_epi: NULL operand");
+    if (g.epi < GPK_EPI_STORE || g.epi > GPK_EPI_QUAD || g.gate < GPK_GATE_NONE || g.gate > GPK_GATE_CLOSED)
+      return fail(GPK_EINVAL, "gpk_dgemm_epi: epi must be 0..2 and gate 0..2");
+    if (!std::isfinite(g.alpha) || !std::isfinite(g.alpha2) || !std::isfinite(g.beta))
+      return fail(GPK_EINVAL, "gpk_dgemm_epi: alpha, alpha2 and beta must be finite");
+    e.a = g.ta ? block_extent(g.K, g.M, g.lda) : block_extent(g.M, g.K, g.lda);
+    e.b = g.tb ? block_extent(g.N, g.K, g.ldb) : block_extent(g.K, g.N, g.ldb);
+    e.c = block_extent(g.M, g.N, g.ldc);
+    bool ok = e.a && e.b && e.c;
+    if (g.K2) {
+      e.a2 = g.ta2 ? block_extent(g.K2, g.M, g.lda2) : block_extent(g.M, g.K2, g.lda2);
+      e.b2 = g.tb2 ? block_extent(g.N, g.K2, g.ldb2) : block_extent(g.K2, g.N, g.ldb2);
+      ok = ok && e.a2 && e.b2;
+    }
+    if (g.C0) {
+      e.c0 = block_extent(g.M, g.N, g.ldc0);
+      ok = ok && e.c0 && (g.C0 != g.C || g.ldc0 == g.ldc);
+    }
+    const bool side = g.Y != nullptr, epi_ops = g.F || g.U || g.Q1 || g.Q2;
+    if (epi_ops) {
+      e.f = block_extent(g.M, g.N, g.ldf);
+      ok = ok && e.f;
+    }
+    if (side || g.Ys) {
+      e.y = block_extent(g.M, g.N, g.ldy);
+      ok = ok && e.y;
+    }
+    if (!ok) return fail(GPK_EINVAL, "gpk_dgemm_epi: a leading dimension is odd or shorter than a row");
+    if (g.beta != 0.0 && !g.C0) return fail(GPK_EINVAL, "gpk_dgemm_epi: beta != 0 needs C0");
+    if (side && (g.epi != GPK_EPI_STORE || !g.Ys))
+      return fail(GPK_EINVAL, "gpk_dgemm_epi: Y is the STORE epilogue's side output and needs Ys");
+    if ((g.epi == GPK_EPI_RESID && (!g.F || (g.ac && !g.U))) || (g.epi == GPK_EPI_QUAD && !g.U))
+      return fail(GPK_EINVAL, "gpk_dgemm_epi: RESID needs F (and U with ac), QUAD needs U");
+    if ((g.red && g.epi == GPK_EPI_STORE) || (g.red2 && (g.epi != GPK_EPI_RESID || !g.Q1 || !g.Q2)))
+      return fail(GPK_EINVAL, "gpk_dgemm_epi: red is formed by RESID and QUAD, red2 by RESID from Q1 and Q2");
+    if ((g.red || g.red2) && g.red_cap < g.tiles)
+      return fail(GPK_EINVAL, "gpk_dgemm_epi: red_cap is below the variant's tile count");
+    for (const void* p : {(const void*)g.A, (const void*)g.B, (const void*)g.A2, (const void*)g.B2,
+                          (const void*)g.C0, (const void*)g.F, (const void*)g.U, (const void*)g.Q1,
+                          (const void*)g.Q2, (const void*)g.Ys})
+      if (p) in.push_back(p);
+    for (const void* p : {(const void*)g.C, (const void*)g.Y, (const void*)g.red, (const void*)g.red2})
+      if (p) out.push_back(p);
+    if (g.C0 == g.C) inplace.push_back(g.C);
+  }
+  if (outputs_alias(in, out, inplace))
+    return fail(GPK_EINVAL, "gpk_dgemm_epi: an output is also an input (other than C0 == C) or another output");
+  TRY(check_device(0));
+  DevSwitch dsw(0);
+  CallScratch tmp("gpk_dgemm_epi");
+  const StepScalars hsc{1.0, v, 1.0, 1.0};
+  StepScalars* sc = nullptr;
+  TRY(tmp.upload(&sc, &hsc, 1));
+  GemmDesc d[GEMM_MAX_BATCH] = {};
+  for (int i = 0; i < ndesc; ++i) {
+    const gpk_gemm_case& g = cases[i];
+    const Ext& e = ex[i];
+    GemmDesc& x = d[i];
+    TRY(upload_opt(tmp, g.A, e.a, &x.A));
+    TRY(upload_opt(tmp, g.B, e.b, &x.B));
+    if (g.K2) TRY(upload_opt(tmp, g.A2, e.a2, &x.A2));
+    if (g.K2) TRY(upload_opt(tmp, g.B2, e.b2, &x.B2));
+    TRY(tmp.upload(&x.C, g.C, e.c));
+    if (g.C0 == g.C)
+      x.C0 = x.C;
+    else
+      TRY(upload_opt(tmp, g.C0, e.c0, &x.C0));
+    TRY(upload_opt(tmp, g.F, e.f, &x.F));
+    TRY(upload_opt(tmp, g.U, e.f, &x.U));
+    TRY(upload_opt(tmp, g.Q1, e.f, &x.Q1));
+    TRY(upload_opt(tmp, g.Q2, e.f, &x.Q2));
+    if (g.Y) TRY(upload_opt(tmp, g.Ys, e.y, &x.Ys));
+    if (g.Y) TRY(tmp.upload(&x.Y, g.Y, e.y));
+    if (g.red) TRY(tmp.upload(&x.red, g.red, (size_t)g.red_cap));
+    if (g.red2) TRY(tmp.upload(&x.red2, g.red2, (size_t)g.red_cap));
+    TRY(upload_gate(tmp, g.gate, &x.gate));
+    x.lda = g.lda; x.ta = g.ta ? 1 : 0; x.ldb = g.ldb; x.tb = g.tb ? 1 : 0;
+    x.lda2 = g.lda2; x.ta2 = g.ta2 ? 1 : 0; x.ldb2 = g.ldb2; x.tb2 = g.tb2 ? 1 : 0;
+    x.alpha = g.alpha; x.alpha2 = g.alpha2; x.beta = g.beta; x.ldc0 = g.ldc0; x.ldc = g.ldc;
+    x.M = g.M; x.N = g.N; x.K = g.K; x.K2 = g.K2; x.epi = g.epi; x.ac = g.ac ? 1 : 0;
+    x.ldf = g.ldf; x.vscale = g.vscale ? 1 : 0; x.vscale2 = g.vscale2 ? 1 : 0; x.ldy = g.ldy;
+  }
+  hipError_t e = launch_gemm_auto(d, ndesc, sc, 0, variant);
+  if (e == hipSuccess) e = hipDeviceSynchronize();
+  for (int i = 0; i < ndesc && e == hipSuccess; ++i) {
+    const gpk_gemm_case& g = cases[i];
+    e = hipMemcpy(g.C, d[i].C, ex[i].c * 8, hipMemcpyDeviceToHost);
+    if (e == hipSuccess && g.Y) e = hipMemcpy(g.Y, d[i].Y, ex[i].y * 8, hipMemcpyDeviceToHost);
+    if (e == hipSuccess && g.red) e = hipMemcpy(g.red, d[i].red, (size_t)g.red_cap * 8, hipMemcpyDeviceToHost);
+    if (e == hipSuccess && g.red2) e = hipMemcpy(g.red2, d[i].red2, (size_t)g.red_cap * 8, hipMemcpyDeviceToHost);
+  }
+  return check_launch(e, "gpk_dgemm_epi");
+}
+
+int gpk_dgemv_epi(int32_t p, int32_t rows, const double* A, const int32_t* cid, const double* cv,
+                  int32_t ncls, double cdiag, int32_t ident, int32_t lda, const double* x, double alpha,
+                  const double* C0, double beta, int32_t epi, int32_t ac, const double* F, const double* U,
+                  const double* U0, const double* Q1, const double* Q2, double* red, double* red2,
+                  int32_t gate, double* y) {
+  if (p <= 0 || (p & 31) || lda < p || (lda & 31) || rows < 1 || rows > p)
+    return fail(GPK_EINVAL, "gpk_dgemv_epi: p and lda multiples of 32, lda >= p, 1 <= rows <= p");
+  if (!x || !y || (!A && (!cid || !cv || ncls < 1)) || (A && cid))
+    return fail(GPK_EINVAL, "gpk_dgemv_epi: needs x, y and either A or the class form (cid, cv, ncls >= 1)");
+  if (epi < GPK_EPI_STORE || epi > GPK_EPI_QUAD || gate < GPK_GATE_NONE || gate > GPK_GATE_CLOSED)
+    return fail(GPK_EINVAL, "gpk_dgemv_epi: epi must be 0..2 and gate 0..2");
+  if (!std::isfinite(alpha) || !std::isfinite(beta) || !std::isfinite(cdiag))
+    return fail(GPK_EINVAL, "gpk_dgemv_epi: alpha, beta and cdiag must be finite");
+  if (beta != 0.0 && !C0) return fail(GPK_EINVAL, "gpk_dgemv_epi: beta != 0 needs C0");
+  if ((epi == GPK_EPI_RESID && (!F || (ac && !U))) || (epi == GPK_EPI_QUAD && !U))
+    return fail(GPK_EINVAL, "gpk_dgemv_epi: RESID needs F (and U with ac), QUAD needs U");
+  if ((red && epi == GPK_EPI_STORE) || (red2 && (!Q1 || !Q2)))
+    return fail(GPK_EINVAL, "gpk_dgemv_epi: red is formed by RESID and QUAD, red2 from Q1 and Q2");
+  const size_t nm = (size_t)(rows - 1) * lda + p;
+  if (cid)
+    for (int i = 0; i < rows; ++i)
+      for (int j = 0; j < p; ++j)
+        if (cid[(size_t)i * lda + j] >= ncls) return fail(GPK_EINVAL, "gpk_dgemv_epi: class id >= ncls");
+  std::vector<const void*> in, out, inplace;
+  for (const void* q : {(const void*)A, (const void*)cv, (const void*)x, (const void*)C0, (const void*)F,
+                        (const void*)U, (const void*)U0, (const void*)Q1, (const void*)Q2})
+    if (q) in.push_back(q);
+  for (const void* q : {(const void*)y, (const void*)red, (const void*)red2})
+    if (q) out.push_back(q);
+  if (C0 == y) inplace.push_back(y);
+  if (outputs_alias(in, out, inplace) || (const void*)cid == (const void*)y)
+    return fail(GPK_EINVAL, "gpk_dgemv_epi: an output is also an input (other than C0 == y) or another output");
+  TRY(check_device(0));
+  DevSwitch dsw(0);
+  CallScratch tmp("gpk_dgemv_epi");
+  GemvDesc d{};
+  const int nblk = gemv_blocks(rows);
+  TRY(upload_opt(tmp, A, nm, &d.A));
+  if (cid) {
+    int* dcid = nullptr;
+    TRY(tmp.upload(&dcid, reinterpret_cast<const int*>(cid), nm));
+    d.cid = dcid;
+    TRY(upload_opt(tmp, cv, (size_t)ncls, &d.cv));
+  }
+  TRY(upload_opt(tmp, x, (size_t)p, &d.x));
+  TRY(tmp.upload(&d.y, y, (size_t)rows));
+  if (C0 == y)
+    d.C0 = d.y;
+  else
+    TRY(upload_opt(tmp, C0, (size_t)rows, &d.C0));
+  TRY(upload_opt(tmp, F, (size_t)rows, &d.F));
+  TRY(upload_opt(tmp, U, (size_t)rows, &d.U));
+  TRY(upload_opt(tmp, U0, (size_t)rows, &d.U0));
+  TRY(upload_opt(tmp, Q1, (size_t)rows, &d.Q1));
+  TRY(upload_opt(tmp, Q2, (size_t)rows, &d.Q2));
+  if (red) TRY(tmp.upload(&d.red, red, (size_t)nblk));
+  if (red2) TRY(tmp.upload(&d.red2, red2, (size_t)nblk));
+  TRY(upload_gate(tmp, gate, &d.gate));
+  d.lda = lda; d.p = p; d.rows = rows; d.alpha = alpha; d.beta = beta; d.epi = epi; d.ac = ac ? 1 : 0;
+  d.cdiag = cdiag; d.ident = ident ? 1 : 0;
+  hipError_t e = launch_gemv(d, 0);
+  if (e == hipSuccess) e = hipDeviceSynchronize();
+  if (e == hipSuccess) e = hipMemcpy(y, d.y, (size_t)rows * 8, hipMemcpyDeviceToHost);
+  if (e == hipSuccess && red) e = hipMemcpy(red, d.red, (size_t)nblk * 8, hipMemcpyDeviceToHost);
+  if (e == hipSuccess && red2) e = hipMemcpy(red2, d.red2, (size_t)nblk * 8, hipMemcpyDeviceToHost);
+  return check_launch(e, "gpk_dgemv_epi");
 }
 
 int gpk_mode_gemm(int32_t variant, int32_t k, int32_t d1, int32_t d2, int32_t d3, int32_t m, double alpha,

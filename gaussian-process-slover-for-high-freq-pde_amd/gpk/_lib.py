@@ -104,6 +104,26 @@ class gpk_coef3(ctypes.Structure):
     _fields_ = [("a", ctypes.POINTER(ctypes.c_double) * 3), ("rho", ctypes.POINTER(ctypes.c_double))]
 
 
+class gpk_gemm_case(ctypes.Structure):
+    _fields_ = [
+        ("M", ctypes.c_int32), ("N", ctypes.c_int32), ("K", ctypes.c_int32), ("K2", ctypes.c_int32),
+        ("A", _dp), ("B", _dp), ("A2", _dp), ("B2", _dp),
+        ("lda", ctypes.c_int32), ("ldb", ctypes.c_int32), ("lda2", ctypes.c_int32), ("ldb2", ctypes.c_int32),
+        ("ta", ctypes.c_int32), ("tb", ctypes.c_int32), ("ta2", ctypes.c_int32), ("tb2", ctypes.c_int32),
+        ("alpha", ctypes.c_double), ("alpha2", ctypes.c_double), ("beta", ctypes.c_double),
+        ("C0", _dp), ("C", _dp),
+        ("ldc0", ctypes.c_int32), ("ldc", ctypes.c_int32),
+        ("epi", ctypes.c_int32), ("ac", ctypes.c_int32),
+        ("F", _dp), ("U", _dp), ("Q1", _dp), ("Q2", _dp),
+        ("Ys", _dp), ("Y", _dp),
+        ("ldf", ctypes.c_int32), ("ldy", ctypes.c_int32),
+        ("vscale", ctypes.c_int32), ("vscale2", ctypes.c_int32),
+        ("gate", ctypes.c_int32), ("red_cap", ctypes.c_int32),
+        ("red", _dp), ("red2", _dp),
+        ("tiles", ctypes.c_int32),
+    ]
+
+
 EXPORTS = {
     "gpk_abi_version": ([], ctypes.c_int),
     "gpk_last_error": ([], ctypes.c_char_p),
@@ -202,6 +222,12 @@ EXPORTS = {
                    ctypes.c_int32, ctypes.c_int32, _dp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
                    ctypes.c_double, _dp, ctypes.c_int32, ctypes.c_int32, _dp, ctypes.c_int32, ctypes.c_int32,
                    ctypes.c_double, _dp, _dp, ctypes.c_int32, ctypes.c_int32, _dp], ctypes.c_int),
+    "gpk_dgemm_epi": ([ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(gpk_gemm_case), ctypes.c_double],
+                      ctypes.c_int),
+    "gpk_dgemv_epi": ([ctypes.c_int32, ctypes.c_int32, _dp, _ip, _dp, ctypes.c_int32, ctypes.c_double,
+                       ctypes.c_int32, ctypes.c_int32, _dp, ctypes.c_double, _dp, ctypes.c_double,
+                       ctypes.c_int32, ctypes.c_int32, _dp, _dp, _dp, _dp, _dp, _dp, _dp, ctypes.c_int32, _dp],
+                      ctypes.c_int),
     "gpk_wide_schedule": ([ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(ctypes.c_uint32), ctypes.c_int64],
                           ctypes.c_int),
     "gpk_trace_reset": ([], ctypes.c_int),
@@ -267,6 +293,125 @@ def dgemm(A, B, ta=False, tb=False, alpha=1.0, A2=None, B2=None, ta2=False, tb2=
                            dptr(C) if C0 is not None else None, dptr(C), N, iters,
                            ctypes.byref(us) if iters else None))
     return C, (us.value if iters else None)
+
+
+EPI_STORE, EPI_RESID, EPI_QUAD = 0, 1, 2  # include/gpk.h GPK_EPI_*
+GATE_NONE, GATE_OPEN, GATE_CLOSED = 0, 1, 2  # GPK_GATE_*
+GEMM_TILE_SIDE = {GEMM_SMALL: 16, GEMM_BIG: 64, GEMM_TILE128: 128}
+SENTINEL = -1.25e300  # what dgemm_epi / dgemv_epi fill their outputs with before the launch
+
+
+def _padded(a, pad):
+    """A C-contiguous copy of the 2D array a in a buffer with `pad` more columns (SENTINEL there);
+    returns (buffer, view of the copy)."""
+    a = np.asarray(a, dtype=np.float64)
+    buf = np.full((a.shape[0], a.shape[1] + pad), SENTINEL)
+    buf[:, :a.shape[1]] = a
+    return buf, buf[:, :a.shape[1]]
+
+
+def gemm_case_shape(c):
+    """(M, N, K, K2) of a dgemm_epi case."""
+    A, B = np.asarray(c["A"]), np.asarray(c["B"])
+    M, K = (A.shape[1], A.shape[0]) if c.get("ta") else A.shape
+    N = B.shape[0] if c.get("tb") else B.shape[1]
+    K2 = 0
+    if c.get("A2") is not None:
+        A2 = np.asarray(c["A2"])
+        K2 = A2.shape[0] if c.get("ta2") else A2.shape[1]
+    return M, N, K, K2
+
+
+def dgemm_epi(variant, cases, v=1.0, spare=2):
+    """One launch of the step's GEMM kernels with their fused epilogues (gpk_dgemm_epi) on a batch of
+    1..4 cases.  A case is a dict: A, B [ta, tb], optional second product A2, B2 [ta2, tb2], alpha,
+    alpha2, beta, C0 [inplace: C0 is passed as C itself], epi [ac, F, U, Q1, Q2], vscale, vscale2,
+    Ys (asks for the side output Y), red / red2 (True asks for the partials), gate, and pad (extra
+    columns in every array's leading dimension).  Outputs are filled with SENTINEL before the call
+    (C with C0 when inplace); the partial arrays have `spare` entries beyond the tile count.
+    Returns one dict per case: C, Y, red, red2 (None where not asked for), tiles, and the whole
+    padded buffers C_buf, Y_buf."""
+    n = len(cases)
+    arr = (gpk_gemm_case * max(n, 1))()
+    outs, keep = [], []
+    for g, c in zip(arr, cases):
+        pad = int(c.get("pad", 0))
+        M, N, K, K2 = gemm_case_shape(c)
+        g.M, g.N, g.K, g.K2 = M, N, K, K2
+
+        def put(name, ldname=None):
+            if c.get(name) is None:
+                return None
+            buf, view = _padded(c[name], pad)
+            keep.append(buf)
+            setattr(g, name, dptr(buf))
+            if ldname:
+                setattr(g, ldname, buf.shape[1])
+            return view
+
+        put("A", "lda"), put("B", "ldb"), put("A2", "lda2"), put("B2", "ldb2")
+        put("F", "ldf"), put("U", "ldf"), put("Q1", "ldf"), put("Q2", "ldf"), put("Ys", "ldy")
+        g.ta, g.tb, g.ta2, g.tb2 = (int(bool(c.get(k))) for k in ("ta", "tb", "ta2", "tb2"))
+        g.alpha, g.alpha2, g.beta = float(c.get("alpha", 1.0)), float(c.get("alpha2", 1.0)), float(c.get("beta", 0.0))
+        g.epi, g.ac = int(c.get("epi", EPI_STORE)), int(bool(c.get("ac")))
+        g.vscale, g.vscale2, g.gate = int(bool(c.get("vscale"))), int(bool(c.get("vscale2"))), int(c.get("gate", GATE_NONE))
+        inplace = bool(c.get("inplace"))
+        Cbuf, C = _padded(c["C0"] if inplace else np.full((M, N), SENTINEL), pad)
+        g.C, g.ldc = dptr(Cbuf), Cbuf.shape[1]
+        if inplace:
+            g.C0, g.ldc0 = g.C, g.ldc
+        else:
+            put("C0", "ldc0")
+        out = {"C": C, "C_buf": Cbuf, "Y": None, "Y_buf": None, "red": None, "red2": None}
+        if c.get("Ys") is not None:
+            out["Y_buf"], out["Y"] = _padded(np.full((M, N), SENTINEL), pad)
+            g.Y = dptr(out["Y_buf"])
+        t = GEMM_TILE_SIDE.get(variant, 16)
+        g.red_cap = -(-M // t) * -(-N // t) + spare
+        for name in ("red", "red2"):
+            if c.get(name):
+                out[name] = np.full(g.red_cap, SENTINEL)
+                setattr(g, name, dptr(out[name]))
+        outs.append(out)
+    check(load().gpk_dgemm_epi(int(variant), n, arr, float(v)))
+    for g, out in zip(arr, outs):
+        out["tiles"] = g.tiles
+    return outs
+
+
+def dgemv_epi(x, A=None, cid=None, cv=None, cdiag=0.0, ident=0, rows=None, alpha=1.0, C0=None, inplace=False,
+              beta=0.0, epi=EPI_STORE, ac=False, F=None, U=None, U0=None, Q1=None, Q2=None, red=False,
+              red2=False, gate=GATE_NONE, pad=0):
+    """One launch of the step's GEMV with its epilogues (gpk_dgemv_epi): y = alpha A x + ... for the
+    matrix A (rows x p) or the class form (cid int32 rows x p, cv, cdiag, ident).  inplace passes C0
+    as y itself; pad adds columns to the operand's leading dimension.  y and the partials are
+    filled with SENTINEL before the call.  Returns (y, red, red2), None where not asked for."""
+    x = f64(x).reshape(-1)
+    p = x.size
+    op = np.asarray(A if A is not None else cid)
+    rows = op.shape[0] if rows is None else int(rows)
+    if A is not None:
+        opbuf, _ = _padded(np.asarray(A)[:rows], pad)
+        pa, pc, pv, ncls = dptr(opbuf), None, None, 0
+    else:
+        opbuf = np.full((rows, op.shape[1] + pad), -1, dtype=np.int32)
+        opbuf[:, :op.shape[1]] = op[:rows]
+        cv = f64(cv).reshape(-1)
+        pa, pc, pv, ncls = None, opbuf.ctypes.data_as(_ip), dptr(cv), cv.size
+    vec = {k: (None if a is None else f64(a).reshape(-1)) for k, a in
+           dict(C0=C0, F=F, U=U, U0=U0, Q1=Q1, Q2=Q2).items()}
+    y = vec["C0"].copy() if inplace else np.full(rows, SENTINEL)
+    ptr = {k: (None if a is None else dptr(a)) for k, a in vec.items()}
+    if inplace:
+        ptr["C0"] = dptr(y)
+    nblk = (rows + 3) // 4
+    r1 = np.full(nblk, SENTINEL) if red else None
+    r2 = np.full(nblk, SENTINEL) if red2 else None
+    check(load().gpk_dgemv_epi(p, rows, pa, pc, pv, ncls, float(cdiag), int(ident), opbuf.shape[1], dptr(x),
+                               float(alpha), ptr["C0"], float(beta), int(epi), int(bool(ac)), ptr["F"], ptr["U"],
+                               ptr["U0"], ptr["Q1"], ptr["Q2"], None if r1 is None else dptr(r1),
+                               None if r2 is None else dptr(r2), int(gate), dptr(y)))
+    return y, r1, r2
 
 
 MODE_SLAB, MODE_PERMUTE, MODE_SLAB32, MODE_SLAB64 = 0, 1, 2, 3

@@ -367,6 +367,71 @@ int gpk_dgemm(int32_t variant, int32_t M, int32_t N, int32_t K, double alpha, co
               int32_t ldb2, int32_t tb2, double beta, const double* C0, double* C, int32_t ldc,
               int32_t iters, double* avg_us);
 
+/* One descriptor of gpk_dgemm_epi: the product of gpk_dgemm with one of the step's fused
+ * epilogues.  Everything is a host array, row-major; M, N, K, K2 multiples of 32 (K2 = 0: no
+ * second product, A2 / B2 unused), leading dimensions even and at least a row long.
+ *   epi GPK_EPI_STORE  C = alpha P1 + alpha2 P2 + beta C0
+ *       GPK_EPI_RESID  C = alpha P1 + alpha2 P2 - F [+ u (u^2 - 1), u = U, when ac];
+ *                      red[tile] = sum C^2, red2[tile] = sum Q1 Q2  (beta is not applied)
+ *       GPK_EPI_QUAD   C = alpha P1 + alpha2 P2 + beta C0; red[tile] = sum C U
+ *   vscale / vscale2   alpha / alpha2 multiplied by v (gpk_dgemm_epi's argument)
+ *   Y (STORE only)     Y = 0.5 Ys + v C, C the stored value
+ *   gate               GPK_GATE_NONE, GPK_GATE_OPEN (identical to none) or GPK_GATE_CLOSED: the
+ *                      launch writes nothing, every output keeps what it was uploaded with
+ * C0 is NULL (beta must be 0) or has C's shape with ldc0; C0 == C (ldc0 == ldc) is the in-place
+ * update.  F, U, Q1, Q2 are M x N with ldf; Ys, Y with ldy.  red / red2 (NULL: not formed) hold
+ * red_cap entries; tile t of the variant's square tiles in row-major order (edge tiles sum rows
+ * < M and columns < N only) goes to entry t.  C, Y, red and red2 are uploaded before the launch
+ * and copied back after it, so entries the launch does not write keep the caller's values.
+ * tiles (output) is the variant's tile count of M x N, set whenever variant, M and N are valid. */
+enum { GPK_EPI_STORE = 0, GPK_EPI_RESID = 1, GPK_EPI_QUAD = 2 };
+enum { GPK_GATE_NONE = 0, GPK_GATE_OPEN = 1, GPK_GATE_CLOSED = 2 };
+typedef struct gpk_gemm_case {
+  int32_t M, N, K, K2;
+  const double* A; const double* B; const double* A2; const double* B2;
+  int32_t lda, ldb, lda2, ldb2;
+  int32_t ta, tb, ta2, tb2;
+  double alpha, alpha2, beta;
+  const double* C0; double* C;
+  int32_t ldc0, ldc;
+  int32_t epi, ac;
+  const double* F; const double* U; const double* Q1; const double* Q2;
+  const double* Ys; double* Y;
+  int32_t ldf, ldy;
+  int32_t vscale, vscale2;
+  int32_t gate, red_cap;
+  double* red; double* red2;
+  int32_t tiles;  /* output */
+} gpk_gemm_case;
+
+/* One launch of ndesc (1..4) descriptors on GEMM variant 1, 2 or 3 (gpk_dgemm's numbers; the
+ * 128x128 tile runs a dual product as two passes and groups the batch by transpose signature),
+ * on device 0, for tests: the epilogues, partial slots, edge tiles, gate and batching exactly as
+ * the step launches them.  v is the step scalar e^{log v} that vscale, vscale2 and Y read.
+ * Every argument is validated before any device work.  Refused with GPK_EINVAL, because the
+ * kernels do not support it: Y with an epilogue other than STORE; red with STORE or red2 without
+ * RESID; partials with red_cap below the tile count; sizes that are not multiples of 32; odd
+ * leading dimensions; beta != 0 without C0; an output (C, Y, red, red2) that is also an input
+ * of the batch (other than C0 == C) or another output of it. */
+int gpk_dgemm_epi(int32_t variant, int32_t ndesc, gpk_gemm_case* cases, double v);
+
+/* One launch of the step's GEMV (the 1D solver's products) on host operands, device 0, for
+ * tests: y = alpha A x + beta C0 with gpk_gemm_case's epilogues on vectors --
+ * RESID y -= F [+ u (u^2 - 1), u = U + U0 (U0 nullable)], red[b] = sum y^2; QUAD red[b] = sum y U;
+ * red2[b] = sum Q1 Q2 (any epilogue); b = the block of 4 consecutive rows, red / red2 (nullable)
+ * hold (rows + 3) / 4 entries.  The operand is the matrix A (rows x p, leading dimension lda), or,
+ * when A is NULL, the class form: A[i][j] = cv[cid[i lda + j]] for ids 0 <= id < ncls, 0 for
+ * negative (pad) ids, and on the diagonal + cdiag (pads: 1) when ident = 1.  p and lda multiples
+ * of 32, lda >= p, 1 <= rows <= p.  C0 (NULL: beta must be 0) may equal y.  y, red and red2 are
+ * uploaded before the launch; a closed gate (GPK_GATE_CLOSED) leaves y as uploaded (the
+ * partials are formed regardless).  Refused with GPK_EINVAL: red with STORE, a class id >=
+ * ncls, y or a partial array that is also an input (other than C0 == y). */
+int gpk_dgemv_epi(int32_t p, int32_t rows, const double* A, const int32_t* cid, const double* cv,
+                  int32_t ncls, double cdiag, int32_t ident, int32_t lda, const double* x, double alpha,
+                  const double* C0, double beta, int32_t epi, int32_t ac, const double* F, const double* U,
+                  const double* U0, const double* Q1, const double* Q2, double* red, double* red2,
+                  int32_t gate, double* y);
+
 /* The 128-wide SPD inverse's two-sweep update schedule (host only, no device): for T2 128-tiles
  * per dimension, T2 rows of wide_sched_stride(T2) = 2 + T2 (T2 + 1) / 2 words -- per sweep k the
  * tile count, the next pivot tile's entry, then the entries J | I << 8 | two << 16 | c0 << 18 |

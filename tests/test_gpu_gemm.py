@@ -11,6 +11,13 @@ beta C0 and the in-place update C += op(A) op(B).
 
 Bar: max |C - C_ref| <= 64 K eps max(|A|)max(|B|) -- fp64 summation of K products of bounded
 operands in any order (the kernels sum in MFMA k-slot order).
+
+gpk_dgemm hard-wires the plain store epilogue of one descriptor.  The fused epilogues (RESID, QUAD,
+the side output Y, vscale, the gate, per-tile partials, batches, the two-pass dual product) and the
+GEMV are pinned in tests/test_gpu_gemm_epilogues.py: bit for bit on integer operands with
+power-of-two scalars, where every intermediate is exactly representable and the summation order
+cannot matter (proved per case in tests/test_gemm_epi_ref.py), and at derived rounding bars on
+real operands.
 """
 import numpy as np
 import pytest
