@@ -82,6 +82,14 @@ struct gpk_handle3 {
   // field, W_k = a_k R (W[1] permuted).  They are allocations of their own: Rx / Ryp / Rz are the
   // refinement's residual scratch after k3_combine (build_refine).
   double *cf[3] = {}, *rho = nullptr, *W[3] = {};
+  // gpk_create3_opn: derivative data on the faces of dfaces (0: none, and nothing below is
+  // allocated or launched).  face[k]: axis k's rows d_f, residual planes r_f and partials, all
+  // allocations of their own (Rx / Ryp / Rz and T* are refinement scratch at various points);
+  // bt: the value gap and the derivative gap of the last step; nd: the derivative faces' entries
+  int dfaces = 0;
+  double *dvals = nullptr, *bt = nullptr, nd = 0.0;
+  K3FaceAxis face[3] = {};
+  int fpart[3] = {}, fchunk[3] = {};
   double *GK[3] = {}, *GD[3] = {};
   double *red_egap = nullptr, *red_quad = nullptr;
   int nred = 0;
@@ -297,6 +305,17 @@ int enqueue_step3(gpk_handle3* h, int apply) {
   TRY(launch_stage(h, 0));
   TRY(check_launch(k3_launch_permute(h->Up, h->Upp, g, h->s), "k3_permute"));
   TRY(launch_stage(h, 1));
+  // derivative faces: the rows d_f, then g_f and r_f from A_1, A_2 and A_3 (all formed by now)
+  if (h->dfaces) {
+    K3FaceRows FR{};
+    for (int a = 0; a < 3; ++a) {
+      FR.x[a] = h->x[a]; FR.n[a] = g.n[a]; FR.p[a] = g.p[a]; FR.row[a] = const_cast<double*>(h->face[a].row);
+    }
+    FR.kc = h->kc; FR.q = q; FR.dfaces = h->dfaces;
+    TRY(check_launch(k3_launch_face_row(kind, FR, h->s), "k3_face_row"));
+    for (int a = 0; a < 3; ++a)
+      if (h->fpart[a]) TRY(check_launch(k3_launch_face_gap(h->face[a], a == 2, h->s), "k3_face_gap"));
+  }
   TRY(check_launch(k3_launch_permute(h->Tm, h->Tp, g, h->s), "k3_permute"));
   TRY(launch_stage(h, 2));
   K3Combine C{};
@@ -312,14 +331,21 @@ int enqueue_step3(gpk_handle3* h, int apply) {
     TRY(check_launch(k3_launch_combine(C, h->s), "k3_combine"));
   }
   // reverse products and G_K, G_D
-  for (int k = 3; k < (int)h->stages.size(); ++k) TRY(launch_stage(h, k));
+  // (T_k takes the derivative faces' term before X_k = K_k^{-1} x_k T_k and its refinement read it)
+  for (int k = 3; k < (int)h->stages.size(); ++k) {
+    TRY(launch_stage(h, k));
+    for (int a = 0; a < 3 && k == 3; ++a)
+      if (h->fpart[a])
+        TRY(check_launch(k3_launch_face_back(h->face[a], a == 2, h->sc, h->prob.llk_weight, h->s), "k3_face_back"));
+  }
   // kernel-parameter contraction (the 2-axis kernels: axes 1-2, then axis 3)
+  const int fb = h->dfaces ? K3_FACE_TAIL_BLOCKS : 0;  // + blocks of partials per axis: the face rows' (k3_face_tail)
   PGradArgs pg[3] = {};
   for (int a = 0; a < 3; ++a) {
     pg[a].x = h->x[a]; pg[a].n = g.n[a]; pg[a].p = g.p[a]; pg[a].kc = h->kc + a;
     pg[a].GK = h->GK[a]; pg[a].GD = h->GD[a]; pg[a].deriv = h->mode[a];
     pg[a].c2 = h->c2[a]; pg[a].c1 = h->c1[a];
-    pg[a].part = h->pgpart + (size_t)a * h->bpa * 3 * QMAX;
+    pg[a].part = h->pgpart + (size_t)a * (h->bpa + fb) * 3 * QMAX;
   }
   if (h->mode[0] == h->mode[1]) {
     TRY(check_launch(launch_pgrad(kind, q, 0, pg, 2, h->bpa, h->sc, h->s), "pgrad"));
@@ -328,7 +354,17 @@ int enqueue_step3(gpk_handle3* h, int apply) {
     TRY(check_launch(launch_pgrad(kind, q, 0, pg + 1, 1, h->bpa, h->sc, h->s), "pgrad"));
   }
   TRY(check_launch(launch_pgrad(kind, q, 0, pg + 2, 1, h->bpa, h->sc, h->s), "pgrad"));
-  TRY(check_launch(launch_reduce_parts(h->pgpart, h->bpa, 3, q, h->pg, h->s), "reduce_parts"));
+  if (fb) {
+    K3FaceTail T{};
+    for (int a = 0; a < 3; ++a) {
+      T.ax[a] = h->face[a]; T.x[a] = h->x[a]; T.npart[a] = h->fpart[a];
+      T.out[a] = h->pgpart + ((size_t)a * (h->bpa + fb) + h->bpa) * 3 * QMAX;
+      if (h->fchunk[a] > 1) TRY(check_launch(k3_launch_face_colsum(h->face[a], h->fchunk[a], h->s), "k3_face_colsum"));
+    }
+    T.kc = h->kc; T.sc = h->sc; T.llk_weight = h->prob.llk_weight; T.q = q; T.bgap = h->bgap; T.bt = h->bt;
+    TRY(check_launch(k3_launch_face_tail(kind, T, h->s), "k3_face_tail"));
+  }
+  TRY(check_launch(launch_reduce_parts(h->pgpart, h->bpa + fb, 3, q, h->pg, h->s), "reduce_parts"));
   // loss + small-parameter Adam, then dL/dU + Adam on U (U is read by nothing after this)
   K3Final F{};
   F.g = g; F.hyper = AdamHyper{h->prob.lr, h->prob.b1, h->prob.b2, h->prob.eps};
@@ -339,7 +375,7 @@ int enqueue_step3(gpk_handle3* h, int apply) {
   F.pg = h->pg; F.kc = h->kc; F.sc = h->sc; F.bgap = h->bgap;
   F.off_tau = h->off_tau; F.off_v = h->off_v; F.off_small = (int)h->nu; F.nsmall = h->nsmall;
   F.params = h->params; F.grad = h->grad; F.m = h->m; F.v = h->v;
-  F.losses = h->losses; F.loss_slot = h->loss_slot; F.diag = h->diag;
+  F.losses = h->losses; F.loss_slot = h->loss_slot; F.diag = h->diag; F.nb_extra = h->nd;
   TRY(check_launch(k3_launch_finalize(F, h->s), "k3_finalize"));
   K3AdamU A{};
   A.g = g; A.hyper = F.hyper; A.llk_weight = h->prob.llk_weight; A.apply = apply; A.eq = C.eq;
@@ -407,7 +443,7 @@ int check_problem3(const gpk_problem3* p) {
 // is its one-order-per-axis part, a mixed axis entered as order 0 with weight 1.0) and
 // gpk_create3_opv (cf: the fields it was given, at least one of them)
 int create3(const gpk_problem3* p, const gpk_operator3* op, double freq_scale, gpk_handle3** out,
-            const gpk_operator3x* opx = nullptr, const gpk_coef3* cf = nullptr) {
+            const gpk_operator3x* opx = nullptr, const gpk_coef3* cf = nullptr, const gpk_bdata3* bd = nullptr) {
   TRY(check_problem3(p));
   const int ns[3] = {p->n1, p->n2, p->n3};
   TRY(check_device(p->device));
@@ -481,7 +517,7 @@ int create3(const gpk_problem3* p, const gpk_operator3* op, double freq_scale, g
   h->nred = k3_combine_blocks(g);
   A3_(h->red_egap, h->nred); A3_(h->red_quad, h->nred);
   h->bpa = std::max(pgrad_blocks(ns[0]), std::max(pgrad_blocks(ns[1]), pgrad_blocks(ns[2])));
-  A3_(h->pgpart, (size_t)3 * h->bpa * 3 * QMAX);
+  A3_(h->pgpart, (size_t)3 * (h->bpa + (bd ? K3_FACE_TAIL_BLOCKS : 0)) * 3 * QMAX);
   A3_(h->pg, (size_t)3 * 3 * QMAX);
   // the fields: zero-padded natural-layout tensors, and W_k for each axis that has one
   if (cf) {
@@ -499,6 +535,41 @@ int create3(const gpk_problem3* p, const gpk_operator3* op, double freq_scale, g
       if (hipMemcpyAsync(*dst[k], fp.data(), np * sizeof(double), hipMemcpyHostToDevice, h->s) != hipSuccess ||
           hipStreamSynchronize(h->s) != hipSuccess)
         return bail(fail(GPK_EHIP, "upload of a coefficient field failed"));
+    }
+  }
+  // derivative data: the six-face array as given (entries of faces outside dfaces are never read),
+  // and per axis with such a face the rows, residual planes and partials
+  if (bd) {
+    static_assert(K3_FACE_MAX_N == K3_MAX_N, "k3_face_tail's LDS rows hold one axis");
+    h->dfaces = bd->dfaces;
+    A3_(h->dvals, nb); A3_(h->bt, 2);
+    if (hipMemcpyAsync(h->dvals, bd->dvals, nb * sizeof(double), hipMemcpyHostToDevice, h->s) != hipSuccess ||
+        hipStreamSynchronize(h->s) != hipSuccess)
+      return bail(fail(GPK_EHIP, "upload of the derivative data failed"));
+    const int pl[3][2] = {{1, 2}, {0, 2}, {0, 1}};  // the face plane's axes
+    long off = 0;
+    for (int a = 0; a < 3; ++a) {
+      K3FaceAxis& F = h->face[a];
+      F.nk = ns[a]; F.pk = g.p[a];
+      F.na = ns[pl[a][0]]; F.nb = ns[pl[a][1]]; F.pa = g.p[pl[a][0]]; F.pb = g.p[pl[a][1]];
+      const long fsz = (long)F.na * F.nb;
+      for (int s2 = 0; s2 < 2; ++s2) {
+        F.on[s2] = (bd->dfaces >> (2 * a + s2)) & 1;
+        F.h[s2] = h->dvals + off + s2 * fsz;
+        if (F.on[s2]) h->nd += (double)fsz;
+      }
+      off += 2 * fsz;
+      F.A = a == 0 ? h->A1 : a == 1 ? h->A2p : h->A3;
+      F.T = a == 0 ? h->T1 : a == 1 ? h->T2p : h->T3;
+      if (!F.on[0] && !F.on[1]) continue;
+      h->fpart[a] = k3_face_gap_blocks(F, a == 2);
+      h->fchunk[a] = k3_face_back_blocks(F, a == 2);
+      double *row = nullptr;
+      A3_(row, (size_t)2 * F.pk); A3_(F.r, (size_t)2 * F.pa * F.pb);
+      A3_(F.part, h->fpart[a]); A3_(F.gv, (size_t)h->fchunk[a] * 2 * F.pk);
+      F.gs = F.gv;  // (one block: its partials are the sums)
+      if (h->fchunk[a] > 1) A3_(F.gs, (size_t)2 * F.pk);
+      F.row = row;
     }
   }
 #undef A3_
@@ -633,6 +704,45 @@ int gpk_create3_opv(const gpk_problem3* p, const gpk_operator3x* op, const gpk_c
   return create3(p, &o, freq_scale, out, op, cf);
 }
 
+int gpk_create3_opn(const gpk_problem3* p, const gpk_operator3x* op, const gpk_coef3* cf, const gpk_bdata3* bd,
+                    double freq_scale, gpk_handle3** out) {
+  if (!bd || bd->dfaces == 0) return gpk_create3_opv(p, op, cf, freq_scale, out);
+  if (!p || !op || !out) return fail(GPK_EINVAL, "NULL argument");
+  *out = nullptr;
+  if (bd->dfaces < 0 || bd->dfaces > K3_ALL_FACES) return fail(GPK_EINVAL, "gpk_create3_opn: dfaces must be in 0..63");
+  if (!bd->dvals) return fail(GPK_EINVAL, "gpk_create3_opn: dvals is NULL with dfaces != 0");
+  // the operator's own checks, with faces = 0 allowed here (data on derivatives alone)
+  gpk_operator3x o = *op;
+  if (o.faces == 0) o.faces = bd->dfaces;
+  TRY(check_operator3x(p, &o, out, "gpk_create3_opn"));
+  TRY(check_problem3(p));
+  {
+    const long fs[3] = {(long)p->n2 * p->n3, (long)p->n1 * p->n3, (long)p->n1 * p->n2};
+    const double* d = bd->dvals;
+    for (int f = 0; f < 6; d += fs[f / 2], ++f)
+      if (((bd->dfaces >> f) & 1) && !std::all_of(d, d + fs[f / 2], [](double x) { return std::isfinite(x); }))
+        return fail(GPK_EINVAL, "gpk_create3_opn: a derivative value on a face of dfaces is not finite");
+  }
+  const size_t n = (size_t)p->n1 * p->n2 * p->n3;
+  const double* given[4] = {cf ? cf->a[0] : nullptr, cf ? cf->a[1] : nullptr, cf ? cf->a[2] : nullptr,
+                            cf ? cf->rho : nullptr};
+  bool any = false;
+  for (const double* f : given) {
+    any = any || f;
+    if (f && !std::all_of(f, f + n, [](double x) { return std::isfinite(x); }))
+      return fail(GPK_EINVAL, "gpk_create3_opn: a coefficient field has a non-finite value");
+  }
+  gpk_operator3 o1 = one_order_part(op);  // (op's own faces: 0 stays 0)
+  return create3(p, &o1, freq_scale, out, op, any ? cf : nullptr, bd);
+}
+
+int gpk_bdata_info3(const gpk_handle3* h, int32_t* faces, int32_t* dfaces) {
+  if (!h || !faces || !dfaces) return fail(GPK_EINVAL, "NULL argument");
+  *faces = h->op.faces;
+  *dfaces = h->dfaces;
+  return GPK_OK;
+}
+
 int gpk_coef_info3(const gpk_handle3* h, int32_t has[4]) {
   if (!h || !has) return fail(GPK_EINVAL, "NULL argument");
   for (int a = 0; a < 3; ++a) has[a] = h->cf[a] != nullptr;
@@ -730,7 +840,29 @@ int gpk_criterion3(gpk_handle3* h, double* out) {
   double Nb = 0.0;  // the active faces' entries
   for (int f = 0; f < 6; ++f)
     if ((h->op.faces >> f) & 1) Nb += fs[f / 2];
+  Nb += h->nd;  // (+ the derivative faces', whose gap diag[6] includes)
   *out = diag[6] / Nb + diag[5] / Nc;  // boundary_gap/Nb + eq_gap/Nc (K3Final::diag)
+  return GPK_OK;
+}
+
+int gpk_boundary_terms3(gpk_handle3* h, double out[4]) {
+  if (!h || !out) return fail(GPK_EINVAL, "NULL argument");
+  DevSwitch ds(h->dev);
+  HIPCHK(hipStreamSynchronize(h->s));
+  const double n1 = h->g.n[0], n2 = h->g.n[1], n3 = h->g.n[2];
+  const double fs[3] = {n2 * n3, n1 * n3, n1 * n2};
+  out[2] = 0.0;
+  for (int f = 0; f < 6; ++f)
+    if ((h->op.faces >> f) & 1) out[2] += fs[f / 2];
+  out[3] = h->nd;
+  if (h->dfaces) {
+    HIPCHK(hipMemcpy(out, h->bt, 2 * sizeof(double), hipMemcpyDeviceToHost));
+  } else {
+    double diag[8];
+    TRY(read_diag3(h, diag));
+    out[0] = diag[6];
+    out[1] = 0.0;
+  }
   return GPK_OK;
 }
 

@@ -81,6 +81,7 @@ struct K3Final {
   double *params, *grad, *m, *v;
   double* losses; int* loss_slot;
   double* diag;              // [8]: loss, logdet1..3, quad, egap, bgap
+  double nb_extra;           // added to Nb: the entries of the derivative faces (0.0: no such data)
 };
 
 struct K3AdamU {
@@ -102,6 +103,56 @@ struct K3AdamUV {
   K3AdamU a;
   const double* rho;
 };
+
+// Derivative boundary data (gpk_create3_opn, kron3_face.hip).  One axis's two faces 2k and 2k + 1:
+// A and T are A_k and T_k in the leading form ([pk][pa pb]: axis 1, and axis 2 in the permuted
+// layout) or the trailing form ([pa pb][pk]: axis 3); the face is the plane [pa][pb], real na x nb.
+constexpr int K3_FACE_MAX_N = 1024;   // = K3_MAX_N (the tail kernel's LDS rows)
+constexpr int K3_FACE_CHUNK = 4096;   // plane entries per workgroup of the leading-form reverse pass
+constexpr int K3_FACE_ROWS = 64;      // rows of A_3 per workgroup of the trailing-form reverse pass
+constexpr int K3_FACE_TAIL_BLOCKS = 8;  // workgroups (= blocks of parameter partials) per axis of k3_face_tail
+struct K3FaceAxis {
+  int on[2];            // face 2k + s carries data
+  int nk, pk, na, nb, pa, pb;
+  const double* A;
+  double* T;
+  const double* row;    // [2][pk]: d_f, zero-padded (zeros for a face without data)
+  double* r;            // [2][pa pb]: r_f, zero pads (zeros for a face without data)
+  const double* h[2];   // face s's data, [na][nb] (read only where on[s])
+  double* part;         // per-block partials of ||r_f||^2 (k3_face_gap_blocks)
+  double* gv;           // [k3_face_back_blocks][2][pk]: partials of sum_face r_f A_k[j, .]
+  double* gs;           // [2][pk]: their sum (k3_face_colsum; gv itself where there is one block)
+};
+
+struct K3FaceRows {
+  const double* x[3];
+  int n[3], p[3];
+  const AxisConst* kc;  // [3], as k3_prep published them
+  int q, dfaces;
+  double* row[3];       // out: K3FaceAxis::row per axis
+};
+
+struct K3FaceTail {
+  K3FaceAxis ax[3];
+  const double* x[3];
+  const AxisConst* kc;
+  const StepScalars* sc;
+  double llk_weight;
+  int q;
+  int npart[3];             // gap partials per axis (0 on an axis without data)
+  double* out[3];           // blocks bpa .. of each axis's parameter partials, [K3_FACE_TAIL_BLOCKS][3][QMAX]
+  double* bgap;             // in: the value gap (k3_prep); out: value gap + derivative gap
+  double* bt;               // out [2]: value gap, derivative gap
+};
+
+hipError_t k3_launch_face_row(int kind, const K3FaceRows& R, hipStream_t s);
+int k3_face_gap_blocks(const K3FaceAxis& F, bool trailing);
+int k3_face_back_blocks(const K3FaceAxis& F, bool trailing);
+hipError_t k3_launch_face_gap(const K3FaceAxis& F, bool trailing, hipStream_t s);
+hipError_t k3_launch_face_back(const K3FaceAxis& F, bool trailing, const StepScalars* sc, double llk_weight,
+                               hipStream_t s);
+hipError_t k3_launch_face_colsum(const K3FaceAxis& F, int nblk, hipStream_t s);
+hipError_t k3_launch_face_tail(int kind, const K3FaceTail& T, hipStream_t s);
 
 hipError_t k3_launch_prep(const K3Prep& P, hipStream_t s);
 hipError_t k3_launch_permute(const double* src, double* dst, const K3Geom& g, hipStream_t s);

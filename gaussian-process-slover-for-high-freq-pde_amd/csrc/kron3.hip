@@ -215,6 +215,7 @@ __global__ __launch_bounds__(256) void k3_finalize_kernel(K3Final F) {
     Nb = ((fm & 1) + ((fm >> 1) & 1)) * (n2 * n3) + (((fm >> 2) & 1) + ((fm >> 3) & 1)) * (n1 * n3) +
          (((fm >> 4) & 1) + ((fm >> 5) & 1)) * (n1 * n2);
   }
+  Nb += F.nb_extra;  // the derivative faces' entries (gpk_create3_opn; + 0.0 elsewhere: exact)
   const double log_tau = F.params[F.off_tau], log_v = F.params[F.off_v];
   if (t == 0) {
     const double bgap = *F.bgap;

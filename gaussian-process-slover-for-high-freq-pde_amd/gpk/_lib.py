@@ -104,6 +104,10 @@ class gpk_coef3(ctypes.Structure):
     _fields_ = [("a", ctypes.POINTER(ctypes.c_double) * 3), ("rho", ctypes.POINTER(ctypes.c_double))]
 
 
+class gpk_bdata3(ctypes.Structure):
+    _fields_ = [("dfaces", ctypes.c_int32), ("dvals", ctypes.POINTER(ctypes.c_double))]
+
+
 class gpk_gemm_case(ctypes.Structure):
     _fields_ = [
         ("M", ctypes.c_int32), ("N", ctypes.c_int32), ("K", ctypes.c_int32), ("K2", ctypes.c_int32),
@@ -188,6 +192,10 @@ EXPORTS = {
     "gpk_create3_opv": ([ctypes.POINTER(gpk_problem3), ctypes.POINTER(gpk_operator3x), ctypes.POINTER(gpk_coef3),
                          ctypes.c_double, ctypes.POINTER(ctypes.c_void_p)], ctypes.c_int),
     "gpk_coef_info3": ([ctypes.c_void_p, ctypes.POINTER(ctypes.c_int32)], ctypes.c_int),
+    "gpk_create3_opn": ([ctypes.POINTER(gpk_problem3), ctypes.POINTER(gpk_operator3x), ctypes.POINTER(gpk_coef3),
+                         ctypes.POINTER(gpk_bdata3), ctypes.c_double, ctypes.POINTER(ctypes.c_void_p)], ctypes.c_int),
+    "gpk_bdata_info3": ([ctypes.c_void_p, _ip, _ip], ctypes.c_int),
+    "gpk_boundary_terms3": ([ctypes.c_void_p, _dp], ctypes.c_int),
     "gpk_destroy3": ([ctypes.c_void_p], ctypes.c_int),
     "gpk_num_params3": ([ctypes.c_void_p, ctypes.POINTER(ctypes.c_int64)], ctypes.c_int),
     "gpk_set_params3": ([ctypes.c_void_p, _dp, ctypes.c_int64], ctypes.c_int),

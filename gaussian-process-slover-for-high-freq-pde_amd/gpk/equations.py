@@ -334,6 +334,64 @@ def solution_3d_opv(equation):
     return _OPV3D[equation]()
 
 
+# Equations with derivative boundary data on [0, 1]^3 (gpk_create3_opn): the operator, the faces that
+# carry d u / d x_k (along the coordinate, not the outward normal) and the closed-form gradient of u.
+_WAVE_C, _WAVE_OM = 0.5, 2.0
+
+
+def _wave_t_sin():
+    # u = sin(2x) sin(3y) sin(om t + 1/2):  u_tt - c^2 (u_xx + u_yy) = (13 c^2 - om^2) u;
+    # u(., 0) and u_t(., 0) both on face 4, the final-time face open
+    c2, om = _WAVE_C ** 2, _WAVE_OM
+    u = lambda x, y, t: s_(2 * x) * s_(3 * y) * s_(om * t + 0.5)
+    grad = (lambda x, y, t: 2.0 * c_(2 * x) * s_(3 * y) * s_(om * t + 0.5),
+            lambda x, y, t: 3.0 * s_(2 * x) * c_(3 * y) * s_(om * t + 0.5),
+            lambda x, y, t: om * s_(2 * x) * s_(3 * y) * c_(om * t + 0.5))
+    return u, (lambda x, y, t: (13.0 * c2 - om * om) * u(x, y, t)), \
+        Operator3X((-c2, -c2, 1.0), (0.0, 0.0, 0.0), faces=NO_FINAL_FACE), 0b010000, grad
+
+
+def _helmholtz_neumann_sin():
+    # helmholtz_3d-sin with u_x given on the two x walls instead of u
+    u = lambda x, y, z: s_(2 * x) * s_(3 * y) * s_(z)
+    grad = (lambda x, y, z: 2.0 * c_(2 * x) * s_(3 * y) * s_(z),
+            lambda x, y, z: 3.0 * s_(2 * x) * c_(3 * y) * s_(z),
+            lambda x, y, z: s_(2 * x) * s_(3 * y) * c_(z))
+    return u, (lambda x, y, z: (_HELM_K ** 2 - 14.0) * u(x, y, z)), \
+        Operator3X((1.0, 1.0, 1.0), (0.0, 0.0, 0.0), react=(_HELM_K ** 2, 0.0, 0.0), faces=0b111100), 0b000011, grad
+
+
+_OPN3D = {"wave_t-sin": _wave_t_sin, "helmholtz_neumann-sin": _helmholtz_neumann_sin}
+EQUATIONS_3D_OPN = list(_OPN3D)
+
+
+def solution_3d_opn(equation):
+    """(u, src, operator, dfaces, grad_u) of an EQUATIONS_3D_OPN entry: operator an Operator3X,
+    dfaces the faces that carry d u / d x_k, grad_u = (u_x1, u_x2, u_x3) as callables."""
+    return _OPN3D[equation]()
+
+
+def deriv_boundary_3d(grad_u, axes, dfaces):
+    """grad_u on a mesh as gpk_bdata3.dvals: the six-face layout of boundary_3d, face f = 2k + s
+    holding d u / d x_k at index 0 (s = 0) or n_k - 1 (s = 1) of axis k; NaN on the faces outside
+    dfaces (never read)."""
+    axes = [np.asarray(x, np.float64).reshape(-1) for x in axes]
+    mesh = np.meshgrid(*axes, indexing="ij")
+    shape = mesh[0].shape
+    out = []
+    for f in range(6):
+        k, s = divmod(f, 2)
+        sl = [slice(None)] * 3
+        sl[k] = -1 if s else 0
+        sl = tuple(sl)
+        if (dfaces >> f) & 1:
+            g = np.asarray(grad_u[k](*[m[sl] for m in mesh]), np.float64) * np.ones(mesh[0][sl].shape)
+            out.append(g.ravel())
+        else:
+            out.append(np.full(mesh[0][sl].size, np.nan))
+    return np.concatenate(out)
+
+
 def boundary_2d(u_mesh):
     """get_boundary_vals: hstack(U[0,:], U[-1,:], U[:,0], U[:,-1]) (model_GP_solver_2d.py:377-379)."""
     return np.hstack((u_mesh[0, :], u_mesh[-1, :], u_mesh[:, 0], u_mesh[:, -1]))

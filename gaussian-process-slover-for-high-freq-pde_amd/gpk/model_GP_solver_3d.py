@@ -26,6 +26,11 @@ Coefficient-field equations (equations.EQUATIONS_3D_OPV: Helmholtz in a medium, 
 conductivity field, transport in a rotating flow) run through gpk_create3_opv: an Operator3V as
 `operator` (its fields evaluated on the collocation mesh), `-equation=heat_var-sin`, configs in
 gpk/config3d_opv/.
+
+Derivative boundary data (equations.EQUATIONS_3D_OPN: the wave equation with u and u_t on the
+initial face, Helmholtz between sound-hard walls) runs through gpk_create3_opn:
+DeviceSolver3(..., dfaces=, dvals=), trick_paras['dfaces'] / ['dvals'] or the equation's own,
+`-equation=wave_t-sin`, configs in gpk/config3d_opn/.
 """
 import ctypes
 import os
@@ -39,8 +44,9 @@ from . import _lib, init_func, replicas, utils
 from ._lib import check, dptr, f64
 from .cli import parse_flags
 from .core import tree_flatten, tree_unflatten
-from .equations import (EQUATIONS_3D, EQUATIONS_3D_OP, EQUATIONS_3D_OPV, EQUATIONS_3D_OPX, Operator3, Operator3V,
-                        Operator3X, solution_3d, solution_3d_op, solution_3d_opv, solution_3d_opx)
+from .equations import (EQUATIONS_3D, EQUATIONS_3D_OP, EQUATIONS_3D_OPN, EQUATIONS_3D_OPV, EQUATIONS_3D_OPX,
+                        Operator3, Operator3V, Operator3X, deriv_boundary_3d, solution_3d, solution_3d_op,
+                        solution_3d_opn, solution_3d_opv, solution_3d_opx)
 from .infras.exp_config import ExpConfig
 from .kernel_matrix import kernel_class
 from .solver_common import SolverBase
@@ -73,13 +79,17 @@ class DeviceSolver3:
 
     def __init__(self, eq, kind, xs, src, bvals, Q=30, jitter=1e-6, llk_weight=200.0, logdet=True,
                  lr=0.01, freq_scale=20.0, device=0, b1=0.9, b2=0.999, eps=1e-8, refine=False,
-                 operator=None):
+                 operator=None, dfaces=0, dvals=None):
         """refine: one gated refinement step after every solve of the step (GPK_FLAG3_REFINE);
         'gemm' also forces its two-GEMM route (GPK_FLAG3_REFINE_GEMM; tests, A/B).
         operator: an Operator3 (or a dict of its fields) -- the handle then solves that operator
         (gpk_create3_op; eq must be 'poisson', the operator says everything else); an Operator3X
         (or a dict with 'c2' and 'c1') goes to gpk_create3_opx, which takes mixed-order axes; an
-        Operator3V goes to gpk_create3_opv with its fields evaluated on the collocation mesh."""
+        Operator3V goes to gpk_create3_opv with its fields evaluated on the collocation mesh.
+        dfaces, dvals: derivative boundary data (gpk_create3_opn): bit f of dfaces puts d u / d x_k
+        (k = f // 2, along the coordinate) on face f, dvals in bvals' six-face layout (entries of
+        faces outside dfaces are never read); needs an Operator3X or Operator3V (or a dict with
+        'c2' and 'c1'), whose faces may then be 0."""
         lib = _lib.load()
         if len(xs) != 3:
             raise ValueError("three coordinate axes")
@@ -106,7 +116,33 @@ class DeviceSolver3:
         self.refine = bool(refine)
         self._prob = p
         h = ctypes.c_void_p()
-        if operator is None:
+        dfaces = int(dfaces)
+        if dfaces:
+            if dvals is None:
+                raise ValueError("dfaces needs dvals (the six-face layout of bvals)")
+            self._dvals = f64(dvals).reshape(-1)
+            if self._dvals.size != self._bvals.size:
+                raise ValueError("dvals must have the six-face layout of bvals (deriv_boundary_3d)")
+            if not (isinstance(operator, (Operator3X, Operator3V)) or (isinstance(operator, dict) and "c2" in operator)):
+                raise ValueError("derivative boundary data needs an Operator3X or Operator3V")
+            c = _lib.gpk_operator3x()
+            cf = _lib.gpk_coef3()
+            if isinstance(operator, Operator3V):
+                self._coef = operator.fields(self._x)
+                for k, f in enumerate(self._coef[:3]):
+                    if f is not None:
+                        cf.a[k] = dptr(f)
+                if self._coef[3] is not None:
+                    cf.rho = dptr(self._coef[3])
+                op = operator
+            else:
+                op = Operator3X.of(operator)
+            c.c2[:], c.c1[:], c.react[:], c.faces = op.c2, op.c1, op.react, op.faces
+            bd = _lib.gpk_bdata3()
+            bd.dfaces, bd.dvals = dfaces, dptr(self._dvals)
+            check(lib.gpk_create3_opn(ctypes.byref(p), ctypes.byref(c), ctypes.byref(cf), ctypes.byref(bd),
+                                      float(freq_scale), ctypes.byref(h)))
+        elif operator is None:
             check(lib.gpk_create3(ctypes.byref(p), float(freq_scale), ctypes.byref(h)))
         elif isinstance(operator, Operator3V):
             c = _lib.gpk_operator3x()
@@ -273,6 +309,20 @@ class DeviceSolver3:
         check(_lib.load().gpk_coef_info3(self._h, has.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))))
         return tuple(bool(v) for v in has)
 
+    def bdata_info(self):
+        """(faces, dfaces): the faces that carry values and derivatives (gpk_bdata_info3); dfaces
+        is 0 on every handle made without derivative data."""
+        f, d = ctypes.c_int32(), ctypes.c_int32()
+        check(_lib.load().gpk_bdata_info3(self._h, ctypes.byref(f), ctypes.byref(d)))
+        return f.value, d.value
+
+    def boundary_terms(self):
+        """{'bgap', 'dgap', 'Nb', 'Nd'}: the value gap, the derivative gap and their entry counts
+        as the last loss_grad() / step() left them (gpk_boundary_terms3)."""
+        out = np.empty(4)
+        check(_lib.load().gpk_boundary_terms3(self._h, dptr(out)))
+        return {"bgap": out[0], "dgap": out[1], "Nb": int(out[2]), "Nd": int(out[3])}
+
     LOSS_TERMS = ("loss", "logdet_1", "logdet_2", "logdet_3", "quad", "egap", "bgap")
 
     def loss_terms(self):
@@ -301,11 +351,13 @@ class GP_solver_3d_single(SolverBase):
     op_eq_types = tuple(sorted({e.split("-")[0] for e in EQUATIONS_3D_OP}))
     opx_eq_types = tuple(sorted({e.split("-")[0] for e in EQUATIONS_3D_OPX}))
     opv_eq_types = tuple(sorted({e.split("-")[0] for e in EQUATIONS_3D_OPV}))
+    opn_eq_types = tuple(sorted({e.split("-")[0] for e in EQUATIONS_3D_OPN}))
     early_stop_enabled = True
 
     def __init__(self, bvals, X_col, src_vals, jitter, trick_paras, device=0, X_test=None, u_test=None):
         self.eq_type = trick_paras["equation"].split("-")[0]
-        assert self.eq_type in self.eq_types + self.op_eq_types + self.opx_eq_types + self.opv_eq_types
+        assert self.eq_type in (self.eq_types + self.op_eq_types + self.opx_eq_types + self.opv_eq_types
+                                + self.opn_eq_types)
         self.operator = None
         given = trick_paras.get("operator")
         if isinstance(given, Operator3V):
@@ -320,13 +372,23 @@ class GP_solver_3d_single(SolverBase):
             self.operator = solution_3d_opx(trick_paras["equation"])[2]
         elif self.eq_type in self.opv_eq_types:  # (a resumed run rebuilds the fields the same way)
             self.operator = solution_3d_opv(trick_paras["equation"])[2]
+        # derivative boundary data: given, or the equation's own on the collocation mesh
+        self.dfaces, self.dvals = int(trick_paras.get("dfaces", 0)), trick_paras.get("dvals")
+        if self.eq_type in self.opn_eq_types:
+            _, _, op, dfaces, grad_u = solution_3d_opn(trick_paras["equation"])
+            self.operator = self.operator or op
+            if "dfaces" not in trick_paras:
+                self.dfaces = dfaces
+            if self.dvals is None and self.dfaces:
+                self.dvals = deriv_boundary_3d(grad_u, X_col, self.dfaces)
         self.cov_func = trick_paras["kernel"]()
         self.trick_paras = trick_paras
         self.bvals = np.asarray(bvals, np.float64)
         self.X_col = X_col
         self.jitter = jitter
         self.N1, self.N2, self.N3 = (np.asarray(x).size for x in X_col)
-        self.Nb = boundary_count_3d((self.N1, self.N2, self.N3), self.operator.faces if self.operator else 63)
+        self.Nb = (boundary_count_3d((self.N1, self.N2, self.N3), self.operator.faces if self.operator else 63)
+                   + boundary_count_3d((self.N1, self.N2, self.N3), self.dfaces))  # (Nb + Nd)
         self.Nc = self.N1 * self.N2 * self.N3
         self.src_vals = np.asarray(src_vals, np.float64)
         self.llk_weight = trick_paras["llk_weight"]
@@ -341,7 +403,8 @@ class GP_solver_3d_single(SolverBase):
                                  Q=tp.get("Q", 30), jitter=self.jitter, llk_weight=tp["llk_weight"],
                                  logdet=tp.get("logdet", True), lr=tp.get("lr", 0.01),
                                  freq_scale=tp.get("freq_scale", 20.0), device=int(tp.get("device", device)),
-                                 refine=bool(tp.get("refine", False)), operator=self.operator)
+                                 refine=bool(tp.get("refine", False)), operator=self.operator,
+                                 dfaces=self.dfaces, dvals=self.dvals)
         self._version = 0
 
     def eq_residual(self, params, X_test, src_test):
@@ -470,6 +533,8 @@ def test(trick_paras, solver_cls=None):
         u, src, op = solution_3d_opx(trick_paras["equation"])
     elif trick_paras["equation"] in EQUATIONS_3D_OPV:
         u, src, op = solution_3d_opv(trick_paras["equation"])
+    elif trick_paras["equation"] in EQUATIONS_3D_OPN:  # (the solver lays its own dvals out)
+        u, src, op = solution_3d_opn(trick_paras["equation"])[:3]
     else:
         u, src = solution_3d(trick_paras["equation"])
     scale = trick_paras["scale"]
@@ -506,9 +571,11 @@ def test(trick_paras, solver_cls=None):
 
 def load_config(equation):
     """./config3d/<equation>.yaml (the operator equations: ./config3d_op/, the mixed-order ones:
-    ./config3d_opx/, the coefficient-field ones: ./config3d_opv/), falling back to the package's copy."""
+    ./config3d_opx/, the coefficient-field ones: ./config3d_opv/, derivative boundary data:
+    ./config3d_opn/), falling back to the package's copy."""
     cdir = ("config3d_op" if equation in EQUATIONS_3D_OP else "config3d_opx" if equation in EQUATIONS_3D_OPX
-            else "config3d_opv" if equation in EQUATIONS_3D_OPV else "config3d")
+            else "config3d_opv" if equation in EQUATIONS_3D_OPV else "config3d_opn" if equation in EQUATIONS_3D_OPN
+            else "config3d")
     for base in (os.getcwd(), os.path.dirname(os.path.abspath(__file__))):
         p = os.path.join(base, cdir, equation + ".yaml")
         if os.path.exists(p):
@@ -517,7 +584,8 @@ def load_config(equation):
     raise FileNotFoundError(cdir + "/" + equation + ".yaml")
 
 
-def build_config(args, allowed=EQUATIONS_3D + EQUATIONS_3D_OP + EQUATIONS_3D_OPX + EQUATIONS_3D_OPV):
+def build_config(args, allowed=EQUATIONS_3D + EQUATIONS_3D_OP + EQUATIONS_3D_OPX + EQUATIONS_3D_OPV
+                 + EQUATIONS_3D_OPN):
     """The 2-axis build_config (scale, kernel class, other_paras) on the config3d files."""
     assert args.equation in allowed
     config = load_config(args.equation)

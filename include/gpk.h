@@ -526,7 +526,7 @@ int gpk_destroy3(gpk_handle3* h);
  * order (2,2,1), coef (-eps,-eps,1), react (-1,0,1), faces 31.
  * Two orders on one axis (a d^2 + b d) are stated with gpk_operator3x / gpk_create3_opx below.
  * Coefficients that vary over the grid are stated with gpk_coef3 / gpk_create3_opv below.
- * Not expressible: derivative (Neumann / initial-velocity) boundary data. */
+ * Derivative (Neumann / initial-velocity) boundary data is stated with gpk_bdata3 / gpk_create3_opn. */
 typedef struct gpk_operator3 {
   int32_t order[3];  /* 1 or 2: the derivative taken along axis k (D_x1_kappa / DD_x1_kappa block) */
   double  coef[3];   /* its weight c_k, any finite value (0 drops that axis's term)               */
@@ -559,8 +559,7 @@ int gpk_operator_info3(const gpk_handle3* h, gpk_operator3* out);
  * D_k = c2_k DD_x1_kappa + c1_k D_x1_kappa (neither symmetric nor antisymmetric; both fields from
  * one evaluation per pair and mixture component) and every product with D_k has weight exactly 1.
  * Example, third axis time: u_t + b1 u_x + b2 u_y - nu (u_xx + u_yy): c2 (-nu,-nu,0), c1 (b1,b2,1),
- * faces 31.  Still not expressible: derivative boundary data; the 1- and 2-axis handles and
- * sharded handles take no such operator. */
+ * faces 31.  The 1- and 2-axis handles and sharded handles take no such operator. */
 typedef struct gpk_operator3x {
   double  c2[3];    /* weight of d^2/dx_k^2 (DD_x1_kappa block) */
   double  c1[3];    /* weight of d/dx_k     (D_x1_kappa block)  */
@@ -584,7 +583,7 @@ int gpk_operator_info3x(const gpk_handle3* h, gpk_operator3x* out);
  * opx handle with this R.  The fields are problem data like src: given at the collocation points,
  * copied at creation, never part of the parameter vector.  One field serves both terms of a
  * mixed-order axis; r2 and r3 stay constants.  Not expressible: two different fields on the two
- * terms of one axis (divergence form -div(a grad u)), derivative boundary data. */
+ * terms of one axis (divergence form -div(a grad u)). */
 typedef struct gpk_coef3 {
   const double* a[3]; /* per axis: NULL (identically 1) or n1*n2*n3 values, row-major [i1][i2][i3] like src */
   const double* rho;  /* NULL (identically 0) or the same layout: + rho . u in the residual               */
@@ -598,6 +597,38 @@ int gpk_create3_opv(const gpk_problem3* p, const gpk_operator3x* op, const gpk_c
 /* has[0..2]: axis k has a field; has[3]: rho is present.  Any 3-axis handle; all zeros on a handle
  * of gpk_create3, gpk_create3_op or gpk_create3_opx. */
 int gpk_coef_info3(const gpk_handle3* h, int32_t has[4]);
+
+/* Data on the derivative of u on faces (Neumann walls; the initial velocity u_t(., 0) of the wave
+ * equation u_tt - c^2 lap u = f, third axis time, next to u(., 0) on the same face).  Face
+ * f = 2k + s belongs to axis k (gpk_operator3.faces' bit order) at index i_f = 0 or n_k - 1.  The
+ * data is d u / d x_k ALONG THE COORDINATE x_k, not along the outward normal: on a face with s = 0
+ * the outward normal derivative is its negative.  The model's value on face f is
+ *     g_f = d_f ._k (K_k^{-1} x_k U),   d_f[j] = D_x1_kappa_k(x_{i_f}, x_j)
+ * (row i_f of gpk_kernel_matrices' deriv 1 block, whatever orders the operator has on axis k), and
+ * dgap = sum_f ||g_f - h_f||^2 over the faces of dfaces, Nd = their entries.  The log joint is the
+ * gpk_create3_opv handle's with boundary_gap + dgap and Nb + Nd in place of boundary_gap and Nb:
+ * in the loss, in d/d log_tau, in gpk_criterion3 and in gpk_loss_terms3's boundary_gap.  A face may
+ * carry both kinds of data: each of its entries then counts once in Nb and once in Nd; no edge
+ * gets special treatment.  One precision tau serves both kinds.  Not built: tangential or oblique
+ * derivatives, Robin data, and derivative data on sharded, 1-axis and 2-axis handles or on the
+ * class path. */
+typedef struct gpk_bdata3 {
+  int32_t dfaces;       /* bit f set: face f carries d u / d x_k data (k = f / 2); 0..63 */
+  const double* dvals;  /* gpk_problem3.bvals' six-face layout; entries of faces outside dfaces are never read */
+} gpk_bdata3;
+/* p, op and cf as on gpk_create3_opv (cf may be NULL).  bd == NULL or dfaces == 0 is
+ * gpk_create3_opv(p, op, cf, ...) itself: the same stage list, launches and bits.  With
+ * dfaces != 0, op->faces may be 0 (derivative data alone; the operator then needs a reaction term
+ * to pin the constant).  GPK_EINVAL, before any device work, on dfaces outside 0..63, dvals NULL
+ * with dfaces != 0, or a non-finite value on a face of dfaces. */
+int gpk_create3_opn(const gpk_problem3* p, const gpk_operator3x* op, const gpk_coef3* cf,
+                    const gpk_bdata3* bd, double freq_scale, gpk_handle3** out);
+/* The faces that carry values and derivatives; dfaces is 0 on every older kind of 3-axis handle. */
+int gpk_bdata_info3(const gpk_handle3* h, int32_t* faces, int32_t* dfaces);
+/* out: value gap, derivative gap, Nb, Nd as the last gpk_step3 or gpk_loss_grad3 left them (the
+ * gaps at the parameters before that step's update).  Any 3-axis handle; derivative gap and Nd
+ * are 0 on the older kinds. */
+int gpk_boundary_terms3(gpk_handle3* h, double out[4]);
 
 int gpk_num_params3(const gpk_handle3* h, int64_t* n);
 int gpk_set_params3(gpk_handle3* h, const double* flat, int64_t n);
