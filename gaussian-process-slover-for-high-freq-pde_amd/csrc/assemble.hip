@@ -83,7 +83,8 @@ __global__ __launch_bounds__(256) void assemble_kernel(AssembleBatch b, int q) {
 
   __shared__ double sw[QMAX], sa[QMAX], so[QMAX], sol[QMAX];
   __shared__ double pk[4][64], pd[4][64];
-  constexpr bool BOTH = DERIV == DERIV_BOTH;  // pd: the order-2 field, pd1: the order-1 field
+  constexpr bool BOTH = deriv_two_fields(DERIV);  // pd: the order-2 field, pd1: the order-1 field
+  constexpr bool SPLIT = DERIV == DERIV_SPLIT;    // ... and the order-1 block stored on its own
   __shared__ double pd1[BOTH ? 4 : 1][64];    // (no reference in the other modes: not allocated)
   if (t < q) axis_component(b.prep, axis, q, t, sw[t], sa[t], so[t], sol[t]);
   if (blockIdx.x == 0 && axis == 0) publish_prep(b.prep, q);
@@ -128,12 +129,14 @@ __global__ __launch_bounds__(256) void assemble_kernel(AssembleBatch b, int q) {
   // each field reduced on its own, then the weighted block: the symmetric part mirrors as it is,
   // the antisymmetric part with its sign, so D is neither
   if constexpr (BOTH) A.D[(size_t)i * A.p + j] = real ? A.c2 * dv + A.c1 * (s_ij * dv1) : 0.0;
+  if constexpr (SPLIT) A.D1[(size_t)i * A.p + j] = real ? s_ij * dv1 : 0.0;
   if (I != J) {
     A.K[(size_t)j * A.p + i] = kv;
     if (A.Kc) A.Kc[(size_t)j * A.p + i] = kv;
     if (DERIV == 2) A.D[(size_t)j * A.p + i] = dv;
     if (DERIV == 1) A.D[(size_t)j * A.p + i] = real ? s_ji * dv : 0.0;
     if constexpr (BOTH) A.D[(size_t)j * A.p + i] = real ? A.c2 * dv + A.c1 * (s_ji * dv1) : 0.0;
+    if constexpr (SPLIT) A.D1[(size_t)j * A.p + i] = real ? s_ji * dv1 : 0.0;
   }
   if (tile == 0 && b.pivot_x >= 0) {  // release this sub-block of tile (0,0) to pivot0
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // (only wave 0 stored)
@@ -492,6 +495,8 @@ static void launch_assemble_t(const AssembleBatch& b, int naxes, int maxt, int q
     hipLaunchKernelGGL((assemble_kernel<MATERN, COS, 1>), grid, dim3(256), 0, s, b, q);
   else if (deriv == DERIV_BOTH)
     hipLaunchKernelGGL((assemble_kernel<MATERN, COS, DERIV_BOTH>), grid, dim3(256), 0, s, b, q);
+  else if (deriv == DERIV_SPLIT)
+    hipLaunchKernelGGL((assemble_kernel<MATERN, COS, DERIV_SPLIT>), grid, dim3(256), 0, s, b, q);
   else
     hipLaunchKernelGGL((assemble_kernel<MATERN, COS, 0>), grid, dim3(256), 0, s, b, q);
 }
@@ -512,10 +517,11 @@ hipError_t launch_assemble(int kind, int q, const AssembleArgs* a, int naxes, co
         (a[k].cls.ncls > 0) != (a[0].cls.ncls > 0))
       return hipErrorInvalidValue;
   int deriv = a[0].deriv;
-  // one mode per launch (DERIV_BOTH carries its weights per axis); the class path stores one dval
-  // per class, so it has no DERIV_BOTH
+  // one mode per launch (DERIV_BOTH and DERIV_SPLIT carry their weights per axis); the class path
+  // stores one dval per class, so it has neither; DERIV_SPLIT needs its second block
   for (int k = 0; k < naxes; ++k)
-    if ((a[k].deriv == DERIV_BOTH) != (deriv == DERIV_BOTH) || (deriv == DERIV_BOTH && a[k].cls.ncls > 0))
+    if ((deriv_two_fields(deriv) && (a[k].deriv != deriv || a[k].cls.ncls > 0)) ||
+        (!deriv_two_fields(deriv) && deriv_two_fields(a[k].deriv)) || (a[k].deriv == DERIV_SPLIT && !a[k].D1))
       return hipErrorInvalidValue;
   if (a[0].cls.ncls > 0) {  // class path: every 32x32 tile of the full matrix, one per workgroup
     int maxc = 0, maxtiles = 0;

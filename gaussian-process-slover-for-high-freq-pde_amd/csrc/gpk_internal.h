@@ -189,6 +189,10 @@ struct ClassArgs {
 // axis's weights: D = c2 DD_x1_kappa + c1 D_x1_kappa (the 3-axis solver's mixed-order axes;
 // per-pair path only).
 constexpr int DERIV_BOTH = 3;
+// DERIV_BOTH with the plain order-1 block D1 = s D_x1_kappa stored next to D, whatever the weights
+// are (the 3-axis solver's convective axes: D carries the linear terms, D1 the term u du/dx_k)
+constexpr int DERIV_SPLIT = 4;
+__host__ __device__ constexpr bool deriv_two_fields(int deriv) { return deriv == DERIV_BOTH || deriv == DERIV_SPLIT; }
 
 struct AssembleArgs {
   const double* x;       // coords [n] (padded buffer ok)
@@ -199,8 +203,9 @@ struct AssembleArgs {
   double* K;             // [p*p]  (consumed in place by the SPD inverse)
   double* Kc;            // [p*p]  kept copy of K for iterative refinement (nullable)
   double* D;             // [p*p]
-  int deriv;             // 1 or 2 (0: K only), or DERIV_BOTH
-  double c2, c1;         // DERIV_BOTH: D = c2 DD + c1 D1 (read in that mode only)
+  int deriv;             // 1 or 2 (0: K only), DERIV_BOTH or DERIV_SPLIT
+  double c2, c1;         // DERIV_BOTH / DERIV_SPLIT: D = c2 DD + c1 D1 (read in those modes only)
+  double* D1;            // [p*p]  DERIV_SPLIT: the order-1 block alone (null in every other mode)
   // pivot block 0 of the SPD inverse, factored by one extra workgroup of the assembly launch
   // (nullable piv: not fused).  Same outputs as the sweep's pivot_init.
   double* piv; double* ldet; double* pst; int* status;
@@ -545,8 +550,9 @@ struct PGradArgs {
   const double* Kinv;                     // 1D mode
   const double* alpha; const double* beta; const double* R;  // 1D mode vectors
   double halfc;                           // 1D mode: 0.5*logdet flag
-  int deriv;                              // 1, 2 or DERIV_BOTH (2D per-pair path only)
-  double c2, c1;                          // DERIV_BOTH: G_D weighs c2 dDD + c1 dD1 (read in that mode only)
+  int deriv;                              // 1, 2, DERIV_BOTH or DERIV_SPLIT (2D per-pair path only)
+  double c2, c1;                          // DERIV_BOTH / DERIV_SPLIT: G_D weighs c2 dDD + c1 dD1 (read in those modes only)
+  const double* GD1;                      // DERIV_SPLIT: dL/dD1 of the order-1 block alone [p*p] (null elsewhere)
   double* part;                           // [nblocks * 3*QMAX]
   // DD (class path, 2D, fused tail): the derivative fields and every sum after them in
   // double-double; part holds the partials' high parts, part_lo their low parts (null: fp64)

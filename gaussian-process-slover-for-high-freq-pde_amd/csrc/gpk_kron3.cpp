@@ -28,6 +28,11 @@
 // (k3_combine_v), and the reverse pass reads W_k = a_k . R where it reads R above -- X_k, G_Dk --
 // so dL/dU and the G's hold with no further change; rho joins r1 in dL/dU's reaction factor
 // (k3_adam_u_v).  An axis without a field has no W_k: its operand stays R (Rp on axis 2).
+// Convective terms (gpk_create3_opc, g_k u du/dx_k): a convective axis assembles in DERIV_SPLIT, which
+// stores the plain order-1 block D1_k next to D_k; V_k = g_k D1_k x_k A_k, N = sum_k V_k and
+// R += U . N (k3_combine_c); the reverse pass reads Q = U . R: T_k += g_k D1_k^T x_k Q (the second
+// product of T_k's descriptor), G_D1k = v g_k Q_(k) A_k,(k)^T joins the order-1 weights of the
+// contraction, and dL/dU += v N . R (k3_adam_u_c) (build_conv_stages).
 // GPK_FLAG3_REFINE: every one of the eight solves (A1, A2, A3, T, S, X1, X2, X3) is followed by
 // one refinement step X += K_k^{-1} (B - K_k X) gated on the axis's pst: one fused panel launch
 // (refine_panel.hip), or two GEMMs where its panels do not fit LDS (build_refine).
@@ -90,12 +95,23 @@ struct gpk_handle3 {
   double *dvals = nullptr, *bt = nullptr, nd = 0.0;
   K3FaceAxis face[3] = {};
   int fpart[3] = {}, fchunk[3] = {};
+  // gpk_create3_opc: the convective weights g_k (conv = 0: none, and nothing below is allocated or
+  // launched).  Per axis with g_k != 0: the order-1 block D1_k (the assembly's DERIV_SPLIT), V_k =
+  // g_k D1_k x_k A_k (V[1] permuted) and G_D1k = v g_k Q_(k) A_k,(k)^T (GD1); N = sum_k V_k and
+  // Q = U . R in the natural layout (Q: axis 1 or 3 convective) and permuted (Qp: axis 2).  All are
+  // allocations of their own (Rx / Ryp / Rz and T* are refinement scratch at various points).
+  int conv = 0;
+  double gconv[3] = {};
+  double *D1[3] = {}, *GD1[3] = {}, *V[3] = {}, *Nsum = nullptr, *Q = nullptr, *Qp = nullptr;
   double *GK[3] = {}, *GD[3] = {};
   double *red_egap = nullptr, *red_quad = nullptr;
   int nred = 0;
   double *pgpart = nullptr, *pg = nullptr;
   int bpa = 0;
   std::vector<std::vector<GemmDesc>> stages;  // GEMM launches in stream order
+  // a convective handle's two further launches: [0] the V_k, after stage 2 and its refinement;
+  // [1] the G_D1k, after stage 3 (empty elsewhere)
+  std::vector<std::vector<GemmDesc>> cstages;
   // GPK_FLAG3_REFINE: the refinement launches, [2 j] the residuals and [2 j + 1] the corrections
   // that follow stage kRefineAfter[j] (empty without the flag)
   std::vector<std::vector<GemmDesc>> rstages;
@@ -106,6 +122,43 @@ struct gpk_handle3 {
 };
 
 namespace {
+
+// Convective axes (gpk_create3_opc), after build_stages has filled stage 3: T_k becomes the dual
+// product D_k^T x_k W_k + g_k D1_k^T x_k Q (same transposes as its first product; no descriptor of
+// that batch reads a T_k, which launch_huge's two passes need), and two launches of their own hold
+// V_k = g_k D1_k x_k A_k (next to the stage-2 products, whose batch is full) and G_D1k =
+// v g_k Q_(k) A_k,(k)^T (next to the G_Dk).  Axis 2 stays in the permuted layout; axis 3 has D1 on
+// the right, transposed like D[2].
+void build_conv_stages(gpk_handle3* h) {
+  const int P1 = h->g.p[0], P2 = h->g.p[1], P3 = h->g.p[2];
+  const int M1 = P2 * P3, M2 = P1 * P3, M3 = P1 * P2;
+  const double* g = h->gconv;
+  double* const* D1 = h->D1;
+  auto scaled = [](GemmDesc d, double alpha) { d.alpha = alpha; return d; };
+  auto dual = [](GemmDesc& d, const double* A2, int lda2, const double* B2, int ldb2, int K2, double alpha2) {
+    d.A2 = A2; d.lda2 = lda2; d.ta2 = d.ta; d.B2 = B2; d.ldb2 = ldb2; d.tb2 = d.tb; d.K2 = K2; d.alpha2 = alpha2;
+  };
+  auto& t = h->stages[3];
+  if (D1[0]) dual(t[0], D1[0], P1, h->Q, M1, P1, g[0]);
+  if (D1[1]) dual(t[1], D1[1], P2, h->Qp, M2, P2, g[1]);
+  if (D1[2]) dual(t[2], h->Q, P3, D1[2], P3, P3, g[2]);
+  h->cstages.assign(2, {});
+  auto& cv = h->cstages[0];
+  auto& cg = h->cstages[1];
+  auto vs = [](GemmDesc d) { d.vscale = 1; return d; };
+  if (D1[0]) {
+    cv.push_back(scaled(gemm_desc(D1[0], P1, 0, h->A1, M1, 0, h->V[0], M1, P1, M1, P1), g[0]));
+    cg.push_back(vs(scaled(gemm_desc(h->Q, M1, 0, h->A1, M1, 1, h->GD1[0], P1, P1, P1, M1), g[0])));
+  }
+  if (D1[1]) {
+    cv.push_back(scaled(gemm_desc(D1[1], P2, 0, h->A2p, M2, 0, h->V[1], M2, P2, M2, P2), g[1]));
+    cg.push_back(vs(scaled(gemm_desc(h->Qp, M2, 0, h->A2p, M2, 1, h->GD1[1], P2, P2, P2, M2), g[1])));
+  }
+  if (D1[2]) {
+    cv.push_back(scaled(gemm_desc(h->A3, P3, 0, D1[2], P3, 1, h->V[2], P3, M3, P3, P3), g[2]));
+    cg.push_back(vs(scaled(gemm_desc(h->Q, P3, 1, h->A3, P3, 0, h->GD1[2], P3, P3, P3, M3), g[2])));
+  }
+}
 
 // the step's GEMM launches (stream order; independent products of one launch batched)
 void build_stages(gpk_handle3* h) {
@@ -141,6 +194,7 @@ void build_stages(gpk_handle3* h) {
                   scaled(gemm_desc(D[1], P2, 1, W2p, M2, 0, h->T2p, M2, P2, M2, P2), w[1]),
                   scaled(gemm_desc(W3, P3, 0, D[2], P3, 0, h->T3, P3, M3, P3, P3), w[2]), gd});
   }
+  if (h->conv) build_conv_stages(h);
   // X_k = K_k^{-1} x_k (c_k D_k^T x_k R) with the side outputs Y_k = S/2 + v X_k;  G_D2
   {
     GemmDesc gd = scaled(gemm_desc(W2p, M2, 0, h->A2p, M2, 1, h->GD[1], P2, P2, P2, M2), w[1]);
@@ -212,11 +266,8 @@ int launch_descs(gpk_handle3* h, const std::vector<GemmDesc>& d) {
                       "gemm");
 }
 
-// the GEMM kernel stage k launches with (what gpk_stage_variants3 reports)
-int stage_variant(const gpk_handle3* h, int k) {
-  const auto& d = h->stages[k];
-  return gemm_variant(d.data(), (int)d.size(), 0);
-}
+// the GEMM kernel a launch of these descriptors runs with (what gpk_stage_variants3 reports)
+int stage_variant(const std::vector<GemmDesc>& d) { return gemm_variant(d.data(), (int)d.size(), 0); }
 
 // stage k, then the refinement of its solves when the handle refines
 int launch_stage(gpk_handle3* h, int k) {
@@ -263,7 +314,7 @@ int enqueue_inverse3(gpk_handle3* h, int apply) {
   for (int a = 0; a < 3; ++a) {
     aa[a].x = h->x[a]; aa[a].n = g.n[a]; aa[a].p = g.p[a]; aa[a].kc = h->kc + a;
     aa[a].jitter = h->prob.jitter; aa[a].K = h->K[a]; aa[a].Kc = h->Kc[a]; aa[a].D = h->D[a];
-    aa[a].deriv = h->mode[a]; aa[a].c2 = h->c2[a]; aa[a].c1 = h->c1[a];
+    aa[a].deriv = h->mode[a]; aa[a].c2 = h->c2[a]; aa[a].c1 = h->c1[a]; aa[a].D1 = h->D1[a];
   }
   // (skip = 1: the constants are published by k3_prep; each workgroup derives its axis's own)
   PrepArgs p12{};
@@ -318,11 +369,18 @@ int enqueue_step3(gpk_handle3* h, int apply) {
   }
   TRY(check_launch(k3_launch_permute(h->Tm, h->Tp, g, h->s), "k3_permute"));
   TRY(launch_stage(h, 2));
+  if (h->conv) TRY(launch_descs(h, h->cstages[0]));  // V_k, from the refined A_k
   K3Combine C{};
   C.g = g; C.Rx = h->Rx; C.Rz = h->Rz; C.Ryp = h->Ryp; C.F = h->F; C.Up = h->Up; C.Sp = h->Sp;
   C.eq = eq_layer(h); C.R = h->R; C.Rp = h->Rp; C.S = h->S;
   C.red_egap = h->red_egap; C.red_quad = h->red_quad;
-  if (h->cf[0] || h->cf[1] || h->cf[2] || h->rho) {
+  if (h->conv) {
+    K3CombineC X{};
+    X.v.c = C; X.v.rho = h->rho;
+    for (int a = 0; a < 3; ++a) { X.v.a[a] = h->cf[a]; X.v.W[a] = h->W[a]; X.V[a] = h->V[a]; }
+    X.N = h->Nsum; X.Q = h->Q; X.Qp = h->Qp;
+    TRY(check_launch(k3_launch_combine_c(X, h->s), "k3_combine_c"));
+  } else if (h->cf[0] || h->cf[1] || h->cf[2] || h->rho) {
     K3CombineV V{};
     V.c = C; V.rho = h->rho;
     for (int a = 0; a < 3; ++a) { V.a[a] = h->cf[a]; V.W[a] = h->W[a]; }
@@ -334,6 +392,7 @@ int enqueue_step3(gpk_handle3* h, int apply) {
   // (T_k takes the derivative faces' term before X_k = K_k^{-1} x_k T_k and its refinement read it)
   for (int k = 3; k < (int)h->stages.size(); ++k) {
     TRY(launch_stage(h, k));
+    if (h->conv && k == 3) TRY(launch_descs(h, h->cstages[1]));  // G_D1k
     for (int a = 0; a < 3 && k == 3; ++a)
       if (h->fpart[a])
         TRY(check_launch(k3_launch_face_back(h->face[a], a == 2, h->sc, h->prob.llk_weight, h->s), "k3_face_back"));
@@ -344,7 +403,7 @@ int enqueue_step3(gpk_handle3* h, int apply) {
   for (int a = 0; a < 3; ++a) {
     pg[a].x = h->x[a]; pg[a].n = g.n[a]; pg[a].p = g.p[a]; pg[a].kc = h->kc + a;
     pg[a].GK = h->GK[a]; pg[a].GD = h->GD[a]; pg[a].deriv = h->mode[a];
-    pg[a].c2 = h->c2[a]; pg[a].c1 = h->c1[a];
+    pg[a].c2 = h->c2[a]; pg[a].c1 = h->c1[a]; pg[a].GD1 = h->GD1[a];
     pg[a].part = h->pgpart + (size_t)a * (h->bpa + fb) * 3 * QMAX;
   }
   if (h->mode[0] == h->mode[1]) {
@@ -381,7 +440,9 @@ int enqueue_step3(gpk_handle3* h, int apply) {
   A.g = g; A.hyper = F.hyper; A.llk_weight = h->prob.llk_weight; A.apply = apply; A.eq = C.eq;
   A.sc = h->sc; A.S = h->S; A.X1 = h->X1; A.X2p = h->X2p; A.X3 = h->X3; A.R = h->R; A.Up = h->Up;
   A.bvals = h->bvals; A.off_u = 0; A.params = h->params; A.grad = h->grad; A.m = h->m; A.v = h->v;
-  if (h->rho) {
+  if (h->conv) {
+    TRY(check_launch(k3_launch_adam_u_c(K3AdamUC{A, h->rho, h->Nsum}, h->s), "k3_adam_u_c"));
+  } else if (h->rho) {
     TRY(check_launch(k3_launch_adam_u_v(K3AdamUV{A, h->rho}, h->s), "k3_adam_u_v"));
   } else {
     TRY(check_launch(k3_launch_adam_u(A, h->s), "k3_adam_u"));
@@ -443,7 +504,8 @@ int check_problem3(const gpk_problem3* p) {
 // is its one-order-per-axis part, a mixed axis entered as order 0 with weight 1.0) and
 // gpk_create3_opv (cf: the fields it was given, at least one of them)
 int create3(const gpk_problem3* p, const gpk_operator3* op, double freq_scale, gpk_handle3** out,
-            const gpk_operator3x* opx = nullptr, const gpk_coef3* cf = nullptr, const gpk_bdata3* bd = nullptr) {
+            const gpk_operator3x* opx = nullptr, const gpk_coef3* cf = nullptr, const gpk_bdata3* bd = nullptr,
+            const gpk_conv3* cv = nullptr) {
   TRY(check_problem3(p));
   const int ns[3] = {p->n1, p->n2, p->n3};
   TRY(check_device(p->device));
@@ -462,6 +524,12 @@ int create3(const gpk_problem3* p, const gpk_operator3* op, double freq_scale, g
   for (int a = 0; a < 3; ++a) {
     const bool mixed = h->op.order[a] == 0;
     h->mode[a] = mixed ? DERIV_BOTH : h->op.order[a];
+    // a convective axis (entered as a mixed one, whatever its weights): the two-block assembly
+    if (cv && cv->g[a] != 0.0) {
+      h->gconv[a] = cv->g[a];
+      h->conv = 1;
+      h->mode[a] = DERIV_SPLIT;
+    }
     h->c2[a] = mixed ? opx->c2[a] : h->op.order[a] == 2 ? h->op.coef[a] : 0.0;
     h->c1[a] = mixed ? opx->c1[a] : h->op.order[a] == 1 ? h->op.coef[a] : 0.0;
   }
@@ -572,6 +640,15 @@ int create3(const gpk_problem3* p, const gpk_operator3* op, double freq_scale, g
       F.row = row;
     }
   }
+  // convective axes: D1_k, V_k and G_D1k per axis, N, and Q in the layouts those axes read
+  for (int a = 0; a < 3 && h->conv; ++a) {
+    if (h->gconv[a] == 0.0) continue;
+    const int P = g.p[a];
+    A3_(h->D1[a], (size_t)P * P); A3_(h->GD1[a], (size_t)P * P); A3_(h->V[a], np);
+    if (a == 1) { A3_(h->Qp, np); }
+    else if (!h->Q) { A3_(h->Q, np); }
+  }
+  if (h->conv) A3_(h->Nsum, np);
 #undef A3_
   // upload: coordinates, the padded source, boundary values, the initial params
   // (model_GP_solver_2d.py:245-261: U = 0, freq = linspace(0,1,Q) freq_scale, log-ls = 0,
@@ -666,7 +743,7 @@ int gpk_create3_op(const gpk_problem3* p, const gpk_operator3* op, double freq_s
 int gpk_operator_info3(const gpk_handle3* h, gpk_operator3* out) {
   if (!h || !out) return fail(GPK_EINVAL, "NULL argument");
   for (int a = 0; a < 3; ++a)
-    if (h->mode[a] == DERIV_BOTH)
+    if (deriv_two_fields(h->mode[a]))
       return fail(GPK_EINVAL, "gpk_operator_info3: the handle has a mixed-order axis (gpk_operator_info3x states it)");
   *out = h->op;
   return GPK_OK;
@@ -704,19 +781,25 @@ int gpk_create3_opv(const gpk_problem3* p, const gpk_operator3x* op, const gpk_c
   return create3(p, &o, freq_scale, out, op, cf);
 }
 
-int gpk_create3_opn(const gpk_problem3* p, const gpk_operator3x* op, const gpk_coef3* cf, const gpk_bdata3* bd,
-                    double freq_scale, gpk_handle3** out) {
-  if (!bd || bd->dfaces == 0) return gpk_create3_opv(p, op, cf, freq_scale, out);
+}  // extern "C"
+
+namespace {
+
+// gpk_create3_opn with derivative faces, and gpk_create3_opc with a convective axis (cv; bd may
+// then be null or without faces): the argument checks of both, then the handle
+int create3_opn(const gpk_problem3* p, const gpk_operator3x* op, const gpk_coef3* cf, const gpk_bdata3* bd,
+                const gpk_conv3* cv, double freq_scale, gpk_handle3** out) {
   if (!p || !op || !out) return fail(GPK_EINVAL, "NULL argument");
   *out = nullptr;
-  if (bd->dfaces < 0 || bd->dfaces > K3_ALL_FACES) return fail(GPK_EINVAL, "gpk_create3_opn: dfaces must be in 0..63");
-  if (!bd->dvals) return fail(GPK_EINVAL, "gpk_create3_opn: dvals is NULL with dfaces != 0");
+  if (bd && bd->dfaces == 0) bd = nullptr;
+  if (bd && (bd->dfaces < 0 || bd->dfaces > K3_ALL_FACES)) return fail(GPK_EINVAL, "gpk_create3_opn: dfaces must be in 0..63");
+  if (bd && !bd->dvals) return fail(GPK_EINVAL, "gpk_create3_opn: dvals is NULL with dfaces != 0");
   // the operator's own checks, with faces = 0 allowed here (data on derivatives alone)
   gpk_operator3x o = *op;
-  if (o.faces == 0) o.faces = bd->dfaces;
-  TRY(check_operator3x(p, &o, out, "gpk_create3_opn"));
+  if (bd && o.faces == 0) o.faces = bd->dfaces;
+  TRY(check_operator3x(p, &o, out, cv ? "gpk_create3_opc" : "gpk_create3_opn"));
   TRY(check_problem3(p));
-  {
+  if (bd) {
     const long fs[3] = {(long)p->n2 * p->n3, (long)p->n1 * p->n3, (long)p->n1 * p->n2};
     const double* d = bd->dvals;
     for (int f = 0; f < 6; d += fs[f / 2], ++f)
@@ -733,7 +816,39 @@ int gpk_create3_opn(const gpk_problem3* p, const gpk_operator3x* op, const gpk_c
       return fail(GPK_EINVAL, "gpk_create3_opn: a coefficient field has a non-finite value");
   }
   gpk_operator3 o1 = one_order_part(op);  // (op's own faces: 0 stays 0)
-  return create3(p, &o1, freq_scale, out, op, any ? cf : nullptr, bd);
+  // a convective axis assembles D_k = c2_k DD_k + c1_k D1_k whatever the weights are: entered as a
+  // mixed axis (order 0, GEMM weight 1.0)
+  for (int a = 0; a < 3 && cv; ++a)
+    if (cv->g[a] != 0.0) { o1.order[a] = 0; o1.coef[a] = 1.0; }
+  return create3(p, &o1, freq_scale, out, op, any ? cf : nullptr, bd, cv);
+}
+
+}  // namespace
+
+extern "C" {
+
+int gpk_create3_opn(const gpk_problem3* p, const gpk_operator3x* op, const gpk_coef3* cf, const gpk_bdata3* bd,
+                    double freq_scale, gpk_handle3** out) {
+  if (!bd || bd->dfaces == 0) return gpk_create3_opv(p, op, cf, freq_scale, out);
+  return create3_opn(p, op, cf, bd, nullptr, freq_scale, out);
+}
+
+int gpk_create3_opc(const gpk_problem3* p, const gpk_operator3x* op, const gpk_coef3* cf, const gpk_bdata3* bd,
+                    const gpk_conv3* cv, double freq_scale, gpk_handle3** out) {
+  if (cv) {
+    if (out) *out = nullptr;
+    for (int a = 0; a < 3; ++a)
+      if (!std::isfinite(cv->g[a])) return fail(GPK_EINVAL, "gpk_create3_opc: g must be finite");
+  }
+  if (!cv || (cv->g[0] == 0.0 && cv->g[1] == 0.0 && cv->g[2] == 0.0))
+    return gpk_create3_opn(p, op, cf, bd, freq_scale, out);
+  return create3_opn(p, op, cf, bd, cv, freq_scale, out);
+}
+
+int gpk_conv_info3(const gpk_handle3* h, double g[3]) {
+  if (!h || !g) return fail(GPK_EINVAL, "NULL argument");
+  for (int a = 0; a < 3; ++a) g[a] = h->gconv[a];
+  return GPK_OK;
 }
 
 int gpk_bdata_info3(const gpk_handle3* h, int32_t* faces, int32_t* dfaces) {
@@ -868,8 +983,14 @@ int gpk_boundary_terms3(gpk_handle3* h, double out[4]) {
 
 int gpk_stage_variants3(gpk_handle3* h, int32_t* out, int32_t cap, int32_t* n) {
   if (!h || !n || cap < 0 || (cap && !out)) return fail(GPK_EINVAL, "NULL argument");
-  *n = (int32_t)h->stages.size();
-  for (int k = 0; k < *n && k < cap; ++k) out[k] = stage_variant(h, k);
+  // stream order: a convective handle's two further launches follow stages 2 and 3
+  std::vector<const std::vector<GemmDesc>*> order;
+  for (size_t k = 0; k < h->stages.size(); ++k) {
+    order.push_back(&h->stages[k]);
+    if (h->conv && (k == 2 || k == 3)) order.push_back(&h->cstages[k - 2]);
+  }
+  *n = (int32_t)order.size();
+  for (int k = 0; k < *n && k < cap; ++k) out[k] = stage_variant(*order[k]);
   return GPK_OK;
 }
 

@@ -104,6 +104,24 @@ struct K3AdamUV {
   const double* rho;
 };
 
+// k3_combine_c (gpk_create3_opc): k3_combine_v plus the convective term u N, N = V_1 + V_3 + V_2p
+// with V_k = g_k D1_k x_k A_k (null: axis k is not convective; V[1] in the mode-2 permuted layout).
+// Every pointer of v may be null here (a handle without fields).  N goes to the U update in the
+// natural layout; Q = u R is the reverse pass's operand of the convective axes, natural (Q: axis 1
+// or 3 convective) and / or permuted (Qp: axis 2), each null when no axis reads it.
+struct K3CombineC {
+  K3CombineV v;
+  const double* V[3];
+  double *N, *Q, *Qp;
+};
+
+// k3_adam_u_c: k3_adam_u_v with N (natural padded layout) added to the factor on R; rho nullable
+struct K3AdamUC {
+  K3AdamU a;
+  const double* rho;
+  const double* N;
+};
+
 // Derivative boundary data (gpk_create3_opn, kron3_face.hip).  One axis's two faces 2k and 2k + 1:
 // A and T are A_k and T_k in the leading form ([pk][pa pb]: axis 1, and axis 2 in the permuted
 // layout) or the trailing form ([pa pb][pk]: axis 3); the face is the plane [pa][pb], real na x nb.
@@ -162,6 +180,8 @@ hipError_t k3_launch_combine_v(const K3CombineV& V, hipStream_t s);
 hipError_t k3_launch_finalize(const K3Final& F, hipStream_t s);
 hipError_t k3_launch_adam_u(const K3AdamU& A, hipStream_t s);
 hipError_t k3_launch_adam_u_v(const K3AdamUV& V, hipStream_t s);
+hipError_t k3_launch_combine_c(const K3CombineC& C, hipStream_t s);
+hipError_t k3_launch_adam_u_c(const K3AdamUC& C, hipStream_t s);
 hipError_t k3_launch_sync_u(const double* params, long off_u, const K3Geom& g, double* Up, hipStream_t s);
 
 }  // namespace gpk

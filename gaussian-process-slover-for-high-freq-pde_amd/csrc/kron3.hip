@@ -20,6 +20,9 @@
 // Coefficient fields (gpk_create3_opv): k3_combine_v multiplies each axis's term by its field,
 // adds rho to r1 and writes the reverse pass's operands W_k = a_k R; k3_adam_u_v carries rho in the
 // reaction factor.  They are kernels of their own: the two above run unchanged on every other handle.
+// Convective terms (gpk_create3_opc): k3_combine_c is k3_combine_v plus u N, N = sum_k g_k D1_k x_k
+// A_k, and writes N and Q = u R for the reverse pass; k3_adam_u_c carries N in the reaction factor.
+// Kernels of their own again.
 // Grids are padded per axis to P_k (multiple of 32); pads of every tensor are zero.
 #include "gpk_internal.h"
 #include "gpk_kron3.h"
@@ -187,6 +190,62 @@ __global__ __launch_bounds__(256) void k3_combine_v_kernel(K3CombineV V) {
   }
 }
 
+// k3_combine_v with convective terms (gpk_create3_opc): R is summed in k3_combine_v's order, then
+// u N is added, N = V_1 + V_3 + V_2p in that fixed order, each term only where its axis is
+// convective (V_2p read at the permuted index).  Besides k3_combine_v's outputs it writes N (natural
+// layout, for the U update) and Q = u R, the reverse pass's operand of the convective axes: natural
+// (Q) and / or permuted (Qp), whichever is asked for.  Fields and V_k are read at real entries only;
+// the pads of every output are zero.
+__global__ __launch_bounds__(256) void k3_combine_c_kernel(K3CombineC X) {
+  const K3CombineV& V = X.v;
+  const K3Combine& C = V.c;
+  const K3Geom& g = C.g;
+  const long e = (long)blockIdx.x * 256 + threadIdx.x;
+  const long tot = (long)g.p[0] * g.p[1] * g.p[2];
+  double r2 = 0.0, us = 0.0;
+  if (e < tot) {
+    const int i3 = (int)(e % g.p[2]);
+    const long rr = e / g.p[2];
+    const int i2 = (int)(rr % g.p[1]), i1 = (int)(rr / g.p[1]);
+    const size_t ep = g.atp(i1, i2, i3);
+    const bool real = i1 < g.n[0] && i2 < g.n[1] && i3 < g.n[2];
+    double R = 0.0, S = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0, N = 0.0, u = 0.0;
+    if (real) {
+      double tx = C.Rx[e], tz = C.Rz[e], ty = C.Ryp[ep];
+      if (V.a[0]) { a1 = V.a[0][e]; tx *= a1; }
+      if (V.a[2]) { a3 = V.a[2][e]; tz *= a3; }
+      if (V.a[1]) { a2 = V.a[1][e]; ty *= a2; }
+      R = tx + tz + ty - C.F[e];
+      u = C.Up[e];
+      if (V.rho) R += u * ((C.eq.r1 + V.rho[e]) + u * (C.eq.r2 + u * C.eq.r3));
+      else if (C.eq.on) R += u * (C.eq.r1 + u * (C.eq.r2 + u * C.eq.r3));
+      if (X.V[0]) N += X.V[0][e];
+      if (X.V[2]) N += X.V[2][e];
+      if (X.V[1]) N += X.V[1][ep];
+      R += u * N;
+      S = C.Sp[ep];
+      r2 = R * R;
+      us = u * S;
+    }
+    C.R[e] = R;
+    C.S[e] = S;
+    if (V.W[0]) V.W[0][e] = a1 * R;
+    if (V.W[1]) V.W[1][ep] = a2 * R;
+    else C.Rp[ep] = R;
+    if (V.W[2]) V.W[2][e] = a3 * R;
+    X.N[e] = N;
+    if (X.Q) X.Q[e] = u * R;
+    if (X.Qp) X.Qp[ep] = u * R;
+  }
+  __shared__ double sh[4];
+  r2 = k3_block_sum(r2, sh);
+  us = k3_block_sum(us, sh);
+  if (threadIdx.x == 0) {
+    C.red_egap[blockIdx.x] = r2;
+    C.red_quad[blockIdx.x] = us;
+  }
+}
+
 // one workgroup: loss (model_GP_solver_2d.py:145-174 with three log-det weights), the small
 // parameters' gradients and their Adam update (optax.adam, :179-182)
 __global__ __launch_bounds__(256) void k3_finalize_kernel(K3Final F) {
@@ -333,6 +392,44 @@ __global__ __launch_bounds__(256) void k3_adam_u_v_kernel(K3AdamUV V) {
   }
 }
 
+// k3_adam_u_v of a convective handle (gpk_create3_opc): d(u N)/du at fixed N joins the factor on R,
+// (r1 + rho + N) + u (2 r2 + 3 r3 u); rho may be absent.  (The other half of the product rule, the
+// dependence of N on U, arrives through X_k: T_k carries g_k D1_k^T x_k (u R).)
+__global__ __launch_bounds__(256) void k3_adam_u_c_kernel(K3AdamUC V) {
+  const K3AdamU& A = V.a;
+  const K3Geom& g = A.g;
+  const long e = (long)blockIdx.x * 256 + threadIdx.x;
+  const long nu = (long)g.n[0] * g.n[1] * g.n[2];
+  if (e >= nu) return;
+  const int i3 = (int)(e % g.n[2]);
+  const long rr = e / g.n[2];
+  const int i2 = (int)(rr % g.n[1]), i1 = (int)(rr / g.n[1]);
+  const size_t pi = g.at(i1, i2, i3), pp = g.atp(i1, i2, i3);
+  const double tau = A.sc->tau, v = A.sc->v, wt = A.llk_weight * tau;
+  const double u = A.Up[pi];
+  double gr = A.S[pi] + v * (A.X1[pi] + A.X2p[pp] + A.X3[pi]);
+  const double lin = (V.rho ? A.eq.r1 + V.rho[pi] : A.eq.r1) + V.N[pi];
+  gr += v * (lin + u * (2.0 * A.eq.r2 + 3.0 * A.eq.r3 * u)) * A.R[pi];
+  const int n1 = g.n[0], n2 = g.n[1], n3 = g.n[2];
+  const int f0 = n2 * n3, f2 = n1 * n3, f4 = n1 * n2;
+  const int b2 = 2 * f0, b4 = 2 * f0 + 2 * f2;
+  const int fm = A.eq.faces;
+  if ((fm & 1) && i1 == 0) gr += wt * (u - A.bvals[i2 * n3 + i3]);
+  if ((fm & 2) && i1 == n1 - 1) gr += wt * (u - A.bvals[f0 + i2 * n3 + i3]);
+  if ((fm & 4) && i2 == 0) gr += wt * (u - A.bvals[b2 + i1 * n3 + i3]);
+  if ((fm & 8) && i2 == n2 - 1) gr += wt * (u - A.bvals[b2 + f2 + i1 * n3 + i3]);
+  if ((fm & 16) && i3 == 0) gr += wt * (u - A.bvals[b4 + i1 * n2 + i2]);
+  if ((fm & 32) && i3 == n3 - 1) gr += wt * (u - A.bvals[b4 + f4 + i1 * n2 + i2]);
+  const long idx = A.off_u + e;
+  A.grad[idx] = gr;
+  if (A.apply) {
+    double p = A.params[idx], m = A.m[idx], vv = A.v[idx];
+    adam1(gr, p, m, vv, A.hyper, A.sc->bc1, A.sc->bc2);
+    A.params[idx] = p; A.m[idx] = m; A.v[idx] = vv;
+    A.Up[pi] = p;
+  }
+}
+
 // flat params (U unpadded) -> padded working copy
 __global__ __launch_bounds__(256) void k3_sync_u_kernel(const double* __restrict__ params, long off_u,
                                                         K3Geom g, double* __restrict__ Up) {
@@ -374,6 +471,14 @@ hipError_t k3_launch_adam_u(const K3AdamU& A, hipStream_t s) {
 }
 hipError_t k3_launch_adam_u_v(const K3AdamUV& V, hipStream_t s) {
   hipLaunchKernelGGL(k3_adam_u_v_kernel, dim3(blocks_of(V.a.g.real())), dim3(256), 0, s, V);
+  return hipGetLastError();
+}
+hipError_t k3_launch_combine_c(const K3CombineC& C, hipStream_t s) {
+  hipLaunchKernelGGL(k3_combine_c_kernel, dim3(blocks_of(C.v.c.g.padded())), dim3(256), 0, s, C);
+  return hipGetLastError();
+}
+hipError_t k3_launch_adam_u_c(const K3AdamUC& C, hipStream_t s) {
+  hipLaunchKernelGGL(k3_adam_u_c_kernel, dim3(blocks_of(C.a.g.real())), dim3(256), 0, s, C);
   return hipGetLastError();
 }
 hipError_t k3_launch_sync_u(const double* params, long off_u, const K3Geom& g, double* Up, hipStream_t s) {

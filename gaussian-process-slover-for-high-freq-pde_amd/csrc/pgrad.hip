@@ -418,8 +418,10 @@ __global__ __launch_bounds__(256) void pgrad_kernel(PGradBatch b, int q,
   __shared__ double sd[PAIRS], swk[PAIRS], swd[PAIRS];
   // DERIV_BOTH: swd weighs the order-2 field, swd1 the order-1 field (no reference in the other
   // modes: not allocated)
-  constexpr bool BOTH = DERIV == DERIV_BOTH;
-  static_assert(!BOTH || (!MODE1D && !CLS && !DD), "DERIV_BOTH: the 2D per-pair contraction only");
+  // DERIV_SPLIT: DERIV_BOTH with the order-1 block's own dL/dD1 (GD1) joining swd1
+  constexpr bool BOTH = deriv_two_fields(DERIV);
+  constexpr bool SPLIT = DERIV == DERIV_SPLIT;
+  static_assert(!BOTH || (!MODE1D && !CLS && !DD), "DERIV_BOTH / DERIV_SPLIT: the 2D per-pair contraction only");
   __shared__ double swd1[BOTH ? PAIRS : 1];
   __shared__ double sw[QMAX], sa[QMAX], so[QMAX], sol[QMAX];
   __shared__ double sacc[8][3][32];
@@ -503,6 +505,10 @@ __global__ __launch_bounds__(256) void pgrad_kernel(PGradBatch b, int q,
       if constexpr (BOTH) {
         wd1 = A.c1 * (I == J ? sij * gdij : sij * gdij + sji * gdji);
         wd = A.c2 * wd;
+      }
+      if constexpr (SPLIT) {  // + the signed pair sum of dL/dD1
+        const double g1ij = A.GD1[(size_t)i * A.p + j], g1ji = A.GD1[(size_t)j * A.p + i];
+        wd1 += I == J ? sij * g1ij : sij * g1ij + sji * g1ji;
       }
     }
     sd[t] = d;
@@ -676,6 +682,9 @@ static void launch_pg_c(const PGradBatch& b, int naxes, int bpa, int q, int deri
   } else if (deriv == DERIV_BOTH) {  // (per-pair only: launch_pgrad refuses it on the class path)
     if constexpr (!CLS)
       hipLaunchKernelGGL((pgrad_kernel<MATERN, COS, DERIV_BOTH, false, false>), grid, dim3(256), 0, s, b, q, sc);
+  } else if (deriv == DERIV_SPLIT) {
+    if constexpr (!CLS)
+      hipLaunchKernelGGL((pgrad_kernel<MATERN, COS, DERIV_SPLIT, false, false>), grid, dim3(256), 0, s, b, q, sc);
   } else {
     hipLaunchKernelGGL((pgrad_kernel<MATERN, COS, 1, false, CLS>), grid, dim3(256), 0, s, b, q, sc);
   }
@@ -731,10 +740,11 @@ hipError_t launch_pgrad(int kind, int q, int mode1d, const PGradArgs* a, int nax
                           shard_n > 1))
     return hipErrorInvalidValue;
   int deriv = a[0].deriv;
-  // one mode per launch (DERIV_BOTH carries its weights per axis): 2D per-pair contraction only
+  // one mode per launch (DERIV_BOTH and DERIV_SPLIT carry their weights per axis): 2D per-pair
+  // contraction only; DERIV_SPLIT needs its second operand
   for (int k = 0; k < naxes; ++k)
-    if ((a[k].deriv == DERIV_BOTH) != (deriv == DERIV_BOTH) ||
-        (deriv == DERIV_BOTH && (a[k].cls.ncls > 0 || mode1d)))
+    if ((deriv_two_fields(deriv) && (a[k].deriv != deriv || a[k].cls.ncls > 0 || mode1d)) ||
+        (!deriv_two_fields(deriv) && deriv_two_fields(a[k].deriv)) || (a[k].deriv == DERIV_SPLIT && !a[k].GD1))
       return hipErrorInvalidValue;
   switch (kind) {
     case SE_COS: launch_pg_t<false, true>(b, naxes, blocks_per_axis, q, deriv, mode1d, sc, s); break;

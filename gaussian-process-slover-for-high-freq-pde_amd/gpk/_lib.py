@@ -108,6 +108,10 @@ class gpk_bdata3(ctypes.Structure):
     _fields_ = [("dfaces", ctypes.c_int32), ("dvals", ctypes.POINTER(ctypes.c_double))]
 
 
+class gpk_conv3(ctypes.Structure):
+    _fields_ = [("g", ctypes.c_double * 3)]
+
+
 class gpk_gemm_case(ctypes.Structure):
     _fields_ = [
         ("M", ctypes.c_int32), ("N", ctypes.c_int32), ("K", ctypes.c_int32), ("K2", ctypes.c_int32),
@@ -196,6 +200,10 @@ EXPORTS = {
                          ctypes.POINTER(gpk_bdata3), ctypes.c_double, ctypes.POINTER(ctypes.c_void_p)], ctypes.c_int),
     "gpk_bdata_info3": ([ctypes.c_void_p, _ip, _ip], ctypes.c_int),
     "gpk_boundary_terms3": ([ctypes.c_void_p, _dp], ctypes.c_int),
+    "gpk_create3_opc": ([ctypes.POINTER(gpk_problem3), ctypes.POINTER(gpk_operator3x), ctypes.POINTER(gpk_coef3),
+                         ctypes.POINTER(gpk_bdata3), ctypes.POINTER(gpk_conv3), ctypes.c_double,
+                         ctypes.POINTER(ctypes.c_void_p)], ctypes.c_int),
+    "gpk_conv_info3": ([ctypes.c_void_p, _dp], ctypes.c_int),
     "gpk_destroy3": ([ctypes.c_void_p], ctypes.c_int),
     "gpk_num_params3": ([ctypes.c_void_p, ctypes.POINTER(ctypes.c_int64)], ctypes.c_int),
     "gpk_set_params3": ([ctypes.c_void_p, _dp, ctypes.c_int64], ctypes.c_int),
@@ -224,6 +232,8 @@ EXPORTS = {
                             ctypes.c_int32, _dp, ctypes.c_int32, _dp], ctypes.c_int),
     "gpk_assemble_pairs": ([ctypes.c_int32, _dp, ctypes.c_int32, _dp, _dp, _dp, ctypes.c_int32, ctypes.c_double,
                             ctypes.c_double, ctypes.c_double, _dp, _dp], ctypes.c_int),
+    "gpk_assemble_pairs2": ([ctypes.c_int32, _dp, ctypes.c_int32, _dp, _dp, _dp, ctypes.c_int32, ctypes.c_double,
+                             ctypes.c_double, ctypes.c_double, _dp, _dp, _dp], ctypes.c_int),
     "gpk_assemble_pairs_time": ([ctypes.c_int32, _dp, ctypes.c_int32, _dp, _dp, _dp, ctypes.c_int32, ctypes.c_double,
                                  ctypes.c_double, ctypes.c_int32, ctypes.c_int32, _dp], ctypes.c_int),
     "gpk_dgemm": ([ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_double, _dp,
@@ -506,6 +516,19 @@ def assemble_pairs(kind, x, paras, jitter=0.0, c2=1.0, c1=0.0):
     check(load().gpk_assemble_pairs(k, dptr(x), n, dptr(lw), dptr(ll), dptr(fr), lw.size, float(jitter),
                                     float(c2), float(c1), dptr(K), dptr(D)))
     return K, D
+
+
+def assemble_pairs2(kind, x, paras, jitter=0.0, c2=1.0, c1=0.0):
+    """The two-block mode of the same kernel (gpk_assemble_pairs2), which a convective axis
+    assembles in: (K, D, D1), D = c2 DD_x1_kappa + c1 D_x1_kappa at any weights, D1 = D_x1_kappa."""
+    x = f64(x).reshape(-1)
+    lw, ll, fr = (f64(paras[k]).reshape(-1) for k in ("log-w", "log-ls", "freq"))
+    n = x.size
+    K, D, D1 = (np.empty((max(n, 1), max(n, 1))) for _ in range(3))
+    k = KIND_IDS[kind] if isinstance(kind, str) else int(kind)
+    check(load().gpk_assemble_pairs2(k, dptr(x), n, dptr(lw), dptr(ll), dptr(fr), lw.size, float(jitter),
+                                     float(c2), float(c1), dptr(K), dptr(D), dptr(D1)))
+    return K, D, D1
 
 
 def assemble_pairs_time(kind, x, paras, c2=1.0, c1=0.0, split=False, iters=200):

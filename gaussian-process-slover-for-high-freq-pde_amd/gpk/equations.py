@@ -392,6 +392,44 @@ def deriv_boundary_3d(grad_u, axes, dfaces):
     return np.concatenate(out)
 
 
+# Equations with convective terms on [0, 1]^3 (gpk_create3_opc): the operator's linear part, the
+# constants g_k of the terms g_k u du / dx_k, and (as for EQUATIONS_3D_OPN) the derivative faces and
+# the closed-form gradient of u.  Viscous Burgers, nu fixed here for both entries.
+_BURGERS_NU = 0.05
+
+
+def _burgers_t_sin():
+    # u = e^{-t} sin(2x) sin(3y):  u_t + u (u_x + u_y) - nu (u_xx + u_yy) = (13 nu - 1) u + u (u_x + u_y)
+    u = lambda x, y, t: np.exp(-t) * s_(2 * x) * s_(3 * y)
+    grad = (lambda x, y, t: 2.0 * np.exp(-t) * c_(2 * x) * s_(3 * y),
+            lambda x, y, t: 3.0 * np.exp(-t) * s_(2 * x) * c_(3 * y),
+            lambda x, y, t: -u(x, y, t))
+    f = lambda x, y, t: (13.0 * _BURGERS_NU - 1.0) * u(x, y, t) + u(x, y, t) * (grad[0](x, y, t) + grad[1](x, y, t))
+    return u, f, Operator3X((-_BURGERS_NU, -_BURGERS_NU, 0.0), (0.0, 0.0, 1.0), faces=NO_FINAL_FACE), 0, grad, \
+        (1.0, 1.0, 0.0)
+
+
+def _burgers_3d_sin():
+    # steady, u = sin(2x) sin(3y) sin(z):  u (u_x + u_y + u_z) - nu lap u = u (u_x + u_y + u_z) + 14 nu u
+    u = lambda x, y, z: s_(2 * x) * s_(3 * y) * s_(z)
+    grad = (lambda x, y, z: 2.0 * c_(2 * x) * s_(3 * y) * s_(z),
+            lambda x, y, z: 3.0 * s_(2 * x) * c_(3 * y) * s_(z),
+            lambda x, y, z: s_(2 * x) * s_(3 * y) * c_(z))
+    f = lambda x, y, z: (u(x, y, z) * (grad[0](x, y, z) + grad[1](x, y, z) + grad[2](x, y, z))
+                         + 14.0 * _BURGERS_NU * u(x, y, z))
+    return u, f, Operator3X((-_BURGERS_NU,) * 3, (0.0, 0.0, 0.0)), 0, grad, (1.0, 1.0, 1.0)
+
+
+_OPC3D = {"burgers_t-sin": _burgers_t_sin, "burgers_3d-sin": _burgers_3d_sin}
+EQUATIONS_3D_OPC = list(_OPC3D)
+
+
+def solution_3d_opc(equation):
+    """(u, src, operator, dfaces, grad_u, conv) of an EQUATIONS_3D_OPC entry: the first five as
+    solution_3d_opn's, conv = (g_1, g_2, g_3), the constants of the terms g_k u du / dx_k."""
+    return _OPC3D[equation]()
+
+
 def boundary_2d(u_mesh):
     """get_boundary_vals: hstack(U[0,:], U[-1,:], U[:,0], U[:,-1]) (model_GP_solver_2d.py:377-379)."""
     return np.hstack((u_mesh[0, :], u_mesh[-1, :], u_mesh[:, 0], u_mesh[:, -1]))

@@ -30,7 +30,8 @@ gpk/config3d_opv/.
 Derivative boundary data (equations.EQUATIONS_3D_OPN: the wave equation with u and u_t on the
 initial face, Helmholtz between sound-hard walls) runs through gpk_create3_opn:
 DeviceSolver3(..., dfaces=, dvals=), trick_paras['dfaces'] / ['dvals'] or the equation's own,
-`-equation=wave_t-sin`, configs in gpk/config3d_opn/.
+`-equation=wave_t-sin`, configs in gpk/config3d_opn/.  Convective terms g_k u du/dx_k (viscous
+Burgers) run through gpk_create3_opc: `-equation=burgers_t-sin`, configs in gpk/config3d_opc/.
 """
 import ctypes
 import os
@@ -44,9 +45,9 @@ from . import _lib, init_func, replicas, utils
 from ._lib import check, dptr, f64
 from .cli import parse_flags
 from .core import tree_flatten, tree_unflatten
-from .equations import (EQUATIONS_3D, EQUATIONS_3D_OP, EQUATIONS_3D_OPN, EQUATIONS_3D_OPV, EQUATIONS_3D_OPX,
-                        Operator3, Operator3V, Operator3X, deriv_boundary_3d, solution_3d, solution_3d_op,
-                        solution_3d_opn, solution_3d_opv, solution_3d_opx)
+from .equations import (EQUATIONS_3D, EQUATIONS_3D_OP, EQUATIONS_3D_OPC, EQUATIONS_3D_OPN, EQUATIONS_3D_OPV,
+                        EQUATIONS_3D_OPX, Operator3, Operator3V, Operator3X, deriv_boundary_3d, solution_3d,
+                        solution_3d_op, solution_3d_opc, solution_3d_opn, solution_3d_opv, solution_3d_opx)
 from .infras.exp_config import ExpConfig
 from .kernel_matrix import kernel_class
 from .solver_common import SolverBase
@@ -79,7 +80,7 @@ class DeviceSolver3:
 
     def __init__(self, eq, kind, xs, src, bvals, Q=30, jitter=1e-6, llk_weight=200.0, logdet=True,
                  lr=0.01, freq_scale=20.0, device=0, b1=0.9, b2=0.999, eps=1e-8, refine=False,
-                 operator=None, dfaces=0, dvals=None):
+                 operator=None, dfaces=0, dvals=None, conv=None):
         """refine: one gated refinement step after every solve of the step (GPK_FLAG3_REFINE);
         'gemm' also forces its two-GEMM route (GPK_FLAG3_REFINE_GEMM; tests, A/B).
         operator: an Operator3 (or a dict of its fields) -- the handle then solves that operator
@@ -89,7 +90,10 @@ class DeviceSolver3:
         dfaces, dvals: derivative boundary data (gpk_create3_opn): bit f of dfaces puts d u / d x_k
         (k = f // 2, along the coordinate) on face f, dvals in bvals' six-face layout (entries of
         faces outside dfaces are never read); needs an Operator3X or Operator3V (or a dict with
-        'c2' and 'c1'), whose faces may then be 0."""
+        'c2' and 'c1'), whose faces may then be 0.
+        conv: three floats g_k, the constants of the convective terms g_k u du / dx_k
+        (gpk_create3_opc; Burgers); a non-zero one needs an Operator3X or Operator3V as dfaces
+        does.  None or three zeros is the handle without them."""
         lib = _lib.load()
         if len(xs) != 3:
             raise ValueError("three coordinate axes")
@@ -117,14 +121,22 @@ class DeviceSolver3:
         self._prob = p
         h = ctypes.c_void_p()
         dfaces = int(dfaces)
-        if dfaces:
-            if dvals is None:
+        if conv is not None:
+            conv = tuple(float(g) for g in np.asarray(conv, np.float64).reshape(-1))
+            if len(conv) != 3:
+                raise ValueError("conv has three entries (g_1, g_2, g_3)")
+            if not any(g != 0.0 for g in conv):
+                conv = None
+        if dfaces or conv:
+            if dfaces and dvals is None:
                 raise ValueError("dfaces needs dvals (the six-face layout of bvals)")
-            self._dvals = f64(dvals).reshape(-1)
-            if self._dvals.size != self._bvals.size:
-                raise ValueError("dvals must have the six-face layout of bvals (deriv_boundary_3d)")
+            if dfaces:
+                self._dvals = f64(dvals).reshape(-1)
+                if self._dvals.size != self._bvals.size:
+                    raise ValueError("dvals must have the six-face layout of bvals (deriv_boundary_3d)")
             if not (isinstance(operator, (Operator3X, Operator3V)) or (isinstance(operator, dict) and "c2" in operator)):
-                raise ValueError("derivative boundary data needs an Operator3X or Operator3V")
+                raise ValueError("%s needs an Operator3X or Operator3V"
+                                 % ("derivative boundary data" if dfaces else "a convective term"))
             c = _lib.gpk_operator3x()
             cf = _lib.gpk_coef3()
             if isinstance(operator, Operator3V):
@@ -139,9 +151,16 @@ class DeviceSolver3:
                 op = Operator3X.of(operator)
             c.c2[:], c.c1[:], c.react[:], c.faces = op.c2, op.c1, op.react, op.faces
             bd = _lib.gpk_bdata3()
-            bd.dfaces, bd.dvals = dfaces, dptr(self._dvals)
-            check(lib.gpk_create3_opn(ctypes.byref(p), ctypes.byref(c), ctypes.byref(cf), ctypes.byref(bd),
-                                      float(freq_scale), ctypes.byref(h)))
+            if dfaces:
+                bd.dfaces, bd.dvals = dfaces, dptr(self._dvals)
+            if conv:
+                cv = _lib.gpk_conv3()
+                cv.g[:] = conv
+                check(lib.gpk_create3_opc(ctypes.byref(p), ctypes.byref(c), ctypes.byref(cf), ctypes.byref(bd),
+                                          ctypes.byref(cv), float(freq_scale), ctypes.byref(h)))
+            else:
+                check(lib.gpk_create3_opn(ctypes.byref(p), ctypes.byref(c), ctypes.byref(cf), ctypes.byref(bd),
+                                          float(freq_scale), ctypes.byref(h)))
         elif operator is None:
             check(lib.gpk_create3(ctypes.byref(p), float(freq_scale), ctypes.byref(h)))
         elif isinstance(operator, Operator3V):
@@ -316,6 +335,13 @@ class DeviceSolver3:
         check(_lib.load().gpk_bdata_info3(self._h, ctypes.byref(f), ctypes.byref(d)))
         return f.value, d.value
 
+    def conv_info(self):
+        """(g_1, g_2, g_3): the constants of the convective terms (gpk_conv_info3); zeros on every
+        handle made without them."""
+        g = np.zeros(3)
+        check(_lib.load().gpk_conv_info3(self._h, dptr(g)))
+        return tuple(g.tolist())
+
     def boundary_terms(self):
         """{'bgap', 'dgap', 'Nb', 'Nd'}: the value gap, the derivative gap and their entry counts
         as the last loss_grad() / step() left them (gpk_boundary_terms3)."""
@@ -352,12 +378,13 @@ class GP_solver_3d_single(SolverBase):
     opx_eq_types = tuple(sorted({e.split("-")[0] for e in EQUATIONS_3D_OPX}))
     opv_eq_types = tuple(sorted({e.split("-")[0] for e in EQUATIONS_3D_OPV}))
     opn_eq_types = tuple(sorted({e.split("-")[0] for e in EQUATIONS_3D_OPN}))
+    opc_eq_types = tuple(sorted({e.split("-")[0] for e in EQUATIONS_3D_OPC}))
     early_stop_enabled = True
 
     def __init__(self, bvals, X_col, src_vals, jitter, trick_paras, device=0, X_test=None, u_test=None):
         self.eq_type = trick_paras["equation"].split("-")[0]
         assert self.eq_type in (self.eq_types + self.op_eq_types + self.opx_eq_types + self.opv_eq_types
-                                + self.opn_eq_types)
+                                + self.opn_eq_types + self.opc_eq_types)
         self.operator = None
         given = trick_paras.get("operator")
         if isinstance(given, Operator3V):
@@ -374,8 +401,16 @@ class GP_solver_3d_single(SolverBase):
             self.operator = solution_3d_opv(trick_paras["equation"])[2]
         # derivative boundary data: given, or the equation's own on the collocation mesh
         self.dfaces, self.dvals = int(trick_paras.get("dfaces", 0)), trick_paras.get("dvals")
-        if self.eq_type in self.opn_eq_types:
-            _, _, op, dfaces, grad_u = solution_3d_opn(trick_paras["equation"])
+        # convective terms: given, or the equation's own (a resumed run rebuilds them from its name)
+        conv = trick_paras.get("conv")
+        self.conv = None if conv is None else tuple(float(g) for g in conv)
+        if self.eq_type in self.opn_eq_types + self.opc_eq_types:
+            if self.eq_type in self.opc_eq_types:
+                _, _, op, dfaces, grad_u, conv = solution_3d_opc(trick_paras["equation"])
+                if self.conv is None:
+                    self.conv = tuple(conv)
+            else:
+                _, _, op, dfaces, grad_u = solution_3d_opn(trick_paras["equation"])
             self.operator = self.operator or op
             if "dfaces" not in trick_paras:
                 self.dfaces = dfaces
@@ -404,7 +439,7 @@ class GP_solver_3d_single(SolverBase):
                                  logdet=tp.get("logdet", True), lr=tp.get("lr", 0.01),
                                  freq_scale=tp.get("freq_scale", 20.0), device=int(tp.get("device", device)),
                                  refine=bool(tp.get("refine", False)), operator=self.operator,
-                                 dfaces=self.dfaces, dvals=self.dvals)
+                                 dfaces=self.dfaces, dvals=self.dvals, conv=self.conv)
         self._version = 0
 
     def eq_residual(self, params, X_test, src_test):
@@ -439,6 +474,13 @@ class GP_solver_3d_single(SolverBase):
             r = r + op.react[0] * u + op.react[1] * u ** 2 + op.react[2] * u ** 3
             if rho is not None:
                 r = r + rho * u
+        if self.conv is not None and any(self.conv):  # + u sum_k g_k du / dx_k
+            u = self.dev.predict(*axes)
+            for k, gk in enumerate(self.conv):
+                if gk != 0.0:
+                    d = [0, 0, 0]
+                    d[k] = 1
+                    r = r + gk * u * self.dev.predict_deriv(*axes, deriv=tuple(d))
         return r - np.asarray(src_test, np.float64).reshape(r.shape)
 
     # the device holds the params: reading fetches them, train()'s final assignment is a no-op
@@ -535,6 +577,8 @@ def test(trick_paras, solver_cls=None):
         u, src, op = solution_3d_opv(trick_paras["equation"])
     elif trick_paras["equation"] in EQUATIONS_3D_OPN:  # (the solver lays its own dvals out)
         u, src, op = solution_3d_opn(trick_paras["equation"])[:3]
+    elif trick_paras["equation"] in EQUATIONS_3D_OPC:  # (... and looks its conv up)
+        u, src, op = solution_3d_opc(trick_paras["equation"])[:3]
     else:
         u, src = solution_3d(trick_paras["equation"])
     scale = trick_paras["scale"]
@@ -572,10 +616,10 @@ def test(trick_paras, solver_cls=None):
 def load_config(equation):
     """./config3d/<equation>.yaml (the operator equations: ./config3d_op/, the mixed-order ones:
     ./config3d_opx/, the coefficient-field ones: ./config3d_opv/, derivative boundary data:
-    ./config3d_opn/), falling back to the package's copy."""
+    ./config3d_opn/, convective terms: ./config3d_opc/), falling back to the package's copy."""
     cdir = ("config3d_op" if equation in EQUATIONS_3D_OP else "config3d_opx" if equation in EQUATIONS_3D_OPX
             else "config3d_opv" if equation in EQUATIONS_3D_OPV else "config3d_opn" if equation in EQUATIONS_3D_OPN
-            else "config3d")
+            else "config3d_opc" if equation in EQUATIONS_3D_OPC else "config3d")
     for base in (os.getcwd(), os.path.dirname(os.path.abspath(__file__))):
         p = os.path.join(base, cdir, equation + ".yaml")
         if os.path.exists(p):
@@ -585,7 +629,7 @@ def load_config(equation):
 
 
 def build_config(args, allowed=EQUATIONS_3D + EQUATIONS_3D_OP + EQUATIONS_3D_OPX + EQUATIONS_3D_OPV
-                 + EQUATIONS_3D_OPN):
+                 + EQUATIONS_3D_OPN + EQUATIONS_3D_OPC):
     """The 2-axis build_config (scale, kernel class, other_paras) on the config3d files."""
     assert args.equation in allowed
     config = load_config(args.equation)

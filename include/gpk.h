@@ -630,6 +630,26 @@ int gpk_bdata_info3(const gpk_handle3* h, int32_t* faces, int32_t* dfaces);
  * are 0 on the older kinds. */
 int gpk_boundary_terms3(gpk_handle3* h, double out[4]);
 
+/* Convective terms (viscous and inviscid Burgers: u_t + u (u_x + u_y) - nu lap u = f).  Axis k adds
+ *     g_k . u . d u / d x_k
+ * to the equation of a gpk_create3_opn handle; with A_k = K_k^{-1} x_k U and D1_k the plain order-1
+ * block of axis k, V_k = g_k D1_k x_k A_k, N = sum_k V_k and the residual is the opn handle's plus
+ * U . N.  g_k is a CONSTANT: the gpk_coef3 fields multiply the linear terms of their axis only,
+ * never this one.  An axis may have c2_k = c1_k = 0 with g_k != 0 (inviscid).  Everything else --
+ * the log joint, the boundary and derivative-boundary terms, gpk_criterion3, gpk_loss_terms3,
+ * gpk_boundary_terms3, the Adam update -- keeps its formula on the new residual; predictions
+ * depend on K_k only.  Not built: the sharded, 1-axis and 2-axis handles, a field on the
+ * convective term, systems of equations, the conservative form d(u^2 / 2) / dx_k. */
+typedef struct gpk_conv3 { double g[3]; } gpk_conv3;
+/* p, op, cf and bd as on gpk_create3_opn (cf and bd may be NULL).  cv == NULL or all three
+ * g_k == 0.0 is gpk_create3_opn(p, op, cf, bd, ...) itself: the same stage list, launches and bits.
+ * GPK_EINVAL, before any device work, on a non-finite g_k, and on everything gpk_create3_opn,
+ * gpk_create3_opv and gpk_create3_opx reject. */
+int gpk_create3_opc(const gpk_problem3* p, const gpk_operator3x* op, const gpk_coef3* cf,
+                    const gpk_bdata3* bd, const gpk_conv3* cv, double freq_scale, gpk_handle3** out);
+/* The convective weights; zeros on every older kind of 3-axis handle. */
+int gpk_conv_info3(const gpk_handle3* h, double g[3]);
+
 int gpk_num_params3(const gpk_handle3* h, int64_t* n);
 int gpk_set_params3(gpk_handle3* h, const double* flat, int64_t n);
 int gpk_get_params3(gpk_handle3* h, double* flat, int64_t n);
@@ -731,6 +751,13 @@ int gpk_assemble_pairs(int32_t kind, const double* x, int32_t n, const double* l
 int gpk_assemble_pairs_time(int32_t kind, const double* x, int32_t n, const double* logw, const double* logls,
                             const double* freq, int32_t q, double c2, double c1, int32_t split,
                             int32_t iters, double* avg_us);
+
+/* The two-block mode of gpk_assemble_pairs' kernel, which a convective axis (gpk_create3_opc) assembles in:
+ * K_out, D_out = c2 DD_x1_kappa + c1 D_x1_kappa at any c2 and c1 (zeros included) and D1_out =
+ * D_x1_kappa alone, each n x n row-major. */
+int gpk_assemble_pairs2(int32_t kind, const double* x, int32_t n, const double* logw, const double* logls,
+                        const double* freq, int32_t q, double jitter, double c2, double c1,
+                        double* K_out, double* D_out, double* D1_out);
 
 #ifdef __cplusplus
 }
