@@ -33,6 +33,12 @@
 // R += U . N (k3_combine_c); the reverse pass reads Q = U . R: T_k += g_k D1_k^T x_k Q (the second
 // product of T_k's descriptor), G_D1k = v g_k Q_(k) A_k,(k)^T joins the order-1 weights of the
 // contraction, and dL/dU += v N . R (k3_adam_u_c) (build_conv_stages).
+// Mixed partials (gpk_create3_opm, m_jk d^2u/dx_j dx_k, j < k): both axes of a pair assemble in
+// DERIV_SPLIT; Z_j = D1_j x_j A_j, H_jk = K_k^{-1} x_k Z_j (a solve, refined like every other),
+// C_jk = m_jk D1_k x_k H_jk and R += C_13 + C_12 + C_23 (k3_combine_m).  The reverse pass forms
+// Hb_jk = m_jk D1_k^T x_k R, Zb_jk = K_k^{-1} x_k Hb_jk (a solve), T_j += D1_j^T x_j Zb_jk before
+// X_j, G_D1j += v Zb_jk,(j) A_j,(j)^T, G_D1k += v m_jk R_(k) H_jk,(k)^T and G_Kk -= v Zb_jk,(k)
+// H_jk,(k)^T: eight further launches (build_cross_stages).
 // GPK_FLAG3_REFINE: every one of the eight solves (A1, A2, A3, T, S, X1, X2, X3) is followed by
 // one refinement step X += K_k^{-1} (B - K_k X) gated on the axis's pst: one fused panel launch
 // (refine_panel.hip), or two GEMMs where its panels do not fit LDS (build_refine).
@@ -103,6 +109,17 @@ struct gpk_handle3 {
   int conv = 0;
   double gconv[3] = {};
   double *D1[3] = {}, *GD1[3] = {}, *V[3] = {}, *Nsum = nullptr, *Q = nullptr, *Qp = nullptr;
+  // gpk_create3_opm: the cross weights of the pairs (1,2), (1,3), (2,3) (cross = 0: none, and
+  // nothing below is allocated or launched).  Pair t = (j, k): Hx[t] = H_jk, Cx[t] = C_jk, Hb[t] =
+  // m D1_k^T x_k R and Zb[t] = K_k^{-1} x_k Hb[t], natural for (1,3) and mode-2 permuted for (1,2)
+  // and (2,3); Z1 = D1_1 x_1 A_1 natural (Z1p: its permuted copy, pair (1,2)), Z2p = D1_2 x_2 A_2
+  // permuted, Zb12 = Zb[0] brought back to the natural layout.  All are allocations of their own;
+  // the refinement's scratch of H_jk is Hb[t] (not yet formed) and that of Zb[t] is Cx[t] (read by
+  // k3_combine_m before), so nothing here aliases build_refine's scratch.
+  int cross = 0;
+  double mx[3] = {};
+  double *Z1 = nullptr, *Z1p = nullptr, *Z2p = nullptr, *Zb12 = nullptr;
+  double *Hx[3] = {}, *Cx[3] = {}, *Hb[3] = {}, *Zb[3] = {};
   double *GK[3] = {}, *GD[3] = {};
   double *red_egap = nullptr, *red_quad = nullptr;
   int nred = 0;
@@ -112,6 +129,11 @@ struct gpk_handle3 {
   // a convective handle's two further launches: [0] the V_k, after stage 2 and its refinement;
   // [1] the G_D1k, after stage 3 (empty elsewhere)
   std::vector<std::vector<GemmDesc>> cstages;
+  // a cross handle's eight further launches (build_cross_stages; empty elsewhere) and the
+  // refinement of its two solves per pair: xrstages[2 i] / [2 i + 1] the residuals / corrections
+  // and xrpanels[i] the fused panels of H_jk (i = 0) and Zb_jk (i = 1)
+  std::vector<std::vector<GemmDesc>> xstages, xrstages;
+  std::vector<std::vector<RefinePanel>> xrpanels;
   // GPK_FLAG3_REFINE: the refinement launches, [2 j] the residuals and [2 j + 1] the corrections
   // that follow stage kRefineAfter[j] (empty without the flag)
   std::vector<std::vector<GemmDesc>> rstages;
@@ -128,7 +150,8 @@ namespace {
 // that batch reads a T_k, which launch_huge's two passes need), and two launches of their own hold
 // V_k = g_k D1_k x_k A_k (next to the stage-2 products, whose batch is full) and G_D1k =
 // v g_k Q_(k) A_k,(k)^T (next to the G_Dk).  Axis 2 stays in the permuted layout; axis 3 has D1 on
-// the right, transposed like D[2].
+// the right, transposed like D[2].  (An axis is convective where g_k != 0: on a cross handle an axis
+// of a pair owns a D1_k without being convective.)
 void build_conv_stages(gpk_handle3* h) {
   const int P1 = h->g.p[0], P2 = h->g.p[1], P3 = h->g.p[2];
   const int M1 = P2 * P3, M2 = P1 * P3, M3 = P1 * P2;
@@ -139,24 +162,123 @@ void build_conv_stages(gpk_handle3* h) {
     d.A2 = A2; d.lda2 = lda2; d.ta2 = d.ta; d.B2 = B2; d.ldb2 = ldb2; d.tb2 = d.tb; d.K2 = K2; d.alpha2 = alpha2;
   };
   auto& t = h->stages[3];
-  if (D1[0]) dual(t[0], D1[0], P1, h->Q, M1, P1, g[0]);
-  if (D1[1]) dual(t[1], D1[1], P2, h->Qp, M2, P2, g[1]);
-  if (D1[2]) dual(t[2], h->Q, P3, D1[2], P3, P3, g[2]);
+  if (g[0] != 0.0) dual(t[0], D1[0], P1, h->Q, M1, P1, g[0]);
+  if (g[1] != 0.0) dual(t[1], D1[1], P2, h->Qp, M2, P2, g[1]);
+  if (g[2] != 0.0) dual(t[2], h->Q, P3, D1[2], P3, P3, g[2]);
   h->cstages.assign(2, {});
   auto& cv = h->cstages[0];
   auto& cg = h->cstages[1];
   auto vs = [](GemmDesc d) { d.vscale = 1; return d; };
-  if (D1[0]) {
+  if (g[0] != 0.0) {
     cv.push_back(scaled(gemm_desc(D1[0], P1, 0, h->A1, M1, 0, h->V[0], M1, P1, M1, P1), g[0]));
     cg.push_back(vs(scaled(gemm_desc(h->Q, M1, 0, h->A1, M1, 1, h->GD1[0], P1, P1, P1, M1), g[0])));
   }
-  if (D1[1]) {
+  if (g[1] != 0.0) {
     cv.push_back(scaled(gemm_desc(D1[1], P2, 0, h->A2p, M2, 0, h->V[1], M2, P2, M2, P2), g[1]));
     cg.push_back(vs(scaled(gemm_desc(h->Qp, M2, 0, h->A2p, M2, 1, h->GD1[1], P2, P2, P2, M2), g[1])));
   }
-  if (D1[2]) {
+  if (g[2] != 0.0) {
     cv.push_back(scaled(gemm_desc(h->A3, P3, 0, D1[2], P3, 1, h->V[2], P3, M3, P3, P3), g[2]));
     cg.push_back(vs(scaled(gemm_desc(h->Q, P3, 1, h->A3, P3, 0, h->GD1[2], P3, P3, P3, M3), g[2])));
+  }
+}
+
+// Mixed partials (gpk_create3_opm), after build_stages, build_conv_stages and build_refine.  Pair
+// (1,2) runs on the permuted copy of Z_1 and brings Zb_12 back to the natural layout for axis 1's
+// sums; (1,3) is natural throughout with K_3^{-1} and D1_3 on the right; (2,3) is permuted
+// throughout, mode 3 still being the contiguous index there.  Launches, in stream order:
+//   [0] Z_j  [1] H_jk (solves)  [2] C_jk             after stage 2, before k3_combine_m
+//   [3] Hb_jk  [4] Zb_jk (solves)  [5] T_j += ...  [6] G_D1     after stage 3, before stage 4
+//   [7] G_Kk += ...                                   after the last stage
+// An axis takes at most two cross products into T_j, G_D1 or G_Kk: they share one descriptor (the
+// dual-product slot), which adds them to what the target holds (C0 = C, beta = 1: every GEMM kernel
+// reads C0 at the element it then writes, in the same thread, as the refinement's in-place
+// corrections rely on; launch_huge's first pass does the same and its second reads C alone).  G_D1
+// of an axis that is not convective holds nothing yet and is written, not added to.
+void build_cross_stages(gpk_handle3* h) {
+  const int P1 = h->g.p[0], P2 = h->g.p[1], P3 = h->g.p[2];
+  const int M1 = P2 * P3, M2 = P1 * P3, M3 = P1 * P2;
+  const double* m = h->mx;
+  double* const* Ki = h->Kinv;
+  double* const* D1 = h->D1;
+  const bool on[3] = {m[0] != 0.0, m[1] != 0.0, m[2] != 0.0};
+  const bool refine = !h->rstages.empty();
+  auto scaled = [](GemmDesc d, double alpha) { d.alpha = alpha; return d; };
+  auto& xs = h->xstages;
+  xs.assign(8, {});
+  h->xrstages.assign(refine ? 4 : 0, {});
+  h->xrpanels.assign(refine ? 2 : 0, {});
+  // solve i (0: H_jk, 1: Zb_jk) of a pair against its outer axis a (1: left, permuted; 2: right)
+  auto solve = [&](int i, int a, const double* B, double* X, double* W) {
+    const bool right = a == 2;
+    const int rows = right ? M3 : P2, cols = right ? P3 : M2;
+    const RefinedSolve s = refined_solve(right, h->Kc[a], Ki[a], B, X, W, rows, cols, h->pst[a]);
+    xs[i ? 4 : 1].push_back(s.solve);
+    if (!refine) return;
+    h->xrstages[2 * i].push_back(s.resid);
+    h->xrstages[2 * i + 1].push_back(s.fix);
+    h->xrpanels[i].push_back(refine_panel_desc(right, h->Kc[a], Ki[a], B, X, rows, cols, h->pst[a]));
+  };
+  if (on[0] || on[1]) xs[0].push_back(gemm_desc(D1[0], P1, 0, h->A1, M1, 0, h->Z1, M1, P1, M1, P1));
+  if (on[2]) xs[0].push_back(gemm_desc(D1[1], P2, 0, h->A2p, M2, 0, h->Z2p, M2, P2, M2, P2));
+  if (on[0]) {  // (1,2), permuted
+    solve(0, 1, h->Z1p, h->Hx[0], h->Hb[0]);
+    xs[2].push_back(scaled(gemm_desc(D1[1], P2, 0, h->Hx[0], M2, 0, h->Cx[0], M2, P2, M2, P2), m[0]));
+    xs[3].push_back(scaled(gemm_desc(D1[1], P2, 1, h->Rp, M2, 0, h->Hb[0], M2, P2, M2, P2), m[0]));
+    solve(1, 1, h->Hb[0], h->Zb[0], h->Cx[0]);
+  }
+  if (on[1]) {  // (1,3), natural
+    solve(0, 2, h->Z1, h->Hx[1], h->Hb[1]);
+    xs[2].push_back(scaled(gemm_desc(h->Hx[1], P3, 0, D1[2], P3, 1, h->Cx[1], P3, M3, P3, P3), m[1]));
+    xs[3].push_back(scaled(gemm_desc(h->R, P3, 0, D1[2], P3, 0, h->Hb[1], P3, M3, P3, P3), m[1]));
+    solve(1, 2, h->Hb[1], h->Zb[1], h->Cx[1]);
+  }
+  if (on[2]) {  // (2,3), permuted
+    solve(0, 2, h->Z2p, h->Hx[2], h->Hb[2]);
+    xs[2].push_back(scaled(gemm_desc(h->Hx[2], P3, 0, D1[2], P3, 1, h->Cx[2], P3, M3, P3, P3), m[2]));
+    xs[3].push_back(scaled(gemm_desc(h->Rp, P3, 0, D1[2], P3, 0, h->Hb[2], P3, M3, P3, P3), m[2]));
+    solve(1, 2, h->Hb[2], h->Zb[2], h->Cx[2]);
+  }
+  // up to two products into one target: the second in the dual slot, each with its own factor
+  struct Prod { const double* A; int lda, ta; const double* B; int ldb, tb, K; double alpha; };
+  auto sum = [](const std::vector<Prod>& p, double* C, int ldc, int M, int N, bool add, int vs) {
+    GemmDesc d = gemm_desc(p[0].A, p[0].lda, p[0].ta, p[0].B, p[0].ldb, p[0].tb, C, ldc, M, N, p[0].K);
+    d.alpha = p[0].alpha; d.vscale = vs;
+    if (p.size() > 1) {
+      d.A2 = p[1].A; d.lda2 = p[1].lda; d.ta2 = p[1].ta; d.B2 = p[1].B; d.ldb2 = p[1].ldb; d.tb2 = p[1].tb;
+      d.K2 = p[1].K; d.alpha2 = p[1].alpha; d.vscale2 = vs;
+    }
+    if (add) { d.beta = 1.0; d.C0 = C; d.ldc0 = ldc; }
+    return d;
+  };
+  // T_1 += D1_1^T x_1 (Zb_12 + Zb_13);  T_2 += D1_2^T x_2 Zb_23 (permuted)
+  {
+    std::vector<Prod> t1;
+    if (on[0]) t1.push_back({D1[0], P1, 1, h->Zb12, M1, 0, P1, 1.0});
+    if (on[1]) t1.push_back({D1[0], P1, 1, h->Zb[1], M1, 0, P1, 1.0});
+    if (!t1.empty()) xs[5].push_back(sum(t1, h->T1, M1, P1, M1, true, 0));
+    if (on[2]) xs[5].push_back(sum({{D1[1], P2, 1, h->Zb[2], M2, 0, P2, 1.0}}, h->T2p, M2, P2, M2, true, 0));
+  }
+  // G_D1 per axis: inner products v Zb_(j) A_j^T, outer products v m R_(k) H_(k)^T
+  {
+    std::vector<Prod> g1, g2, g3;
+    if (on[0]) g1.push_back({h->Zb12, M1, 0, h->A1, M1, 1, M1, 1.0});
+    if (on[1]) g1.push_back({h->Zb[1], M1, 0, h->A1, M1, 1, M1, 1.0});
+    if (on[0]) g2.push_back({h->Rp, M2, 0, h->Hx[0], M2, 1, M2, m[0]});
+    if (on[2]) g2.push_back({h->Zb[2], M2, 0, h->A2p, M2, 1, M2, 1.0});
+    if (on[1]) g3.push_back({h->R, P3, 1, h->Hx[1], P3, 0, M3, m[1]});
+    if (on[2]) g3.push_back({h->Rp, P3, 1, h->Hx[2], P3, 0, M3, m[2]});
+    if (!g1.empty()) xs[6].push_back(sum(g1, h->GD1[0], P1, P1, P1, h->gconv[0] != 0.0, 1));
+    if (!g2.empty()) xs[6].push_back(sum(g2, h->GD1[1], P2, P2, P2, h->gconv[1] != 0.0, 1));
+    if (!g3.empty()) xs[6].push_back(sum(g3, h->GD1[2], P3, P3, P3, h->gconv[2] != 0.0, 1));
+  }
+  // G_K2 -= v Zb_12,(2) H_12,(2)^T;  G_K3 -= v (Zb_13,(3) H_13,(3)^T + Zb_23,(3) H_23,(3)^T)
+  {
+    std::vector<Prod> k3;
+    if (on[0]) xs[7].push_back(sum({{h->Zb[0], M2, 0, h->Hx[0], M2, 1, M2, -1.0}}, h->GK[1], P2, P2, P2, true, 1));
+    if (on[1]) k3.push_back({h->Zb[1], P3, 1, h->Hx[1], P3, 0, M3, -1.0});
+    if (on[2]) k3.push_back({h->Zb[2], P3, 1, h->Hx[2], P3, 0, M3, -1.0});
+    if (!k3.empty()) xs[7].push_back(sum(k3, h->GK[2], P3, P3, P3, true, 1));
   }
 }
 
@@ -285,6 +407,18 @@ int launch_stage(gpk_handle3* h, int k) {
   return GPK_OK;
 }
 
+// a cross handle's solves i (0: the H_jk, 1: the Zb_jk), then their refinement when the handle refines
+int launch_cross_solves(gpk_handle3* h, int i) {
+  TRY(launch_descs(h, h->xstages[i ? 4 : 1]));
+  if (h->xrstages.empty()) return GPK_OK;
+  if (h->route) {
+    const auto& f = h->xrpanels[i];
+    return check_launch(launch_refine_panel(f.data(), (int)f.size(), h->sc, h->s), "refine_panel");
+  }
+  TRY(launch_descs(h, h->xrstages[2 * i]));
+  return launch_descs(h, h->xrstages[2 * i + 1]);
+}
+
 K3Eq eq_layer(const gpk_handle3* h) {
   const double* r = h->op.react;
   K3Eq e{};
@@ -370,16 +504,30 @@ int enqueue_step3(gpk_handle3* h, int apply) {
   TRY(check_launch(k3_launch_permute(h->Tm, h->Tp, g, h->s), "k3_permute"));
   TRY(launch_stage(h, 2));
   if (h->conv) TRY(launch_descs(h, h->cstages[0]));  // V_k, from the refined A_k
+  if (h->cross) {  // Z_j from the refined A_j, H_jk (pair (1,2): on the permuted Z_1), C_jk
+    TRY(launch_descs(h, h->xstages[0]));
+    if (h->Z1p) TRY(check_launch(k3_launch_permute(h->Z1, h->Z1p, g, h->s), "k3_permute"));
+    TRY(launch_cross_solves(h, 0));
+    TRY(launch_descs(h, h->xstages[2]));
+  }
   K3Combine C{};
   C.g = g; C.Rx = h->Rx; C.Rz = h->Rz; C.Ryp = h->Ryp; C.F = h->F; C.Up = h->Up; C.Sp = h->Sp;
   C.eq = eq_layer(h); C.R = h->R; C.Rp = h->Rp; C.S = h->S;
   C.red_egap = h->red_egap; C.red_quad = h->red_quad;
-  if (h->conv) {
+  if (h->conv || h->cross) {
     K3CombineC X{};
     X.v.c = C; X.v.rho = h->rho;
     for (int a = 0; a < 3; ++a) { X.v.a[a] = h->cf[a]; X.v.W[a] = h->W[a]; X.V[a] = h->V[a]; }
     X.N = h->Nsum; X.Q = h->Q; X.Qp = h->Qp;
-    TRY(check_launch(k3_launch_combine_c(X, h->s), "k3_combine_c"));
+    if (h->cross) {
+      K3CombineM Mx{};
+      Mx.c = X;
+      Mx.C[0] = h->Cx[0]; Mx.C[1] = h->Cx[1]; Mx.C[2] = h->Cx[2];
+      Mx.rp = h->Cx[0] || h->Cx[2];
+      TRY(check_launch(k3_launch_combine_m(Mx, h->s), "k3_combine_m"));
+    } else {
+      TRY(check_launch(k3_launch_combine_c(X, h->s), "k3_combine_c"));
+    }
   } else if (h->cf[0] || h->cf[1] || h->cf[2] || h->rho) {
     K3CombineV V{};
     V.c = C; V.rho = h->rho;
@@ -396,7 +544,15 @@ int enqueue_step3(gpk_handle3* h, int apply) {
     for (int a = 0; a < 3 && k == 3; ++a)
       if (h->fpart[a])
         TRY(check_launch(k3_launch_face_back(h->face[a], a == 2, h->sc, h->prob.llk_weight, h->s), "k3_face_back"));
+    if (h->cross && k == 3) {  // Hb_jk, Zb_jk, then T_j's share before X_j = K_j^{-1} x_j T_j reads it; G_D1
+      TRY(launch_descs(h, h->xstages[3]));
+      TRY(launch_cross_solves(h, 1));
+      if (h->Zb12) TRY(check_launch(k3_launch_unpermute(h->Zb[0], h->Zb12, g, h->s), "k3_permute"));
+      TRY(launch_descs(h, h->xstages[5]));
+      TRY(launch_descs(h, h->xstages[6]));
+    }
   }
+  if (h->cross) TRY(launch_descs(h, h->xstages[7]));  // G_Kk's share, added to the last stage's G_Kk
   // kernel-parameter contraction (the 2-axis kernels: axes 1-2, then axis 3)
   const int fb = h->dfaces ? K3_FACE_TAIL_BLOCKS : 0;  // + blocks of partials per axis: the face rows' (k3_face_tail)
   PGradArgs pg[3] = {};
@@ -505,7 +661,7 @@ int check_problem3(const gpk_problem3* p) {
 // gpk_create3_opv (cf: the fields it was given, at least one of them)
 int create3(const gpk_problem3* p, const gpk_operator3* op, double freq_scale, gpk_handle3** out,
             const gpk_operator3x* opx = nullptr, const gpk_coef3* cf = nullptr, const gpk_bdata3* bd = nullptr,
-            const gpk_conv3* cv = nullptr) {
+            const gpk_conv3* cv = nullptr, const gpk_cross3* mx = nullptr) {
   TRY(check_problem3(p));
   const int ns[3] = {p->n1, p->n2, p->n3};
   TRY(check_device(p->device));
@@ -530,6 +686,14 @@ int create3(const gpk_problem3* p, const gpk_operator3* op, double freq_scale, g
       h->conv = 1;
       h->mode[a] = DERIV_SPLIT;
     }
+    // so does an axis of a pair with a cross weight (it owns D1_k and G_D1k as well)
+    static const int pairs[3][2] = {{0, 1}, {0, 2}, {1, 2}};
+    for (int t = 0; t < 3 && mx; ++t)
+      if (mx->m[t] != 0.0 && (pairs[t][0] == a || pairs[t][1] == a)) {
+        h->mx[t] = mx->m[t];
+        h->cross = 1;
+        h->mode[a] = DERIV_SPLIT;
+      }
     h->c2[a] = mixed ? opx->c2[a] : h->op.order[a] == 2 ? h->op.coef[a] : 0.0;
     h->c1[a] = mixed ? opx->c1[a] : h->op.order[a] == 1 ? h->op.coef[a] : 0.0;
   }
@@ -641,14 +805,26 @@ int create3(const gpk_problem3* p, const gpk_operator3* op, double freq_scale, g
     }
   }
   // convective axes: D1_k, V_k and G_D1k per axis, N, and Q in the layouts those axes read
-  for (int a = 0; a < 3 && h->conv; ++a) {
-    if (h->gconv[a] == 0.0) continue;
+  // (and D1_k, G_D1k on the axes of a cross pair)
+  for (int a = 0; a < 3 && (h->conv || h->cross); ++a) {
+    if (h->mode[a] != DERIV_SPLIT) continue;
     const int P = g.p[a];
-    A3_(h->D1[a], (size_t)P * P); A3_(h->GD1[a], (size_t)P * P); A3_(h->V[a], np);
+    A3_(h->D1[a], (size_t)P * P); A3_(h->GD1[a], (size_t)P * P);
+    if (h->gconv[a] == 0.0) continue;
+    A3_(h->V[a], np);
     if (a == 1) { A3_(h->Qp, np); }
     else if (!h->Q) { A3_(h->Q, np); }
   }
   if (h->conv) A3_(h->Nsum, np);
+  // cross pairs: per pair H, C, Hb and Zb; Z_1 / Z_2 for the pairs that start from them, and the
+  // two copies pair (1,2) goes through
+  for (int t = 0; t < 3 && h->cross; ++t) {
+    if (h->mx[t] == 0.0) continue;
+    A3_(h->Hx[t], np); A3_(h->Cx[t], np); A3_(h->Hb[t], np); A3_(h->Zb[t], np);
+    if (t < 2 && !h->Z1) A3_(h->Z1, np);
+    if (t == 0) { A3_(h->Z1p, np); A3_(h->Zb12, np); }
+    if (t == 2) A3_(h->Z2p, np);
+  }
 #undef A3_
   // upload: coordinates, the padded source, boundary values, the initial params
   // (model_GP_solver_2d.py:245-261: U = 0, freq = linspace(0,1,Q) freq_scale, log-ls = 0,
@@ -679,6 +855,7 @@ int create3(const gpk_problem3* p, const gpk_operator3* op, double freq_scale, g
     build_refine(h);
     if (h->route && refine_panel_prepare() != hipSuccess) return bail(fail(GPK_EHIP, "refine_panel_prepare failed"));
   }
+  if (h->cross) build_cross_stages(h);
   *out = h;
   return GPK_OK;
 }
@@ -788,7 +965,7 @@ namespace {
 // gpk_create3_opn with derivative faces, and gpk_create3_opc with a convective axis (cv; bd may
 // then be null or without faces): the argument checks of both, then the handle
 int create3_opn(const gpk_problem3* p, const gpk_operator3x* op, const gpk_coef3* cf, const gpk_bdata3* bd,
-                const gpk_conv3* cv, double freq_scale, gpk_handle3** out) {
+                const gpk_conv3* cv, double freq_scale, gpk_handle3** out, const gpk_cross3* mx = nullptr) {
   if (!p || !op || !out) return fail(GPK_EINVAL, "NULL argument");
   *out = nullptr;
   if (bd && bd->dfaces == 0) bd = nullptr;
@@ -797,7 +974,7 @@ int create3_opn(const gpk_problem3* p, const gpk_operator3x* op, const gpk_coef3
   // the operator's own checks, with faces = 0 allowed here (data on derivatives alone)
   gpk_operator3x o = *op;
   if (bd && o.faces == 0) o.faces = bd->dfaces;
-  TRY(check_operator3x(p, &o, out, cv ? "gpk_create3_opc" : "gpk_create3_opn"));
+  TRY(check_operator3x(p, &o, out, mx ? "gpk_create3_opm" : cv ? "gpk_create3_opc" : "gpk_create3_opn"));
   TRY(check_problem3(p));
   if (bd) {
     const long fs[3] = {(long)p->n2 * p->n3, (long)p->n1 * p->n3, (long)p->n1 * p->n2};
@@ -820,7 +997,24 @@ int create3_opn(const gpk_problem3* p, const gpk_operator3x* op, const gpk_coef3
   // mixed axis (order 0, GEMM weight 1.0)
   for (int a = 0; a < 3 && cv; ++a)
     if (cv->g[a] != 0.0) { o1.order[a] = 0; o1.coef[a] = 1.0; }
-  return create3(p, &o1, freq_scale, out, op, any ? cf : nullptr, bd, cv);
+  // and so are both axes of a pair with a cross weight
+  if (mx) {
+    const bool in[3] = {mx->m[0] != 0.0 || mx->m[1] != 0.0, mx->m[0] != 0.0 || mx->m[2] != 0.0,
+                        mx->m[1] != 0.0 || mx->m[2] != 0.0};
+    for (int a = 0; a < 3; ++a)
+      if (in[a]) { o1.order[a] = 0; o1.coef[a] = 1.0; }
+  }
+  return create3(p, &o1, freq_scale, out, op, any ? cf : nullptr, bd, cv, mx);
+}
+
+// the convective weights as gpk_create3_opc and gpk_create3_opm (`who`) take them: GPK_EINVAL on a
+// non-finite g_k, and cv becomes null when all three are zero (no convective axis)
+int check_conv3(const gpk_conv3*& cv, const char* who) {
+  if (!cv) return GPK_OK;
+  for (int a = 0; a < 3; ++a)
+    if (!std::isfinite(cv->g[a])) return fail(GPK_EINVAL, std::string(who) + ": g must be finite");
+  if (cv->g[0] == 0.0 && cv->g[1] == 0.0 && cv->g[2] == 0.0) cv = nullptr;
+  return GPK_OK;
 }
 
 }  // namespace
@@ -835,14 +1029,29 @@ int gpk_create3_opn(const gpk_problem3* p, const gpk_operator3x* op, const gpk_c
 
 int gpk_create3_opc(const gpk_problem3* p, const gpk_operator3x* op, const gpk_coef3* cf, const gpk_bdata3* bd,
                     const gpk_conv3* cv, double freq_scale, gpk_handle3** out) {
-  if (cv) {
-    if (out) *out = nullptr;
-    for (int a = 0; a < 3; ++a)
-      if (!std::isfinite(cv->g[a])) return fail(GPK_EINVAL, "gpk_create3_opc: g must be finite");
-  }
-  if (!cv || (cv->g[0] == 0.0 && cv->g[1] == 0.0 && cv->g[2] == 0.0))
-    return gpk_create3_opn(p, op, cf, bd, freq_scale, out);
+  if (cv && out) *out = nullptr;
+  TRY(check_conv3(cv, "gpk_create3_opc"));
+  if (!cv) return gpk_create3_opn(p, op, cf, bd, freq_scale, out);
   return create3_opn(p, op, cf, bd, cv, freq_scale, out);
+}
+
+int gpk_create3_opm(const gpk_problem3* p, const gpk_operator3x* op, const gpk_coef3* cf, const gpk_bdata3* bd,
+                    const gpk_conv3* cv, const gpk_cross3* mx, double freq_scale, gpk_handle3** out) {
+  if (mx) {
+    if (out) *out = nullptr;
+    for (int t = 0; t < 3; ++t)
+      if (!std::isfinite(mx->m[t])) return fail(GPK_EINVAL, "gpk_create3_opm: m must be finite");
+  }
+  if (!mx || (mx->m[0] == 0.0 && mx->m[1] == 0.0 && mx->m[2] == 0.0))
+    return gpk_create3_opc(p, op, cf, bd, cv, freq_scale, out);
+  TRY(check_conv3(cv, "gpk_create3_opm"));
+  return create3_opn(p, op, cf, bd, cv, freq_scale, out, mx);
+}
+
+int gpk_cross_info3(const gpk_handle3* h, double m[3]) {
+  if (!h || !m) return fail(GPK_EINVAL, "NULL argument");
+  for (int t = 0; t < 3; ++t) m[t] = h->mx[t];
+  return GPK_OK;
 }
 
 int gpk_conv_info3(const gpk_handle3* h, double g[3]) {
@@ -983,12 +1192,16 @@ int gpk_boundary_terms3(gpk_handle3* h, double out[4]) {
 
 int gpk_stage_variants3(gpk_handle3* h, int32_t* out, int32_t cap, int32_t* n) {
   if (!h || !n || cap < 0 || (cap && !out)) return fail(GPK_EINVAL, "NULL argument");
-  // stream order: a convective handle's two further launches follow stages 2 and 3
+  // stream order: a convective handle's two further launches follow stages 2 and 3; a cross
+  // handle's eight follow those (three, four) and the last stage (one)
   std::vector<const std::vector<GemmDesc>*> order;
   for (size_t k = 0; k < h->stages.size(); ++k) {
     order.push_back(&h->stages[k]);
     if (h->conv && (k == 2 || k == 3)) order.push_back(&h->cstages[k - 2]);
+    if (h->cross && k == 2) for (int i = 0; i < 3; ++i) order.push_back(&h->xstages[i]);
+    if (h->cross && k == 3) for (int i = 3; i < 7; ++i) order.push_back(&h->xstages[i]);
   }
+  if (h->cross) order.push_back(&h->xstages[7]);
   *n = (int32_t)order.size();
   for (int k = 0; k < *n && k < cap; ++k) out[k] = stage_variant(*order[k]);
   return GPK_OK;

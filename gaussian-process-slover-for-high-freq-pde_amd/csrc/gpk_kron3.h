@@ -115,6 +115,17 @@ struct K3CombineC {
   double *N, *Q, *Qp;
 };
 
+// k3_combine_m (gpk_create3_opm): k3_combine_c plus the mixed partials C_13 + C_12 + C_23, C_jk =
+// m_jk D1_k x_k K_k^{-1} x_k D1_j x_j A_j (null: the pair is absent; C[0] = C_12 and C[2] = C_23 in
+// the mode-2 permuted layout, C[1] = C_13 natural).  Every pointer of c.v and c.V, and c.N, c.Q and
+// c.Qp, may be null here (a handle without fields or convective axes).  rp = 1 writes v.c.Rp even
+// when axis 2 has a field: the pairs (1,2) and (2,3) read R itself in the permuted layout.
+struct K3CombineM {
+  K3CombineC c;
+  const double* C[3];
+  int rp;
+};
+
 // k3_adam_u_c: k3_adam_u_v with N (natural padded layout) added to the factor on R; rho nullable
 struct K3AdamUC {
   K3AdamU a;
@@ -182,6 +193,10 @@ hipError_t k3_launch_adam_u(const K3AdamU& A, hipStream_t s);
 hipError_t k3_launch_adam_u_v(const K3AdamUV& V, hipStream_t s);
 hipError_t k3_launch_combine_c(const K3CombineC& C, hipStream_t s);
 hipError_t k3_launch_adam_u_c(const K3AdamUC& C, hipStream_t s);
+hipError_t k3_launch_combine_m(const K3CombineM& M, hipStream_t s);
+// dst[i1][i2][i3] = src[i2][i1][i3]: k3_permute's inverse (k3_permute itself on the grid with axes
+// 1 and 2 swapped, where its source index is this one's and its target index the natural one)
+hipError_t k3_launch_unpermute(const double* src, double* dst, const K3Geom& g, hipStream_t s);
 hipError_t k3_launch_sync_u(const double* params, long off_u, const K3Geom& g, double* Up, hipStream_t s);
 
 }  // namespace gpk

@@ -23,6 +23,9 @@
 // Convective terms (gpk_create3_opc): k3_combine_c is k3_combine_v plus u N, N = sum_k g_k D1_k x_k
 // A_k, and writes N and Q = u R for the reverse pass; k3_adam_u_c carries N in the reaction factor.
 // Kernels of their own again.
+// Mixed partials (gpk_create3_opm): k3_combine_m is k3_combine_c plus the cross terms C_13 + C_12 +
+// C_23 (formed by GEMMs, gpk_kron3.cpp build_cross_stages); the back-permute of Zb_12 is k3_permute
+// on the grid with axes 1 and 2 swapped.  A kernel of its own once more.
 // Grids are padded per axis to P_k (multiple of 32); pads of every tensor are zero.
 #include "gpk_internal.h"
 #include "gpk_kron3.h"
@@ -234,6 +237,65 @@ __global__ __launch_bounds__(256) void k3_combine_c_kernel(K3CombineC X) {
     else C.Rp[ep] = R;
     if (V.W[2]) V.W[2][e] = a3 * R;
     X.N[e] = N;
+    if (X.Q) X.Q[e] = u * R;
+    if (X.Qp) X.Qp[ep] = u * R;
+  }
+  __shared__ double sh[4];
+  r2 = k3_block_sum(r2, sh);
+  us = k3_block_sum(us, sh);
+  if (threadIdx.x == 0) {
+    C.red_egap[blockIdx.x] = r2;
+    C.red_quad[blockIdx.x] = us;
+  }
+}
+
+// k3_combine_c with mixed partials (gpk_create3_opm): R is summed in k3_combine_c's order, then
+// + C_13 + C_12 + C_23 in that fixed order, each only where its pair is present (C_12 and C_23 read
+// at the permuted index).  N, Q and Qp are written where asked for (a handle without a convective
+// axis asks for none); Rp is written when axis 2 has no field or a permuted pair reads it (rp).
+// Fields, V_k and C_jk are read at real entries only; the pads of every output are zero.
+__global__ __launch_bounds__(256) void k3_combine_m_kernel(K3CombineM Mx) {
+  const K3CombineC& X = Mx.c;
+  const K3CombineV& V = X.v;
+  const K3Combine& C = V.c;
+  const K3Geom& g = C.g;
+  const long e = (long)blockIdx.x * 256 + threadIdx.x;
+  const long tot = (long)g.p[0] * g.p[1] * g.p[2];
+  double r2 = 0.0, us = 0.0;
+  if (e < tot) {
+    const int i3 = (int)(e % g.p[2]);
+    const long rr = e / g.p[2];
+    const int i2 = (int)(rr % g.p[1]), i1 = (int)(rr / g.p[1]);
+    const size_t ep = g.atp(i1, i2, i3);
+    const bool real = i1 < g.n[0] && i2 < g.n[1] && i3 < g.n[2];
+    double R = 0.0, S = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0, N = 0.0, u = 0.0;
+    if (real) {
+      double tx = C.Rx[e], tz = C.Rz[e], ty = C.Ryp[ep];
+      if (V.a[0]) { a1 = V.a[0][e]; tx *= a1; }
+      if (V.a[2]) { a3 = V.a[2][e]; tz *= a3; }
+      if (V.a[1]) { a2 = V.a[1][e]; ty *= a2; }
+      R = tx + tz + ty - C.F[e];
+      u = C.Up[e];
+      if (V.rho) R += u * ((C.eq.r1 + V.rho[e]) + u * (C.eq.r2 + u * C.eq.r3));
+      else if (C.eq.on) R += u * (C.eq.r1 + u * (C.eq.r2 + u * C.eq.r3));
+      if (X.V[0]) N += X.V[0][e];
+      if (X.V[2]) N += X.V[2][e];
+      if (X.V[1]) N += X.V[1][ep];
+      R += u * N;
+      if (Mx.C[1]) R += Mx.C[1][e];
+      if (Mx.C[0]) R += Mx.C[0][ep];
+      if (Mx.C[2]) R += Mx.C[2][ep];
+      S = C.Sp[ep];
+      r2 = R * R;
+      us = u * S;
+    }
+    C.R[e] = R;
+    C.S[e] = S;
+    if (V.W[0]) V.W[0][e] = a1 * R;
+    if (V.W[1]) V.W[1][ep] = a2 * R;
+    if (!V.W[1] || Mx.rp) C.Rp[ep] = R;
+    if (V.W[2]) V.W[2][e] = a3 * R;
+    if (X.N) X.N[e] = N;
     if (X.Q) X.Q[e] = u * R;
     if (X.Qp) X.Qp[ep] = u * R;
   }
@@ -480,6 +542,15 @@ hipError_t k3_launch_combine_c(const K3CombineC& C, hipStream_t s) {
 hipError_t k3_launch_adam_u_c(const K3AdamUC& C, hipStream_t s) {
   hipLaunchKernelGGL(k3_adam_u_c_kernel, dim3(blocks_of(C.a.g.real())), dim3(256), 0, s, C);
   return hipGetLastError();
+}
+hipError_t k3_launch_combine_m(const K3CombineM& M, hipStream_t s) {
+  hipLaunchKernelGGL(k3_combine_m_kernel, dim3(blocks_of(M.c.v.c.g.padded())), dim3(256), 0, s, M);
+  return hipGetLastError();
+}
+hipError_t k3_launch_unpermute(const double* src, double* dst, const K3Geom& g, hipStream_t s) {
+  K3Geom w = g;  // axes 1 and 2 swapped: src is [w.p0][w.p1][p3] and w.atp the natural index of g
+  w.n[0] = g.n[1]; w.n[1] = g.n[0]; w.p[0] = g.p[1]; w.p[1] = g.p[0];
+  return k3_launch_permute(src, dst, w, s);
 }
 hipError_t k3_launch_sync_u(const double* params, long off_u, const K3Geom& g, double* Up, hipStream_t s) {
   hipLaunchKernelGGL(k3_sync_u_kernel, dim3(blocks_of(g.real())), dim3(256), 0, s, params, off_u, g, Up);

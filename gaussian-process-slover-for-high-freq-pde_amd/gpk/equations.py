@@ -430,6 +430,49 @@ def solution_3d_opc(equation):
     return _OPC3D[equation]()
 
 
+# Equations with mixed partials on [0, 1]^3 (gpk_create3_opm): as EQUATIONS_3D_OPC's entries, plus the
+# constants m_12, m_13, m_23 of the terms m_jk d^2 u / dx_j dx_k.  Anisotropic diffusion whose tensor
+# has off-diagonal entries: -div(A grad u) = -sum_k A_kk u_kk - 2 sum_{j<k} A_jk u_jk.
+_ANISO_HEAT = (0.1, 0.04, 0.06)  # (a, b, c) of [[a, b], [b, c]]
+_ANISO_A = ((1.0, 0.3, 0.2), (0.3, 1.0, 0.1), (0.2, 0.1, 1.0))
+
+
+def _aniso_heat_t_sin():
+    # u = e^{-t} sin(2x) sin(3y):  u_t - (a u_xx + 2 b u_xy + c u_yy) = (4a + 9c - 1) u - 12 b e^{-t} cos(2x) cos(3y)
+    a, b, c = _ANISO_HEAT
+    u = lambda x, y, t: np.exp(-t) * s_(2 * x) * s_(3 * y)
+    grad = (lambda x, y, t: 2.0 * np.exp(-t) * c_(2 * x) * s_(3 * y),
+            lambda x, y, t: 3.0 * np.exp(-t) * s_(2 * x) * c_(3 * y),
+            lambda x, y, t: -u(x, y, t))
+    f = lambda x, y, t: (4.0 * a + 9.0 * c - 1.0) * u(x, y, t) - 12.0 * b * np.exp(-t) * c_(2 * x) * c_(3 * y)
+    return u, f, Operator3X((-a, -c, 0.0), (0.0, 0.0, 1.0), faces=NO_FINAL_FACE), 0, grad, (0.0, 0.0, 0.0), \
+        (-2.0 * b, 0.0, 0.0)
+
+
+def _aniso_3d_sin():
+    # steady, u = sin(2x) sin(3y) sin(z):  -div(A grad u) = 14 u - 2 (A_12 u_xy + A_13 u_xz + A_23 u_yz)
+    A = _ANISO_A
+    u = lambda x, y, z: s_(2 * x) * s_(3 * y) * s_(z)
+    grad = (lambda x, y, z: 2.0 * c_(2 * x) * s_(3 * y) * s_(z),
+            lambda x, y, z: 3.0 * s_(2 * x) * c_(3 * y) * s_(z),
+            lambda x, y, z: s_(2 * x) * s_(3 * y) * c_(z))
+    f = lambda x, y, z: (14.0 * u(x, y, z) - 2.0 * (A[0][1] * 6.0 * c_(2 * x) * c_(3 * y) * s_(z)
+                                                     + A[0][2] * 2.0 * c_(2 * x) * s_(3 * y) * c_(z)
+                                                     + A[1][2] * 3.0 * s_(2 * x) * c_(3 * y) * c_(z)))
+    return u, f, Operator3X((-A[0][0], -A[1][1], -A[2][2]), (0.0, 0.0, 0.0)), 0, grad, (0.0, 0.0, 0.0), \
+        (-2.0 * A[0][1], -2.0 * A[0][2], -2.0 * A[1][2])
+
+
+_OPM3D = {"aniso_heat_t-sin": _aniso_heat_t_sin, "aniso_3d-sin": _aniso_3d_sin}
+EQUATIONS_3D_OPM = list(_OPM3D)
+
+
+def solution_3d_opm(equation):
+    """(u, src, operator, dfaces, grad_u, conv, cross) of an EQUATIONS_3D_OPM entry: the first six as
+    solution_3d_opc's, cross = (m_12, m_13, m_23), the constants of the terms m_jk d^2 u / dx_j dx_k."""
+    return _OPM3D[equation]()
+
+
 def boundary_2d(u_mesh):
     """get_boundary_vals: hstack(U[0,:], U[-1,:], U[:,0], U[:,-1]) (model_GP_solver_2d.py:377-379)."""
     return np.hstack((u_mesh[0, :], u_mesh[-1, :], u_mesh[:, 0], u_mesh[:, -1]))

@@ -32,6 +32,8 @@ initial face, Helmholtz between sound-hard walls) runs through gpk_create3_opn:
 DeviceSolver3(..., dfaces=, dvals=), trick_paras['dfaces'] / ['dvals'] or the equation's own,
 `-equation=wave_t-sin`, configs in gpk/config3d_opn/.  Convective terms g_k u du/dx_k (viscous
 Burgers) run through gpk_create3_opc: `-equation=burgers_t-sin`, configs in gpk/config3d_opc/.
+Mixed partials m_jk d^2u/dx_j dx_k (anisotropic diffusion with off-diagonal entries) run through
+gpk_create3_opm: `-equation=aniso_heat_t-sin`, configs in gpk/config3d_opm/.
 """
 import ctypes
 import os
@@ -45,9 +47,10 @@ from . import _lib, init_func, replicas, utils
 from ._lib import check, dptr, f64
 from .cli import parse_flags
 from .core import tree_flatten, tree_unflatten
-from .equations import (EQUATIONS_3D, EQUATIONS_3D_OP, EQUATIONS_3D_OPC, EQUATIONS_3D_OPN, EQUATIONS_3D_OPV,
-                        EQUATIONS_3D_OPX, Operator3, Operator3V, Operator3X, deriv_boundary_3d, solution_3d,
-                        solution_3d_op, solution_3d_opc, solution_3d_opn, solution_3d_opv, solution_3d_opx)
+from .equations import (EQUATIONS_3D, EQUATIONS_3D_OP, EQUATIONS_3D_OPC, EQUATIONS_3D_OPM, EQUATIONS_3D_OPN,
+                        EQUATIONS_3D_OPV, EQUATIONS_3D_OPX, Operator3, Operator3V, Operator3X, deriv_boundary_3d,
+                        solution_3d, solution_3d_op, solution_3d_opc, solution_3d_opm, solution_3d_opn,
+                        solution_3d_opv, solution_3d_opx)
 from .infras.exp_config import ExpConfig
 from .kernel_matrix import kernel_class
 from .solver_common import SolverBase
@@ -80,7 +83,7 @@ class DeviceSolver3:
 
     def __init__(self, eq, kind, xs, src, bvals, Q=30, jitter=1e-6, llk_weight=200.0, logdet=True,
                  lr=0.01, freq_scale=20.0, device=0, b1=0.9, b2=0.999, eps=1e-8, refine=False,
-                 operator=None, dfaces=0, dvals=None, conv=None):
+                 operator=None, dfaces=0, dvals=None, conv=None, cross=None):
         """refine: one gated refinement step after every solve of the step (GPK_FLAG3_REFINE);
         'gemm' also forces its two-GEMM route (GPK_FLAG3_REFINE_GEMM; tests, A/B).
         operator: an Operator3 (or a dict of its fields) -- the handle then solves that operator
@@ -93,7 +96,11 @@ class DeviceSolver3:
         'c2' and 'c1'), whose faces may then be 0.
         conv: three floats g_k, the constants of the convective terms g_k u du / dx_k
         (gpk_create3_opc; Burgers); a non-zero one needs an Operator3X or Operator3V as dfaces
-        does.  None or three zeros is the handle without them."""
+        does.  None or three zeros is the handle without them.
+        cross: three floats m_12, m_13, m_23, the constants of the mixed partials m_jk d^2 u /
+        dx_j dx_k (gpk_create3_opm; anisotropic diffusion with off-diagonal entries); a non-zero one
+        needs an Operator3X or Operator3V as conv does.  None or three zeros is the handle without
+        them."""
         lib = _lib.load()
         if len(xs) != 3:
             raise ValueError("three coordinate axes")
@@ -127,7 +134,13 @@ class DeviceSolver3:
                 raise ValueError("conv has three entries (g_1, g_2, g_3)")
             if not any(g != 0.0 for g in conv):
                 conv = None
-        if dfaces or conv:
+        if cross is not None:
+            cross = tuple(float(m) for m in np.asarray(cross, np.float64).reshape(-1))
+            if len(cross) != 3:
+                raise ValueError("cross has three entries (m_12, m_13, m_23)")
+            if not any(m != 0.0 for m in cross):
+                cross = None
+        if dfaces or conv or cross:
             if dfaces and dvals is None:
                 raise ValueError("dfaces needs dvals (the six-face layout of bvals)")
             if dfaces:
@@ -136,7 +149,7 @@ class DeviceSolver3:
                     raise ValueError("dvals must have the six-face layout of bvals (deriv_boundary_3d)")
             if not (isinstance(operator, (Operator3X, Operator3V)) or (isinstance(operator, dict) and "c2" in operator)):
                 raise ValueError("%s needs an Operator3X or Operator3V"
-                                 % ("derivative boundary data" if dfaces else "a convective term"))
+                                 % ("derivative boundary data" if dfaces else "a convective term" if conv else "a mixed partial"))
             c = _lib.gpk_operator3x()
             cf = _lib.gpk_coef3()
             if isinstance(operator, Operator3V):
@@ -153,7 +166,13 @@ class DeviceSolver3:
             bd = _lib.gpk_bdata3()
             if dfaces:
                 bd.dfaces, bd.dvals = dfaces, dptr(self._dvals)
-            if conv:
+            if cross:
+                cv, mx = _lib.gpk_conv3(), _lib.gpk_cross3()
+                cv.g[:] = conv or (0.0, 0.0, 0.0)
+                mx.m[:] = cross
+                check(lib.gpk_create3_opm(ctypes.byref(p), ctypes.byref(c), ctypes.byref(cf), ctypes.byref(bd),
+                                          ctypes.byref(cv), ctypes.byref(mx), float(freq_scale), ctypes.byref(h)))
+            elif conv:
                 cv = _lib.gpk_conv3()
                 cv.g[:] = conv
                 check(lib.gpk_create3_opc(ctypes.byref(p), ctypes.byref(c), ctypes.byref(cf), ctypes.byref(bd),
@@ -342,6 +361,13 @@ class DeviceSolver3:
         check(_lib.load().gpk_conv_info3(self._h, dptr(g)))
         return tuple(g.tolist())
 
+    def cross_info(self):
+        """(m_12, m_13, m_23): the constants of the mixed partials (gpk_cross_info3); zeros on every
+        handle made without them."""
+        m = np.zeros(3)
+        check(_lib.load().gpk_cross_info3(self._h, dptr(m)))
+        return tuple(m.tolist())
+
     def boundary_terms(self):
         """{'bgap', 'dgap', 'Nb', 'Nd'}: the value gap, the derivative gap and their entry counts
         as the last loss_grad() / step() left them (gpk_boundary_terms3)."""
@@ -379,12 +405,13 @@ class GP_solver_3d_single(SolverBase):
     opv_eq_types = tuple(sorted({e.split("-")[0] for e in EQUATIONS_3D_OPV}))
     opn_eq_types = tuple(sorted({e.split("-")[0] for e in EQUATIONS_3D_OPN}))
     opc_eq_types = tuple(sorted({e.split("-")[0] for e in EQUATIONS_3D_OPC}))
+    opm_eq_types = tuple(sorted({e.split("-")[0] for e in EQUATIONS_3D_OPM}))
     early_stop_enabled = True
 
     def __init__(self, bvals, X_col, src_vals, jitter, trick_paras, device=0, X_test=None, u_test=None):
         self.eq_type = trick_paras["equation"].split("-")[0]
         assert self.eq_type in (self.eq_types + self.op_eq_types + self.opx_eq_types + self.opv_eq_types
-                                + self.opn_eq_types + self.opc_eq_types)
+                                + self.opn_eq_types + self.opc_eq_types + self.opm_eq_types)
         self.operator = None
         given = trick_paras.get("operator")
         if isinstance(given, Operator3V):
@@ -404,8 +431,17 @@ class GP_solver_3d_single(SolverBase):
         # convective terms: given, or the equation's own (a resumed run rebuilds them from its name)
         conv = trick_paras.get("conv")
         self.conv = None if conv is None else tuple(float(g) for g in conv)
-        if self.eq_type in self.opn_eq_types + self.opc_eq_types:
-            if self.eq_type in self.opc_eq_types:
+        # mixed partials: given, or the equation's own (likewise)
+        cross = trick_paras.get("cross")
+        self.cross = None if cross is None else tuple(float(m) for m in cross)
+        if self.eq_type in self.opn_eq_types + self.opc_eq_types + self.opm_eq_types:
+            if self.eq_type in self.opm_eq_types:
+                _, _, op, dfaces, grad_u, conv, cross = solution_3d_opm(trick_paras["equation"])
+                if self.conv is None:
+                    self.conv = tuple(conv)
+                if self.cross is None:
+                    self.cross = tuple(cross)
+            elif self.eq_type in self.opc_eq_types:
                 _, _, op, dfaces, grad_u, conv = solution_3d_opc(trick_paras["equation"])
                 if self.conv is None:
                     self.conv = tuple(conv)
@@ -439,7 +475,7 @@ class GP_solver_3d_single(SolverBase):
                                  logdet=tp.get("logdet", True), lr=tp.get("lr", 0.01),
                                  freq_scale=tp.get("freq_scale", 20.0), device=int(tp.get("device", device)),
                                  refine=bool(tp.get("refine", False)), operator=self.operator,
-                                 dfaces=self.dfaces, dvals=self.dvals, conv=self.conv)
+                                 dfaces=self.dfaces, dvals=self.dvals, conv=self.conv, cross=self.cross)
         self._version = 0
 
     def eq_residual(self, params, X_test, src_test):
@@ -481,6 +517,12 @@ class GP_solver_3d_single(SolverBase):
                     d = [0, 0, 0]
                     d[k] = 1
                     r = r + gk * u * self.dev.predict_deriv(*axes, deriv=tuple(d))
+        if self.cross is not None and any(self.cross):  # + sum_{j<k} m_jk d^2 u / dx_j dx_k
+            for (j, k), m in zip(((0, 1), (0, 2), (1, 2)), self.cross):
+                if m != 0.0:
+                    d = [0, 0, 0]
+                    d[j] = d[k] = 1
+                    r = r + m * self.dev.predict_deriv(*axes, deriv=tuple(d))
         return r - np.asarray(src_test, np.float64).reshape(r.shape)
 
     # the device holds the params: reading fetches them, train()'s final assignment is a no-op
@@ -579,6 +621,8 @@ def test(trick_paras, solver_cls=None):
         u, src, op = solution_3d_opn(trick_paras["equation"])[:3]
     elif trick_paras["equation"] in EQUATIONS_3D_OPC:  # (... and looks its conv up)
         u, src, op = solution_3d_opc(trick_paras["equation"])[:3]
+    elif trick_paras["equation"] in EQUATIONS_3D_OPM:  # (... and its cross weights)
+        u, src, op = solution_3d_opm(trick_paras["equation"])[:3]
     else:
         u, src = solution_3d(trick_paras["equation"])
     scale = trick_paras["scale"]
@@ -616,10 +660,11 @@ def test(trick_paras, solver_cls=None):
 def load_config(equation):
     """./config3d/<equation>.yaml (the operator equations: ./config3d_op/, the mixed-order ones:
     ./config3d_opx/, the coefficient-field ones: ./config3d_opv/, derivative boundary data:
-    ./config3d_opn/, convective terms: ./config3d_opc/), falling back to the package's copy."""
+    ./config3d_opn/, convective terms: ./config3d_opc/, mixed partials: ./config3d_opm/), falling back to the package's copy."""
     cdir = ("config3d_op" if equation in EQUATIONS_3D_OP else "config3d_opx" if equation in EQUATIONS_3D_OPX
             else "config3d_opv" if equation in EQUATIONS_3D_OPV else "config3d_opn" if equation in EQUATIONS_3D_OPN
-            else "config3d_opc" if equation in EQUATIONS_3D_OPC else "config3d")
+            else "config3d_opc" if equation in EQUATIONS_3D_OPC
+            else "config3d_opm" if equation in EQUATIONS_3D_OPM else "config3d")
     for base in (os.getcwd(), os.path.dirname(os.path.abspath(__file__))):
         p = os.path.join(base, cdir, equation + ".yaml")
         if os.path.exists(p):
@@ -629,7 +674,7 @@ def load_config(equation):
 
 
 def build_config(args, allowed=EQUATIONS_3D + EQUATIONS_3D_OP + EQUATIONS_3D_OPX + EQUATIONS_3D_OPV
-                 + EQUATIONS_3D_OPN + EQUATIONS_3D_OPC):
+                 + EQUATIONS_3D_OPN + EQUATIONS_3D_OPC + EQUATIONS_3D_OPM):
     """The 2-axis build_config (scale, kernel class, other_paras) on the config3d files."""
     assert args.equation in allowed
     config = load_config(args.equation)

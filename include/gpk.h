@@ -650,6 +650,33 @@ int gpk_create3_opc(const gpk_problem3* p, const gpk_operator3x* op, const gpk_c
 /* The convective weights; zeros on every older kind of 3-axis handle. */
 int gpk_conv_info3(const gpk_handle3* h, double g[3]);
 
+/* Mixed partials (a rotated or sheared anisotropic medium, -div(A grad u) with off-diagonal A; an
+ * equation in non-orthogonal coordinates).  The pair (j, k), j < k, adds
+ *     m_jk . d^2 u / d x_j d x_k
+ * to the equation of a gpk_create3_opc handle; m holds the weights of the pairs (1,2), (1,3), (2,3)
+ * in that order.  With A_j = K_j^{-1} x_j U and D1_k the plain order-1 block of axis k,
+ *     Z_j = D1_j x_j A_j,   H_jk = K_k^{-1} x_k Z_j,   C_jk = m_jk D1_k x_k H_jk,
+ * and the residual is the opc handle's plus C_13 + C_12 + C_23 (that order, each only where its
+ * weight is non-zero).  m_jk is a CONSTANT: the gpk_coef3 fields multiply the linear terms of their
+ * own axis only, never a cross term.  A pair's axes may have c2 = c1 = 0.  Everything else -- the
+ * log joint, the boundary and derivative-boundary terms, gpk_criterion3, gpk_loss_terms3,
+ * gpk_boundary_terms3, the Adam update -- keeps its formula on the new residual; predictions depend
+ * on K_k only.  gpk_stage_variants3 reports eight further GEMM launches on a handle with any pair
+ * set, whichever pairs they are: three after the convective handle's first (Z_j; H_jk; C_jk), four
+ * after its second (the reverse products D1_k^T x_k R; their solves; the sums into T_j; the G_D1)
+ * and one at the end (the sums into G_Kk).  Not built: the sharded, 1-axis and 2-axis handles, a
+ * field on a cross weight, mixed terms of total order above two. */
+typedef struct gpk_cross3 { double m[3]; } gpk_cross3;
+/* p, op, cf, bd and cv as on gpk_create3_opc (cf, bd and cv may be NULL).  mx == NULL or all three
+ * m == 0.0 is gpk_create3_opc(p, op, cf, bd, cv, ...) itself: the same stage list, launches and
+ * bits.  GPK_EINVAL, before any device work, on a non-finite m, and on everything gpk_create3_opc,
+ * gpk_create3_opn, gpk_create3_opv and gpk_create3_opx reject. */
+int gpk_create3_opm(const gpk_problem3* p, const gpk_operator3x* op, const gpk_coef3* cf,
+                    const gpk_bdata3* bd, const gpk_conv3* cv, const gpk_cross3* mx, double freq_scale,
+                    gpk_handle3** out);
+/* The cross weights (1,2), (1,3), (2,3); zeros on every older kind of 3-axis handle. */
+int gpk_cross_info3(const gpk_handle3* h, double m[3]);
+
 int gpk_num_params3(const gpk_handle3* h, int64_t* n);
 int gpk_set_params3(gpk_handle3* h, const double* flat, int64_t n);
 int gpk_get_params3(gpk_handle3* h, double* flat, int64_t n);
