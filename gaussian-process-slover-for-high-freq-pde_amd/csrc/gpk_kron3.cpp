@@ -39,6 +39,11 @@
 // Hb_jk = m_jk D1_k^T x_k R, Zb_jk = K_k^{-1} x_k Hb_jk (a solve), T_j += D1_j^T x_j Zb_jk before
 // X_j, G_D1j += v Zb_jk,(j) A_j,(j)^T, G_D1k += v m_jk R_(k) H_jk,(k)^T and G_Kk -= v Zb_jk,(k)
 // H_jk,(k)^T: eight further launches (build_cross_stages).
+// Drift fields (gpk_create3_opb, b_k(x) du/dx_k): a drift axis assembles in DERIV_SPLIT; Z_k = D1_k
+// x_k A_k (a cross pair's own Z_1 / Z_2p where it forms them), R += b_1 Z_1 + b_3 Z_3 + b_2 Z_2
+// (k3_combine_b), and the reverse pass reads E_k = b_k R: T_k += D1_k^T x_k E_k before X_k and
+// G_D1k += v E_k,(k) A_k,(k)^T: two or three further launches (build_drift_stages).  b_k is data: dL/dU
+// has no direct term.
 // GPK_FLAG3_REFINE: every one of the eight solves (A1, A2, A3, T, S, X1, X2, X3) is followed by
 // one refinement step X += K_k^{-1} (B - K_k X) gated on the axis's pst: one fused panel launch
 // (refine_panel.hip), or two GEMMs where its panels do not fit LDS (build_refine).
@@ -120,6 +125,13 @@ struct gpk_handle3 {
   double mx[3] = {};
   double *Z1 = nullptr, *Z1p = nullptr, *Z2p = nullptr, *Zb12 = nullptr;
   double *Hx[3] = {}, *Cx[3] = {}, *Hb[3] = {}, *Zb[3] = {};
+  // gpk_create3_opb: the drift fields b_k (drift = 0: none, and nothing below is allocated or
+  // launched).  Per axis with a field: bf[k] (padded, natural layout), Zd[k] = D1_k x_k A_k (Zd[1]
+  // permuted; Z1 / Z2p themselves where a cross pair already forms them, else an allocation of its
+  // own) and Ed[k] = b_k R (Ed[1] permuted), the reverse pass's operand.  None of them aliases
+  // build_refine's scratch (Rx / Ryp / Rz, T1 / T2p / T3).
+  int drift = 0;
+  double *bf[3] = {}, *Zd[3] = {}, *Ed[3] = {};
   double *GK[3] = {}, *GD[3] = {};
   double *red_egap = nullptr, *red_quad = nullptr;
   int nred = 0;
@@ -134,6 +146,9 @@ struct gpk_handle3 {
   // and xrpanels[i] the fused panels of H_jk (i = 0) and Zb_jk (i = 1)
   std::vector<std::vector<GemmDesc>> xstages, xrstages;
   std::vector<std::vector<RefinePanel>> xrpanels;
+  // a drift handle's further launches (build_drift_stages; empty elsewhere): [0] the Z_k no cross
+  // pair forms (may be empty), [1] the sums into T_k, [2] the G_D1k
+  std::vector<std::vector<GemmDesc>> dstages;
   // GPK_FLAG3_REFINE: the refinement launches, [2 j] the residuals and [2 j + 1] the corrections
   // that follow stage kRefineAfter[j] (empty without the flag)
   std::vector<std::vector<GemmDesc>> rstages;
@@ -279,6 +294,50 @@ void build_cross_stages(gpk_handle3* h) {
     if (on[1]) k3.push_back({h->Zb[1], P3, 1, h->Hx[1], P3, 0, M3, -1.0});
     if (on[2]) k3.push_back({h->Zb[2], P3, 1, h->Hx[2], P3, 0, M3, -1.0});
     if (!k3.empty()) xs[7].push_back(sum(k3, h->GK[2], P3, P3, P3, true, 1));
+  }
+}
+
+// Drift fields (gpk_create3_opb), after build_stages, build_conv_stages and build_cross_stages.
+// Axis 2 stays in the permuted layout; axis 3 has D1 on the right, transposed like D[2].  Launches,
+// in stream order:
+//   [0] Z_k = D1_k x_k A_k of the drift axes no cross pair serves    after stage 2 and the V_k
+//   [1] T_k += D1_k^T x_k E_k   [2] G_D1k (+)= v E_k,(k) A_k,(k)^T   after stage 3 and the cross
+//                                                                    handle's G_D1, before stage 4
+// The stage-3 dual slot (a convective axis) and the cross sums' two slots can all be full on one
+// axis, so the sums into T_k are launches of their own under build_cross_stages' aliasing rule
+// (C0 = C, beta = 1).  These launches are the last producers of G_D1k in the stream: the convective
+// launch writes it, the cross launch writes or adds, and a drift axis adds when either came before
+// and writes when it is the first.
+void build_drift_stages(gpk_handle3* h) {
+  const int P1 = h->g.p[0], P2 = h->g.p[1], P3 = h->g.p[2];
+  const int M1 = P2 * P3, M2 = P1 * P3, M3 = P1 * P2;
+  double* const* D1 = h->D1;
+  const double* m = h->mx;
+  // axis k already has a G_D1k in the stream: convective, or an axis of a present pair
+  const bool held[3] = {h->gconv[0] != 0.0 || m[0] != 0.0 || m[1] != 0.0,
+                        h->gconv[1] != 0.0 || m[0] != 0.0 || m[2] != 0.0,
+                        h->gconv[2] != 0.0 || m[1] != 0.0 || m[2] != 0.0};
+  auto into = [](GemmDesc d, bool add, int vs) {
+    d.vscale = vs;
+    if (add) { d.beta = 1.0; d.C0 = d.C; d.ldc0 = d.ldc; }
+    return d;
+  };
+  auto& ds = h->dstages;
+  ds.assign(3, {});
+  if (h->bf[0]) {
+    if (h->Zd[0] != h->Z1) ds[0].push_back(gemm_desc(D1[0], P1, 0, h->A1, M1, 0, h->Zd[0], M1, P1, M1, P1));
+    ds[1].push_back(into(gemm_desc(D1[0], P1, 1, h->Ed[0], M1, 0, h->T1, M1, P1, M1, P1), true, 0));
+    ds[2].push_back(into(gemm_desc(h->Ed[0], M1, 0, h->A1, M1, 1, h->GD1[0], P1, P1, P1, M1), held[0], 1));
+  }
+  if (h->bf[1]) {
+    if (h->Zd[1] != h->Z2p) ds[0].push_back(gemm_desc(D1[1], P2, 0, h->A2p, M2, 0, h->Zd[1], M2, P2, M2, P2));
+    ds[1].push_back(into(gemm_desc(D1[1], P2, 1, h->Ed[1], M2, 0, h->T2p, M2, P2, M2, P2), true, 0));
+    ds[2].push_back(into(gemm_desc(h->Ed[1], M2, 0, h->A2p, M2, 1, h->GD1[1], P2, P2, P2, M2), held[1], 1));
+  }
+  if (h->bf[2]) {
+    ds[0].push_back(gemm_desc(h->A3, P3, 0, D1[2], P3, 1, h->Zd[2], P3, M3, P3, P3));
+    ds[1].push_back(into(gemm_desc(h->Ed[2], P3, 0, D1[2], P3, 0, h->T3, P3, M3, P3, P3), true, 0));
+    ds[2].push_back(into(gemm_desc(h->Ed[2], P3, 1, h->A3, P3, 0, h->GD1[2], P3, P3, P3, M3), held[2], 1));
   }
 }
 
@@ -504,6 +563,7 @@ int enqueue_step3(gpk_handle3* h, int apply) {
   TRY(check_launch(k3_launch_permute(h->Tm, h->Tp, g, h->s), "k3_permute"));
   TRY(launch_stage(h, 2));
   if (h->conv) TRY(launch_descs(h, h->cstages[0]));  // V_k, from the refined A_k
+  if (h->drift && !h->dstages[0].empty()) TRY(launch_descs(h, h->dstages[0]));  // Z_k no cross pair forms
   if (h->cross) {  // Z_j from the refined A_j, H_jk (pair (1,2): on the permuted Z_1), C_jk
     TRY(launch_descs(h, h->xstages[0]));
     if (h->Z1p) TRY(check_launch(k3_launch_permute(h->Z1, h->Z1p, g, h->s), "k3_permute"));
@@ -514,17 +574,24 @@ int enqueue_step3(gpk_handle3* h, int apply) {
   C.g = g; C.Rx = h->Rx; C.Rz = h->Rz; C.Ryp = h->Ryp; C.F = h->F; C.Up = h->Up; C.Sp = h->Sp;
   C.eq = eq_layer(h); C.R = h->R; C.Rp = h->Rp; C.S = h->S;
   C.red_egap = h->red_egap; C.red_quad = h->red_quad;
-  if (h->conv || h->cross) {
+  if (h->conv || h->cross || h->drift) {
     K3CombineC X{};
     X.v.c = C; X.v.rho = h->rho;
     for (int a = 0; a < 3; ++a) { X.v.a[a] = h->cf[a]; X.v.W[a] = h->W[a]; X.V[a] = h->V[a]; }
     X.N = h->Nsum; X.Q = h->Q; X.Qp = h->Qp;
-    if (h->cross) {
+    if (h->cross || h->drift) {
       K3CombineM Mx{};
       Mx.c = X;
       Mx.C[0] = h->Cx[0]; Mx.C[1] = h->Cx[1]; Mx.C[2] = h->Cx[2];
       Mx.rp = h->Cx[0] || h->Cx[2];
-      TRY(check_launch(k3_launch_combine_m(Mx, h->s), "k3_combine_m"));
+      if (h->drift) {
+        K3CombineB B{};
+        B.m = Mx;
+        for (int a = 0; a < 3; ++a) { B.b[a] = h->bf[a]; B.Z[a] = h->Zd[a]; B.E[a] = h->Ed[a]; }
+        TRY(check_launch(k3_launch_combine_b(B, h->s), "k3_combine_b"));
+      } else {
+        TRY(check_launch(k3_launch_combine_m(Mx, h->s), "k3_combine_m"));
+      }
     } else {
       TRY(check_launch(k3_launch_combine_c(X, h->s), "k3_combine_c"));
     }
@@ -550,6 +617,10 @@ int enqueue_step3(gpk_handle3* h, int apply) {
       if (h->Zb12) TRY(check_launch(k3_launch_unpermute(h->Zb[0], h->Zb12, g, h->s), "k3_permute"));
       TRY(launch_descs(h, h->xstages[5]));
       TRY(launch_descs(h, h->xstages[6]));
+    }
+    if (h->drift && k == 3) {  // T_k's drift share before X_k = K_k^{-1} x_k T_k reads it; G_D1k
+      TRY(launch_descs(h, h->dstages[1]));
+      TRY(launch_descs(h, h->dstages[2]));
     }
   }
   if (h->cross) TRY(launch_descs(h, h->xstages[7]));  // G_Kk's share, added to the last stage's G_Kk
@@ -661,7 +732,7 @@ int check_problem3(const gpk_problem3* p) {
 // gpk_create3_opv (cf: the fields it was given, at least one of them)
 int create3(const gpk_problem3* p, const gpk_operator3* op, double freq_scale, gpk_handle3** out,
             const gpk_operator3x* opx = nullptr, const gpk_coef3* cf = nullptr, const gpk_bdata3* bd = nullptr,
-            const gpk_conv3* cv = nullptr, const gpk_cross3* mx = nullptr) {
+            const gpk_conv3* cv = nullptr, const gpk_cross3* mx = nullptr, const gpk_drift3* dr = nullptr) {
   TRY(check_problem3(p));
   const int ns[3] = {p->n1, p->n2, p->n3};
   TRY(check_device(p->device));
@@ -694,6 +765,11 @@ int create3(const gpk_problem3* p, const gpk_operator3* op, double freq_scale, g
         h->cross = 1;
         h->mode[a] = DERIV_SPLIT;
       }
+    // and a drift axis (D1_k and G_D1k likewise)
+    if (dr && dr->b[a]) {
+      h->drift = 1;
+      h->mode[a] = DERIV_SPLIT;
+    }
     h->c2[a] = mixed ? opx->c2[a] : h->op.order[a] == 2 ? h->op.coef[a] : 0.0;
     h->c1[a] = mixed ? opx->c1[a] : h->op.order[a] == 1 ? h->op.coef[a] : 0.0;
   }
@@ -806,7 +882,7 @@ int create3(const gpk_problem3* p, const gpk_operator3* op, double freq_scale, g
   }
   // convective axes: D1_k, V_k and G_D1k per axis, N, and Q in the layouts those axes read
   // (and D1_k, G_D1k on the axes of a cross pair)
-  for (int a = 0; a < 3 && (h->conv || h->cross); ++a) {
+  for (int a = 0; a < 3 && (h->conv || h->cross || h->drift); ++a) {
     if (h->mode[a] != DERIV_SPLIT) continue;
     const int P = g.p[a];
     A3_(h->D1[a], (size_t)P * P); A3_(h->GD1[a], (size_t)P * P);
@@ -824,6 +900,20 @@ int create3(const gpk_problem3* p, const gpk_operator3* op, double freq_scale, g
     if (t < 2 && !h->Z1) A3_(h->Z1, np);
     if (t == 0) { A3_(h->Z1p, np); A3_(h->Zb12, np); }
     if (t == 2) A3_(h->Z2p, np);
+  }
+  // drift axes: the field (zero-padded, natural layout), E_k, and Z_k where no pair forms it
+  for (int a = 0; a < 3 && h->drift; ++a) {
+    if (!dr->b[a]) continue;
+    A3_(h->bf[a], np); A3_(h->Ed[a], np);
+    h->Zd[a] = a == 0 ? h->Z1 : a == 1 ? h->Z2p : nullptr;
+    if (!h->Zd[a]) A3_(h->Zd[a], np);
+    std::vector<double> fp(np, 0.0);
+    for (int i1 = 0; i1 < ns[0]; ++i1)
+      for (int i2 = 0; i2 < ns[1]; ++i2)
+        std::memcpy(&fp[g.at(i1, i2, 0)], dr->b[a] + ((size_t)i1 * ns[1] + i2) * ns[2], ns[2] * sizeof(double));
+    if (hipMemcpyAsync(h->bf[a], fp.data(), np * sizeof(double), hipMemcpyHostToDevice, h->s) != hipSuccess ||
+        hipStreamSynchronize(h->s) != hipSuccess)
+      return bail(fail(GPK_EHIP, "upload of a drift field failed"));
   }
 #undef A3_
   // upload: coordinates, the padded source, boundary values, the initial params
@@ -856,6 +946,7 @@ int create3(const gpk_problem3* p, const gpk_operator3* op, double freq_scale, g
     if (h->route && refine_panel_prepare() != hipSuccess) return bail(fail(GPK_EHIP, "refine_panel_prepare failed"));
   }
   if (h->cross) build_cross_stages(h);
+  if (h->drift) build_drift_stages(h);
   *out = h;
   return GPK_OK;
 }
@@ -965,7 +1056,8 @@ namespace {
 // gpk_create3_opn with derivative faces, and gpk_create3_opc with a convective axis (cv; bd may
 // then be null or without faces): the argument checks of both, then the handle
 int create3_opn(const gpk_problem3* p, const gpk_operator3x* op, const gpk_coef3* cf, const gpk_bdata3* bd,
-                const gpk_conv3* cv, double freq_scale, gpk_handle3** out, const gpk_cross3* mx = nullptr) {
+                const gpk_conv3* cv, double freq_scale, gpk_handle3** out, const gpk_cross3* mx = nullptr,
+                const gpk_drift3* dr = nullptr) {
   if (!p || !op || !out) return fail(GPK_EINVAL, "NULL argument");
   *out = nullptr;
   if (bd && bd->dfaces == 0) bd = nullptr;
@@ -974,7 +1066,7 @@ int create3_opn(const gpk_problem3* p, const gpk_operator3x* op, const gpk_coef3
   // the operator's own checks, with faces = 0 allowed here (data on derivatives alone)
   gpk_operator3x o = *op;
   if (bd && o.faces == 0) o.faces = bd->dfaces;
-  TRY(check_operator3x(p, &o, out, mx ? "gpk_create3_opm" : cv ? "gpk_create3_opc" : "gpk_create3_opn"));
+  TRY(check_operator3x(p, &o, out, dr ? "gpk_create3_opb" : mx ? "gpk_create3_opm" : cv ? "gpk_create3_opc" : "gpk_create3_opn"));
   TRY(check_problem3(p));
   if (bd) {
     const long fs[3] = {(long)p->n2 * p->n3, (long)p->n1 * p->n3, (long)p->n1 * p->n2};
@@ -992,6 +1084,9 @@ int create3_opn(const gpk_problem3* p, const gpk_operator3x* op, const gpk_coef3
     if (f && !std::all_of(f, f + n, [](double x) { return std::isfinite(x); }))
       return fail(GPK_EINVAL, "gpk_create3_opn: a coefficient field has a non-finite value");
   }
+  for (int a = 0; a < 3 && dr; ++a)
+    if (dr->b[a] && !std::all_of(dr->b[a], dr->b[a] + n, [](double x) { return std::isfinite(x); }))
+      return fail(GPK_EINVAL, "gpk_create3_opb: a drift field has a non-finite value");
   gpk_operator3 o1 = one_order_part(op);  // (op's own faces: 0 stays 0)
   // a convective axis assembles D_k = c2_k DD_k + c1_k D1_k whatever the weights are: entered as a
   // mixed axis (order 0, GEMM weight 1.0)
@@ -1004,7 +1099,10 @@ int create3_opn(const gpk_problem3* p, const gpk_operator3x* op, const gpk_coef3
     for (int a = 0; a < 3; ++a)
       if (in[a]) { o1.order[a] = 0; o1.coef[a] = 1.0; }
   }
-  return create3(p, &o1, freq_scale, out, op, any ? cf : nullptr, bd, cv, mx);
+  // and a drift axis
+  for (int a = 0; a < 3 && dr; ++a)
+    if (dr->b[a]) { o1.order[a] = 0; o1.coef[a] = 1.0; }
+  return create3(p, &o1, freq_scale, out, op, any ? cf : nullptr, bd, cv, mx, dr);
 }
 
 // the convective weights as gpk_create3_opc and gpk_create3_opm (`who`) take them: GPK_EINVAL on a
@@ -1046,6 +1144,26 @@ int gpk_create3_opm(const gpk_problem3* p, const gpk_operator3x* op, const gpk_c
     return gpk_create3_opc(p, op, cf, bd, cv, freq_scale, out);
   TRY(check_conv3(cv, "gpk_create3_opm"));
   return create3_opn(p, op, cf, bd, cv, freq_scale, out, mx);
+}
+
+int gpk_create3_opb(const gpk_problem3* p, const gpk_operator3x* op, const gpk_coef3* cf, const gpk_bdata3* bd,
+                    const gpk_conv3* cv, const gpk_cross3* mx, const gpk_drift3* dr, double freq_scale,
+                    gpk_handle3** out) {
+  if (!dr || (!dr->b[0] && !dr->b[1] && !dr->b[2])) return gpk_create3_opm(p, op, cf, bd, cv, mx, freq_scale, out);
+  if (out) *out = nullptr;
+  if (mx) {
+    for (int t = 0; t < 3; ++t)
+      if (!std::isfinite(mx->m[t])) return fail(GPK_EINVAL, "gpk_create3_opb: m must be finite");
+    if (mx->m[0] == 0.0 && mx->m[1] == 0.0 && mx->m[2] == 0.0) mx = nullptr;
+  }
+  TRY(check_conv3(cv, "gpk_create3_opb"));
+  return create3_opn(p, op, cf, bd, cv, freq_scale, out, mx, dr);
+}
+
+int gpk_drift_info3(const gpk_handle3* h, int32_t has[3]) {
+  if (!h || !has) return fail(GPK_EINVAL, "NULL argument");
+  for (int a = 0; a < 3; ++a) has[a] = h->bf[a] != nullptr;
+  return GPK_OK;
 }
 
 int gpk_cross_info3(const gpk_handle3* h, double m[3]) {
@@ -1193,13 +1311,16 @@ int gpk_boundary_terms3(gpk_handle3* h, double out[4]) {
 int gpk_stage_variants3(gpk_handle3* h, int32_t* out, int32_t cap, int32_t* n) {
   if (!h || !n || cap < 0 || (cap && !out)) return fail(GPK_EINVAL, "NULL argument");
   // stream order: a convective handle's two further launches follow stages 2 and 3; a cross
-  // handle's eight follow those (three, four) and the last stage (one)
+  // handle's eight follow those (three, four) and the last stage (one); a drift handle's Z_k launch
+  // (if any) follows the convective handle's first, its other two the cross handle's after stage 3
   std::vector<const std::vector<GemmDesc>*> order;
   for (size_t k = 0; k < h->stages.size(); ++k) {
     order.push_back(&h->stages[k]);
     if (h->conv && (k == 2 || k == 3)) order.push_back(&h->cstages[k - 2]);
+    if (h->drift && k == 2 && !h->dstages[0].empty()) order.push_back(&h->dstages[0]);
     if (h->cross && k == 2) for (int i = 0; i < 3; ++i) order.push_back(&h->xstages[i]);
     if (h->cross && k == 3) for (int i = 3; i < 7; ++i) order.push_back(&h->xstages[i]);
+    if (h->drift && k == 3) for (int i = 1; i < 3; ++i) order.push_back(&h->dstages[i]);
   }
   if (h->cross) order.push_back(&h->xstages[7]);
   *n = (int32_t)order.size();

@@ -126,6 +126,17 @@ struct K3CombineM {
   int rp;
 };
 
+// k3_combine_b (gpk_create3_opb): k3_combine_m plus the drift terms b_1 Z_1 + b_3 Z_3 + b_2 Z_2, Z_k =
+// D1_k x_k A_k (b[k] null: axis k has no drift field, and Z[k], E[k] are then null as well).  b[k] is a
+// natural-layout padded tensor; Z[1] and E[1] are in the mode-2 permuted layout.  E[k] = b_k R is
+// the reverse pass's operand of the drift term.  Every pointer of m may be null as on k3_combine_m.
+struct K3CombineB {
+  K3CombineM m;
+  const double* b[3];
+  const double* Z[3];
+  double* E[3];
+};
+
 // k3_adam_u_c: k3_adam_u_v with N (natural padded layout) added to the factor on R; rho nullable
 struct K3AdamUC {
   K3AdamU a;
@@ -194,6 +205,7 @@ hipError_t k3_launch_adam_u_v(const K3AdamUV& V, hipStream_t s);
 hipError_t k3_launch_combine_c(const K3CombineC& C, hipStream_t s);
 hipError_t k3_launch_adam_u_c(const K3AdamUC& C, hipStream_t s);
 hipError_t k3_launch_combine_m(const K3CombineM& M, hipStream_t s);
+hipError_t k3_launch_combine_b(const K3CombineB& B, hipStream_t s);
 // dst[i1][i2][i3] = src[i2][i1][i3]: k3_permute's inverse (k3_permute itself on the grid with axes
 // 1 and 2 swapped, where its source index is this one's and its target index the natural one)
 hipError_t k3_launch_unpermute(const double* src, double* dst, const K3Geom& g, hipStream_t s);

@@ -473,6 +473,111 @@ def solution_3d_opm(equation):
     return _OPM3D[equation]()
 
 
+# Equations with drift fields on [0, 1]^3 (gpk_create3_opb): as EQUATIONS_3D_OPM's entries, plus the
+# fields b_k(x) of the terms b_k du / dx_k, each None or a callable of the three meshes.  Divergence
+# form c2_k d/dx_k (a du/dx_k) is an Operator3V with a on axis k plus the drift c2_k da/dx_k.
+def divergence_drift(grad_a, c2):
+    """The drift (b_1, b_2, b_3) with b_k = c2[k] * grad_a[k], so that Operator3V(c2, ..., a=(a, a, a))
+    plus this drift states sum_k c2[k] d/dx_k (a du/dx_k).  grad_a: three entries, each None (a does
+    not vary along x_k), an array of the grid's shape or a callable of the meshes; b_k is None where
+    grad_a[k] is None or c2[k] == 0."""
+    if len(grad_a) != 3 or len(c2) != 3:
+        raise ValueError("grad_a and c2 have three entries")
+    out = []
+    for g, w in zip(grad_a, c2):
+        w = float(w)
+        if g is None or w == 0.0:
+            out.append(None)
+        elif callable(g):
+            out.append(lambda x, y, z, g=g, w=w: w * np.asarray(g(x, y, z), np.float64))
+        else:
+            out.append(w * np.asarray(g, np.float64))
+    return tuple(out)
+
+
+def drift_fields(drift, axes):
+    """[b_1, b_2, b_3] on the tensor grid of the three coordinate axes, as Operator3V.fields lays its
+    fields out: float64 arrays of shape (n1, n2, n3), None where absent.  Callables get the 'ij' meshes."""
+    if len(drift) != 3:
+        raise ValueError("drift has three entries (None for an axis without a field)")
+    axes = [np.asarray(x, np.float64).reshape(-1) for x in axes]
+    shape = tuple(x.size for x in axes)
+    mesh = None
+    out = []
+    for f in drift:
+        if f is None:
+            out.append(None)
+            continue
+        if callable(f):
+            mesh = np.meshgrid(*axes, indexing="ij") if mesh is None else mesh
+            v = np.asarray(f(*mesh), np.float64) * np.ones(shape)
+        else:
+            v = np.asarray(f, np.float64)
+            if v.shape != shape:
+                raise ValueError("a drift field given as an array must have the grid's shape %r" % (shape,))
+        out.append(np.ascontiguousarray(v))
+    return out
+
+
+_DARCY_A = lambda x, y, z: 1.0 + 0.5 * s_(2 * np.pi * x) * c_(2 * np.pi * y) + 0.25 * z
+_DARCY_GRAD_A = (lambda x, y, z: np.pi * c_(2 * np.pi * x) * c_(2 * np.pi * y),
+                 lambda x, y, z: -np.pi * s_(2 * np.pi * x) * s_(2 * np.pi * y),
+                 lambda x, y, z: 0.25 + 0.0 * z)
+_HEATV_GRAD_A = (lambda x, y, t: np.pi * c_(2 * np.pi * x) * c_(2 * np.pi * y),
+                 lambda x, y, t: -np.pi * s_(2 * np.pi * x) * s_(2 * np.pi * y), None)
+_ROT_NU = 0.05
+
+
+def _darcy_3d_sin():
+    # steady, u = sin(2x) sin(3y) sin(z):  -div(a grad u) = 14 a u - grad a . grad u
+    u = lambda x, y, z: s_(2 * x) * s_(3 * y) * s_(z)
+    grad = (lambda x, y, z: 2.0 * c_(2 * x) * s_(3 * y) * s_(z),
+            lambda x, y, z: 3.0 * s_(2 * x) * c_(3 * y) * s_(z),
+            lambda x, y, z: s_(2 * x) * s_(3 * y) * c_(z))
+    f = lambda x, y, z: (14.0 * _DARCY_A(x, y, z) * u(x, y, z)
+                         - sum(_DARCY_GRAD_A[k](x, y, z) * grad[k](x, y, z) for k in range(3)))
+    c2 = (-1.0, -1.0, -1.0)
+    return u, f, Operator3V(c2, (0.0, 0.0, 0.0), a=(_DARCY_A,) * 3), 0, grad, (0.0, 0.0, 0.0), (0.0, 0.0, 0.0), \
+        divergence_drift(_DARCY_GRAD_A, c2)
+
+
+def _heat_div_t_sin():
+    # u = e^{-t} sin(2x) sin(3y):  u_t - div(nu grad u) = (13 nu - 1) u - grad nu . grad u, nu = _HEAT_NU a(x, y)
+    u = lambda x, y, t: np.exp(-t) * s_(2 * x) * s_(3 * y)
+    grad = (lambda x, y, t: 2.0 * np.exp(-t) * c_(2 * x) * s_(3 * y),
+            lambda x, y, t: 3.0 * np.exp(-t) * s_(2 * x) * c_(3 * y),
+            lambda x, y, t: -u(x, y, t))
+    f = lambda x, y, t: ((13.0 * _HEAT_NU * _HEATV_A(x, y, t) - 1.0) * u(x, y, t)
+                         - _HEAT_NU * sum(_HEATV_GRAD_A[k](x, y, t) * grad[k](x, y, t) for k in range(2)))
+    c2 = (-_HEAT_NU, -_HEAT_NU, 0.0)
+    return u, f, Operator3V(c2, (0.0, 0.0, 1.0), faces=NO_FINAL_FACE, a=(_HEATV_A, _HEATV_A, None)), 0, grad, \
+        (0.0, 0.0, 0.0), (0.0, 0.0, 0.0), divergence_drift(_HEATV_GRAD_A, c2)
+
+
+def _convdiff_rot_t_sin():
+    # the same u:  u_t + b . grad u - nu lap u = (13 nu - 1) u + b1 u_x + b2 u_y, b the rotating flow
+    u = lambda x, y, t: np.exp(-t) * s_(2 * x) * s_(3 * y)
+    grad = (lambda x, y, t: 2.0 * np.exp(-t) * c_(2 * x) * s_(3 * y),
+            lambda x, y, t: 3.0 * np.exp(-t) * s_(2 * x) * c_(3 * y),
+            lambda x, y, t: -u(x, y, t))
+    f = lambda x, y, t: ((13.0 * _ROT_NU - 1.0) * u(x, y, t) + _ROT_B1(x, y, t) * grad[0](x, y, t)
+                         + _ROT_B2(x, y, t) * grad[1](x, y, t))
+    return u, f, Operator3X((-_ROT_NU, -_ROT_NU, 0.0), (0.0, 0.0, 1.0), faces=NO_FINAL_FACE), 0, grad, \
+        (0.0, 0.0, 0.0), (0.0, 0.0, 0.0), (_ROT_B1, _ROT_B2, None)
+
+
+_OPB3D = {"darcy_3d-sin": _darcy_3d_sin, "heat_div_t-sin": _heat_div_t_sin,
+          "convdiff_rot_t-sin": _convdiff_rot_t_sin}
+EQUATIONS_3D_OPB = list(_OPB3D)
+
+
+def solution_3d_opb(equation):
+    """(u, src, operator, dfaces, grad_u, conv, cross, drift) of an EQUATIONS_3D_OPB entry: the first
+    seven as solution_3d_opm's (operator an Operator3X or an Operator3V of callables), drift =
+    (b_1, b_2, b_3), the fields of the terms b_k du / dx_k as callables (None: no such term)."""
+    return _OPB3D[equation]()
+
+
 def boundary_2d(u_mesh):
     """get_boundary_vals: hstack(U[0,:], U[-1,:], U[:,0], U[:,-1]) (model_GP_solver_2d.py:377-379)."""
     return np.hstack((u_mesh[0, :], u_mesh[-1, :], u_mesh[:, 0], u_mesh[:, -1]))

@@ -33,7 +33,10 @@ DeviceSolver3(..., dfaces=, dvals=), trick_paras['dfaces'] / ['dvals'] or the eq
 `-equation=wave_t-sin`, configs in gpk/config3d_opn/.  Convective terms g_k u du/dx_k (viscous
 Burgers) run through gpk_create3_opc: `-equation=burgers_t-sin`, configs in gpk/config3d_opc/.
 Mixed partials m_jk d^2u/dx_j dx_k (anisotropic diffusion with off-diagonal entries) run through
-gpk_create3_opm: `-equation=aniso_heat_t-sin`, configs in gpk/config3d_opm/.
+gpk_create3_opm: `-equation=aniso_heat_t-sin`, configs in gpk/config3d_opm/.  Drift fields
+b_k(x) du/dx_k (divergence form -div(a grad u), a variable velocity over a constant viscosity) run
+through gpk_create3_opb: DeviceSolver3(..., drift=), `-equation=heat_div_t-sin`, configs in
+gpk/config3d_opb/.
 """
 import ctypes
 import os
@@ -47,10 +50,10 @@ from . import _lib, init_func, replicas, utils
 from ._lib import check, dptr, f64
 from .cli import parse_flags
 from .core import tree_flatten, tree_unflatten
-from .equations import (EQUATIONS_3D, EQUATIONS_3D_OP, EQUATIONS_3D_OPC, EQUATIONS_3D_OPM, EQUATIONS_3D_OPN,
-                        EQUATIONS_3D_OPV, EQUATIONS_3D_OPX, Operator3, Operator3V, Operator3X, deriv_boundary_3d,
-                        solution_3d, solution_3d_op, solution_3d_opc, solution_3d_opm, solution_3d_opn,
-                        solution_3d_opv, solution_3d_opx)
+from .equations import (EQUATIONS_3D, EQUATIONS_3D_OP, EQUATIONS_3D_OPB, EQUATIONS_3D_OPC, EQUATIONS_3D_OPM,
+                        EQUATIONS_3D_OPN, EQUATIONS_3D_OPV, EQUATIONS_3D_OPX, Operator3, Operator3V, Operator3X,
+                        deriv_boundary_3d, drift_fields, solution_3d, solution_3d_op, solution_3d_opb,
+                        solution_3d_opc, solution_3d_opm, solution_3d_opn, solution_3d_opv, solution_3d_opx)
 from .infras.exp_config import ExpConfig
 from .kernel_matrix import kernel_class
 from .solver_common import SolverBase
@@ -83,7 +86,7 @@ class DeviceSolver3:
 
     def __init__(self, eq, kind, xs, src, bvals, Q=30, jitter=1e-6, llk_weight=200.0, logdet=True,
                  lr=0.01, freq_scale=20.0, device=0, b1=0.9, b2=0.999, eps=1e-8, refine=False,
-                 operator=None, dfaces=0, dvals=None, conv=None, cross=None):
+                 operator=None, dfaces=0, dvals=None, conv=None, cross=None, drift=None):
         """refine: one gated refinement step after every solve of the step (GPK_FLAG3_REFINE);
         'gemm' also forces its two-GEMM route (GPK_FLAG3_REFINE_GEMM; tests, A/B).
         operator: an Operator3 (or a dict of its fields) -- the handle then solves that operator
@@ -100,7 +103,12 @@ class DeviceSolver3:
         cross: three floats m_12, m_13, m_23, the constants of the mixed partials m_jk d^2 u /
         dx_j dx_k (gpk_create3_opm; anisotropic diffusion with off-diagonal entries); a non-zero one
         needs an Operator3X or Operator3V as conv does.  None or three zeros is the handle without
-        them."""
+        them.
+        drift: three entries b_1, b_2, b_3, the fields of the drift terms b_k(x) du / dx_k
+        (gpk_create3_opb): each None, an array of the grid's shape or a callable of the three
+        coordinate meshes, as Operator3V.a; the operator's fields a_k do not multiply them.  A
+        non-None entry needs an Operator3X or Operator3V as conv does.  None or three Nones is the
+        handle without them."""
         lib = _lib.load()
         if len(xs) != 3:
             raise ValueError("three coordinate axes")
@@ -140,7 +148,13 @@ class DeviceSolver3:
                 raise ValueError("cross has three entries (m_12, m_13, m_23)")
             if not any(m != 0.0 for m in cross):
                 cross = None
-        if dfaces or conv or cross:
+        if drift is not None:
+            drift = tuple(drift)
+            if len(drift) != 3:
+                raise ValueError("drift has three entries (b_1, b_2, b_3; None for an axis without a field)")
+            if all(b is None for b in drift):
+                drift = None
+        if dfaces or conv or cross or drift:
             if dfaces and dvals is None:
                 raise ValueError("dfaces needs dvals (the six-face layout of bvals)")
             if dfaces:
@@ -149,7 +163,8 @@ class DeviceSolver3:
                     raise ValueError("dvals must have the six-face layout of bvals (deriv_boundary_3d)")
             if not (isinstance(operator, (Operator3X, Operator3V)) or (isinstance(operator, dict) and "c2" in operator)):
                 raise ValueError("%s needs an Operator3X or Operator3V"
-                                 % ("derivative boundary data" if dfaces else "a convective term" if conv else "a mixed partial"))
+                                 % ("derivative boundary data" if dfaces else "a convective term" if conv
+                                    else "a mixed partial" if cross else "a drift field"))
             c = _lib.gpk_operator3x()
             cf = _lib.gpk_coef3()
             if isinstance(operator, Operator3V):
@@ -166,7 +181,18 @@ class DeviceSolver3:
             bd = _lib.gpk_bdata3()
             if dfaces:
                 bd.dfaces, bd.dvals = dfaces, dptr(self._dvals)
-            if cross:
+            if drift:
+                cv, mx, dr = _lib.gpk_conv3(), _lib.gpk_cross3(), _lib.gpk_drift3()
+                cv.g[:] = conv or (0.0, 0.0, 0.0)
+                mx.m[:] = cross or (0.0, 0.0, 0.0)
+                self._drift = drift_fields(drift, self._x)  # (the library copies them; kept for the call)
+                for k, b in enumerate(self._drift):
+                    if b is not None:
+                        dr.b[k] = dptr(b)
+                check(lib.gpk_create3_opb(ctypes.byref(p), ctypes.byref(c), ctypes.byref(cf), ctypes.byref(bd),
+                                          ctypes.byref(cv), ctypes.byref(mx), ctypes.byref(dr), float(freq_scale),
+                                          ctypes.byref(h)))
+            elif cross:
                 cv, mx = _lib.gpk_conv3(), _lib.gpk_cross3()
                 cv.g[:] = conv or (0.0, 0.0, 0.0)
                 mx.m[:] = cross
@@ -307,7 +333,7 @@ class DeviceSolver3:
     def stage_variants(self):
         """The GEMM kernel of each of the step's GEMM launches, in stream order
         (_lib.GEMM_SMALL / GEMM_BIG / GEMM_TILE128; gpk_stage_variants3)."""
-        out = np.zeros(16, np.int32)
+        out = np.zeros(32, np.int32)
         n = ctypes.c_int32()
         check(_lib.load().gpk_stage_variants3(self._h, out.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
                                               out.size, ctypes.byref(n)))
@@ -368,6 +394,13 @@ class DeviceSolver3:
         check(_lib.load().gpk_cross_info3(self._h, dptr(m)))
         return tuple(m.tolist())
 
+    def drift_info(self):
+        """(b_1, b_2, b_3) present, as bools (gpk_drift_info3); all False on every handle made
+        without a drift field."""
+        has = np.zeros(3, np.int32)
+        check(_lib.load().gpk_drift_info3(self._h, has.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))))
+        return tuple(bool(v) for v in has)
+
     def boundary_terms(self):
         """{'bgap', 'dgap', 'Nb', 'Nd'}: the value gap, the derivative gap and their entry counts
         as the last loss_grad() / step() left them (gpk_boundary_terms3)."""
@@ -406,12 +439,13 @@ class GP_solver_3d_single(SolverBase):
     opn_eq_types = tuple(sorted({e.split("-")[0] for e in EQUATIONS_3D_OPN}))
     opc_eq_types = tuple(sorted({e.split("-")[0] for e in EQUATIONS_3D_OPC}))
     opm_eq_types = tuple(sorted({e.split("-")[0] for e in EQUATIONS_3D_OPM}))
+    opb_eq_types = tuple(sorted({e.split("-")[0] for e in EQUATIONS_3D_OPB}))
     early_stop_enabled = True
 
     def __init__(self, bvals, X_col, src_vals, jitter, trick_paras, device=0, X_test=None, u_test=None):
         self.eq_type = trick_paras["equation"].split("-")[0]
         assert self.eq_type in (self.eq_types + self.op_eq_types + self.opx_eq_types + self.opv_eq_types
-                                + self.opn_eq_types + self.opc_eq_types + self.opm_eq_types)
+                                + self.opn_eq_types + self.opc_eq_types + self.opm_eq_types + self.opb_eq_types)
         self.operator = None
         given = trick_paras.get("operator")
         if isinstance(given, Operator3V):
@@ -434,8 +468,19 @@ class GP_solver_3d_single(SolverBase):
         # mixed partials: given, or the equation's own (likewise)
         cross = trick_paras.get("cross")
         self.cross = None if cross is None else tuple(float(m) for m in cross)
-        if self.eq_type in self.opn_eq_types + self.opc_eq_types + self.opm_eq_types:
-            if self.eq_type in self.opm_eq_types:
+        # drift fields: given, or the equation's own (likewise; callables, evaluated on each mesh)
+        drift = trick_paras.get("drift")
+        self.drift = None if drift is None else tuple(drift)
+        if self.eq_type in self.opn_eq_types + self.opc_eq_types + self.opm_eq_types + self.opb_eq_types:
+            if self.eq_type in self.opb_eq_types:
+                _, _, op, dfaces, grad_u, conv, cross, drift = solution_3d_opb(trick_paras["equation"])
+                if self.conv is None:
+                    self.conv = tuple(conv)
+                if self.cross is None:
+                    self.cross = tuple(cross)
+                if self.drift is None:
+                    self.drift = tuple(drift)
+            elif self.eq_type in self.opm_eq_types:
                 _, _, op, dfaces, grad_u, conv, cross = solution_3d_opm(trick_paras["equation"])
                 if self.conv is None:
                     self.conv = tuple(conv)
@@ -475,7 +520,8 @@ class GP_solver_3d_single(SolverBase):
                                  logdet=tp.get("logdet", True), lr=tp.get("lr", 0.01),
                                  freq_scale=tp.get("freq_scale", 20.0), device=int(tp.get("device", device)),
                                  refine=bool(tp.get("refine", False)), operator=self.operator,
-                                 dfaces=self.dfaces, dvals=self.dvals, conv=self.conv, cross=self.cross)
+                                 dfaces=self.dfaces, dvals=self.dvals, conv=self.conv, cross=self.cross,
+                                 drift=self.drift)
         self._version = 0
 
     def eq_residual(self, params, X_test, src_test):
@@ -523,6 +569,14 @@ class GP_solver_3d_single(SolverBase):
                     d = [0, 0, 0]
                     d[j] = d[k] = 1
                     r = r + m * self.dev.predict_deriv(*axes, deriv=tuple(d))
+        if self.drift is not None and any(b is not None for b in self.drift):  # + sum_k b_k(x_test) du / dx_k
+            if not all(b is None or callable(b) for b in self.drift):
+                raise ValueError("eq_residual needs the drift fields as callables (to evaluate them on the test mesh)")
+            for k, b in enumerate(drift_fields(self.drift, axes)):
+                if b is not None:
+                    d = [0, 0, 0]
+                    d[k] = 1
+                    r = r + b * self.dev.predict_deriv(*axes, deriv=tuple(d))
         return r - np.asarray(src_test, np.float64).reshape(r.shape)
 
     # the device holds the params: reading fetches them, train()'s final assignment is a no-op
@@ -623,6 +677,8 @@ def test(trick_paras, solver_cls=None):
         u, src, op = solution_3d_opc(trick_paras["equation"])[:3]
     elif trick_paras["equation"] in EQUATIONS_3D_OPM:  # (... and its cross weights)
         u, src, op = solution_3d_opm(trick_paras["equation"])[:3]
+    elif trick_paras["equation"] in EQUATIONS_3D_OPB:  # (... and its drift fields)
+        u, src, op = solution_3d_opb(trick_paras["equation"])[:3]
     else:
         u, src = solution_3d(trick_paras["equation"])
     scale = trick_paras["scale"]
@@ -660,11 +716,13 @@ def test(trick_paras, solver_cls=None):
 def load_config(equation):
     """./config3d/<equation>.yaml (the operator equations: ./config3d_op/, the mixed-order ones:
     ./config3d_opx/, the coefficient-field ones: ./config3d_opv/, derivative boundary data:
-    ./config3d_opn/, convective terms: ./config3d_opc/, mixed partials: ./config3d_opm/), falling back to the package's copy."""
+    ./config3d_opn/, convective terms: ./config3d_opc/, mixed partials: ./config3d_opm/, drift fields:
+    ./config3d_opb/), falling back to the package's copy."""
     cdir = ("config3d_op" if equation in EQUATIONS_3D_OP else "config3d_opx" if equation in EQUATIONS_3D_OPX
             else "config3d_opv" if equation in EQUATIONS_3D_OPV else "config3d_opn" if equation in EQUATIONS_3D_OPN
             else "config3d_opc" if equation in EQUATIONS_3D_OPC
-            else "config3d_opm" if equation in EQUATIONS_3D_OPM else "config3d")
+            else "config3d_opm" if equation in EQUATIONS_3D_OPM
+            else "config3d_opb" if equation in EQUATIONS_3D_OPB else "config3d")
     for base in (os.getcwd(), os.path.dirname(os.path.abspath(__file__))):
         p = os.path.join(base, cdir, equation + ".yaml")
         if os.path.exists(p):
@@ -674,7 +732,7 @@ def load_config(equation):
 
 
 def build_config(args, allowed=EQUATIONS_3D + EQUATIONS_3D_OP + EQUATIONS_3D_OPX + EQUATIONS_3D_OPV
-                 + EQUATIONS_3D_OPN + EQUATIONS_3D_OPC + EQUATIONS_3D_OPM):
+                 + EQUATIONS_3D_OPN + EQUATIONS_3D_OPC + EQUATIONS_3D_OPM + EQUATIONS_3D_OPB):
     """The 2-axis build_config (scale, kernel class, other_paras) on the config3d files."""
     assert args.equation in allowed
     config = load_config(args.equation)

@@ -677,6 +677,39 @@ int gpk_create3_opm(const gpk_problem3* p, const gpk_operator3x* op, const gpk_c
 /* The cross weights (1,2), (1,3), (2,3); zeros on every older kind of 3-axis handle. */
 int gpk_cross_info3(const gpk_handle3* h, double m[3]);
 
+/* Drift fields (divergence form -div(a grad u) = -a lap u - grad a . grad u: Darcy flow, heat in
+ * conservation form; convection-diffusion with a variable velocity and a constant viscosity;
+ * Fokker-Planck / Ornstein-Uhlenbeck drifts).  Axis k adds
+ *     b_k(x) . d u / d x_k
+ * ( . elementwise) to the equation of a gpk_create3_opm handle: with A_k = K_k^{-1} x_k U and D1_k
+ * the plain order-1 block of axis k, Z_k = D1_k x_k A_k and the residual is the opm handle's plus
+ * b_1 . Z_1 + b_3 . Z_3 + b_2 . Z_2 (that order, after the cross terms, each only where its field
+ * is given).  b_k is problem data like the gpk_coef3 fields: given at the collocation points,
+ * copied at creation, never part of the parameter vector.  It is a field of its own: THE gpk_coef3
+ * FIELDS a_k DO NOT MULTIPLY THE DRIFT TERM (a_k serves c2_k d^2 + c1_k d of its axis, b_k stands
+ * alone), which is what divergence form needs: c2_k a on the second derivative and c2_k da/dx_k as
+ * b_k on the first.  A drift axis may have c2_k = c1_k = g_k = 0.  Everything else -- the log
+ * joint, the boundary and derivative-boundary terms, gpk_criterion3, gpk_loss_terms3,
+ * gpk_boundary_terms3, the Adam update -- keeps its formula on the new residual; predictions depend
+ * on K_k only.  gpk_stage_variants3 reports two or three further GEMM launches on a handle with any
+ * drift field: one after the convective handle's first launch (the Z_k; absent when every drift
+ * axis's Z_k is already a cross pair's: axis 1 of the pairs (1,2) and (1,3), axis 2 of (2,3)), and
+ * two after the cross handle's G_D1 launch, before the X_k (the sums into T_k; the G_D1k).  Not
+ * built: fields on g_k and on m_jk, the sharded, 1-axis and 2-axis handles, the class path. */
+typedef struct gpk_drift3 {
+  const double* b[3]; /* per axis: NULL (no drift term) or n1*n2*n3 values, row-major [i1][i2][i3] like src */
+} gpk_drift3;
+/* p, op, cf, bd, cv and mx as on gpk_create3_opm (cf, bd, cv and mx may be NULL).  dr == NULL or
+ * all three pointers NULL is gpk_create3_opm(p, op, cf, bd, cv, mx, ...) itself: the same stage
+ * list, launches and bits.  GPK_EINVAL, before any device work, on a non-finite value in a given
+ * drift field, and on everything gpk_create3_opm, gpk_create3_opc, gpk_create3_opn, gpk_create3_opv
+ * and gpk_create3_opx reject. */
+int gpk_create3_opb(const gpk_problem3* p, const gpk_operator3x* op, const gpk_coef3* cf,
+                    const gpk_bdata3* bd, const gpk_conv3* cv, const gpk_cross3* mx, const gpk_drift3* dr,
+                    double freq_scale, gpk_handle3** out);
+/* has[k]: axis k has a drift field; zeros on every older kind of 3-axis handle. */
+int gpk_drift_info3(const gpk_handle3* h, int32_t has[3]);
+
 int gpk_num_params3(const gpk_handle3* h, int64_t* n);
 int gpk_set_params3(gpk_handle3* h, const double* flat, int64_t n);
 int gpk_get_params3(gpk_handle3* h, double* flat, int64_t n);
