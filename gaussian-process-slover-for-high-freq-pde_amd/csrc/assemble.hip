@@ -85,7 +85,10 @@ __global__ __launch_bounds__(256) void assemble_kernel(AssembleBatch b, int q) {
   __shared__ double pk[4][64], pd[4][64];
   constexpr bool BOTH = deriv_two_fields(DERIV);  // pd: the order-2 field, pd1: the order-1 field
   constexpr bool SPLIT = DERIV == DERIV_SPLIT;    // ... and the order-1 block stored on its own
-  __shared__ double pd1[BOTH ? 4 : 1][64];    // (no reference in the other modes: not allocated)
+  constexpr bool HIGH = deriv_high(DERIV);        // pd: order 2, pd1: order 1, pd3, pd4: orders 3 and 4
+  constexpr bool HSPLIT = DERIV == DERIV_HIGH_SPLIT;  // ... and the order-1 block stored on its own
+  __shared__ double pd1[BOTH || HIGH ? 4 : 1][64];    // (no reference in the other modes: not allocated)
+  __shared__ double pd3[HIGH ? 4 : 1][64], pd4[HIGH ? 4 : 1][64];
   if (t < q) axis_component(b.prep, axis, q, t, sw[t], sa[t], so[t], sol[t]);
   if (blockIdx.x == 0 && axis == 0) publish_prep(b.prep, q);
   __syncthreads();
@@ -100,21 +103,30 @@ __global__ __launch_bounds__(256) void assemble_kernel(AssembleBatch b, int q) {
   const int e = t & 63, g = t >> 6;
   const int i = I * 32 + 2 * sub + (e >> 5), j = J * 32 + (e & 31);
   const bool real = i < A.n && j < A.n;
-  double diff = 0.0, kv = 0.0, dv = 0.0, dv1 = 0.0;
+  double diff = 0.0, kv = 0.0, dv = 0.0, dv1 = 0.0, dv3 = 0.0, dv4 = 0.0;
   if (real) {
     diff = A.x[i] - A.x[j];
-    if constexpr (BOTH) eval_kd_part<MATERN, COS>(diff, sw, sa, so, sol, g, 4, q, kv, dv, dv1);
+    if constexpr (HIGH) eval_kd_part<MATERN, COS>(diff, sw, sa, so, sol, g, 4, q, kv, dv4, dv3, dv, dv1);
+    else if constexpr (BOTH) eval_kd_part<MATERN, COS>(diff, sw, sa, so, sol, g, 4, q, kv, dv, dv1);
     else eval_kd_part<MATERN, COS, DERIV>(diff, sw, sa, so, sol, g, 4, q, kv, dv);
   }
   pk[g][e] = kv;
   pd[g][e] = dv;
-  if constexpr (BOTH) pd1[g][e] = dv1;
+  if constexpr (BOTH || HIGH) pd1[g][e] = dv1;
+  if constexpr (HIGH) {
+    pd3[g][e] = dv3;
+    pd4[g][e] = dv4;
+  }
   __syncthreads();
   if (g != 0) return;
   if (real) {
     kv = (pk[0][e] + pk[1][e]) + (pk[2][e] + pk[3][e]);
     dv = (pd[0][e] + pd[1][e]) + (pd[2][e] + pd[3][e]);
-    if constexpr (BOTH) dv1 = (pd1[0][e] + pd1[1][e]) + (pd1[2][e] + pd1[3][e]);
+    if constexpr (BOTH || HIGH) dv1 = (pd1[0][e] + pd1[1][e]) + (pd1[2][e] + pd1[3][e]);
+    if constexpr (HIGH) {
+      dv3 = (pd3[0][e] + pd3[1][e]) + (pd3[2][e] + pd3[3][e]);
+      dv4 = (pd4[0][e] + pd4[1][e]) + (pd4[2][e] + pd4[3][e]);
+    }
     if (i == j) kv += A.jitter;
   } else {
     kv = (i == j) ? 1.0 : 0.0;  // padded block is the identity
@@ -130,6 +142,11 @@ __global__ __launch_bounds__(256) void assemble_kernel(AssembleBatch b, int q) {
   // the antisymmetric part with its sign, so D is neither
   if constexpr (BOTH) A.D[(size_t)i * A.p + j] = real ? A.c2 * dv + A.c1 * (s_ij * dv1) : 0.0;
   if constexpr (SPLIT) A.D1[(size_t)i * A.p + j] = real ? s_ij * dv1 : 0.0;
+  // the high-order block: the two lower orders combined as above, then the two upper ones; the even
+  // parts (orders 4, 2) mirror as they are, the odd parts (3, 1) with their sign
+  if constexpr (HIGH)
+    A.D[(size_t)i * A.p + j] = real ? (A.c2 * dv + A.c1 * (s_ij * dv1)) + (A.c4 * dv4 + A.c3 * (s_ij * dv3)) : 0.0;
+  if constexpr (HSPLIT) A.D1[(size_t)i * A.p + j] = real ? s_ij * dv1 : 0.0;
   if (I != J) {
     A.K[(size_t)j * A.p + i] = kv;
     if (A.Kc) A.Kc[(size_t)j * A.p + i] = kv;
@@ -137,6 +154,9 @@ __global__ __launch_bounds__(256) void assemble_kernel(AssembleBatch b, int q) {
     if (DERIV == 1) A.D[(size_t)j * A.p + i] = real ? s_ji * dv : 0.0;
     if constexpr (BOTH) A.D[(size_t)j * A.p + i] = real ? A.c2 * dv + A.c1 * (s_ji * dv1) : 0.0;
     if constexpr (SPLIT) A.D1[(size_t)j * A.p + i] = real ? s_ji * dv1 : 0.0;
+    if constexpr (HIGH)
+      A.D[(size_t)j * A.p + i] = real ? (A.c2 * dv + A.c1 * (s_ji * dv1)) + (A.c4 * dv4 + A.c3 * (s_ji * dv3)) : 0.0;
+    if constexpr (HSPLIT) A.D1[(size_t)j * A.p + i] = real ? s_ji * dv1 : 0.0;
   }
   if (tile == 0 && b.pivot_x >= 0) {  // release this sub-block of tile (0,0) to pivot0
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // (only wave 0 stored)
@@ -497,6 +517,10 @@ static void launch_assemble_t(const AssembleBatch& b, int naxes, int maxt, int q
     hipLaunchKernelGGL((assemble_kernel<MATERN, COS, DERIV_BOTH>), grid, dim3(256), 0, s, b, q);
   else if (deriv == DERIV_SPLIT)
     hipLaunchKernelGGL((assemble_kernel<MATERN, COS, DERIV_SPLIT>), grid, dim3(256), 0, s, b, q);
+  else if (deriv == DERIV_HIGH)
+    hipLaunchKernelGGL((assemble_kernel<MATERN, COS, DERIV_HIGH>), grid, dim3(256), 0, s, b, q);
+  else if (deriv == DERIV_HIGH_SPLIT)
+    hipLaunchKernelGGL((assemble_kernel<MATERN, COS, DERIV_HIGH_SPLIT>), grid, dim3(256), 0, s, b, q);
   else
     hipLaunchKernelGGL((assemble_kernel<MATERN, COS, 0>), grid, dim3(256), 0, s, b, q);
 }
@@ -517,11 +541,12 @@ hipError_t launch_assemble(int kind, int q, const AssembleArgs* a, int naxes, co
         (a[k].cls.ncls > 0) != (a[0].cls.ncls > 0))
       return hipErrorInvalidValue;
   int deriv = a[0].deriv;
-  // one mode per launch (DERIV_BOTH and DERIV_SPLIT carry their weights per axis); the class path
-  // stores one dval per class, so it has neither; DERIV_SPLIT needs its second block
+  // one mode per launch (the weighted modes, DERIV_BOTH to DERIV_HIGH_SPLIT, carry their weights per
+  // axis); the class path stores one dval per class, so it has none of them; DERIV_SPLIT and
+  // DERIV_HIGH_SPLIT need their second block
   for (int k = 0; k < naxes; ++k)
-    if ((deriv_two_fields(deriv) && (a[k].deriv != deriv || a[k].cls.ncls > 0)) ||
-        (!deriv_two_fields(deriv) && deriv_two_fields(a[k].deriv)) || (a[k].deriv == DERIV_SPLIT && !a[k].D1))
+    if ((deriv_weighted(deriv) && (a[k].deriv != deriv || a[k].cls.ncls > 0)) ||
+        (!deriv_weighted(deriv) && deriv_weighted(a[k].deriv)) || (deriv_stores_d1(a[k].deriv) && !a[k].D1))
       return hipErrorInvalidValue;
   if (a[0].cls.ncls > 0) {  // class path: every 32x32 tile of the full matrix, one per workgroup
     int maxc = 0, maxtiles = 0;

@@ -114,6 +114,67 @@ __device__ __forceinline__ void radial_l(double d, double a, double& m0, double&
   }
 }
 
+// radial factor and its first four derivatives m[0..4] (high-order terms of the 3-axis solver: the
+// order-3 and order-4 blocks).  m[0..2] are radial's expressions; Matern52 with r = sqrt5 a d:
+// m3 = (5 sqrt5 / 3) a^3 r (3 - r) e^{-r}, m4 = (25 / 3) a^4 (r^2 - 5 r + 3) e^{-r} (continuous, with
+// a kink at d = 0: there is no fifth derivative, so order 4 is the ceiling for both families); SE:
+// m3 = -4 a^2 d (2 a d^2 - 3) g, m4 = 4 a^2 (4 a^2 d^4 - 12 a d^2 + 3) g.
+template <bool MATERN>
+__device__ __forceinline__ void radial4(double d, double a, double (&m)[5]) {
+  double r;
+  const double E = radial_exp<MATERN>(d, a, r);
+  if (MATERN) {
+    const double a2 = a * a;
+    m[0] = (1.0 + r + r * r * (1.0 / 3.0)) * E;
+    m[1] = -(SQRT5 / 3.0) * a * r * (1.0 + r) * E;
+    m[2] = (5.0 / 3.0) * a * a * (r * r - r - 1.0) * E;
+    m[3] = (5.0 * SQRT5 / 3.0) * (a2 * a) * r * (3.0 - r) * E;
+    m[4] = (25.0 / 3.0) * (a2 * a2) * (r * r - 5.0 * r + 3.0) * E;
+  } else {
+    const double d2 = d * d, g = E;
+    m[0] = g;
+    m[1] = -2.0 * a * d * g;
+    m[2] = (4.0 * a * a * d2 - 2.0 * a) * g;
+    m[3] = -4.0 * a * a * d * (2.0 * a * d2 - 3.0) * g;
+    m[4] = 4.0 * a * a * (4.0 * a * a * d2 * d2 - 12.0 * a * d2 + 3.0) * g;
+  }
+}
+
+// ... plus their log-ls derivatives ml[0..4] (a d/da at fixed d; Matern52: m_n = p^n h_n(r), p =
+// sqrt5 a, so a dm_n/da = p^n (n h_n + r h_{n+1}))
+template <bool MATERN>
+__device__ __forceinline__ void radial4_l(double d, double a, double (&m)[5], double (&ml)[5]) {
+  double r;
+  const double E = radial_exp<MATERN>(d, a, r);
+  if (MATERN) {
+    const double ka = (SQRT5 / 3.0) * a, k2 = (5.0 / 3.0) * a * a;
+    const double k3 = (5.0 * SQRT5 / 3.0) * (a * a * a), k4 = (25.0 / 3.0) * (a * a) * (a * a);
+    const double r2 = r * r;
+    m[0] = (1.0 + r + r2 * (1.0 / 3.0)) * E;
+    m[1] = -ka * r * (1.0 + r) * E;
+    m[2] = k2 * (r2 - r - 1.0) * E;
+    m[3] = k3 * r * (3.0 - r) * E;
+    m[4] = k4 * (r2 - 5.0 * r + 3.0) * E;
+    ml[0] = -(r2 * (1.0 / 3.0)) * (1.0 + r) * E;
+    ml[1] = -ka * r * (2.0 + 2.0 * r - r2) * E;
+    ml[2] = k2 * (-r2 * r + 5.0 * r2 - 2.0 * r - 2.0) * E;
+    ml[3] = k3 * r * (r2 - 8.0 * r + 12.0) * E;
+    ml[4] = k4 * (-r2 * r + 11.0 * r2 - 28.0 * r + 12.0) * E;
+  } else {
+    const double d2 = d * d, g = E, a2 = a * a, u = a * d2;  // u = a d^2
+    m[0] = g;
+    m[1] = -2.0 * a * d * g;
+    m[2] = (4.0 * a * a * d2 - 2.0 * a) * g;
+    m[3] = -4.0 * a2 * d * (2.0 * u - 3.0) * g;
+    m[4] = 4.0 * a2 * (4.0 * u * u - 12.0 * u + 3.0) * g;
+    ml[0] = -a * d2 * g;
+    ml[1] = (-2.0 * a * d + 2.0 * a * a * d2 * d) * g;
+    ml[2] = (10.0 * a * a * d2 - 2.0 * a - 4.0 * a * a * a * d2 * d2) * g;
+    ml[3] = a2 * d * (24.0 - 36.0 * u + 8.0 * u * u) * g;
+    ml[4] = a2 * (24.0 - 156.0 * u + 112.0 * u * u - 16.0 * u * u * u) * g;
+  }
+}
+
 }  // namespace gpk
 
 // ------------------------------------------------------------------------------------------
@@ -193,6 +254,17 @@ constexpr int DERIV_BOTH = 3;
 // are (the 3-axis solver's convective axes: D carries the linear terms, D1 the term u du/dx_k)
 constexpr int DERIV_SPLIT = 4;
 __host__ __device__ constexpr bool deriv_two_fields(int deriv) { return deriv == DERIV_BOTH || deriv == DERIV_SPLIT; }
+// High-order axes (gpk_create3_oph): D = c4 D4 + c3 D3 + c2 DD + c1 D1, Dn the n-th derivative in the
+// first argument of kappa, all four fields from one exp / sincos set per mixture component; odd
+// orders carry the sign s_ij and mirror with it.  DERIV_HIGH_SPLIT also stores the plain order-1
+// block D1 next to D (as DERIV_SPLIT does).  2D per-pair path only, like DERIV_BOTH.
+constexpr int DERIV_HIGH = 5;
+constexpr int DERIV_HIGH_SPLIT = 6;
+__host__ __device__ constexpr bool deriv_high(int deriv) { return deriv == DERIV_HIGH || deriv == DERIV_HIGH_SPLIT; }
+// modes that carry their weights per axis (one mode per launch, per-pair path only)
+__host__ __device__ constexpr bool deriv_weighted(int deriv) { return deriv_two_fields(deriv) || deriv_high(deriv); }
+// modes that store the order-1 block D1 on its own (and contract its dL/dD1)
+__host__ __device__ constexpr bool deriv_stores_d1(int deriv) { return deriv == DERIV_SPLIT || deriv == DERIV_HIGH_SPLIT; }
 
 struct AssembleArgs {
   const double* x;       // coords [n] (padded buffer ok)
@@ -203,9 +275,10 @@ struct AssembleArgs {
   double* K;             // [p*p]  (consumed in place by the SPD inverse)
   double* Kc;            // [p*p]  kept copy of K for iterative refinement (nullable)
   double* D;             // [p*p]
-  int deriv;             // 1 or 2 (0: K only), DERIV_BOTH or DERIV_SPLIT
+  int deriv;             // 1 or 2 (0: K only), DERIV_BOTH, DERIV_SPLIT, DERIV_HIGH or DERIV_HIGH_SPLIT
   double c2, c1;         // DERIV_BOTH / DERIV_SPLIT: D = c2 DD + c1 D1 (read in those modes only)
-  double* D1;            // [p*p]  DERIV_SPLIT: the order-1 block alone (null in every other mode)
+  double* D1;            // [p*p]  DERIV_SPLIT / DERIV_HIGH_SPLIT: the order-1 block alone (null in every other mode)
+  double c4, c3;         // DERIV_HIGH / DERIV_HIGH_SPLIT: D = c4 D4 + c3 D3 + c2 DD + c1 D1 (read in those modes only)
   // pivot block 0 of the SPD inverse, factored by one extra workgroup of the assembly launch
   // (nullable piv: not fused).  Same outputs as the sweep's pivot_init.
   double* piv; double* ldet; double* pst; int* status;
@@ -550,9 +623,10 @@ struct PGradArgs {
   const double* Kinv;                     // 1D mode
   const double* alpha; const double* beta; const double* R;  // 1D mode vectors
   double halfc;                           // 1D mode: 0.5*logdet flag
-  int deriv;                              // 1, 2, DERIV_BOTH or DERIV_SPLIT (2D per-pair path only)
+  int deriv;                              // 1, 2, or a weighted mode (DERIV_BOTH ... DERIV_HIGH_SPLIT: 2D per-pair path only)
   double c2, c1;                          // DERIV_BOTH / DERIV_SPLIT: G_D weighs c2 dDD + c1 dD1 (read in those modes only)
-  const double* GD1;                      // DERIV_SPLIT: dL/dD1 of the order-1 block alone [p*p] (null elsewhere)
+  const double* GD1;                      // DERIV_SPLIT / DERIV_HIGH_SPLIT: dL/dD1 of the order-1 block alone [p*p] (null elsewhere)
+  double c4, c3;                          // DERIV_HIGH / DERIV_HIGH_SPLIT: G_D weighs c4 dD4 + c3 dD3 + c2 dDD + c1 dD1
   double* part;                           // [nblocks * 3*QMAX]
   // DD (class path, 2D, fused tail): the derivative fields and every sum after them in
   // double-double; part holds the partials' high parts, part_lo their low parts (null: fp64)

@@ -39,6 +39,10 @@
 // Hb_jk = m_jk D1_k^T x_k R, Zb_jk = K_k^{-1} x_k Hb_jk (a solve), T_j += D1_j^T x_j Zb_jk before
 // X_j, G_D1j += v Zb_jk,(j) A_j,(j)^T, G_D1k += v m_jk R_(k) H_jk,(k)^T and G_Kk -= v Zb_jk,(k)
 // H_jk,(k)^T: eight further launches (build_cross_stages).
+// High-order terms (gpk_create3_oph, c4_k d^4u/dx_k^4 + c3_k d^3u/dx_k^3): the axis's block is D_k =
+// c4_k D4_k + c3_k D3_k + c2_k DD_k + c1_k D1_k, assembled and contracted in DERIV_HIGH (DERIV_HIGH_SPLIT
+// where the axis also owns D1_k: convective, cross, drift).  The host treats D_k as opaque: the stage
+// list, the refinement and the face kernels are untouched.
 // Drift fields (gpk_create3_opb, b_k(x) du/dx_k): a drift axis assembles in DERIV_SPLIT; Z_k = D1_k
 // x_k A_k (a cross pair's own Z_1 / Z_2p where it forms them), R += b_1 Z_1 + b_3 Z_3 + b_2 Z_2
 // (k3_combine_b), and the reverse pass reads E_k = b_k R: T_k += D1_k^T x_k E_k before X_k and
@@ -72,6 +76,10 @@ struct gpk_handle3 {
   // where op.order[k] = 0 and op.coef[k] = 1.0, the GEMM weight) and the weights as stated
   int mode[3] = {2, 2, 2};
   double c2[3] = {}, c1[3] = {};
+  // gpk_create3_oph: the weights of the order-4 and order-3 fields (zeros: none).  An axis with one
+  // of them is entered as a mixed axis and assembles / contracts in DERIV_HIGH, or in DERIV_HIGH_SPLIT
+  // where DERIV_SPLIT would stand (its D1_k and G_D1k as there); nothing else knows of them
+  double c4[3] = {}, c3[3] = {};
   K3Geom g{};
   int q = 0;
   long nu = 0, nparams = 0;
@@ -508,6 +516,7 @@ int enqueue_inverse3(gpk_handle3* h, int apply) {
     aa[a].x = h->x[a]; aa[a].n = g.n[a]; aa[a].p = g.p[a]; aa[a].kc = h->kc + a;
     aa[a].jitter = h->prob.jitter; aa[a].K = h->K[a]; aa[a].Kc = h->Kc[a]; aa[a].D = h->D[a];
     aa[a].deriv = h->mode[a]; aa[a].c2 = h->c2[a]; aa[a].c1 = h->c1[a]; aa[a].D1 = h->D1[a];
+    aa[a].c4 = h->c4[a]; aa[a].c3 = h->c3[a];
   }
   // (skip = 1: the constants are published by k3_prep; each workgroup derives its axis's own)
   PrepArgs p12{};
@@ -631,6 +640,7 @@ int enqueue_step3(gpk_handle3* h, int apply) {
     pg[a].x = h->x[a]; pg[a].n = g.n[a]; pg[a].p = g.p[a]; pg[a].kc = h->kc + a;
     pg[a].GK = h->GK[a]; pg[a].GD = h->GD[a]; pg[a].deriv = h->mode[a];
     pg[a].c2 = h->c2[a]; pg[a].c1 = h->c1[a]; pg[a].GD1 = h->GD1[a];
+    pg[a].c4 = h->c4[a]; pg[a].c3 = h->c3[a];
     pg[a].part = h->pgpart + (size_t)a * (h->bpa + fb) * 3 * QMAX;
   }
   if (h->mode[0] == h->mode[1]) {
@@ -732,7 +742,8 @@ int check_problem3(const gpk_problem3* p) {
 // gpk_create3_opv (cf: the fields it was given, at least one of them)
 int create3(const gpk_problem3* p, const gpk_operator3* op, double freq_scale, gpk_handle3** out,
             const gpk_operator3x* opx = nullptr, const gpk_coef3* cf = nullptr, const gpk_bdata3* bd = nullptr,
-            const gpk_conv3* cv = nullptr, const gpk_cross3* mx = nullptr, const gpk_drift3* dr = nullptr) {
+            const gpk_conv3* cv = nullptr, const gpk_cross3* mx = nullptr, const gpk_drift3* dr = nullptr,
+            const gpk_high3* hi = nullptr) {
   TRY(check_problem3(p));
   const int ns[3] = {p->n1, p->n2, p->n3};
   TRY(check_device(p->device));
@@ -769,6 +780,13 @@ int create3(const gpk_problem3* p, const gpk_operator3* op, double freq_scale, g
     if (dr && dr->b[a]) {
       h->drift = 1;
       h->mode[a] = DERIV_SPLIT;
+    }
+    // a high-order axis (entered as a mixed one): the four-field block, with D1_k alongside where
+    // the axis owns one
+    if (hi && (hi->c4[a] != 0.0 || hi->c3[a] != 0.0)) {
+      h->c4[a] = hi->c4[a];
+      h->c3[a] = hi->c3[a];
+      h->mode[a] = h->mode[a] == DERIV_SPLIT ? DERIV_HIGH_SPLIT : DERIV_HIGH;
     }
     h->c2[a] = mixed ? opx->c2[a] : h->op.order[a] == 2 ? h->op.coef[a] : 0.0;
     h->c1[a] = mixed ? opx->c1[a] : h->op.order[a] == 1 ? h->op.coef[a] : 0.0;
@@ -883,7 +901,7 @@ int create3(const gpk_problem3* p, const gpk_operator3* op, double freq_scale, g
   // convective axes: D1_k, V_k and G_D1k per axis, N, and Q in the layouts those axes read
   // (and D1_k, G_D1k on the axes of a cross pair)
   for (int a = 0; a < 3 && (h->conv || h->cross || h->drift); ++a) {
-    if (h->mode[a] != DERIV_SPLIT) continue;
+    if (!deriv_stores_d1(h->mode[a])) continue;
     const int P = g.p[a];
     A3_(h->D1[a], (size_t)P * P); A3_(h->GD1[a], (size_t)P * P);
     if (h->gconv[a] == 0.0) continue;
@@ -1011,7 +1029,7 @@ int gpk_create3_op(const gpk_problem3* p, const gpk_operator3* op, double freq_s
 int gpk_operator_info3(const gpk_handle3* h, gpk_operator3* out) {
   if (!h || !out) return fail(GPK_EINVAL, "NULL argument");
   for (int a = 0; a < 3; ++a)
-    if (deriv_two_fields(h->mode[a]))
+    if (deriv_weighted(h->mode[a]))
       return fail(GPK_EINVAL, "gpk_operator_info3: the handle has a mixed-order axis (gpk_operator_info3x states it)");
   *out = h->op;
   return GPK_OK;
@@ -1057,7 +1075,7 @@ namespace {
 // then be null or without faces): the argument checks of both, then the handle
 int create3_opn(const gpk_problem3* p, const gpk_operator3x* op, const gpk_coef3* cf, const gpk_bdata3* bd,
                 const gpk_conv3* cv, double freq_scale, gpk_handle3** out, const gpk_cross3* mx = nullptr,
-                const gpk_drift3* dr = nullptr) {
+                const gpk_drift3* dr = nullptr, const gpk_high3* hi = nullptr) {
   if (!p || !op || !out) return fail(GPK_EINVAL, "NULL argument");
   *out = nullptr;
   if (bd && bd->dfaces == 0) bd = nullptr;
@@ -1066,7 +1084,7 @@ int create3_opn(const gpk_problem3* p, const gpk_operator3x* op, const gpk_coef3
   // the operator's own checks, with faces = 0 allowed here (data on derivatives alone)
   gpk_operator3x o = *op;
   if (bd && o.faces == 0) o.faces = bd->dfaces;
-  TRY(check_operator3x(p, &o, out, dr ? "gpk_create3_opb" : mx ? "gpk_create3_opm" : cv ? "gpk_create3_opc" : "gpk_create3_opn"));
+  TRY(check_operator3x(p, &o, out, hi ? "gpk_create3_oph" : dr ? "gpk_create3_opb" : mx ? "gpk_create3_opm" : cv ? "gpk_create3_opc" : "gpk_create3_opn"));
   TRY(check_problem3(p));
   if (bd) {
     const long fs[3] = {(long)p->n2 * p->n3, (long)p->n1 * p->n3, (long)p->n1 * p->n2};
@@ -1102,7 +1120,10 @@ int create3_opn(const gpk_problem3* p, const gpk_operator3x* op, const gpk_coef3
   // and a drift axis
   for (int a = 0; a < 3 && dr; ++a)
     if (dr->b[a]) { o1.order[a] = 0; o1.coef[a] = 1.0; }
-  return create3(p, &o1, freq_scale, out, op, any ? cf : nullptr, bd, cv, mx, dr);
+  // and a high-order axis
+  for (int a = 0; a < 3 && hi; ++a)
+    if (hi->c4[a] != 0.0 || hi->c3[a] != 0.0) { o1.order[a] = 0; o1.coef[a] = 1.0; }
+  return create3(p, &o1, freq_scale, out, op, any ? cf : nullptr, bd, cv, mx, dr, hi);
 }
 
 // the convective weights as gpk_create3_opc and gpk_create3_opm (`who`) take them: GPK_EINVAL on a
@@ -1158,6 +1179,38 @@ int gpk_create3_opb(const gpk_problem3* p, const gpk_operator3x* op, const gpk_c
   }
   TRY(check_conv3(cv, "gpk_create3_opb"));
   return create3_opn(p, op, cf, bd, cv, freq_scale, out, mx, dr);
+}
+
+int gpk_create3_oph(const gpk_problem3* p, const gpk_operator3x* op, const gpk_coef3* cf, const gpk_bdata3* bd,
+                    const gpk_conv3* cv, const gpk_cross3* mx, const gpk_drift3* dr, const gpk_high3* hi,
+                    double freq_scale, gpk_handle3** out) {
+  bool any = false;
+  if (hi) {
+    if (out) *out = nullptr;
+    for (int a = 0; a < 3; ++a) {
+      if (!std::isfinite(hi->c4[a]) || !std::isfinite(hi->c3[a]))
+        return fail(GPK_EINVAL, "gpk_create3_oph: c4 and c3 must be finite");
+      any = any || hi->c4[a] != 0.0 || hi->c3[a] != 0.0;
+    }
+  }
+  if (!any) return gpk_create3_opb(p, op, cf, bd, cv, mx, dr, freq_scale, out);
+  if (mx) {
+    for (int t = 0; t < 3; ++t)
+      if (!std::isfinite(mx->m[t])) return fail(GPK_EINVAL, "gpk_create3_oph: m must be finite");
+    if (mx->m[0] == 0.0 && mx->m[1] == 0.0 && mx->m[2] == 0.0) mx = nullptr;
+  }
+  TRY(check_conv3(cv, "gpk_create3_oph"));
+  if (dr && !dr->b[0] && !dr->b[1] && !dr->b[2]) dr = nullptr;
+  return create3_opn(p, op, cf, bd, cv, freq_scale, out, mx, dr, hi);
+}
+
+int gpk_high_info3(const gpk_handle3* h, double c4[3], double c3[3]) {
+  if (!h || !c4 || !c3) return fail(GPK_EINVAL, "NULL argument");
+  for (int a = 0; a < 3; ++a) {
+    c4[a] = h->c4[a];
+    c3[a] = h->c3[a];
+  }
+  return GPK_OK;
 }
 
 int gpk_drift_info3(const gpk_handle3* h, int32_t has[3]) {

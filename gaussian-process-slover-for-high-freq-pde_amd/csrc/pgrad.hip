@@ -379,6 +379,17 @@ __global__ __launch_bounds__(256) void class_sum_kernel(PGradBatch b,
 
 constexpr int PG_CLS = 16;  // classes per contraction workgroup
 
+// The order-1 to order-4 fields of one mixture component from its radial values m[0..4] and phase
+// values k[0..4] (DERIV_HIGH): f_n = sum_j C(n, j) m_j k_{n-j}.  With the log-ls derivatives for m,
+// or the freq derivatives for k, the same sums are the fields' derivatives.
+__device__ __forceinline__ void high_fields(const double (&m)[5], const double (&k)[5], double& f4,
+                                            double& f3, double& f2, double& f1) {
+  f1 = m[1] * k[0] + m[0] * k[1];
+  f2 = m[2] * k[0] + 2.0 * m[1] * k[1] + m[0] * k[2];
+  f3 = m[3] * k[0] + 3.0 * m[2] * k[1] + 3.0 * m[1] * k[2] + m[0] * k[3];
+  f4 = m[4] * k[0] + 4.0 * m[3] * k[1] + 6.0 * m[2] * k[2] + 4.0 * m[1] * k[3] + m[0] * k[4];
+}
+
 template <bool MATERN, bool COS, int DERIV, bool MODE1D, bool CLS, bool DD = false>
 __global__ __launch_bounds__(256) void pgrad_kernel(PGradBatch b, int q,
                                                     const StepScalars* __restrict__ sc) {
@@ -422,7 +433,14 @@ __global__ __launch_bounds__(256) void pgrad_kernel(PGradBatch b, int q,
   constexpr bool BOTH = deriv_two_fields(DERIV);
   constexpr bool SPLIT = DERIV == DERIV_SPLIT;
   static_assert(!BOTH || (!MODE1D && !CLS && !DD), "DERIV_BOTH / DERIV_SPLIT: the 2D per-pair contraction only");
-  __shared__ double swd1[BOTH ? PAIRS : 1];
+  // DERIV_HIGH: swd the symmetric pair sum of G_D (orders 4 and 2), swd1 its signed pair sum (orders 3
+  // and 1), the axis's weights applied per component; DERIV_HIGH_SPLIT: swg1 the signed pair sum of
+  // dL/dD1 (the plain order-1 block)
+  constexpr bool HIGH = deriv_high(DERIV);
+  constexpr bool HSPLIT = DERIV == DERIV_HIGH_SPLIT;
+  static_assert(!HIGH || (!MODE1D && !CLS && !DD), "DERIV_HIGH / DERIV_HIGH_SPLIT: the 2D per-pair contraction only");
+  __shared__ double swd1[BOTH || HIGH ? PAIRS : 1];
+  __shared__ double swg1[HSPLIT ? PAIRS : 1];
   __shared__ double sw[QMAX], sa[QMAX], so[QMAX], sol[QMAX];
   __shared__ double sacc[8][3][32];
   const int t = threadIdx.x;
@@ -470,7 +488,7 @@ __global__ __launch_bounds__(256) void pgrad_kernel(PGradBatch b, int q,
     while (I * (I + 1) / 2 > tile) --I;
     const int J = tile - I * (I + 1) / 2;
     const int i = I * 32 + chunk * (PAIRS / 32) + (t >> 5), j = J * 32 + (t & 31);
-    double d = 0.0, wk = 0.0, wd = 0.0, wd1 = 0.0;
+    double d = 0.0, wk = 0.0, wd = 0.0, wd1 = 0.0, wg1 = 0.0;
     if (i < A.n && j < A.n) {
       const double diff = A.x[i] - A.x[j];
       d = fabs(diff);
@@ -510,11 +528,17 @@ __global__ __launch_bounds__(256) void pgrad_kernel(PGradBatch b, int q,
         const double g1ij = A.GD1[(size_t)i * A.p + j], g1ji = A.GD1[(size_t)j * A.p + i];
         wd1 += I == J ? sij * g1ij : sij * g1ij + sji * g1ji;
       }
+      if constexpr (HIGH) wd1 = I == J ? sij * gdij : sij * gdij + sji * gdji;
+      if constexpr (HSPLIT) {
+        const double g1ij = A.GD1[(size_t)i * A.p + j], g1ji = A.GD1[(size_t)j * A.p + i];
+        wg1 = I == J ? sij * g1ij : sij * g1ij + sji * g1ji;
+      }
     }
     sd[t] = d;
     swk[t] = wk;
     swd[t] = wd;
-    if constexpr (BOTH) swd1[t] = wd1;
+    if constexpr (BOTH || HIGH) swd1[t] = wd1;
+    if constexpr (HSPLIT) swg1[t] = wg1;
   }
   __syncthreads();
   if (TR_FIRST) TR_HI(SLOT_PG_STAGED);
@@ -530,9 +554,10 @@ __global__ __launch_bounds__(256) void pgrad_kernel(PGradBatch b, int q,
       const double a = sa[c], om = so[c], oml = sol[c];
       for (int e = g; e < NP; e += 8) {
         const double wk = swk[e], wd = swd[e];
-        double wd1 = 0.0;
-        if constexpr (BOTH) wd1 = swd1[e];
-        if (wk == 0.0 && wd == 0.0 && wd1 == 0.0) continue;
+        double wd1 = 0.0, wg1 = 0.0;
+        if constexpr (BOTH || HIGH) wd1 = swd1[e];
+        if constexpr (HSPLIT) wg1 = swg1[e];
+        if (wk == 0.0 && wd == 0.0 && wd1 == 0.0 && wg1 == 0.0) continue;
         const double d = sd[e];
         if constexpr (DD) {
           dd::D fw, fl, ff, dw, dl, df;
@@ -540,6 +565,30 @@ __global__ __launch_bounds__(256) void pgrad_kernel(PGradBatch b, int q,
           xw = dd::add(xw, dd::add(dd::mul_d(fw, wk), dd::mul_d(dw, wd)));
           xl = dd::add(xl, dd::add(dd::mul_d(fl, wk), dd::mul_d(dl, wd)));
           xf = dd::add(xf, dd::add(dd::mul_d(ff, wk), dd::mul_d(df, wd)));
+          continue;
+        }
+        if constexpr (HIGH) {  // four orders from one exp / sincos set
+          double m[5], ml[5];
+          radial4_l<MATERN>(d, a, m, ml);
+          if (COS) {
+            double S, C;
+            phase_sincos(om, oml, d, S, C);
+            const double o2 = om * om, o3 = o2 * om, o4 = o2 * o2;
+            const double k[5] = {C, -om * S, -o2 * C, o3 * S, o4 * C};
+            const double kf[5] = {-TWO_PI * d * S, -TWO_PI * S - TWO_PI * om * d * C,
+                                  -2.0 * TWO_PI * om * C + TWO_PI * o2 * d * S,
+                                  TWO_PI * (3.0 * o2 * S + o3 * d * C), TWO_PI * (4.0 * o3 * C - o4 * d * S)};
+            double w4, w3, w2, w1, l4, l3, l2, l1, f4, f3, f2, f1;
+            high_fields(m, k, w4, w3, w2, w1);
+            high_fields(ml, k, l4, l3, l2, l1);
+            high_fields(m, kf, f4, f3, f2, f1);
+            accw += wk * (m[0] * k[0]) + wd * (A.c4 * w4 + A.c2 * w2) + wd1 * (A.c3 * w3 + A.c1 * w1) + wg1 * w1;
+            accl += wk * (ml[0] * k[0]) + wd * (A.c4 * l4 + A.c2 * l2) + wd1 * (A.c3 * l3 + A.c1 * l1) + wg1 * l1;
+            accf += wk * (m[0] * kf[0]) + wd * (A.c4 * f4 + A.c2 * f2) + wd1 * (A.c3 * f3 + A.c1 * f1) + wg1 * f1;
+          } else {
+            accw += wk * m[0] + wd * (A.c4 * m[4] + A.c2 * m[2]) + wd1 * (A.c3 * m[3] + A.c1 * m[1]) + wg1 * m[1];
+            accl += wk * ml[0] + wd * (A.c4 * ml[4] + A.c2 * ml[2]) + wd1 * (A.c3 * ml[3] + A.c1 * ml[1]) + wg1 * ml[1];
+          }
           continue;
         }
         double m0, m1, m2, m0l, m1l, m2l;
@@ -685,6 +734,12 @@ static void launch_pg_c(const PGradBatch& b, int naxes, int bpa, int q, int deri
   } else if (deriv == DERIV_SPLIT) {
     if constexpr (!CLS)
       hipLaunchKernelGGL((pgrad_kernel<MATERN, COS, DERIV_SPLIT, false, false>), grid, dim3(256), 0, s, b, q, sc);
+  } else if (deriv == DERIV_HIGH) {
+    if constexpr (!CLS)
+      hipLaunchKernelGGL((pgrad_kernel<MATERN, COS, DERIV_HIGH, false, false>), grid, dim3(256), 0, s, b, q, sc);
+  } else if (deriv == DERIV_HIGH_SPLIT) {
+    if constexpr (!CLS)
+      hipLaunchKernelGGL((pgrad_kernel<MATERN, COS, DERIV_HIGH_SPLIT, false, false>), grid, dim3(256), 0, s, b, q, sc);
   } else {
     hipLaunchKernelGGL((pgrad_kernel<MATERN, COS, 1, false, CLS>), grid, dim3(256), 0, s, b, q, sc);
   }
@@ -740,11 +795,11 @@ hipError_t launch_pgrad(int kind, int q, int mode1d, const PGradArgs* a, int nax
                           shard_n > 1))
     return hipErrorInvalidValue;
   int deriv = a[0].deriv;
-  // one mode per launch (DERIV_BOTH and DERIV_SPLIT carry their weights per axis): 2D per-pair
-  // contraction only; DERIV_SPLIT needs its second operand
+  // one mode per launch (the weighted modes, DERIV_BOTH to DERIV_HIGH_SPLIT, carry their weights per
+  // axis): 2D per-pair contraction only; DERIV_SPLIT and DERIV_HIGH_SPLIT need their second operand
   for (int k = 0; k < naxes; ++k)
-    if ((deriv_two_fields(deriv) && (a[k].deriv != deriv || a[k].cls.ncls > 0 || mode1d)) ||
-        (!deriv_two_fields(deriv) && deriv_two_fields(a[k].deriv)) || (a[k].deriv == DERIV_SPLIT && !a[k].GD1))
+    if ((deriv_weighted(deriv) && (a[k].deriv != deriv || a[k].cls.ncls > 0 || mode1d)) ||
+        (!deriv_weighted(deriv) && deriv_weighted(a[k].deriv)) || (deriv_stores_d1(a[k].deriv) && !a[k].GD1))
       return hipErrorInvalidValue;
   switch (kind) {
     case SE_COS: launch_pg_t<false, true>(b, naxes, blocks_per_axis, q, deriv, mode1d, sc, s); break;

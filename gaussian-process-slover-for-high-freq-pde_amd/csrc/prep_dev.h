@@ -80,6 +80,47 @@ __device__ __forceinline__ void eval_kd_part(double diff, const double* w, const
   D1 = dv1;
 }
 
+// The five-output form (DERIV_HIGH, DERIV_HIGH_SPLIT): K and the order-4, 3, 2 and 1 partial sums from
+// one radial_exp and one phase_sincos per component.  Order n adds w sum_m C(n, m) m_m c_{n-m} with
+// c_0..c_4 = C, -om S, -om^2 C, om^3 S, om^4 C; the order-2 and order-1 sums are the expressions of
+// the two-output form.  All unsigned: the caller applies s_ij to the odd orders.
+template <bool MATERN, bool COS>
+__device__ __forceinline__ void eval_kd_part(double diff, const double* w, const double* a,
+                                             const double* om, const double* oml, int c0, int cs,
+                                             int q, double& K, double& D4, double& D3, double& D2,
+                                             double& D1) {
+  double d = fabs(diff);
+  double k = 0.0, dv4 = 0.0, dv3 = 0.0, dv2 = 0.0, dv1 = 0.0;
+  for (int c = c0; c < q; c += cs) {
+    double m[5];
+    radial4<MATERN>(d, a[c], m);
+    const double m0 = m[0], m1 = m[1], m2 = m[2];
+    if (COS) {
+      double S, C;
+      phase_sincos(om[c], oml[c], d, S, C);
+      double o = om[c];
+      k += w[c] * (m0 * C);
+      dv2 += w[c] * (m2 * C - 2.0 * m1 * (o * S) - m0 * (o * o * C));
+      dv1 += w[c] * (m1 * C - m0 * (o * S));
+      const double o2 = o * o;
+      const double k1 = -o * S, k2 = -o2 * C, k3 = o2 * o * S, k4 = o2 * o2 * C;
+      dv3 += w[c] * (m[3] * C + 3.0 * m2 * k1 + 3.0 * m1 * k2 + m0 * k3);
+      dv4 += w[c] * (m[4] * C + 4.0 * m[3] * k1 + 6.0 * m2 * k2 + 4.0 * m1 * k3 + m0 * k4);
+    } else {
+      k += w[c] * m0;
+      dv2 += w[c] * m2;
+      dv1 += w[c] * m1;
+      dv3 += w[c] * m[3];
+      dv4 += w[c] * m[4];
+    }
+  }
+  K = k;
+  D4 = dv4;
+  D3 = dv3;
+  D2 = dv2;
+  D1 = dv1;
+}
+
 // K and the signed derivative field at one pair (cross_kernel, pairs_kernel, point_eval.hip): all
 // q components in order, the D_x1 sign applied.
 template <bool MATERN, bool COS, int DERIV>

@@ -578,6 +578,59 @@ def solution_3d_opb(equation):
     return _OPB3D[equation]()
 
 
+# Equations with third- and fourth-order terms on [0, 1]^3 (gpk_create3_oph): as EQUATIONS_3D_OPB's
+# entries, plus high = (c4, c3), the constants of c4_k d^4 u / dx_k^4 + c3_k d^3 u / dx_k^3.  The third
+# axis is time and the final-time face is open.
+_KDV_DELTA, _KS_NU, _BEAM_KAPPA, _BEAM_OM = 0.01, 0.02, 0.01, 2.0
+
+
+def _kdv_t_sin():
+    # u = e^{-t} sin(2x) sin(3y):  u_t + u u_x + delta u_xxx = -u + u u_x - 8 delta e^{-t} cos(2x) sin(3y)
+    u = lambda x, y, t: np.exp(-t) * s_(2 * x) * s_(3 * y)
+    grad = (lambda x, y, t: 2.0 * np.exp(-t) * c_(2 * x) * s_(3 * y),
+            lambda x, y, t: 3.0 * np.exp(-t) * s_(2 * x) * c_(3 * y),
+            lambda x, y, t: -u(x, y, t))
+    f = lambda x, y, t: (-u(x, y, t) + u(x, y, t) * grad[0](x, y, t)
+                         - 8.0 * _KDV_DELTA * np.exp(-t) * c_(2 * x) * s_(3 * y))
+    return u, f, Operator3X((0.0, 0.0, 0.0), (0.0, 0.0, 1.0), faces=NO_FINAL_FACE), 0, grad, (1.0, 0.0, 0.0), \
+        (0.0, 0.0, 0.0), (None, None, None), ((0.0, 0.0, 0.0), (_KDV_DELTA, 0.0, 0.0))
+
+
+def _ks_t_sin():
+    # the same u, Kuramoto-Sivashinsky axis-wise in x:  u_t + u u_x + u_xx + nu u_xxxx = (16 nu - 5) u + u u_x
+    u = lambda x, y, t: np.exp(-t) * s_(2 * x) * s_(3 * y)
+    grad = (lambda x, y, t: 2.0 * np.exp(-t) * c_(2 * x) * s_(3 * y),
+            lambda x, y, t: 3.0 * np.exp(-t) * s_(2 * x) * c_(3 * y),
+            lambda x, y, t: -u(x, y, t))
+    f = lambda x, y, t: (16.0 * _KS_NU - 5.0) * u(x, y, t) + u(x, y, t) * grad[0](x, y, t)
+    return u, f, Operator3X((1.0, 0.0, 0.0), (0.0, 0.0, 1.0), faces=NO_FINAL_FACE), 0, grad, (1.0, 0.0, 0.0), \
+        (0.0, 0.0, 0.0), (None, None, None), ((_KS_NU, 0.0, 0.0), (0.0, 0.0, 0.0))
+
+
+def _beam_t_sin():
+    # u = sin(2x) sin(3y) sin(om t + 1/2), the Euler-Bernoulli beam in x:  u_tt + kappa u_xxxx = (16 kappa - om^2) u;
+    # clamped ends: u and u_x on both x walls (faces 0, 1); u and u_t on the initial face (4)
+    om = _BEAM_OM
+    u = lambda x, y, t: s_(2 * x) * s_(3 * y) * s_(om * t + 0.5)
+    grad = (lambda x, y, t: 2.0 * c_(2 * x) * s_(3 * y) * s_(om * t + 0.5),
+            lambda x, y, t: 3.0 * s_(2 * x) * c_(3 * y) * s_(om * t + 0.5),
+            lambda x, y, t: om * s_(2 * x) * s_(3 * y) * c_(om * t + 0.5))
+    f = lambda x, y, t: (16.0 * _BEAM_KAPPA - om * om) * u(x, y, t)
+    return u, f, Operator3X((0.0, 0.0, 1.0), (0.0, 0.0, 0.0), faces=NO_FINAL_FACE), 0b010011, grad, \
+        (0.0, 0.0, 0.0), (0.0, 0.0, 0.0), (None, None, None), ((_BEAM_KAPPA, 0.0, 0.0), (0.0, 0.0, 0.0))
+
+
+_OPH3D = {"kdv_t-sin": _kdv_t_sin, "ks_t-sin": _ks_t_sin, "beam_t-sin": _beam_t_sin}
+EQUATIONS_3D_OPH = list(_OPH3D)
+
+
+def solution_3d_oph(equation):
+    """(u, src, operator, dfaces, grad_u, conv, cross, drift, high) of an EQUATIONS_3D_OPH entry: the
+    first eight as solution_3d_opb's, high = (c4, c3), two triples: the constants of the terms c4_k
+    d^4 u / dx_k^4 + c3_k d^3 u / dx_k^3."""
+    return _OPH3D[equation]()
+
+
 def boundary_2d(u_mesh):
     """get_boundary_vals: hstack(U[0,:], U[-1,:], U[:,0], U[:,-1]) (model_GP_solver_2d.py:377-379)."""
     return np.hstack((u_mesh[0, :], u_mesh[-1, :], u_mesh[:, 0], u_mesh[:, -1]))

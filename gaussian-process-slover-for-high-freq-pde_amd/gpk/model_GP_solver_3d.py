@@ -36,7 +36,9 @@ Mixed partials m_jk d^2u/dx_j dx_k (anisotropic diffusion with off-diagonal entr
 gpk_create3_opm: `-equation=aniso_heat_t-sin`, configs in gpk/config3d_opm/.  Drift fields
 b_k(x) du/dx_k (divergence form -div(a grad u), a variable velocity over a constant viscosity) run
 through gpk_create3_opb: DeviceSolver3(..., drift=), `-equation=heat_div_t-sin`, configs in
-gpk/config3d_opb/.
+gpk/config3d_opb/.  Third- and fourth-order terms c4_k d^4u/dx_k^4 + c3_k d^3u/dx_k^3 (KdV,
+Kuramoto-Sivashinsky, the clamped beam) run through gpk_create3_oph: DeviceSolver3(..., high=(c4, c3)),
+`-equation=kdv_t-sin`, configs in gpk/config3d_oph/.
 """
 import ctypes
 import os
@@ -50,10 +52,11 @@ from . import _lib, init_func, replicas, utils
 from ._lib import check, dptr, f64
 from .cli import parse_flags
 from .core import tree_flatten, tree_unflatten
-from .equations import (EQUATIONS_3D, EQUATIONS_3D_OP, EQUATIONS_3D_OPB, EQUATIONS_3D_OPC, EQUATIONS_3D_OPM,
+from .equations import (EQUATIONS_3D, EQUATIONS_3D_OP, EQUATIONS_3D_OPB, EQUATIONS_3D_OPC, EQUATIONS_3D_OPH,
+                        EQUATIONS_3D_OPM,
                         EQUATIONS_3D_OPN, EQUATIONS_3D_OPV, EQUATIONS_3D_OPX, Operator3, Operator3V, Operator3X,
                         deriv_boundary_3d, drift_fields, solution_3d, solution_3d_op, solution_3d_opb,
-                        solution_3d_opc, solution_3d_opm, solution_3d_opn, solution_3d_opv, solution_3d_opx)
+                        solution_3d_opc, solution_3d_oph, solution_3d_opm, solution_3d_opn, solution_3d_opv, solution_3d_opx)
 from .infras.exp_config import ExpConfig
 from .kernel_matrix import kernel_class
 from .solver_common import SolverBase
@@ -86,7 +89,7 @@ class DeviceSolver3:
 
     def __init__(self, eq, kind, xs, src, bvals, Q=30, jitter=1e-6, llk_weight=200.0, logdet=True,
                  lr=0.01, freq_scale=20.0, device=0, b1=0.9, b2=0.999, eps=1e-8, refine=False,
-                 operator=None, dfaces=0, dvals=None, conv=None, cross=None, drift=None):
+                 operator=None, dfaces=0, dvals=None, conv=None, cross=None, drift=None, high=None):
         """refine: one gated refinement step after every solve of the step (GPK_FLAG3_REFINE);
         'gemm' also forces its two-GEMM route (GPK_FLAG3_REFINE_GEMM; tests, A/B).
         operator: an Operator3 (or a dict of its fields) -- the handle then solves that operator
@@ -108,7 +111,11 @@ class DeviceSolver3:
         (gpk_create3_opb): each None, an array of the grid's shape or a callable of the three
         coordinate meshes, as Operator3V.a; the operator's fields a_k do not multiply them.  A
         non-None entry needs an Operator3X or Operator3V as conv does.  None or three Nones is the
-        handle without them."""
+        handle without them.
+        high: (c4, c3), two triples of floats, the constants of the terms c4_k d^4 u / dx_k^4 + c3_k
+        d^3 u / dx_k^3 (gpk_create3_oph; KdV, Kuramoto-Sivashinsky, the beam); a non-zero one needs
+        an Operator3X or Operator3V as conv does, and an Operator3V's field a_k multiplies all four
+        orders of its axis.  None or six zeros is the handle without them."""
         lib = _lib.load()
         if len(xs) != 3:
             raise ValueError("three coordinate axes")
@@ -154,7 +161,15 @@ class DeviceSolver3:
                 raise ValueError("drift has three entries (b_1, b_2, b_3; None for an axis without a field)")
             if all(b is None for b in drift):
                 drift = None
-        if dfaces or conv or cross or drift:
+        if high is not None:
+            if len(high) != 2:
+                raise ValueError("high has two entries (c4, c3), each a triple")
+            high = tuple(tuple(float(c) for c in np.asarray(t, np.float64).reshape(-1)) for t in high)
+            if len(high[0]) != 3 or len(high[1]) != 3:
+                raise ValueError("high has two entries (c4, c3), each a triple")
+            if not any(c != 0.0 for t in high for c in t):
+                high = None
+        if dfaces or conv or cross or drift or high:
             if dfaces and dvals is None:
                 raise ValueError("dfaces needs dvals (the six-face layout of bvals)")
             if dfaces:
@@ -164,7 +179,8 @@ class DeviceSolver3:
             if not (isinstance(operator, (Operator3X, Operator3V)) or (isinstance(operator, dict) and "c2" in operator)):
                 raise ValueError("%s needs an Operator3X or Operator3V"
                                  % ("derivative boundary data" if dfaces else "a convective term" if conv
-                                    else "a mixed partial" if cross else "a drift field"))
+                                    else "a mixed partial" if cross else "a drift field" if drift
+                                    else "a high-order term"))
             c = _lib.gpk_operator3x()
             cf = _lib.gpk_coef3()
             if isinstance(operator, Operator3V):
@@ -181,7 +197,19 @@ class DeviceSolver3:
             bd = _lib.gpk_bdata3()
             if dfaces:
                 bd.dfaces, bd.dvals = dfaces, dptr(self._dvals)
-            if drift:
+            if high:
+                cv, mx, dr, hi = _lib.gpk_conv3(), _lib.gpk_cross3(), _lib.gpk_drift3(), _lib.gpk_high3()
+                cv.g[:] = conv or (0.0, 0.0, 0.0)
+                mx.m[:] = cross or (0.0, 0.0, 0.0)
+                self._drift = drift_fields(drift, self._x) if drift else (None, None, None)
+                for k, b in enumerate(self._drift):
+                    if b is not None:
+                        dr.b[k] = dptr(b)
+                hi.c4[:], hi.c3[:] = high
+                check(lib.gpk_create3_oph(ctypes.byref(p), ctypes.byref(c), ctypes.byref(cf), ctypes.byref(bd),
+                                          ctypes.byref(cv), ctypes.byref(mx), ctypes.byref(dr), ctypes.byref(hi),
+                                          float(freq_scale), ctypes.byref(h)))
+            elif drift:
                 cv, mx, dr = _lib.gpk_conv3(), _lib.gpk_cross3(), _lib.gpk_drift3()
                 cv.g[:] = conv or (0.0, 0.0, 0.0)
                 mx.m[:] = cross or (0.0, 0.0, 0.0)
@@ -394,6 +422,13 @@ class DeviceSolver3:
         check(_lib.load().gpk_cross_info3(self._h, dptr(m)))
         return tuple(m.tolist())
 
+    def high_info(self):
+        """(c4, c3), two triples (gpk_high_info3); zeros on every handle made without high-order
+        terms."""
+        c4, c3 = np.zeros(3), np.zeros(3)
+        check(_lib.load().gpk_high_info3(self._h, dptr(c4), dptr(c3)))
+        return tuple(float(c) for c in c4), tuple(float(c) for c in c3)
+
     def drift_info(self):
         """(b_1, b_2, b_3) present, as bools (gpk_drift_info3); all False on every handle made
         without a drift field."""
@@ -440,12 +475,14 @@ class GP_solver_3d_single(SolverBase):
     opc_eq_types = tuple(sorted({e.split("-")[0] for e in EQUATIONS_3D_OPC}))
     opm_eq_types = tuple(sorted({e.split("-")[0] for e in EQUATIONS_3D_OPM}))
     opb_eq_types = tuple(sorted({e.split("-")[0] for e in EQUATIONS_3D_OPB}))
+    oph_eq_types = tuple(sorted({e.split("-")[0] for e in EQUATIONS_3D_OPH}))
     early_stop_enabled = True
 
     def __init__(self, bvals, X_col, src_vals, jitter, trick_paras, device=0, X_test=None, u_test=None):
         self.eq_type = trick_paras["equation"].split("-")[0]
         assert self.eq_type in (self.eq_types + self.op_eq_types + self.opx_eq_types + self.opv_eq_types
-                                + self.opn_eq_types + self.opc_eq_types + self.opm_eq_types + self.opb_eq_types)
+                                + self.opn_eq_types + self.opc_eq_types + self.opm_eq_types + self.opb_eq_types
+                                + self.oph_eq_types)
         self.operator = None
         given = trick_paras.get("operator")
         if isinstance(given, Operator3V):
@@ -471,8 +508,22 @@ class GP_solver_3d_single(SolverBase):
         # drift fields: given, or the equation's own (likewise; callables, evaluated on each mesh)
         drift = trick_paras.get("drift")
         self.drift = None if drift is None else tuple(drift)
-        if self.eq_type in self.opn_eq_types + self.opc_eq_types + self.opm_eq_types + self.opb_eq_types:
-            if self.eq_type in self.opb_eq_types:
+        # high-order terms: given as (c4, c3), or the equation's own (likewise)
+        high = trick_paras.get("high")
+        self.high = None if high is None else tuple(tuple(float(c) for c in t) for t in high)
+        if self.eq_type in (self.opn_eq_types + self.opc_eq_types + self.opm_eq_types + self.opb_eq_types
+                            + self.oph_eq_types):
+            if self.eq_type in self.oph_eq_types:
+                _, _, op, dfaces, grad_u, conv, cross, drift, high = solution_3d_oph(trick_paras["equation"])
+                if self.conv is None:
+                    self.conv = tuple(conv)
+                if self.cross is None:
+                    self.cross = tuple(cross)
+                if self.drift is None:
+                    self.drift = tuple(drift)
+                if self.high is None:
+                    self.high = tuple(tuple(t) for t in high)
+            elif self.eq_type in self.opb_eq_types:
                 _, _, op, dfaces, grad_u, conv, cross, drift = solution_3d_opb(trick_paras["equation"])
                 if self.conv is None:
                     self.conv = tuple(conv)
@@ -521,7 +572,7 @@ class GP_solver_3d_single(SolverBase):
                                  freq_scale=tp.get("freq_scale", 20.0), device=int(tp.get("device", device)),
                                  refine=bool(tp.get("refine", False)), operator=self.operator,
                                  dfaces=self.dfaces, dvals=self.dvals, conv=self.conv, cross=self.cross,
-                                 drift=self.drift)
+                                 drift=self.drift, high=self.high)
         self._version = 0
 
     def eq_residual(self, params, X_test, src_test):
@@ -532,6 +583,9 @@ class GP_solver_3d_single(SolverBase):
         op = self.operator
         if op is None:
             return SolverBase.eq_residual(self, params, X_test, src_test)
+        if self.high is not None and any(c != 0.0 for t in self.high for c in t):
+            raise ValueError("eq_residual: a handle with third- or fourth-order terms needs derivatives above 2 "
+                             "on the test mesh, which predict_deriv does not form")
         self._sync(params)
         axes = self._test_axes(X_test)
         r = np.zeros(tuple(a.size for a in axes))
@@ -679,6 +733,8 @@ def test(trick_paras, solver_cls=None):
         u, src, op = solution_3d_opm(trick_paras["equation"])[:3]
     elif trick_paras["equation"] in EQUATIONS_3D_OPB:  # (... and its drift fields)
         u, src, op = solution_3d_opb(trick_paras["equation"])[:3]
+    elif trick_paras["equation"] in EQUATIONS_3D_OPH:  # (... and its high-order weights)
+        u, src, op = solution_3d_oph(trick_paras["equation"])[:3]
     else:
         u, src = solution_3d(trick_paras["equation"])
     scale = trick_paras["scale"]
@@ -717,12 +773,13 @@ def load_config(equation):
     """./config3d/<equation>.yaml (the operator equations: ./config3d_op/, the mixed-order ones:
     ./config3d_opx/, the coefficient-field ones: ./config3d_opv/, derivative boundary data:
     ./config3d_opn/, convective terms: ./config3d_opc/, mixed partials: ./config3d_opm/, drift fields:
-    ./config3d_opb/), falling back to the package's copy."""
+    ./config3d_opb/, third- and fourth-order terms: ./config3d_oph/), falling back to the package's copy."""
     cdir = ("config3d_op" if equation in EQUATIONS_3D_OP else "config3d_opx" if equation in EQUATIONS_3D_OPX
             else "config3d_opv" if equation in EQUATIONS_3D_OPV else "config3d_opn" if equation in EQUATIONS_3D_OPN
             else "config3d_opc" if equation in EQUATIONS_3D_OPC
             else "config3d_opm" if equation in EQUATIONS_3D_OPM
-            else "config3d_opb" if equation in EQUATIONS_3D_OPB else "config3d")
+            else "config3d_opb" if equation in EQUATIONS_3D_OPB
+            else "config3d_oph" if equation in EQUATIONS_3D_OPH else "config3d")
     for base in (os.getcwd(), os.path.dirname(os.path.abspath(__file__))):
         p = os.path.join(base, cdir, equation + ".yaml")
         if os.path.exists(p):
@@ -732,7 +789,7 @@ def load_config(equation):
 
 
 def build_config(args, allowed=EQUATIONS_3D + EQUATIONS_3D_OP + EQUATIONS_3D_OPX + EQUATIONS_3D_OPV
-                 + EQUATIONS_3D_OPN + EQUATIONS_3D_OPC + EQUATIONS_3D_OPM + EQUATIONS_3D_OPB):
+                 + EQUATIONS_3D_OPN + EQUATIONS_3D_OPC + EQUATIONS_3D_OPM + EQUATIONS_3D_OPB + EQUATIONS_3D_OPH):
     """The 2-axis build_config (scale, kernel class, other_paras) on the config3d files."""
     assert args.equation in allowed
     config = load_config(args.equation)

@@ -710,6 +710,45 @@ int gpk_create3_opb(const gpk_problem3* p, const gpk_operator3x* op, const gpk_c
 /* has[k]: axis k has a drift field; zeros on every older kind of 3-axis handle. */
 int gpk_drift_info3(const gpk_handle3* h, int32_t has[3]);
 
+/* Third- and fourth-order terms (KdV u_t + u u_x + delta u_xxx; Kuramoto-Sivashinsky u_t + u u_x +
+ * u_xx + nu u_xxxx axis-wise; the Euler-Bernoulli beam u_tt + kappa u_xxxx with clamped ends; the
+ * linear part of Cahn-Hilliard).  Axis k adds
+ *     c4_k d^4 u / d x_k^4 + c3_k d^3 u / d x_k^3
+ * to the linear operator of a gpk_create3_opb handle: the assembled block of that axis becomes
+ *     D_k = c4_k D4_k + c3_k D3_k + c2_k DD_k + c1_k D1_k,
+ * Dn_k[i][j] the n-th derivative in the first argument of kappa_k at (x_i, x_j): per mixture
+ * component sum_m C(n, m) m_m(d) c_{n-m}(d) with c_0..c_4 = C, -om S, -om^2 C, om^3 S, om^4 C and the
+ * radial derivatives m_3, m_4 in closed form.  Odd orders carry the sign s_ij of x_i - x_j (s = +1
+ * at 0; their diagonal is exactly 0), even orders are symmetric.  Such an axis is entered like a
+ * mixed-order one: every product with its D_k has GEMM weight exactly 1.0.  The gpk_coef3 field a_k
+ * multiplies the whole term of its axis, all four orders.  Convective terms, cross pairs, drift
+ * terms and derivative face data on the same axis keep using the plain order-1 block D1_k.  Nothing
+ * else in the log joint changes: the boundary and derivative-boundary terms, gpk_criterion3,
+ * gpk_loss_terms3 and gpk_boundary_terms3 keep their formulas; the stage list, the refinement and the
+ * face kernels are those of the same handle without the high-order weights.
+ * ORDER 4 IS THE CEILING: the Matern-5/2 radial factor has a continuous fourth derivative with a
+ * kink at d = 0 and no fifth derivative, and both kernel families stop there.
+ * Not built: orders above four; mixed high-order partials such as u_xxyy (the true biharmonic and
+ * 2-D Kuramoto-Sivashinsky need them; a follow-up that reuses the cross-pair stages with order-2
+ * blocks); boundary data on second derivatives (simply supported ends); the sharded, 1-axis and
+ * 2-axis handles; the class path; derivatives above 2 in gpk_predict_deriv3 and gpk_evaluate3, which
+ * keep rejecting 3. */
+typedef struct gpk_high3 {
+  double c4[3]; /* weight of d^4 u / d x_k^4 */
+  double c3[3]; /* weight of d^3 u / d x_k^3 */
+} gpk_high3;
+/* p, op, cf, bd, cv, mx and dr as on gpk_create3_opb (cf, bd, cv, mx and dr may be NULL).  hi == NULL
+ * or all six weights 0.0 is gpk_create3_opb(p, op, cf, bd, cv, mx, dr, ...) itself: the same stage
+ * list, launches and bits.  GPK_EINVAL, before any device work, on a non-finite weight, and on
+ * everything the older create calls reject. */
+int gpk_create3_oph(const gpk_problem3* p, const gpk_operator3x* op, const gpk_coef3* cf,
+                    const gpk_bdata3* bd, const gpk_conv3* cv, const gpk_cross3* mx, const gpk_drift3* dr,
+                    const gpk_high3* hi, double freq_scale, gpk_handle3** out);
+/* The high-order weights; zeros on every older kind of 3-axis handle.  gpk_operator_info3x keeps
+ * reporting c2 and c1; gpk_operator_info3 returns GPK_EINVAL on a handle with a high-order axis, as
+ * it does for a mixed axis. */
+int gpk_high_info3(const gpk_handle3* h, double c4[3], double c3[3]);
+
 int gpk_num_params3(const gpk_handle3* h, int64_t* n);
 int gpk_set_params3(gpk_handle3* h, const double* flat, int64_t n);
 int gpk_get_params3(gpk_handle3* h, double* flat, int64_t n);
@@ -818,6 +857,16 @@ int gpk_assemble_pairs_time(int32_t kind, const double* x, int32_t n, const doub
 int gpk_assemble_pairs2(int32_t kind, const double* x, int32_t n, const double* logw, const double* logls,
                         const double* freq, int32_t q, double jitter, double c2, double c1,
                         double* K_out, double* D_out, double* D1_out);
+
+/* The high-order modes of the same kernel, which an axis with c4_k or c3_k non-zero (gpk_create3_oph)
+ * assembles in: K_out and D_out = c4 D4 + c3 D3 + c2 DD_x1_kappa + c1 D_x1_kappa at any weights
+ * (zeros included; D4, D3 the fourth and the signed third derivative in the first argument), each
+ * n x n row-major.  D1_out == NULL: the plain mode; otherwise the two-block mode, which also stores
+ * D1_out = D_x1_kappa alone.  At c4 = c3 = 0 the blocks are gpk_assemble_pairs2's, bit for bit.
+ * 1 <= n <= 1024, 1 <= q <= 64, weights and jitter finite. */
+int gpk_assemble_pairs4(int32_t kind, const double* x, int32_t n, const double* logw, const double* logls,
+                        const double* freq, int32_t q, double jitter, double c4, double c3, double c2,
+                        double c1, double* K_out, double* D_out, double* D1_out);
 
 #ifdef __cplusplus
 }
