@@ -86,7 +86,8 @@ __global__ __launch_bounds__(256) void assemble_kernel(AssembleBatch b, int q) {
   constexpr bool BOTH = deriv_two_fields(DERIV);  // pd: the order-2 field, pd1: the order-1 field
   constexpr bool SPLIT = DERIV == DERIV_SPLIT;    // ... and the order-1 block stored on its own
   constexpr bool HIGH = deriv_high(DERIV);        // pd: order 2, pd1: order 1, pd3, pd4: orders 3 and 4
-  constexpr bool HSPLIT = DERIV == DERIV_HIGH_SPLIT;  // ... and the order-1 block stored on its own
+  constexpr bool HSPLIT = DERIV == DERIV_HIGH_SPLIT || DERIV == DERIV_HIGH_SPLIT_D2;  // ... and the order-1 block stored on its own
+  constexpr bool HD2 = deriv_stores_d2(DERIV);        // ... and the order-2 block stored on its own
   __shared__ double pd1[BOTH || HIGH ? 4 : 1][64];    // (no reference in the other modes: not allocated)
   __shared__ double pd3[HIGH ? 4 : 1][64], pd4[HIGH ? 4 : 1][64];
   if (t < q) axis_component(b.prep, axis, q, t, sw[t], sa[t], so[t], sol[t]);
@@ -147,6 +148,7 @@ __global__ __launch_bounds__(256) void assemble_kernel(AssembleBatch b, int q) {
   if constexpr (HIGH)
     A.D[(size_t)i * A.p + j] = real ? (A.c2 * dv + A.c1 * (s_ij * dv1)) + (A.c4 * dv4 + A.c3 * (s_ij * dv3)) : 0.0;
   if constexpr (HSPLIT) A.D1[(size_t)i * A.p + j] = real ? s_ij * dv1 : 0.0;
+  if constexpr (HD2) A.D2[(size_t)i * A.p + j] = dv;  // (dv = 0 on a pad)
   if (I != J) {
     A.K[(size_t)j * A.p + i] = kv;
     if (A.Kc) A.Kc[(size_t)j * A.p + i] = kv;
@@ -157,6 +159,7 @@ __global__ __launch_bounds__(256) void assemble_kernel(AssembleBatch b, int q) {
     if constexpr (HIGH)
       A.D[(size_t)j * A.p + i] = real ? (A.c2 * dv + A.c1 * (s_ji * dv1)) + (A.c4 * dv4 + A.c3 * (s_ji * dv3)) : 0.0;
     if constexpr (HSPLIT) A.D1[(size_t)j * A.p + i] = real ? s_ji * dv1 : 0.0;
+    if constexpr (HD2) A.D2[(size_t)j * A.p + i] = dv;
   }
   if (tile == 0 && b.pivot_x >= 0) {  // release this sub-block of tile (0,0) to pivot0
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // (only wave 0 stored)
@@ -521,6 +524,10 @@ static void launch_assemble_t(const AssembleBatch& b, int naxes, int maxt, int q
     hipLaunchKernelGGL((assemble_kernel<MATERN, COS, DERIV_HIGH>), grid, dim3(256), 0, s, b, q);
   else if (deriv == DERIV_HIGH_SPLIT)
     hipLaunchKernelGGL((assemble_kernel<MATERN, COS, DERIV_HIGH_SPLIT>), grid, dim3(256), 0, s, b, q);
+  else if (deriv == DERIV_HIGH_D2)
+    hipLaunchKernelGGL((assemble_kernel<MATERN, COS, DERIV_HIGH_D2>), grid, dim3(256), 0, s, b, q);
+  else if (deriv == DERIV_HIGH_SPLIT_D2)
+    hipLaunchKernelGGL((assemble_kernel<MATERN, COS, DERIV_HIGH_SPLIT_D2>), grid, dim3(256), 0, s, b, q);
   else
     hipLaunchKernelGGL((assemble_kernel<MATERN, COS, 0>), grid, dim3(256), 0, s, b, q);
 }
@@ -541,12 +548,13 @@ hipError_t launch_assemble(int kind, int q, const AssembleArgs* a, int naxes, co
         (a[k].cls.ncls > 0) != (a[0].cls.ncls > 0))
       return hipErrorInvalidValue;
   int deriv = a[0].deriv;
-  // one mode per launch (the weighted modes, DERIV_BOTH to DERIV_HIGH_SPLIT, carry their weights per
-  // axis); the class path stores one dval per class, so it has none of them; DERIV_SPLIT and
-  // DERIV_HIGH_SPLIT need their second block
+  // one mode per launch (the weighted modes, DERIV_BOTH to DERIV_HIGH_SPLIT_D2, carry their weights per
+  // axis); the class path stores one dval per class, so it has none of them; the modes that store D1
+  // or DD on their own need that block
   for (int k = 0; k < naxes; ++k)
     if ((deriv_weighted(deriv) && (a[k].deriv != deriv || a[k].cls.ncls > 0)) ||
-        (!deriv_weighted(deriv) && deriv_weighted(a[k].deriv)) || (deriv_stores_d1(a[k].deriv) && !a[k].D1))
+        (!deriv_weighted(deriv) && deriv_weighted(a[k].deriv)) || (deriv_stores_d1(a[k].deriv) && !a[k].D1) ||
+        (deriv_stores_d2(a[k].deriv) && !a[k].D2))
       return hipErrorInvalidValue;
   if (a[0].cls.ncls > 0) {  // class path: every 32x32 tile of the full matrix, one per workgroup
     int maxc = 0, maxtiles = 0;

@@ -1128,6 +1128,48 @@ int gpk_assemble_pairs4(int32_t kind, const double* x, int32_t n, const double* 
   return check_launch(e, "gpk_assemble_pairs4");
 }
 
+// The bi-pair modes (DERIV_HIGH_D2; DERIV_HIGH_SPLIT_D2 when D1_out is given): gpk_assemble_pairs5's
+// blocks and the plain order-2 block D2
+int gpk_assemble_pairs5(int32_t kind, const double* x, int32_t n, const double* logw, const double* logls,
+                        const double* freq, int32_t q, double jitter, double c4, double c3, double c2,
+                        double c1, double* K_out, double* D_out, double* D1_out, double* D2_out) {
+  if (kind < 0 || kind > 3) return fail(GPK_EINVAL, "Invalid Kernel");
+  if (n < 1 || n > K3_MAX_N || q <= 0 || q > QMAX)
+    return fail(GPK_EINVAL, "gpk_assemble_pairs5: bad sizes (1 <= n <= 1024, 0 < q <= 64)");
+  if (!x || !logw || !logls || !freq || !K_out || !D_out || !D2_out)
+    return fail(GPK_EINVAL, "gpk_assemble_pairs5: NULL pointer argument");
+  if (!std::isfinite(c4) || !std::isfinite(c3) || !std::isfinite(c2) || !std::isfinite(c1) || !std::isfinite(jitter))
+    return fail(GPK_EINVAL, "gpk_assemble_pairs5: c4, c3, c2, c1 and jitter must be finite");
+  TRY(check_device(0));
+  DevSwitch dsw(0);
+  const int P = pad_up(n);
+  std::vector<double> kp(3 * (size_t)q);  // flat params laid out (freq, log-ls, log-w)
+  std::copy(freq, freq + q, kp.begin());
+  std::copy(logls, logls + q, kp.begin() + q);
+  std::copy(logw, logw + q, kp.begin() + 2 * q);
+  CallScratch tmp("gpk_assemble_pairs5");
+  double *dx = nullptr, *dkp = nullptr, *dK = nullptr, *dD = nullptr, *dD1 = nullptr, *dD2 = nullptr;
+  TRY(tmp.alloc(&dx, (size_t)P, true));
+  TRY(check_launch(hipMemcpy(dx, x, (size_t)n * sizeof(double), hipMemcpyHostToDevice), "gpk_assemble_pairs5"));
+  TRY(tmp.upload(&dkp, kp.data(), kp.size()));
+  TRY(tmp.alloc(&dK, (size_t)P * P, true));
+  TRY(tmp.alloc(&dD, (size_t)P * P, true));
+  if (D1_out) TRY(tmp.alloc(&dD1, (size_t)P * P, true));
+  TRY(tmp.alloc(&dD2, (size_t)P * P, true));
+  AssembleArgs aa{};
+  aa.x = dx; aa.n = n; aa.p = P; aa.jitter = jitter; aa.K = dK; aa.D = dD; aa.D1 = dD1; aa.D2 = dD2;
+  aa.deriv = D1_out ? DERIV_HIGH_SPLIT_D2 : DERIV_HIGH_D2;
+  aa.c4 = c4; aa.c3 = c3; aa.c2 = c2; aa.c1 = c1;
+  PrepArgs prep{};
+  prep.params = dkp; prep.naxes = 1; prep.skip = 1;  // (no step constants to publish)
+  hipError_t e = launch_assemble(kind, q, &aa, 1, prep, 0);
+  if (e == hipSuccess) e = hipDeviceSynchronize();
+  const size_t row = (size_t)n * sizeof(double);
+  for (auto [dst, src] : {std::pair<double*, double*>{K_out, dK}, {D_out, dD}, {D1_out, dD1}, {D2_out, dD2}})
+    if (e == hipSuccess && dst) e = hipMemcpy2D(dst, row, src, (size_t)P * sizeof(double), row, n, hipMemcpyDeviceToHost);
+  return check_launch(e, "gpk_assemble_pairs5");
+}
+
 int gpk_assemble_pairs_time(int32_t kind, const double* x, int32_t n, const double* logw, const double* logls,
                             const double* freq, int32_t q, double c2, double c1, int32_t split,
                             int32_t iters, double* avg_us) {

@@ -260,11 +260,19 @@ __host__ __device__ constexpr bool deriv_two_fields(int deriv) { return deriv ==
 // block D1 next to D (as DERIV_SPLIT does).  2D per-pair path only, like DERIV_BOTH.
 constexpr int DERIV_HIGH = 5;
 constexpr int DERIV_HIGH_SPLIT = 6;
-__host__ __device__ constexpr bool deriv_high(int deriv) { return deriv == DERIV_HIGH || deriv == DERIV_HIGH_SPLIT; }
+// Bi-pair axes (gpk_create3_opq): DERIV_HIGH / DERIV_HIGH_SPLIT with the plain order-2 block DD stored
+// next to D (D2; its dL/dDD, GD2, joins the contraction).  D, D1 and K are those modes' own expressions.
+constexpr int DERIV_HIGH_D2 = 7;
+constexpr int DERIV_HIGH_SPLIT_D2 = 8;
+__host__ __device__ constexpr bool deriv_high(int deriv) { return deriv >= DERIV_HIGH && deriv <= DERIV_HIGH_SPLIT_D2; }
 // modes that carry their weights per axis (one mode per launch, per-pair path only)
 __host__ __device__ constexpr bool deriv_weighted(int deriv) { return deriv_two_fields(deriv) || deriv_high(deriv); }
 // modes that store the order-1 block D1 on its own (and contract its dL/dD1)
-__host__ __device__ constexpr bool deriv_stores_d1(int deriv) { return deriv == DERIV_SPLIT || deriv == DERIV_HIGH_SPLIT; }
+__host__ __device__ constexpr bool deriv_stores_d1(int deriv) {
+  return deriv == DERIV_SPLIT || deriv == DERIV_HIGH_SPLIT || deriv == DERIV_HIGH_SPLIT_D2;
+}
+// modes that store the plain order-2 block DD on its own (and contract its dL/dDD)
+__host__ __device__ constexpr bool deriv_stores_d2(int deriv) { return deriv == DERIV_HIGH_D2 || deriv == DERIV_HIGH_SPLIT_D2; }
 
 struct AssembleArgs {
   const double* x;       // coords [n] (padded buffer ok)
@@ -279,6 +287,7 @@ struct AssembleArgs {
   double c2, c1;         // DERIV_BOTH / DERIV_SPLIT: D = c2 DD + c1 D1 (read in those modes only)
   double* D1;            // [p*p]  DERIV_SPLIT / DERIV_HIGH_SPLIT: the order-1 block alone (null in every other mode)
   double c4, c3;         // DERIV_HIGH / DERIV_HIGH_SPLIT: D = c4 D4 + c3 D3 + c2 DD + c1 D1 (read in those modes only)
+  double* D2;            // [p*p]  DERIV_HIGH_D2 / DERIV_HIGH_SPLIT_D2: the order-2 block alone (null in every other mode)
   // pivot block 0 of the SPD inverse, factored by one extra workgroup of the assembly launch
   // (nullable piv: not fused).  Same outputs as the sweep's pivot_init.
   double* piv; double* ldet; double* pst; int* status;
@@ -627,6 +636,7 @@ struct PGradArgs {
   double c2, c1;                          // DERIV_BOTH / DERIV_SPLIT: G_D weighs c2 dDD + c1 dD1 (read in those modes only)
   const double* GD1;                      // DERIV_SPLIT / DERIV_HIGH_SPLIT: dL/dD1 of the order-1 block alone [p*p] (null elsewhere)
   double c4, c3;                          // DERIV_HIGH / DERIV_HIGH_SPLIT: G_D weighs c4 dD4 + c3 dD3 + c2 dDD + c1 dD1
+  const double* GD2;                      // DERIV_HIGH_D2 / DERIV_HIGH_SPLIT_D2: dL/dDD of the order-2 block alone [p*p] (null elsewhere)
   double* part;                           // [nblocks * 3*QMAX]
   // DD (class path, 2D, fused tail): the derivative fields and every sum after them in
   // double-double; part holds the partials' high parts, part_lo their low parts (null: fp64)

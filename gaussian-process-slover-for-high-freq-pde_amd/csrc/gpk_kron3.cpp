@@ -38,11 +38,18 @@
 // C_jk = m_jk D1_k x_k H_jk and R += C_13 + C_12 + C_23 (k3_combine_m).  The reverse pass forms
 // Hb_jk = m_jk D1_k^T x_k R, Zb_jk = K_k^{-1} x_k Hb_jk (a solve), T_j += D1_j^T x_j Zb_jk before
 // X_j, G_D1j += v Zb_jk,(j) A_j,(j)^T, G_D1k += v m_jk R_(k) H_jk,(k)^T and G_Kk -= v Zb_jk,(k)
-// H_jk,(k)^T: eight further launches (build_cross_stages).
+// H_jk,(k)^T: eight further launches (build_pair_stages).
 // High-order terms (gpk_create3_oph, c4_k d^4u/dx_k^4 + c3_k d^3u/dx_k^3): the axis's block is D_k =
 // c4_k D4_k + c3_k D3_k + c2_k DD_k + c1_k D1_k, assembled and contracted in DERIV_HIGH (DERIV_HIGH_SPLIT
 // where the axis also owns D1_k: convective, cross, drift).  The host treats D_k as opaque: the stage
 // list, the refinement and the face kernels are untouched.
+// Mixed fourth-order partials (gpk_create3_opq, q_jk d^4u/dx_j^2 dx_k^2, j < k): both axes of a pair
+// assemble in DERIV_HIGH_D2 (DERIV_HIGH_SPLIT_D2 where the axis owns D1_k), which stores the plain
+// order-2 block DD_k next to D_k.  The pair is the cross pair with DD for D1: Z2_j = DD_j x_j A_j, H2_jk =
+// K_k^{-1} x_k Z2_j, B_jk = q_jk DD_k x_k H2_jk, R += B_13 + B_12 + B_23 after every older term
+// (k3_combine_q); Hb2_jk = q_jk DD_k^T x_k R, Zb2_jk = K_k^{-1} x_k Hb2_jk, T_j += DD_j^T x_j Zb2_jk,
+// G_DDj += v Zb2_jk,(j) A_j,(j)^T, G_DDk += v q_jk R_(k) H2_jk,(k)^T, G_Kk -= v Zb2_jk,(k) H2_jk,(k)^T:
+// eight further launches from the same builder (build_pair_stages), each after the cross pairs' own.
 // Drift fields (gpk_create3_opb, b_k(x) du/dx_k): a drift axis assembles in DERIV_SPLIT; Z_k = D1_k
 // x_k A_k (a cross pair's own Z_1 / Z_2p where it forms them), R += b_1 Z_1 + b_3 Z_3 + b_2 Z_2
 // (k3_combine_b), and the reverse pass reads E_k = b_k R: T_k += D1_k^T x_k E_k before X_k and
@@ -65,6 +72,14 @@
 namespace {
 constexpr int K3_LOSS_CAP = 4096;
 }  // namespace
+
+// A pair set's eight launches (build_pair_stages) and the refinement of its two solves per pair:
+// rst[2 i] / [2 i + 1] the residuals / corrections and rp[i] the fused panels of H_jk (i = 0) and
+// Zb_jk (i = 1)
+struct PairStages {
+  std::vector<std::vector<gpk::GemmDesc>> st, rst;
+  std::vector<std::vector<gpk::RefinePanel>> rp;
+};
 
 struct gpk_handle3 {
   gpk_problem3 prob{};
@@ -133,6 +148,17 @@ struct gpk_handle3 {
   double mx[3] = {};
   double *Z1 = nullptr, *Z1p = nullptr, *Z2p = nullptr, *Zb12 = nullptr;
   double *Hx[3] = {}, *Cx[3] = {}, *Hb[3] = {}, *Zb[3] = {};
+  // gpk_create3_opq: the weights of the bi-pairs (1,2), (1,3), (2,3) (bi = 0: none, and nothing below
+  // is allocated or launched).  Per axis of a present pair: the order-2 block DD_k (D2, the assembly's
+  // DERIV_HIGH_D2 / DERIV_HIGH_SPLIT_D2) and its gradient G_DDk (GD2).  The grid tensors are the cross
+  // pairs' with DD for D1: Hq[t] = H2_jk, Bq[t] = B_jk, Hbq[t] = q DD_k^T x_k R, Zbq[t] = K_k^{-1} x_k
+  // Hbq[t]; Z21 = DD_1 x_1 A_1 (Z21p permuted), Z22p = DD_2 x_2 A_2, Zb212 = Zbq[0] in the natural
+  // layout.  All are allocations of their own, so nothing aliases build_refine's scratch.
+  int bi = 0;
+  double bq[3] = {};
+  double *D2[3] = {}, *GD2[3] = {};
+  double *Z21 = nullptr, *Z21p = nullptr, *Z22p = nullptr, *Zb212 = nullptr;
+  double *Hq[3] = {}, *Bq[3] = {}, *Hbq[3] = {}, *Zbq[3] = {};
   // gpk_create3_opb: the drift fields b_k (drift = 0: none, and nothing below is allocated or
   // launched).  Per axis with a field: bf[k] (padded, natural layout), Zd[k] = D1_k x_k A_k (Zd[1]
   // permuted; Z1 / Z2p themselves where a cross pair already forms them, else an allocation of its
@@ -149,11 +175,9 @@ struct gpk_handle3 {
   // a convective handle's two further launches: [0] the V_k, after stage 2 and its refinement;
   // [1] the G_D1k, after stage 3 (empty elsewhere)
   std::vector<std::vector<GemmDesc>> cstages;
-  // a cross handle's eight further launches (build_cross_stages; empty elsewhere) and the
-  // refinement of its two solves per pair: xrstages[2 i] / [2 i + 1] the residuals / corrections
-  // and xrpanels[i] the fused panels of H_jk (i = 0) and Zb_jk (i = 1)
-  std::vector<std::vector<GemmDesc>> xstages, xrstages;
-  std::vector<std::vector<RefinePanel>> xrpanels;
+  // a cross handle's eight further launches (build_pair_stages; empty elsewhere), and a bi-pair
+  // handle's eight (qs)
+  PairStages xs, qs;
   // a drift handle's further launches (build_drift_stages; empty elsewhere): [0] the Z_k no cross
   // pair forms (may be empty), [1] the sums into T_k, [2] the G_D1k
   std::vector<std::vector<GemmDesc>> dstages;
@@ -206,31 +230,46 @@ void build_conv_stages(gpk_handle3* h) {
   }
 }
 
-// Mixed partials (gpk_create3_opm), after build_stages, build_conv_stages and build_refine.  Pair
-// (1,2) runs on the permuted copy of Z_1 and brings Zb_12 back to the natural layout for axis 1's
-// sums; (1,3) is natural throughout with K_3^{-1} and D1_3 on the right; (2,3) is permuted
-// throughout, mode 3 still being the contiguous index there.  Launches, in stream order:
-//   [0] Z_j  [1] H_jk (solves)  [2] C_jk             after stage 2, before k3_combine_m
-//   [3] Hb_jk  [4] Zb_jk (solves)  [5] T_j += ...  [6] G_D1     after stage 3, before stage 4
-//   [7] G_Kk += ...                                   after the last stage
-// An axis takes at most two cross products into T_j, G_D1 or G_Kk: they share one descriptor (the
+// Pairs of axes (j, k), j < k, in the order (1,2), (1,3), (2,3): the mixed partials m_jk d^2u/dx_j dx_k
+// (gpk_create3_opm; the block G is D1) and the mixed fourth-order partials q_jk d^4u/dx_j^2 dx_k^2
+// (gpk_create3_opq; G is DD).  One builder serves both: a PairSet names the weights, the block per
+// axis, its gradient target per axis (add[k]: the target already holds something in the stream) and
+// the buffers; it runs after build_stages, build_conv_stages and build_refine.  Pair (1,2) runs on
+// the permuted copy of Z_1 and brings Zb_12 back to the natural layout for axis 1's sums; (1,3) is
+// natural throughout with K_3^{-1} and G_3 on the right; (2,3) is permuted throughout, mode 3 still
+// being the contiguous index there.  Launches, in stream order:
+//   [0] Z_j = G_j x_j A_j  [1] H_jk (solves)  [2] C_jk = w G_k x_k H_jk    after stage 2, before the combine
+//   [3] Hb_jk = w G_k^T x_k R  [4] Zb_jk (solves)  [5] T_j += G_j^T x_j Zb_jk  [6] dL/dG
+//                                                     after stage 3, before stage 4
+//   [7] G_Kk -= v Zb_jk,(k) H_jk,(k)^T                after the last stage
+// An axis takes at most two pair products into T_j, dL/dG or G_Kk: they share one descriptor (the
 // dual-product slot), which adds them to what the target holds (C0 = C, beta = 1: every GEMM kernel
 // reads C0 at the element it then writes, in the same thread, as the refinement's in-place
-// corrections rely on; launch_huge's first pass does the same and its second reads C alone).  G_D1
-// of an axis that is not convective holds nothing yet and is written, not added to.
-void build_cross_stages(gpk_handle3* h) {
+// corrections rely on; launch_huge's first pass does the same and its second reads C alone).  A
+// dL/dG that holds nothing yet is written, not added to.  The refinement's scratch of H_jk is Hb_jk
+// (not yet formed) and that of Zb_jk is C_jk (the combine kernel has read it).
+struct PairSet {
+  const double* w;       // [3] pair weights (0: absent)
+  double* const* G;      // [3] the block per axis
+  double* const* GG;     // [3] dL/dG per axis
+  bool add[3];
+  double *Z1, *Z1p, *Z2p, *Zb12;
+  double* const* Hx; double* const* Cx; double* const* Hb; double* const* Zb;
+};
+
+void build_pair_stages(gpk_handle3* h, const PairSet& ps, PairStages& out) {
   const int P1 = h->g.p[0], P2 = h->g.p[1], P3 = h->g.p[2];
   const int M1 = P2 * P3, M2 = P1 * P3, M3 = P1 * P2;
-  const double* m = h->mx;
+  const double* m = ps.w;
   double* const* Ki = h->Kinv;
-  double* const* D1 = h->D1;
+  double* const* G = ps.G;
   const bool on[3] = {m[0] != 0.0, m[1] != 0.0, m[2] != 0.0};
   const bool refine = !h->rstages.empty();
   auto scaled = [](GemmDesc d, double alpha) { d.alpha = alpha; return d; };
-  auto& xs = h->xstages;
+  auto& xs = out.st;
   xs.assign(8, {});
-  h->xrstages.assign(refine ? 4 : 0, {});
-  h->xrpanels.assign(refine ? 2 : 0, {});
+  out.rst.assign(refine ? 4 : 0, {});
+  out.rp.assign(refine ? 2 : 0, {});
   // solve i (0: H_jk, 1: Zb_jk) of a pair against its outer axis a (1: left, permuted; 2: right)
   auto solve = [&](int i, int a, const double* B, double* X, double* W) {
     const bool right = a == 2;
@@ -238,29 +277,29 @@ void build_cross_stages(gpk_handle3* h) {
     const RefinedSolve s = refined_solve(right, h->Kc[a], Ki[a], B, X, W, rows, cols, h->pst[a]);
     xs[i ? 4 : 1].push_back(s.solve);
     if (!refine) return;
-    h->xrstages[2 * i].push_back(s.resid);
-    h->xrstages[2 * i + 1].push_back(s.fix);
-    h->xrpanels[i].push_back(refine_panel_desc(right, h->Kc[a], Ki[a], B, X, rows, cols, h->pst[a]));
+    out.rst[2 * i].push_back(s.resid);
+    out.rst[2 * i + 1].push_back(s.fix);
+    out.rp[i].push_back(refine_panel_desc(right, h->Kc[a], Ki[a], B, X, rows, cols, h->pst[a]));
   };
-  if (on[0] || on[1]) xs[0].push_back(gemm_desc(D1[0], P1, 0, h->A1, M1, 0, h->Z1, M1, P1, M1, P1));
-  if (on[2]) xs[0].push_back(gemm_desc(D1[1], P2, 0, h->A2p, M2, 0, h->Z2p, M2, P2, M2, P2));
+  if (on[0] || on[1]) xs[0].push_back(gemm_desc(G[0], P1, 0, h->A1, M1, 0, ps.Z1, M1, P1, M1, P1));
+  if (on[2]) xs[0].push_back(gemm_desc(G[1], P2, 0, h->A2p, M2, 0, ps.Z2p, M2, P2, M2, P2));
   if (on[0]) {  // (1,2), permuted
-    solve(0, 1, h->Z1p, h->Hx[0], h->Hb[0]);
-    xs[2].push_back(scaled(gemm_desc(D1[1], P2, 0, h->Hx[0], M2, 0, h->Cx[0], M2, P2, M2, P2), m[0]));
-    xs[3].push_back(scaled(gemm_desc(D1[1], P2, 1, h->Rp, M2, 0, h->Hb[0], M2, P2, M2, P2), m[0]));
-    solve(1, 1, h->Hb[0], h->Zb[0], h->Cx[0]);
+    solve(0, 1, ps.Z1p, ps.Hx[0], ps.Hb[0]);
+    xs[2].push_back(scaled(gemm_desc(G[1], P2, 0, ps.Hx[0], M2, 0, ps.Cx[0], M2, P2, M2, P2), m[0]));
+    xs[3].push_back(scaled(gemm_desc(G[1], P2, 1, h->Rp, M2, 0, ps.Hb[0], M2, P2, M2, P2), m[0]));
+    solve(1, 1, ps.Hb[0], ps.Zb[0], ps.Cx[0]);
   }
   if (on[1]) {  // (1,3), natural
-    solve(0, 2, h->Z1, h->Hx[1], h->Hb[1]);
-    xs[2].push_back(scaled(gemm_desc(h->Hx[1], P3, 0, D1[2], P3, 1, h->Cx[1], P3, M3, P3, P3), m[1]));
-    xs[3].push_back(scaled(gemm_desc(h->R, P3, 0, D1[2], P3, 0, h->Hb[1], P3, M3, P3, P3), m[1]));
-    solve(1, 2, h->Hb[1], h->Zb[1], h->Cx[1]);
+    solve(0, 2, ps.Z1, ps.Hx[1], ps.Hb[1]);
+    xs[2].push_back(scaled(gemm_desc(ps.Hx[1], P3, 0, G[2], P3, 1, ps.Cx[1], P3, M3, P3, P3), m[1]));
+    xs[3].push_back(scaled(gemm_desc(h->R, P3, 0, G[2], P3, 0, ps.Hb[1], P3, M3, P3, P3), m[1]));
+    solve(1, 2, ps.Hb[1], ps.Zb[1], ps.Cx[1]);
   }
   if (on[2]) {  // (2,3), permuted
-    solve(0, 2, h->Z2p, h->Hx[2], h->Hb[2]);
-    xs[2].push_back(scaled(gemm_desc(h->Hx[2], P3, 0, D1[2], P3, 1, h->Cx[2], P3, M3, P3, P3), m[2]));
-    xs[3].push_back(scaled(gemm_desc(h->Rp, P3, 0, D1[2], P3, 0, h->Hb[2], P3, M3, P3, P3), m[2]));
-    solve(1, 2, h->Hb[2], h->Zb[2], h->Cx[2]);
+    solve(0, 2, ps.Z2p, ps.Hx[2], ps.Hb[2]);
+    xs[2].push_back(scaled(gemm_desc(ps.Hx[2], P3, 0, G[2], P3, 1, ps.Cx[2], P3, M3, P3, P3), m[2]));
+    xs[3].push_back(scaled(gemm_desc(h->Rp, P3, 0, G[2], P3, 0, ps.Hb[2], P3, M3, P3, P3), m[2]));
+    solve(1, 2, ps.Hb[2], ps.Zb[2], ps.Cx[2]);
   }
   // up to two products into one target: the second in the dual slot, each with its own factor
   struct Prod { const double* A; int lda, ta; const double* B; int ldb, tb, K; double alpha; };
@@ -274,45 +313,59 @@ void build_cross_stages(gpk_handle3* h) {
     if (add) { d.beta = 1.0; d.C0 = C; d.ldc0 = ldc; }
     return d;
   };
-  // T_1 += D1_1^T x_1 (Zb_12 + Zb_13);  T_2 += D1_2^T x_2 Zb_23 (permuted)
+  // T_1 += G_1^T x_1 (Zb_12 + Zb_13);  T_2 += G_2^T x_2 Zb_23 (permuted)
   {
     std::vector<Prod> t1;
-    if (on[0]) t1.push_back({D1[0], P1, 1, h->Zb12, M1, 0, P1, 1.0});
-    if (on[1]) t1.push_back({D1[0], P1, 1, h->Zb[1], M1, 0, P1, 1.0});
+    if (on[0]) t1.push_back({G[0], P1, 1, ps.Zb12, M1, 0, P1, 1.0});
+    if (on[1]) t1.push_back({G[0], P1, 1, ps.Zb[1], M1, 0, P1, 1.0});
     if (!t1.empty()) xs[5].push_back(sum(t1, h->T1, M1, P1, M1, true, 0));
-    if (on[2]) xs[5].push_back(sum({{D1[1], P2, 1, h->Zb[2], M2, 0, P2, 1.0}}, h->T2p, M2, P2, M2, true, 0));
+    if (on[2]) xs[5].push_back(sum({{G[1], P2, 1, ps.Zb[2], M2, 0, P2, 1.0}}, h->T2p, M2, P2, M2, true, 0));
   }
-  // G_D1 per axis: inner products v Zb_(j) A_j^T, outer products v m R_(k) H_(k)^T
+  // dL/dG per axis: inner products v Zb_(j) A_j^T, outer products v w R_(k) H_(k)^T
   {
     std::vector<Prod> g1, g2, g3;
-    if (on[0]) g1.push_back({h->Zb12, M1, 0, h->A1, M1, 1, M1, 1.0});
-    if (on[1]) g1.push_back({h->Zb[1], M1, 0, h->A1, M1, 1, M1, 1.0});
-    if (on[0]) g2.push_back({h->Rp, M2, 0, h->Hx[0], M2, 1, M2, m[0]});
-    if (on[2]) g2.push_back({h->Zb[2], M2, 0, h->A2p, M2, 1, M2, 1.0});
-    if (on[1]) g3.push_back({h->R, P3, 1, h->Hx[1], P3, 0, M3, m[1]});
-    if (on[2]) g3.push_back({h->Rp, P3, 1, h->Hx[2], P3, 0, M3, m[2]});
-    if (!g1.empty()) xs[6].push_back(sum(g1, h->GD1[0], P1, P1, P1, h->gconv[0] != 0.0, 1));
-    if (!g2.empty()) xs[6].push_back(sum(g2, h->GD1[1], P2, P2, P2, h->gconv[1] != 0.0, 1));
-    if (!g3.empty()) xs[6].push_back(sum(g3, h->GD1[2], P3, P3, P3, h->gconv[2] != 0.0, 1));
+    if (on[0]) g1.push_back({ps.Zb12, M1, 0, h->A1, M1, 1, M1, 1.0});
+    if (on[1]) g1.push_back({ps.Zb[1], M1, 0, h->A1, M1, 1, M1, 1.0});
+    if (on[0]) g2.push_back({h->Rp, M2, 0, ps.Hx[0], M2, 1, M2, m[0]});
+    if (on[2]) g2.push_back({ps.Zb[2], M2, 0, h->A2p, M2, 1, M2, 1.0});
+    if (on[1]) g3.push_back({h->R, P3, 1, ps.Hx[1], P3, 0, M3, m[1]});
+    if (on[2]) g3.push_back({h->Rp, P3, 1, ps.Hx[2], P3, 0, M3, m[2]});
+    if (!g1.empty()) xs[6].push_back(sum(g1, ps.GG[0], P1, P1, P1, ps.add[0], 1));
+    if (!g2.empty()) xs[6].push_back(sum(g2, ps.GG[1], P2, P2, P2, ps.add[1], 1));
+    if (!g3.empty()) xs[6].push_back(sum(g3, ps.GG[2], P3, P3, P3, ps.add[2], 1));
   }
   // G_K2 -= v Zb_12,(2) H_12,(2)^T;  G_K3 -= v (Zb_13,(3) H_13,(3)^T + Zb_23,(3) H_23,(3)^T)
   {
     std::vector<Prod> k3;
-    if (on[0]) xs[7].push_back(sum({{h->Zb[0], M2, 0, h->Hx[0], M2, 1, M2, -1.0}}, h->GK[1], P2, P2, P2, true, 1));
-    if (on[1]) k3.push_back({h->Zb[1], P3, 1, h->Hx[1], P3, 0, M3, -1.0});
-    if (on[2]) k3.push_back({h->Zb[2], P3, 1, h->Hx[2], P3, 0, M3, -1.0});
+    if (on[0]) xs[7].push_back(sum({{ps.Zb[0], M2, 0, ps.Hx[0], M2, 1, M2, -1.0}}, h->GK[1], P2, P2, P2, true, 1));
+    if (on[1]) k3.push_back({ps.Zb[1], P3, 1, ps.Hx[1], P3, 0, M3, -1.0});
+    if (on[2]) k3.push_back({ps.Zb[2], P3, 1, ps.Hx[2], P3, 0, M3, -1.0});
     if (!k3.empty()) xs[7].push_back(sum(k3, h->GK[2], P3, P3, P3, true, 1));
   }
 }
 
-// Drift fields (gpk_create3_opb), after build_stages, build_conv_stages and build_cross_stages.
+// the cross pairs: G = D1, dL/dD1 added to where the axis is convective (its G_D1k came first)
+void build_cross_stages(gpk_handle3* h) {
+  const PairSet ps{h->mx, h->D1, h->GD1, {h->gconv[0] != 0.0, h->gconv[1] != 0.0, h->gconv[2] != 0.0},
+                   h->Z1, h->Z1p, h->Z2p, h->Zb12, h->Hx, h->Cx, h->Hb, h->Zb};
+  build_pair_stages(h, ps, h->xs);
+}
+
+// the bi-pairs: G = DD, and nothing precedes dL/dDD in the stream (written, beta = 0)
+void build_bicross_stages(gpk_handle3* h) {
+  const PairSet ps{h->bq, h->D2, h->GD2, {false, false, false},
+                   h->Z21, h->Z21p, h->Z22p, h->Zb212, h->Hq, h->Bq, h->Hbq, h->Zbq};
+  build_pair_stages(h, ps, h->qs);
+}
+
+// Drift fields (gpk_create3_opb), after build_stages, build_conv_stages and the pair stages.
 // Axis 2 stays in the permuted layout; axis 3 has D1 on the right, transposed like D[2].  Launches,
 // in stream order:
 //   [0] Z_k = D1_k x_k A_k of the drift axes no cross pair serves    after stage 2 and the V_k
 //   [1] T_k += D1_k^T x_k E_k   [2] G_D1k (+)= v E_k,(k) A_k,(k)^T   after stage 3 and the cross
 //                                                                    handle's G_D1, before stage 4
 // The stage-3 dual slot (a convective axis) and the cross sums' two slots can all be full on one
-// axis, so the sums into T_k are launches of their own under build_cross_stages' aliasing rule
+// axis, so the sums into T_k are launches of their own under build_pair_stages' aliasing rule
 // (C0 = C, beta = 1).  These launches are the last producers of G_D1k in the stream: the convective
 // launch writes it, the cross launch writes or adds, and a drift axis adds when either came before
 // and writes when it is the first.
@@ -474,16 +527,16 @@ int launch_stage(gpk_handle3* h, int k) {
   return GPK_OK;
 }
 
-// a cross handle's solves i (0: the H_jk, 1: the Zb_jk), then their refinement when the handle refines
-int launch_cross_solves(gpk_handle3* h, int i) {
-  TRY(launch_descs(h, h->xstages[i ? 4 : 1]));
-  if (h->xrstages.empty()) return GPK_OK;
+// a pair set's solves i (0: the H_jk, 1: the Zb_jk), then their refinement when the handle refines
+int launch_pair_solves(gpk_handle3* h, const PairStages& p, int i) {
+  TRY(launch_descs(h, p.st[i ? 4 : 1]));
+  if (p.rst.empty()) return GPK_OK;
   if (h->route) {
-    const auto& f = h->xrpanels[i];
+    const auto& f = p.rp[i];
     return check_launch(launch_refine_panel(f.data(), (int)f.size(), h->sc, h->s), "refine_panel");
   }
-  TRY(launch_descs(h, h->xrstages[2 * i]));
-  return launch_descs(h, h->xrstages[2 * i + 1]);
+  TRY(launch_descs(h, p.rst[2 * i]));
+  return launch_descs(h, p.rst[2 * i + 1]);
 }
 
 K3Eq eq_layer(const gpk_handle3* h) {
@@ -516,7 +569,7 @@ int enqueue_inverse3(gpk_handle3* h, int apply) {
     aa[a].x = h->x[a]; aa[a].n = g.n[a]; aa[a].p = g.p[a]; aa[a].kc = h->kc + a;
     aa[a].jitter = h->prob.jitter; aa[a].K = h->K[a]; aa[a].Kc = h->Kc[a]; aa[a].D = h->D[a];
     aa[a].deriv = h->mode[a]; aa[a].c2 = h->c2[a]; aa[a].c1 = h->c1[a]; aa[a].D1 = h->D1[a];
-    aa[a].c4 = h->c4[a]; aa[a].c3 = h->c3[a];
+    aa[a].c4 = h->c4[a]; aa[a].c3 = h->c3[a]; aa[a].D2 = h->D2[a];
   }
   // (skip = 1: the constants are published by k3_prep; each workgroup derives its axis's own)
   PrepArgs p12{};
@@ -574,16 +627,36 @@ int enqueue_step3(gpk_handle3* h, int apply) {
   if (h->conv) TRY(launch_descs(h, h->cstages[0]));  // V_k, from the refined A_k
   if (h->drift && !h->dstages[0].empty()) TRY(launch_descs(h, h->dstages[0]));  // Z_k no cross pair forms
   if (h->cross) {  // Z_j from the refined A_j, H_jk (pair (1,2): on the permuted Z_1), C_jk
-    TRY(launch_descs(h, h->xstages[0]));
+    TRY(launch_descs(h, h->xs.st[0]));
     if (h->Z1p) TRY(check_launch(k3_launch_permute(h->Z1, h->Z1p, g, h->s), "k3_permute"));
-    TRY(launch_cross_solves(h, 0));
-    TRY(launch_descs(h, h->xstages[2]));
+    TRY(launch_pair_solves(h, h->xs, 0));
+    TRY(launch_descs(h, h->xs.st[2]));
+  }
+  if (h->bi) {  // the same with DD: Z2_j, H2_jk (pair (1,2): on the permuted Z2_1), B_jk
+    TRY(launch_descs(h, h->qs.st[0]));
+    if (h->Z21p) TRY(check_launch(k3_launch_permute(h->Z21, h->Z21p, g, h->s), "k3_permute"));
+    TRY(launch_pair_solves(h, h->qs, 0));
+    TRY(launch_descs(h, h->qs.st[2]));
   }
   K3Combine C{};
   C.g = g; C.Rx = h->Rx; C.Rz = h->Rz; C.Ryp = h->Ryp; C.F = h->F; C.Up = h->Up; C.Sp = h->Sp;
   C.eq = eq_layer(h); C.R = h->R; C.Rp = h->Rp; C.S = h->S;
   C.red_egap = h->red_egap; C.red_quad = h->red_quad;
-  if (h->conv || h->cross || h->drift) {
+  if (h->bi) {  // k3_combine_b's superset: every older layer as the handle has it, absent ones null
+    K3CombineQ Qx{};
+    K3CombineB& B = Qx.b;
+    K3CombineC& X = B.m.c;
+    X.v.c = C; X.v.rho = h->rho;
+    for (int a = 0; a < 3; ++a) {
+      X.v.a[a] = h->cf[a]; X.v.W[a] = h->W[a]; X.V[a] = h->V[a];
+      B.m.C[a] = h->Cx[a];
+      B.b[a] = h->bf[a]; B.Z[a] = h->Zd[a]; B.E[a] = h->Ed[a];
+      Qx.B[a] = h->Bq[a];
+    }
+    X.N = h->Nsum; X.Q = h->Q; X.Qp = h->Qp;
+    B.m.rp = h->Cx[0] || h->Cx[2] || h->Bq[0] || h->Bq[2];
+    TRY(check_launch(k3_launch_combine_q(Qx, h->s), "k3_combine_q"));
+  } else if (h->conv || h->cross || h->drift) {
     K3CombineC X{};
     X.v.c = C; X.v.rho = h->rho;
     for (int a = 0; a < 3; ++a) { X.v.a[a] = h->cf[a]; X.v.W[a] = h->W[a]; X.V[a] = h->V[a]; }
@@ -621,18 +694,26 @@ int enqueue_step3(gpk_handle3* h, int apply) {
       if (h->fpart[a])
         TRY(check_launch(k3_launch_face_back(h->face[a], a == 2, h->sc, h->prob.llk_weight, h->s), "k3_face_back"));
     if (h->cross && k == 3) {  // Hb_jk, Zb_jk, then T_j's share before X_j = K_j^{-1} x_j T_j reads it; G_D1
-      TRY(launch_descs(h, h->xstages[3]));
-      TRY(launch_cross_solves(h, 1));
+      TRY(launch_descs(h, h->xs.st[3]));
+      TRY(launch_pair_solves(h, h->xs, 1));
       if (h->Zb12) TRY(check_launch(k3_launch_unpermute(h->Zb[0], h->Zb12, g, h->s), "k3_permute"));
-      TRY(launch_descs(h, h->xstages[5]));
-      TRY(launch_descs(h, h->xstages[6]));
+      TRY(launch_descs(h, h->xs.st[5]));
+      TRY(launch_descs(h, h->xs.st[6]));
+    }
+    if (h->bi && k == 3) {  // Hb2_jk, Zb2_jk, T_j's share, G_DD
+      TRY(launch_descs(h, h->qs.st[3]));
+      TRY(launch_pair_solves(h, h->qs, 1));
+      if (h->Zb212) TRY(check_launch(k3_launch_unpermute(h->Zbq[0], h->Zb212, g, h->s), "k3_permute"));
+      TRY(launch_descs(h, h->qs.st[5]));
+      TRY(launch_descs(h, h->qs.st[6]));
     }
     if (h->drift && k == 3) {  // T_k's drift share before X_k = K_k^{-1} x_k T_k reads it; G_D1k
       TRY(launch_descs(h, h->dstages[1]));
       TRY(launch_descs(h, h->dstages[2]));
     }
   }
-  if (h->cross) TRY(launch_descs(h, h->xstages[7]));  // G_Kk's share, added to the last stage's G_Kk
+  if (h->cross) TRY(launch_descs(h, h->xs.st[7]));  // G_Kk's share, added to the last stage's G_Kk
+  if (h->bi) TRY(launch_descs(h, h->qs.st[7]));     // and the bi-pairs', after it
   // kernel-parameter contraction (the 2-axis kernels: axes 1-2, then axis 3)
   const int fb = h->dfaces ? K3_FACE_TAIL_BLOCKS : 0;  // + blocks of partials per axis: the face rows' (k3_face_tail)
   PGradArgs pg[3] = {};
@@ -640,7 +721,7 @@ int enqueue_step3(gpk_handle3* h, int apply) {
     pg[a].x = h->x[a]; pg[a].n = g.n[a]; pg[a].p = g.p[a]; pg[a].kc = h->kc + a;
     pg[a].GK = h->GK[a]; pg[a].GD = h->GD[a]; pg[a].deriv = h->mode[a];
     pg[a].c2 = h->c2[a]; pg[a].c1 = h->c1[a]; pg[a].GD1 = h->GD1[a];
-    pg[a].c4 = h->c4[a]; pg[a].c3 = h->c3[a];
+    pg[a].c4 = h->c4[a]; pg[a].c3 = h->c3[a]; pg[a].GD2 = h->GD2[a];
     pg[a].part = h->pgpart + (size_t)a * (h->bpa + fb) * 3 * QMAX;
   }
   if (h->mode[0] == h->mode[1]) {
@@ -743,7 +824,7 @@ int check_problem3(const gpk_problem3* p) {
 int create3(const gpk_problem3* p, const gpk_operator3* op, double freq_scale, gpk_handle3** out,
             const gpk_operator3x* opx = nullptr, const gpk_coef3* cf = nullptr, const gpk_bdata3* bd = nullptr,
             const gpk_conv3* cv = nullptr, const gpk_cross3* mx = nullptr, const gpk_drift3* dr = nullptr,
-            const gpk_high3* hi = nullptr) {
+            const gpk_high3* hi = nullptr, const gpk_bicross3* bq = nullptr) {
   TRY(check_problem3(p));
   const int ns[3] = {p->n1, p->n2, p->n3};
   TRY(check_device(p->device));
@@ -788,6 +869,14 @@ int create3(const gpk_problem3* p, const gpk_operator3* op, double freq_scale, g
       h->c3[a] = hi->c3[a];
       h->mode[a] = h->mode[a] == DERIV_SPLIT ? DERIV_HIGH_SPLIT : DERIV_HIGH;
     }
+    // an axis of a pair with a bi weight (entered as a mixed one): the four-field block whatever c4
+    // and c3 are, with DD_k stored alongside (and D1_k where the axis owns one)
+    for (int t = 0; t < 3 && bq; ++t)
+      if (bq->q[t] != 0.0 && (pairs[t][0] == a || pairs[t][1] == a)) {
+        h->bq[t] = bq->q[t];
+        h->bi = 1;
+        h->mode[a] = deriv_stores_d1(h->mode[a]) ? DERIV_HIGH_SPLIT_D2 : DERIV_HIGH_D2;
+      }
     h->c2[a] = mixed ? opx->c2[a] : h->op.order[a] == 2 ? h->op.coef[a] : 0.0;
     h->c1[a] = mixed ? opx->c1[a] : h->op.order[a] == 1 ? h->op.coef[a] : 0.0;
   }
@@ -919,6 +1008,20 @@ int create3(const gpk_problem3* p, const gpk_operator3* op, double freq_scale, g
     if (t == 0) { A3_(h->Z1p, np); A3_(h->Zb12, np); }
     if (t == 2) A3_(h->Z2p, np);
   }
+  // bi-pairs: DD_k and G_DDk per axis of a present pair; per pair H2, B, Hb2 and Zb2; Z2_1 / Z2_2 for
+  // the pairs that start from them, and the two copies pair (1,2) goes through
+  for (int a = 0; a < 3 && h->bi; ++a) {
+    if (!deriv_stores_d2(h->mode[a])) continue;
+    const int P = g.p[a];
+    A3_(h->D2[a], (size_t)P * P); A3_(h->GD2[a], (size_t)P * P);
+  }
+  for (int t = 0; t < 3 && h->bi; ++t) {
+    if (h->bq[t] == 0.0) continue;
+    A3_(h->Hq[t], np); A3_(h->Bq[t], np); A3_(h->Hbq[t], np); A3_(h->Zbq[t], np);
+    if (t < 2 && !h->Z21) A3_(h->Z21, np);
+    if (t == 0) { A3_(h->Z21p, np); A3_(h->Zb212, np); }
+    if (t == 2) A3_(h->Z22p, np);
+  }
   // drift axes: the field (zero-padded, natural layout), E_k, and Z_k where no pair forms it
   for (int a = 0; a < 3 && h->drift; ++a) {
     if (!dr->b[a]) continue;
@@ -964,6 +1067,7 @@ int create3(const gpk_problem3* p, const gpk_operator3* op, double freq_scale, g
     if (h->route && refine_panel_prepare() != hipSuccess) return bail(fail(GPK_EHIP, "refine_panel_prepare failed"));
   }
   if (h->cross) build_cross_stages(h);
+  if (h->bi) build_bicross_stages(h);
   if (h->drift) build_drift_stages(h);
   *out = h;
   return GPK_OK;
@@ -1075,7 +1179,7 @@ namespace {
 // then be null or without faces): the argument checks of both, then the handle
 int create3_opn(const gpk_problem3* p, const gpk_operator3x* op, const gpk_coef3* cf, const gpk_bdata3* bd,
                 const gpk_conv3* cv, double freq_scale, gpk_handle3** out, const gpk_cross3* mx = nullptr,
-                const gpk_drift3* dr = nullptr, const gpk_high3* hi = nullptr) {
+                const gpk_drift3* dr = nullptr, const gpk_high3* hi = nullptr, const gpk_bicross3* bq = nullptr) {
   if (!p || !op || !out) return fail(GPK_EINVAL, "NULL argument");
   *out = nullptr;
   if (bd && bd->dfaces == 0) bd = nullptr;
@@ -1084,7 +1188,7 @@ int create3_opn(const gpk_problem3* p, const gpk_operator3x* op, const gpk_coef3
   // the operator's own checks, with faces = 0 allowed here (data on derivatives alone)
   gpk_operator3x o = *op;
   if (bd && o.faces == 0) o.faces = bd->dfaces;
-  TRY(check_operator3x(p, &o, out, hi ? "gpk_create3_oph" : dr ? "gpk_create3_opb" : mx ? "gpk_create3_opm" : cv ? "gpk_create3_opc" : "gpk_create3_opn"));
+  TRY(check_operator3x(p, &o, out, bq ? "gpk_create3_opq" : hi ? "gpk_create3_oph" : dr ? "gpk_create3_opb" : mx ? "gpk_create3_opm" : cv ? "gpk_create3_opc" : "gpk_create3_opn"));
   TRY(check_problem3(p));
   if (bd) {
     const long fs[3] = {(long)p->n2 * p->n3, (long)p->n1 * p->n3, (long)p->n1 * p->n2};
@@ -1123,7 +1227,14 @@ int create3_opn(const gpk_problem3* p, const gpk_operator3x* op, const gpk_coef3
   // and a high-order axis
   for (int a = 0; a < 3 && hi; ++a)
     if (hi->c4[a] != 0.0 || hi->c3[a] != 0.0) { o1.order[a] = 0; o1.coef[a] = 1.0; }
-  return create3(p, &o1, freq_scale, out, op, any ? cf : nullptr, bd, cv, mx, dr, hi);
+  // and both axes of a pair with a bi weight
+  if (bq) {
+    const bool in[3] = {bq->q[0] != 0.0 || bq->q[1] != 0.0, bq->q[0] != 0.0 || bq->q[2] != 0.0,
+                        bq->q[1] != 0.0 || bq->q[2] != 0.0};
+    for (int a = 0; a < 3; ++a)
+      if (in[a]) { o1.order[a] = 0; o1.coef[a] = 1.0; }
+  }
+  return create3(p, &o1, freq_scale, out, op, any ? cf : nullptr, bd, cv, mx, dr, hi, bq);
 }
 
 // the convective weights as gpk_create3_opc and gpk_create3_opm (`who`) take them: GPK_EINVAL on a
@@ -1202,6 +1313,41 @@ int gpk_create3_oph(const gpk_problem3* p, const gpk_operator3x* op, const gpk_c
   TRY(check_conv3(cv, "gpk_create3_oph"));
   if (dr && !dr->b[0] && !dr->b[1] && !dr->b[2]) dr = nullptr;
   return create3_opn(p, op, cf, bd, cv, freq_scale, out, mx, dr, hi);
+}
+
+int gpk_create3_opq(const gpk_problem3* p, const gpk_operator3x* op, const gpk_coef3* cf, const gpk_bdata3* bd,
+                    const gpk_conv3* cv, const gpk_cross3* mx, const gpk_drift3* dr, const gpk_high3* hi,
+                    const gpk_bicross3* bq, double freq_scale, gpk_handle3** out) {
+  if (bq) {
+    if (out) *out = nullptr;
+    for (int t = 0; t < 3; ++t)
+      if (!std::isfinite(bq->q[t])) return fail(GPK_EINVAL, "gpk_create3_opq: q must be finite");
+  }
+  if (!bq || (bq->q[0] == 0.0 && bq->q[1] == 0.0 && bq->q[2] == 0.0))
+    return gpk_create3_oph(p, op, cf, bd, cv, mx, dr, hi, freq_scale, out);
+  if (hi) {
+    bool any = false;
+    for (int a = 0; a < 3; ++a) {
+      if (!std::isfinite(hi->c4[a]) || !std::isfinite(hi->c3[a]))
+        return fail(GPK_EINVAL, "gpk_create3_opq: c4 and c3 must be finite");
+      any = any || hi->c4[a] != 0.0 || hi->c3[a] != 0.0;
+    }
+    if (!any) hi = nullptr;
+  }
+  if (mx) {
+    for (int t = 0; t < 3; ++t)
+      if (!std::isfinite(mx->m[t])) return fail(GPK_EINVAL, "gpk_create3_opq: m must be finite");
+    if (mx->m[0] == 0.0 && mx->m[1] == 0.0 && mx->m[2] == 0.0) mx = nullptr;
+  }
+  TRY(check_conv3(cv, "gpk_create3_opq"));
+  if (dr && !dr->b[0] && !dr->b[1] && !dr->b[2]) dr = nullptr;
+  return create3_opn(p, op, cf, bd, cv, freq_scale, out, mx, dr, hi, bq);
+}
+
+int gpk_bicross_info3(const gpk_handle3* h, double q[3]) {
+  if (!h || !q) return fail(GPK_EINVAL, "NULL argument");
+  for (int t = 0; t < 3; ++t) q[t] = h->bq[t];
+  return GPK_OK;
 }
 
 int gpk_high_info3(const gpk_handle3* h, double c4[3], double c3[3]) {
@@ -1371,11 +1517,14 @@ int gpk_stage_variants3(gpk_handle3* h, int32_t* out, int32_t cap, int32_t* n) {
     order.push_back(&h->stages[k]);
     if (h->conv && (k == 2 || k == 3)) order.push_back(&h->cstages[k - 2]);
     if (h->drift && k == 2 && !h->dstages[0].empty()) order.push_back(&h->dstages[0]);
-    if (h->cross && k == 2) for (int i = 0; i < 3; ++i) order.push_back(&h->xstages[i]);
-    if (h->cross && k == 3) for (int i = 3; i < 7; ++i) order.push_back(&h->xstages[i]);
+    if (h->cross && k == 2) for (int i = 0; i < 3; ++i) order.push_back(&h->xs.st[i]);
+    if (h->bi && k == 2) for (int i = 0; i < 3; ++i) order.push_back(&h->qs.st[i]);
+    if (h->cross && k == 3) for (int i = 3; i < 7; ++i) order.push_back(&h->xs.st[i]);
+    if (h->bi && k == 3) for (int i = 3; i < 7; ++i) order.push_back(&h->qs.st[i]);
     if (h->drift && k == 3) for (int i = 1; i < 3; ++i) order.push_back(&h->dstages[i]);
   }
-  if (h->cross) order.push_back(&h->xstages[7]);
+  if (h->cross) order.push_back(&h->xs.st[7]);
+  if (h->bi) order.push_back(&h->qs.st[7]);
   *n = (int32_t)order.size();
   for (int k = 0; k < *n && k < cap; ++k) out[k] = stage_variant(*order[k]);
   return GPK_OK;

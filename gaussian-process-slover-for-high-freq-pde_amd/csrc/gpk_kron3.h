@@ -137,6 +137,15 @@ struct K3CombineB {
   double* E[3];
 };
 
+// k3_combine_q (gpk_create3_opq): k3_combine_b plus the mixed fourth-order partials B_13 + B_12 + B_23,
+// B_jk = q_jk DD_k x_k K_k^{-1} x_k DD_j x_j A_j (null: the pair is absent; B[0] = B_12 and B[2] = B_23
+// in the mode-2 permuted layout, B[1] = B_13 natural).  Every pointer of b may be null (a handle
+// without drift fields); b.m.rp also covers a permuted bi-pair, which reads R itself from Rp.
+struct K3CombineQ {
+  K3CombineB b;
+  const double* B[3];
+};
+
 // k3_adam_u_c: k3_adam_u_v with N (natural padded layout) added to the factor on R; rho nullable
 struct K3AdamUC {
   K3AdamU a;
@@ -206,6 +215,7 @@ hipError_t k3_launch_combine_c(const K3CombineC& C, hipStream_t s);
 hipError_t k3_launch_adam_u_c(const K3AdamUC& C, hipStream_t s);
 hipError_t k3_launch_combine_m(const K3CombineM& M, hipStream_t s);
 hipError_t k3_launch_combine_b(const K3CombineB& B, hipStream_t s);
+hipError_t k3_launch_combine_q(const K3CombineQ& Q, hipStream_t s);
 // dst[i1][i2][i3] = src[i2][i1][i3]: k3_permute's inverse (k3_permute itself on the grid with axes
 // 1 and 2 swapped, where its source index is this one's and its target index the natural one)
 hipError_t k3_launch_unpermute(const double* src, double* dst, const K3Geom& g, hipStream_t s);

@@ -28,6 +28,9 @@
 // on the grid with axes 1 and 2 swapped.  A kernel of its own once more.
 // Drift fields (gpk_create3_opb): k3_combine_b is k3_combine_m plus b_1 Z_1 + b_3 Z_3 + b_2 Z_2, Z_k =
 // D1_k x_k A_k, and writes the reverse pass's operands E_k = b_k R.  A kernel of its own as well.
+// Mixed fourth-order partials (gpk_create3_opq): k3_combine_q is k3_combine_b plus B_13 + B_12 + B_23
+// (formed by GEMMs, the bi-pair run of build_pair_stages).  A kernel of its own, launched only on a
+// handle with a bi-pair.
 // Grids are padded per axis to P_k (multiple of 32); pads of every tensor are zero.
 #include "gpk_internal.h"
 #include "gpk_kron3.h"
@@ -377,6 +380,78 @@ __global__ __launch_bounds__(256) void k3_combine_b_kernel(K3CombineB B) {
   }
 }
 
+// k3_combine_b with mixed fourth-order partials (gpk_create3_opq): R is summed in k3_combine_b's
+// order, then + B_13 + B_12 + B_23 in that fixed order, each only where its pair is present (B_12 and
+// B_23 read at the permuted index).  Every output of k3_combine_b is written from the final R; Rp is
+// written when axis 2 has no field or a permuted pair, cross or bi, reads it (m.rp).  Every pointer
+// of b may be null (a handle without drift fields).  Inputs are read at real entries only; the pads
+// of every output are zero.
+__global__ __launch_bounds__(256) void k3_combine_q_kernel(K3CombineQ Qx) {
+  const K3CombineB& B = Qx.b;
+  const K3CombineM& Mx = B.m;
+  const K3CombineC& X = Mx.c;
+  const K3CombineV& V = X.v;
+  const K3Combine& C = V.c;
+  const K3Geom& g = C.g;
+  const long e = (long)blockIdx.x * 256 + threadIdx.x;
+  const long tot = (long)g.p[0] * g.p[1] * g.p[2];
+  double r2 = 0.0, us = 0.0;
+  if (e < tot) {
+    const int i3 = (int)(e % g.p[2]);
+    const long rr = e / g.p[2];
+    const int i2 = (int)(rr % g.p[1]), i1 = (int)(rr / g.p[1]);
+    const size_t ep = g.atp(i1, i2, i3);
+    const bool real = i1 < g.n[0] && i2 < g.n[1] && i3 < g.n[2];
+    double R = 0.0, S = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0, N = 0.0, u = 0.0;
+    double b1 = 0.0, b2 = 0.0, b3 = 0.0;
+    if (real) {
+      double tx = C.Rx[e], tz = C.Rz[e], ty = C.Ryp[ep];
+      if (V.a[0]) { a1 = V.a[0][e]; tx *= a1; }
+      if (V.a[2]) { a3 = V.a[2][e]; tz *= a3; }
+      if (V.a[1]) { a2 = V.a[1][e]; ty *= a2; }
+      R = tx + tz + ty - C.F[e];
+      u = C.Up[e];
+      if (V.rho) R += u * ((C.eq.r1 + V.rho[e]) + u * (C.eq.r2 + u * C.eq.r3));
+      else if (C.eq.on) R += u * (C.eq.r1 + u * (C.eq.r2 + u * C.eq.r3));
+      if (X.V[0]) N += X.V[0][e];
+      if (X.V[2]) N += X.V[2][e];
+      if (X.V[1]) N += X.V[1][ep];
+      R += u * N;
+      if (Mx.C[1]) R += Mx.C[1][e];
+      if (Mx.C[0]) R += Mx.C[0][ep];
+      if (Mx.C[2]) R += Mx.C[2][ep];
+      if (B.b[0]) { b1 = B.b[0][e]; R += b1 * B.Z[0][e]; }
+      if (B.b[2]) { b3 = B.b[2][e]; R += b3 * B.Z[2][e]; }
+      if (B.b[1]) { b2 = B.b[1][e]; R += b2 * B.Z[1][ep]; }
+      if (Qx.B[1]) R += Qx.B[1][e];
+      if (Qx.B[0]) R += Qx.B[0][ep];
+      if (Qx.B[2]) R += Qx.B[2][ep];
+      S = C.Sp[ep];
+      r2 = R * R;
+      us = u * S;
+    }
+    C.R[e] = R;
+    C.S[e] = S;
+    if (V.W[0]) V.W[0][e] = a1 * R;
+    if (V.W[1]) V.W[1][ep] = a2 * R;
+    if (!V.W[1] || Mx.rp) C.Rp[ep] = R;
+    if (V.W[2]) V.W[2][e] = a3 * R;
+    if (X.N) X.N[e] = N;
+    if (X.Q) X.Q[e] = u * R;
+    if (X.Qp) X.Qp[ep] = u * R;
+    if (B.E[0]) B.E[0][e] = b1 * R;
+    if (B.E[1]) B.E[1][ep] = b2 * R;
+    if (B.E[2]) B.E[2][e] = b3 * R;
+  }
+  __shared__ double sh[4];
+  r2 = k3_block_sum(r2, sh);
+  us = k3_block_sum(us, sh);
+  if (threadIdx.x == 0) {
+    C.red_egap[blockIdx.x] = r2;
+    C.red_quad[blockIdx.x] = us;
+  }
+}
+
 // one workgroup: loss (model_GP_solver_2d.py:145-174 with three log-det weights), the small
 // parameters' gradients and their Adam update (optax.adam, :179-182)
 __global__ __launch_bounds__(256) void k3_finalize_kernel(K3Final F) {
@@ -618,6 +693,10 @@ hipError_t k3_launch_combine_m(const K3CombineM& M, hipStream_t s) {
 }
 hipError_t k3_launch_combine_b(const K3CombineB& B, hipStream_t s) {
   hipLaunchKernelGGL(k3_combine_b_kernel, dim3(blocks_of(B.m.c.v.c.g.padded())), dim3(256), 0, s, B);
+  return hipGetLastError();
+}
+hipError_t k3_launch_combine_q(const K3CombineQ& Q, hipStream_t s) {
+  hipLaunchKernelGGL(k3_combine_q_kernel, dim3(blocks_of(Q.b.m.c.v.c.g.padded())), dim3(256), 0, s, Q);
   return hipGetLastError();
 }
 hipError_t k3_launch_unpermute(const double* src, double* dst, const K3Geom& g, hipStream_t s) {

@@ -437,10 +437,13 @@ __global__ __launch_bounds__(256) void pgrad_kernel(PGradBatch b, int q,
   // and 1), the axis's weights applied per component; DERIV_HIGH_SPLIT: swg1 the signed pair sum of
   // dL/dD1 (the plain order-1 block)
   constexpr bool HIGH = deriv_high(DERIV);
-  constexpr bool HSPLIT = DERIV == DERIV_HIGH_SPLIT;
+  constexpr bool HSPLIT = DERIV == DERIV_HIGH_SPLIT || DERIV == DERIV_HIGH_SPLIT_D2;
+  // DERIV_HIGH_D2 / DERIV_HIGH_SPLIT_D2: swg2 the symmetric pair sum of dL/dDD (the plain order-2 block)
+  constexpr bool HD2 = deriv_stores_d2(DERIV);
   static_assert(!HIGH || (!MODE1D && !CLS && !DD), "DERIV_HIGH / DERIV_HIGH_SPLIT: the 2D per-pair contraction only");
   __shared__ double swd1[BOTH || HIGH ? PAIRS : 1];
   __shared__ double swg1[HSPLIT ? PAIRS : 1];
+  __shared__ double swg2[HD2 ? PAIRS : 1];
   __shared__ double sw[QMAX], sa[QMAX], so[QMAX], sol[QMAX];
   __shared__ double sacc[8][3][32];
   const int t = threadIdx.x;
@@ -488,7 +491,7 @@ __global__ __launch_bounds__(256) void pgrad_kernel(PGradBatch b, int q,
     while (I * (I + 1) / 2 > tile) --I;
     const int J = tile - I * (I + 1) / 2;
     const int i = I * 32 + chunk * (PAIRS / 32) + (t >> 5), j = J * 32 + (t & 31);
-    double d = 0.0, wk = 0.0, wd = 0.0, wd1 = 0.0, wg1 = 0.0;
+    double d = 0.0, wk = 0.0, wd = 0.0, wd1 = 0.0, wg1 = 0.0, wg2 = 0.0;
     if (i < A.n && j < A.n) {
       const double diff = A.x[i] - A.x[j];
       d = fabs(diff);
@@ -533,18 +536,30 @@ __global__ __launch_bounds__(256) void pgrad_kernel(PGradBatch b, int q,
         const double g1ij = A.GD1[(size_t)i * A.p + j], g1ji = A.GD1[(size_t)j * A.p + i];
         wg1 = I == J ? sij * g1ij : sij * g1ij + sji * g1ji;
       }
+      if constexpr (HD2) {
+        const double g2ij = A.GD2[(size_t)i * A.p + j], g2ji = A.GD2[(size_t)j * A.p + i];
+        wg2 = I == J ? g2ij : g2ij + g2ji;
+      }
     }
     sd[t] = d;
     swk[t] = wk;
     swd[t] = wd;
     if constexpr (BOTH || HIGH) swd1[t] = wd1;
     if constexpr (HSPLIT) swg1[t] = wg1;
+    if constexpr (HD2) swg2[t] = wg2;
   }
   __syncthreads();
   if (TR_FIRST) TR_HI(SLOT_PG_STAGED);
 
   const int g = t >> 5, ql = t & 31;
   double* out = A.part + (size_t)blk * (3 * QMAX);
+  // the D2-storing modes keep the two upper weights in vector registers: their Matern-Cos contraction
+  // is at the scalar-register limit (the other modes read all four from the argument block, as before)
+  double vc4 = 0.0, vc3 = 0.0;
+  if constexpr (HD2) {
+    vc4 = A.c4; vc3 = A.c3;
+    asm volatile("" : "+v"(vc4), "+v"(vc3));
+  }
   __shared__ double slo[DD ? 8 : 1][3][32];  // DD: the low parts of sacc
   for (int q0 = 0; q0 < q; q0 += 32) {
     const int c = q0 + ql;
@@ -554,10 +569,11 @@ __global__ __launch_bounds__(256) void pgrad_kernel(PGradBatch b, int q,
       const double a = sa[c], om = so[c], oml = sol[c];
       for (int e = g; e < NP; e += 8) {
         const double wk = swk[e], wd = swd[e];
-        double wd1 = 0.0, wg1 = 0.0;
+        double wd1 = 0.0, wg1 = 0.0, wg2 = 0.0;
         if constexpr (BOTH || HIGH) wd1 = swd1[e];
         if constexpr (HSPLIT) wg1 = swg1[e];
-        if (wk == 0.0 && wd == 0.0 && wd1 == 0.0 && wg1 == 0.0) continue;
+        if constexpr (HD2) wg2 = swg2[e];
+        if (wk == 0.0 && wd == 0.0 && wd1 == 0.0 && wg1 == 0.0 && wg2 == 0.0) continue;
         const double d = sd[e];
         if constexpr (DD) {
           dd::D fw, fl, ff, dw, dl, df;
@@ -568,6 +584,7 @@ __global__ __launch_bounds__(256) void pgrad_kernel(PGradBatch b, int q,
           continue;
         }
         if constexpr (HIGH) {  // four orders from one exp / sincos set
+          const double hc4 = HD2 ? vc4 : A.c4, hc3 = HD2 ? vc3 : A.c3, hc2 = A.c2, hc1 = A.c1;
           double m[5], ml[5];
           radial4_l<MATERN>(d, a, m, ml);
           if (COS) {
@@ -582,12 +599,12 @@ __global__ __launch_bounds__(256) void pgrad_kernel(PGradBatch b, int q,
             high_fields(m, k, w4, w3, w2, w1);
             high_fields(ml, k, l4, l3, l2, l1);
             high_fields(m, kf, f4, f3, f2, f1);
-            accw += wk * (m[0] * k[0]) + wd * (A.c4 * w4 + A.c2 * w2) + wd1 * (A.c3 * w3 + A.c1 * w1) + wg1 * w1;
-            accl += wk * (ml[0] * k[0]) + wd * (A.c4 * l4 + A.c2 * l2) + wd1 * (A.c3 * l3 + A.c1 * l1) + wg1 * l1;
-            accf += wk * (m[0] * kf[0]) + wd * (A.c4 * f4 + A.c2 * f2) + wd1 * (A.c3 * f3 + A.c1 * f1) + wg1 * f1;
+            accw += wk * (m[0] * k[0]) + wd * (hc4 * w4 + hc2 * w2) + wd1 * (hc3 * w3 + hc1 * w1) + wg1 * w1 + wg2 * w2;
+            accl += wk * (ml[0] * k[0]) + wd * (hc4 * l4 + hc2 * l2) + wd1 * (hc3 * l3 + hc1 * l1) + wg1 * l1 + wg2 * l2;
+            accf += wk * (m[0] * kf[0]) + wd * (hc4 * f4 + hc2 * f2) + wd1 * (hc3 * f3 + hc1 * f1) + wg1 * f1 + wg2 * f2;
           } else {
-            accw += wk * m[0] + wd * (A.c4 * m[4] + A.c2 * m[2]) + wd1 * (A.c3 * m[3] + A.c1 * m[1]) + wg1 * m[1];
-            accl += wk * ml[0] + wd * (A.c4 * ml[4] + A.c2 * ml[2]) + wd1 * (A.c3 * ml[3] + A.c1 * ml[1]) + wg1 * ml[1];
+            accw += wk * m[0] + wd * (hc4 * m[4] + hc2 * m[2]) + wd1 * (hc3 * m[3] + hc1 * m[1]) + wg1 * m[1] + wg2 * m[2];
+            accl += wk * ml[0] + wd * (hc4 * ml[4] + hc2 * ml[2]) + wd1 * (hc3 * ml[3] + hc1 * ml[1]) + wg1 * ml[1] + wg2 * ml[2];
           }
           continue;
         }
@@ -740,6 +757,12 @@ static void launch_pg_c(const PGradBatch& b, int naxes, int bpa, int q, int deri
   } else if (deriv == DERIV_HIGH_SPLIT) {
     if constexpr (!CLS)
       hipLaunchKernelGGL((pgrad_kernel<MATERN, COS, DERIV_HIGH_SPLIT, false, false>), grid, dim3(256), 0, s, b, q, sc);
+  } else if (deriv == DERIV_HIGH_D2) {
+    if constexpr (!CLS)
+      hipLaunchKernelGGL((pgrad_kernel<MATERN, COS, DERIV_HIGH_D2, false, false>), grid, dim3(256), 0, s, b, q, sc);
+  } else if (deriv == DERIV_HIGH_SPLIT_D2) {
+    if constexpr (!CLS)
+      hipLaunchKernelGGL((pgrad_kernel<MATERN, COS, DERIV_HIGH_SPLIT_D2, false, false>), grid, dim3(256), 0, s, b, q, sc);
   } else {
     hipLaunchKernelGGL((pgrad_kernel<MATERN, COS, 1, false, CLS>), grid, dim3(256), 0, s, b, q, sc);
   }
@@ -795,11 +818,12 @@ hipError_t launch_pgrad(int kind, int q, int mode1d, const PGradArgs* a, int nax
                           shard_n > 1))
     return hipErrorInvalidValue;
   int deriv = a[0].deriv;
-  // one mode per launch (the weighted modes, DERIV_BOTH to DERIV_HIGH_SPLIT, carry their weights per
-  // axis): 2D per-pair contraction only; DERIV_SPLIT and DERIV_HIGH_SPLIT need their second operand
+  // one mode per launch (the weighted modes, DERIV_BOTH to DERIV_HIGH_SPLIT_D2, carry their weights per
+  // axis): 2D per-pair contraction only; the modes that contract dL/dD1 or dL/dDD need that operand
   for (int k = 0; k < naxes; ++k)
     if ((deriv_weighted(deriv) && (a[k].deriv != deriv || a[k].cls.ncls > 0 || mode1d)) ||
-        (!deriv_weighted(deriv) && deriv_weighted(a[k].deriv)) || (deriv_stores_d1(a[k].deriv) && !a[k].GD1))
+        (!deriv_weighted(deriv) && deriv_weighted(a[k].deriv)) || (deriv_stores_d1(a[k].deriv) && !a[k].GD1) ||
+        (deriv_stores_d2(a[k].deriv) && !a[k].GD2))
       return hipErrorInvalidValue;
   switch (kind) {
     case SE_COS: launch_pg_t<false, true>(b, naxes, blocks_per_axis, q, deriv, mode1d, sc, s); break;

@@ -124,6 +124,10 @@ class gpk_high3(ctypes.Structure):
     _fields_ = [("c4", ctypes.c_double * 3), ("c3", ctypes.c_double * 3)]
 
 
+class gpk_bicross3(ctypes.Structure):
+    _fields_ = [("q", ctypes.c_double * 3)]
+
+
 class gpk_gemm_case(ctypes.Structure):
     _fields_ = [
         ("M", ctypes.c_int32), ("N", ctypes.c_int32), ("K", ctypes.c_int32), ("K2", ctypes.c_int32),
@@ -229,6 +233,11 @@ EXPORTS = {
                          ctypes.POINTER(gpk_drift3), ctypes.POINTER(gpk_high3), ctypes.c_double,
                          ctypes.POINTER(ctypes.c_void_p)], ctypes.c_int),
     "gpk_high_info3": ([ctypes.c_void_p, _dp, _dp], ctypes.c_int),
+    "gpk_create3_opq": ([ctypes.POINTER(gpk_problem3), ctypes.POINTER(gpk_operator3x), ctypes.POINTER(gpk_coef3),
+                         ctypes.POINTER(gpk_bdata3), ctypes.POINTER(gpk_conv3), ctypes.POINTER(gpk_cross3),
+                         ctypes.POINTER(gpk_drift3), ctypes.POINTER(gpk_high3), ctypes.POINTER(gpk_bicross3),
+                         ctypes.c_double, ctypes.POINTER(ctypes.c_void_p)], ctypes.c_int),
+    "gpk_bicross_info3": ([ctypes.c_void_p, _dp], ctypes.c_int),
     "gpk_destroy3": ([ctypes.c_void_p], ctypes.c_int),
     "gpk_num_params3": ([ctypes.c_void_p, ctypes.POINTER(ctypes.c_int64)], ctypes.c_int),
     "gpk_set_params3": ([ctypes.c_void_p, _dp, ctypes.c_int64], ctypes.c_int),
@@ -261,6 +270,9 @@ EXPORTS = {
                              ctypes.c_double, ctypes.c_double, _dp, _dp, _dp], ctypes.c_int),
     "gpk_assemble_pairs4": ([ctypes.c_int32, _dp, ctypes.c_int32, _dp, _dp, _dp, ctypes.c_int32, ctypes.c_double,
                              ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, _dp, _dp, _dp],
+                            ctypes.c_int),
+    "gpk_assemble_pairs5": ([ctypes.c_int32, _dp, ctypes.c_int32, _dp, _dp, _dp, ctypes.c_int32, ctypes.c_double,
+                             ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, _dp, _dp, _dp, _dp],
                             ctypes.c_int),
     "gpk_assemble_pairs_time": ([ctypes.c_int32, _dp, ctypes.c_int32, _dp, _dp, _dp, ctypes.c_int32, ctypes.c_double,
                                  ctypes.c_double, ctypes.c_int32, ctypes.c_int32, _dp], ctypes.c_int),
@@ -572,6 +584,20 @@ def assemble_pairs4(kind, x, paras, jitter=0.0, c4=0.0, c3=0.0, c2=1.0, c1=0.0, 
                                      float(c4), float(c3), float(c2), float(c1), dptr(K), dptr(D),
                                      dptr(D1) if split else None))
     return (K, D, D1) if split else (K, D)
+
+
+def assemble_pairs5(kind, x, paras, jitter=0.0, c4=0.0, c3=0.0, c2=1.0, c1=0.0, split=False):
+    """The modes an axis of a bi-pair assembles in (gpk_assemble_pairs5): assemble_pairs4's blocks and
+    D2 = DD_x1_kappa alone: (K, D, D2), or with split (K, D, D1, D2)."""
+    x = f64(x).reshape(-1)
+    lw, ll, fr = (f64(paras[k]).reshape(-1) for k in ("log-w", "log-ls", "freq"))
+    n = x.size
+    K, D, D1, D2 = (np.empty((max(n, 1), max(n, 1))) for _ in range(4))
+    k = KIND_IDS[kind] if isinstance(kind, str) else int(kind)
+    check(load().gpk_assemble_pairs5(k, dptr(x), n, dptr(lw), dptr(ll), dptr(fr), lw.size, float(jitter),
+                                     float(c4), float(c3), float(c2), float(c1), dptr(K), dptr(D),
+                                     dptr(D1) if split else None, dptr(D2)))
+    return (K, D, D1, D2) if split else (K, D, D2)
 
 
 def assemble_pairs_time(kind, x, paras, c2=1.0, c1=0.0, split=False, iters=200):

@@ -631,6 +631,75 @@ def solution_3d_oph(equation):
     return _OPH3D[equation]()
 
 
+# Equations with mixed fourth-order partials on [0, 1]^3 (gpk_create3_opq): as EQUATIONS_3D_OPH's entries,
+# plus bicross = (q_12, q_13, q_23), the constants of q_jk d^4 u / dx_j^2 dx_k^2.
+_PLATE_KAPPA, _PLATE_OM, _SH_EPS, _SH_R, _MIXED4_Q = 0.01, 2.0, 0.1, 0.3, 0.01
+_NO_DRIFT, _ZERO3 = (None, None, None), (0.0, 0.0, 0.0)
+
+
+def _plate_t_sin():
+    # u = sin(2x) sin(3y) sin(om t + 1/2), the Kirchhoff plate in (x, y):  u_tt + kappa (u_xxxx + 2 u_xxyy + u_yyyy)
+    # = (169 kappa - om^2) u; clamped edges: u and u_x on the x walls, u and u_y on the y walls (faces 0-3); u and u_t
+    # on the initial face (4)
+    om, ka = _PLATE_OM, _PLATE_KAPPA
+    u = lambda x, y, t: s_(2 * x) * s_(3 * y) * s_(om * t + 0.5)
+    grad = (lambda x, y, t: 2.0 * c_(2 * x) * s_(3 * y) * s_(om * t + 0.5),
+            lambda x, y, t: 3.0 * s_(2 * x) * c_(3 * y) * s_(om * t + 0.5),
+            lambda x, y, t: om * s_(2 * x) * s_(3 * y) * c_(om * t + 0.5))
+    f = lambda x, y, t: (169.0 * ka - om * om) * u(x, y, t)
+    return u, f, Operator3X((0.0, 0.0, 1.0), _ZERO3, faces=NO_FINAL_FACE), 0b011111, grad, \
+        _ZERO3, _ZERO3, _NO_DRIFT, ((ka, ka, 0.0), _ZERO3), (2.0 * ka, 0.0, 0.0)
+
+
+def _biharmonic_3d_sin():
+    # steady, u = sin(2x) sin(3y) sin(z):  lap^2 u = 196 u; u and du/dn on all six faces
+    u = lambda x, y, z: s_(2 * x) * s_(3 * y) * s_(z)
+    grad = (lambda x, y, z: 2.0 * c_(2 * x) * s_(3 * y) * s_(z),
+            lambda x, y, z: 3.0 * s_(2 * x) * c_(3 * y) * s_(z),
+            lambda x, y, z: s_(2 * x) * s_(3 * y) * c_(z))
+    f = lambda x, y, z: 196.0 * u(x, y, z)
+    return u, f, Operator3X(_ZERO3, _ZERO3), ALL_FACES, grad, _ZERO3, _ZERO3, _NO_DRIFT, \
+        ((1.0, 1.0, 1.0), _ZERO3), (2.0, 2.0, 2.0)
+
+
+def _swift_hohenberg_t_sin():
+    # u = e^{-t} sin(2x) sin(3y):  u_t + (1 - r) u + 2 eps lap u + eps^2 lap^2 u + u^3
+    # = (-r - 26 eps + 169 eps^2) u + u^3; u and du/dn on the four space walls, u on the initial face
+    e, r = _SH_EPS, _SH_R
+    u = lambda x, y, t: np.exp(-t) * s_(2 * x) * s_(3 * y)
+    grad = (lambda x, y, t: 2.0 * np.exp(-t) * c_(2 * x) * s_(3 * y),
+            lambda x, y, t: 3.0 * np.exp(-t) * s_(2 * x) * c_(3 * y),
+            lambda x, y, t: -u(x, y, t))
+    f = lambda x, y, t: (-r - 26.0 * e + 169.0 * e * e) * u(x, y, t) + u(x, y, t) ** 3
+    return u, f, Operator3X((2.0 * e, 2.0 * e, 0.0), (0.0, 0.0, 1.0), react=(1.0 - r, 0.0, 1.0), faces=NO_FINAL_FACE), \
+        0b001111, grad, _ZERO3, _ZERO3, _NO_DRIFT, ((e * e, e * e, 0.0), _ZERO3), (2.0 * e * e, 0.0, 0.0)
+
+
+def _mixed4_3d_sin():
+    # steady, u = sin(2x) sin(3y) sin(z), no order above two on one axis (so eq_residual can run):
+    # -lap u + q (u_xxyy + u_xxzz + u_yyzz) = (14 + 49 q) u
+    q = _MIXED4_Q
+    u = lambda x, y, z: s_(2 * x) * s_(3 * y) * s_(z)
+    grad = (lambda x, y, z: 2.0 * c_(2 * x) * s_(3 * y) * s_(z),
+            lambda x, y, z: 3.0 * s_(2 * x) * c_(3 * y) * s_(z),
+            lambda x, y, z: s_(2 * x) * s_(3 * y) * c_(z))
+    f = lambda x, y, z: (14.0 + 49.0 * q) * u(x, y, z)
+    return u, f, Operator3X((-1.0, -1.0, -1.0), _ZERO3), 0, grad, _ZERO3, _ZERO3, _NO_DRIFT, \
+        (_ZERO3, _ZERO3), (q, q, q)
+
+
+_OPQ3D = {"plate_t-sin": _plate_t_sin, "biharmonic_3d-sin": _biharmonic_3d_sin,
+          "swift_hohenberg_t-sin": _swift_hohenberg_t_sin, "mixed4_3d-sin": _mixed4_3d_sin}
+EQUATIONS_3D_OPQ = list(_OPQ3D)
+
+
+def solution_3d_opq(equation):
+    """(u, src, operator, dfaces, grad_u, conv, cross, drift, high, bicross) of an EQUATIONS_3D_OPQ entry:
+    the first nine as solution_3d_oph's, bicross = (q_12, q_13, q_23), the constants of the terms q_jk
+    d^4 u / dx_j^2 dx_k^2."""
+    return _OPQ3D[equation]()
+
+
 def boundary_2d(u_mesh):
     """get_boundary_vals: hstack(U[0,:], U[-1,:], U[:,0], U[:,-1]) (model_GP_solver_2d.py:377-379)."""
     return np.hstack((u_mesh[0, :], u_mesh[-1, :], u_mesh[:, 0], u_mesh[:, -1]))

@@ -38,7 +38,9 @@ b_k(x) du/dx_k (divergence form -div(a grad u), a variable velocity over a const
 through gpk_create3_opb: DeviceSolver3(..., drift=), `-equation=heat_div_t-sin`, configs in
 gpk/config3d_opb/.  Third- and fourth-order terms c4_k d^4u/dx_k^4 + c3_k d^3u/dx_k^3 (KdV,
 Kuramoto-Sivashinsky, the clamped beam) run through gpk_create3_oph: DeviceSolver3(..., high=(c4, c3)),
-`-equation=kdv_t-sin`, configs in gpk/config3d_oph/.
+`-equation=kdv_t-sin`, configs in gpk/config3d_oph/.  Mixed fourth-order partials q_jk
+d^4u/dx_j^2 dx_k^2 (the Kirchhoff plate, the biharmonic, Swift-Hohenberg) run through gpk_create3_opq:
+DeviceSolver3(..., bicross=(q12, q13, q23)), `-equation=plate_t-sin`, configs in gpk/config3d_opq/.
 """
 import ctypes
 import os
@@ -53,7 +55,7 @@ from ._lib import check, dptr, f64
 from .cli import parse_flags
 from .core import tree_flatten, tree_unflatten
 from .equations import (EQUATIONS_3D, EQUATIONS_3D_OP, EQUATIONS_3D_OPB, EQUATIONS_3D_OPC, EQUATIONS_3D_OPH,
-                        EQUATIONS_3D_OPM,
+                        EQUATIONS_3D_OPM, EQUATIONS_3D_OPQ, solution_3d_opq,
                         EQUATIONS_3D_OPN, EQUATIONS_3D_OPV, EQUATIONS_3D_OPX, Operator3, Operator3V, Operator3X,
                         deriv_boundary_3d, drift_fields, solution_3d, solution_3d_op, solution_3d_opb,
                         solution_3d_opc, solution_3d_oph, solution_3d_opm, solution_3d_opn, solution_3d_opv, solution_3d_opx)
@@ -89,7 +91,8 @@ class DeviceSolver3:
 
     def __init__(self, eq, kind, xs, src, bvals, Q=30, jitter=1e-6, llk_weight=200.0, logdet=True,
                  lr=0.01, freq_scale=20.0, device=0, b1=0.9, b2=0.999, eps=1e-8, refine=False,
-                 operator=None, dfaces=0, dvals=None, conv=None, cross=None, drift=None, high=None):
+                 operator=None, dfaces=0, dvals=None, conv=None, cross=None, drift=None, high=None,
+                 bicross=None):
         """refine: one gated refinement step after every solve of the step (GPK_FLAG3_REFINE);
         'gemm' also forces its two-GEMM route (GPK_FLAG3_REFINE_GEMM; tests, A/B).
         operator: an Operator3 (or a dict of its fields) -- the handle then solves that operator
@@ -115,7 +118,11 @@ class DeviceSolver3:
         high: (c4, c3), two triples of floats, the constants of the terms c4_k d^4 u / dx_k^4 + c3_k
         d^3 u / dx_k^3 (gpk_create3_oph; KdV, Kuramoto-Sivashinsky, the beam); a non-zero one needs
         an Operator3X or Operator3V as conv does, and an Operator3V's field a_k multiplies all four
-        orders of its axis.  None or six zeros is the handle without them."""
+        orders of its axis.  None or six zeros is the handle without them.
+        bicross: three floats q_12, q_13, q_23, the constants of the mixed fourth-order partials q_jk
+        d^4 u / dx_j^2 dx_k^2 (gpk_create3_opq; the plate, the biharmonic); a non-zero one needs an
+        Operator3X or Operator3V as cross does, whose fields a_k do not multiply it.  None or three
+        zeros is the handle without them."""
         lib = _lib.load()
         if len(xs) != 3:
             raise ValueError("three coordinate axes")
@@ -169,7 +176,13 @@ class DeviceSolver3:
                 raise ValueError("high has two entries (c4, c3), each a triple")
             if not any(c != 0.0 for t in high for c in t):
                 high = None
-        if dfaces or conv or cross or drift or high:
+        if bicross is not None:
+            bicross = tuple(float(q) for q in np.asarray(bicross, np.float64).reshape(-1))
+            if len(bicross) != 3:
+                raise ValueError("bicross has three entries (q_12, q_13, q_23)")
+            if not any(q != 0.0 for q in bicross):
+                bicross = None
+        if dfaces or conv or cross or drift or high or bicross:
             if dfaces and dvals is None:
                 raise ValueError("dfaces needs dvals (the six-face layout of bvals)")
             if dfaces:
@@ -180,7 +193,7 @@ class DeviceSolver3:
                 raise ValueError("%s needs an Operator3X or Operator3V"
                                  % ("derivative boundary data" if dfaces else "a convective term" if conv
                                     else "a mixed partial" if cross else "a drift field" if drift
-                                    else "a high-order term"))
+                                    else "a high-order term" if high else "a mixed fourth-order partial"))
             c = _lib.gpk_operator3x()
             cf = _lib.gpk_coef3()
             if isinstance(operator, Operator3V):
@@ -197,7 +210,7 @@ class DeviceSolver3:
             bd = _lib.gpk_bdata3()
             if dfaces:
                 bd.dfaces, bd.dvals = dfaces, dptr(self._dvals)
-            if high:
+            if high or bicross:
                 cv, mx, dr, hi = _lib.gpk_conv3(), _lib.gpk_cross3(), _lib.gpk_drift3(), _lib.gpk_high3()
                 cv.g[:] = conv or (0.0, 0.0, 0.0)
                 mx.m[:] = cross or (0.0, 0.0, 0.0)
@@ -205,7 +218,14 @@ class DeviceSolver3:
                 for k, b in enumerate(self._drift):
                     if b is not None:
                         dr.b[k] = dptr(b)
-                hi.c4[:], hi.c3[:] = high
+                hi.c4[:], hi.c3[:] = high or ((0.0, 0.0, 0.0), (0.0, 0.0, 0.0))
+            if bicross:
+                bq = _lib.gpk_bicross3()
+                bq.q[:] = bicross
+                check(lib.gpk_create3_opq(ctypes.byref(p), ctypes.byref(c), ctypes.byref(cf), ctypes.byref(bd),
+                                          ctypes.byref(cv), ctypes.byref(mx), ctypes.byref(dr), ctypes.byref(hi),
+                                          ctypes.byref(bq), float(freq_scale), ctypes.byref(h)))
+            elif high:
                 check(lib.gpk_create3_oph(ctypes.byref(p), ctypes.byref(c), ctypes.byref(cf), ctypes.byref(bd),
                                           ctypes.byref(cv), ctypes.byref(mx), ctypes.byref(dr), ctypes.byref(hi),
                                           float(freq_scale), ctypes.byref(h)))
@@ -422,6 +442,12 @@ class DeviceSolver3:
         check(_lib.load().gpk_cross_info3(self._h, dptr(m)))
         return tuple(m.tolist())
 
+    def bicross_info(self):
+        """(q_12, q_13, q_23) (gpk_bicross_info3); zeros on every handle made without bi-pairs."""
+        q = np.zeros(3)
+        check(_lib.load().gpk_bicross_info3(self._h, dptr(q)))
+        return tuple(q)
+
     def high_info(self):
         """(c4, c3), two triples (gpk_high_info3); zeros on every handle made without high-order
         terms."""
@@ -476,13 +502,14 @@ class GP_solver_3d_single(SolverBase):
     opm_eq_types = tuple(sorted({e.split("-")[0] for e in EQUATIONS_3D_OPM}))
     opb_eq_types = tuple(sorted({e.split("-")[0] for e in EQUATIONS_3D_OPB}))
     oph_eq_types = tuple(sorted({e.split("-")[0] for e in EQUATIONS_3D_OPH}))
+    opq_eq_types = tuple(sorted({e.split("-")[0] for e in EQUATIONS_3D_OPQ}))
     early_stop_enabled = True
 
     def __init__(self, bvals, X_col, src_vals, jitter, trick_paras, device=0, X_test=None, u_test=None):
         self.eq_type = trick_paras["equation"].split("-")[0]
         assert self.eq_type in (self.eq_types + self.op_eq_types + self.opx_eq_types + self.opv_eq_types
                                 + self.opn_eq_types + self.opc_eq_types + self.opm_eq_types + self.opb_eq_types
-                                + self.oph_eq_types)
+                                + self.oph_eq_types + self.opq_eq_types)
         self.operator = None
         given = trick_paras.get("operator")
         if isinstance(given, Operator3V):
@@ -511,10 +538,18 @@ class GP_solver_3d_single(SolverBase):
         # high-order terms: given as (c4, c3), or the equation's own (likewise)
         high = trick_paras.get("high")
         self.high = None if high is None else tuple(tuple(float(c) for c in t) for t in high)
+        # mixed fourth-order partials: given as (q12, q13, q23), or the equation's own (likewise)
+        bicross = trick_paras.get("bicross")
+        self.bicross = None if bicross is None else tuple(float(q) for q in bicross)
         if self.eq_type in (self.opn_eq_types + self.opc_eq_types + self.opm_eq_types + self.opb_eq_types
-                            + self.oph_eq_types):
-            if self.eq_type in self.oph_eq_types:
-                _, _, op, dfaces, grad_u, conv, cross, drift, high = solution_3d_oph(trick_paras["equation"])
+                            + self.oph_eq_types + self.opq_eq_types):
+            if self.eq_type in self.oph_eq_types + self.opq_eq_types:
+                if self.eq_type in self.opq_eq_types:
+                    _, _, op, dfaces, grad_u, conv, cross, drift, high, bicross = solution_3d_opq(trick_paras["equation"])
+                    if self.bicross is None:
+                        self.bicross = tuple(bicross)
+                else:
+                    _, _, op, dfaces, grad_u, conv, cross, drift, high = solution_3d_oph(trick_paras["equation"])
                 if self.conv is None:
                     self.conv = tuple(conv)
                 if self.cross is None:
@@ -572,7 +607,7 @@ class GP_solver_3d_single(SolverBase):
                                  freq_scale=tp.get("freq_scale", 20.0), device=int(tp.get("device", device)),
                                  refine=bool(tp.get("refine", False)), operator=self.operator,
                                  dfaces=self.dfaces, dvals=self.dvals, conv=self.conv, cross=self.cross,
-                                 drift=self.drift, high=self.high)
+                                 drift=self.drift, high=self.high, bicross=self.bicross)
         self._version = 0
 
     def eq_residual(self, params, X_test, src_test):
@@ -631,6 +666,12 @@ class GP_solver_3d_single(SolverBase):
                     d = [0, 0, 0]
                     d[k] = 1
                     r = r + b * self.dev.predict_deriv(*axes, deriv=tuple(d))
+        if self.bicross is not None and any(self.bicross):  # + sum_{j<k} q_jk d^4 u / dx_j^2 dx_k^2
+            for (j, k), q in zip(((0, 1), (0, 2), (1, 2)), self.bicross):
+                if q != 0.0:
+                    d = [0, 0, 0]
+                    d[j] = d[k] = 2
+                    r = r + q * self.dev.predict_deriv(*axes, deriv=tuple(d))
         return r - np.asarray(src_test, np.float64).reshape(r.shape)
 
     # the device holds the params: reading fetches them, train()'s final assignment is a no-op
@@ -735,6 +776,8 @@ def test(trick_paras, solver_cls=None):
         u, src, op = solution_3d_opb(trick_paras["equation"])[:3]
     elif trick_paras["equation"] in EQUATIONS_3D_OPH:  # (... and its high-order weights)
         u, src, op = solution_3d_oph(trick_paras["equation"])[:3]
+    elif trick_paras["equation"] in EQUATIONS_3D_OPQ:  # (... and its bi-pair weights)
+        u, src, op = solution_3d_opq(trick_paras["equation"])[:3]
     else:
         u, src = solution_3d(trick_paras["equation"])
     scale = trick_paras["scale"]
@@ -773,13 +816,15 @@ def load_config(equation):
     """./config3d/<equation>.yaml (the operator equations: ./config3d_op/, the mixed-order ones:
     ./config3d_opx/, the coefficient-field ones: ./config3d_opv/, derivative boundary data:
     ./config3d_opn/, convective terms: ./config3d_opc/, mixed partials: ./config3d_opm/, drift fields:
-    ./config3d_opb/, third- and fourth-order terms: ./config3d_oph/), falling back to the package's copy."""
+    ./config3d_opb/, third- and fourth-order terms: ./config3d_oph/, mixed fourth-order partials:
+    ./config3d_opq/), falling back to the package's copy."""
     cdir = ("config3d_op" if equation in EQUATIONS_3D_OP else "config3d_opx" if equation in EQUATIONS_3D_OPX
             else "config3d_opv" if equation in EQUATIONS_3D_OPV else "config3d_opn" if equation in EQUATIONS_3D_OPN
             else "config3d_opc" if equation in EQUATIONS_3D_OPC
             else "config3d_opm" if equation in EQUATIONS_3D_OPM
             else "config3d_opb" if equation in EQUATIONS_3D_OPB
-            else "config3d_oph" if equation in EQUATIONS_3D_OPH else "config3d")
+            else "config3d_oph" if equation in EQUATIONS_3D_OPH
+            else "config3d_opq" if equation in EQUATIONS_3D_OPQ else "config3d")
     for base in (os.getcwd(), os.path.dirname(os.path.abspath(__file__))):
         p = os.path.join(base, cdir, equation + ".yaml")
         if os.path.exists(p):
@@ -789,7 +834,8 @@ def load_config(equation):
 
 
 def build_config(args, allowed=EQUATIONS_3D + EQUATIONS_3D_OP + EQUATIONS_3D_OPX + EQUATIONS_3D_OPV
-                 + EQUATIONS_3D_OPN + EQUATIONS_3D_OPC + EQUATIONS_3D_OPM + EQUATIONS_3D_OPB + EQUATIONS_3D_OPH):
+                 + EQUATIONS_3D_OPN + EQUATIONS_3D_OPC + EQUATIONS_3D_OPM + EQUATIONS_3D_OPB + EQUATIONS_3D_OPH
+                 + EQUATIONS_3D_OPQ):
     """The 2-axis build_config (scale, kernel class, other_paras) on the config3d files."""
     assert args.equation in allowed
     config = load_config(args.equation)

@@ -728,9 +728,7 @@ int gpk_drift_info3(const gpk_handle3* h, int32_t has[3]);
  * face kernels are those of the same handle without the high-order weights.
  * ORDER 4 IS THE CEILING: the Matern-5/2 radial factor has a continuous fourth derivative with a
  * kink at d = 0 and no fifth derivative, and both kernel families stop there.
- * Not built: orders above four; mixed high-order partials such as u_xxyy (the true biharmonic and
- * 2-D Kuramoto-Sivashinsky need them; a follow-up that reuses the cross-pair stages with order-2
- * blocks); boundary data on second derivatives (simply supported ends); the sharded, 1-axis and
+ * Not built: orders above four; boundary data on second derivatives (simply supported ends); the sharded, 1-axis and
  * 2-axis handles; the class path; derivatives above 2 in gpk_predict_deriv3 and gpk_evaluate3, which
  * keep rejecting 3. */
 typedef struct gpk_high3 {
@@ -748,6 +746,44 @@ int gpk_create3_oph(const gpk_problem3* p, const gpk_operator3x* op, const gpk_c
  * reporting c2 and c1; gpk_operator_info3 returns GPK_EINVAL on a handle with a high-order axis, as
  * it does for a mixed axis. */
 int gpk_high_info3(const gpk_handle3* h, double c4[3], double c3[3]);
+
+/* Mixed fourth-order partials (the Kirchhoff plate u_tt + kappa Delta^2 u, the true biharmonic
+ * Delta^2, Swift-Hohenberg, the linear part of Cahn-Hilliard in two space dimensions).  A pair
+ * (j, k), j < k, of weight q_jk != 0 adds
+ *     q_jk d^4 u / d x_j^2 d x_k^2
+ * (u_xxyy for the pair (1,2)) to the equation of a gpk_create3_oph handle.  q_jk is a constant, like m_jk: the gpk_coef3 fields
+ * a_k do not multiply it, and the reverse pass reads R itself, never W_k.  Everything is fp64.  With
+ * A_j, T_j, K_k^{-1} and R as on the oph handle and DD_k the plain, unweighted second-derivative
+ * block of axis k (the block gpk_assemble_pairs assembles at c1 = 0), per present pair:
+ *     Z2_j  = DD_j x_j A_j                    (shared by the pairs (1,2) and (1,3))
+ *     H2_jk = K_k^{-1} x_k Z2_j               (a solve)
+ *     B_jk  = q_jk DD_k x_k H2_jk
+ *     R     = [the oph handle's R, drift terms included] + B_13 + B_12 + B_23   (that fixed order)
+ *     Hb2_jk = q_jk DD_k^T x_k R,   Zb2_jk = K_k^{-1} x_k Hb2_jk   (a solve)
+ *     G_DDk += v q_jk R_(k) H2_jk,(k)^T,   G_Kk -= v Zb2_jk,(k) H2_jk,(k)^T        (outer axis)
+ *     G_DDj += v Zb2_jk,(j) A_j,(j)^T,     T_j += DD_j^T x_j Zb2_jk before X_j = K_j^{-1} x_j T_j
+ * The drift outputs E_k = b_k R are formed on the final R; eq_gap, the log joint, the boundary and
+ * derivative-boundary terms, gpk_criterion3, gpk_loss_terms3, gpk_boundary_terms3 and the Adam
+ * kernels keep their formulas on the new R; predictions depend on K_k only.  Both axes of a pair
+ * are entered like mixed-order ones and may have every other weight zero; they always assemble and
+ * contract with the four-field evaluation.  Under GPK_FLAG3_REFINE both solves of a pair are refined
+ * on both routes, gated on the outer axis.  gpk_stage_variants3 reports eight further launches.
+ * The per-axis ceiling of order four is untouched: Delta^2 needs only the second derivative of each
+ * factor, which Matern-5/2 has.
+ * Not built: fields on q; pairs of other orders such as u_xxxy or u_xyy; boundary data on second
+ * derivatives; the sharded, 1-axis and 2-axis handles; the class path. */
+typedef struct gpk_bicross3 {
+  double q[3]; /* pairs (1,2), (1,3), (2,3) */
+} gpk_bicross3;
+/* p, op, cf, bd, cv, mx, dr and hi as on gpk_create3_oph (all but p and op may be NULL).  bq == NULL
+ * or q = (0, 0, 0) is gpk_create3_oph(p, op, cf, bd, cv, mx, dr, hi, ...) itself: the same stage list,
+ * launches and bits.  GPK_EINVAL, before any device work, on a non-finite q, and on everything the
+ * older create calls reject. */
+int gpk_create3_opq(const gpk_problem3* p, const gpk_operator3x* op, const gpk_coef3* cf,
+                    const gpk_bdata3* bd, const gpk_conv3* cv, const gpk_cross3* mx, const gpk_drift3* dr,
+                    const gpk_high3* hi, const gpk_bicross3* bq, double freq_scale, gpk_handle3** out);
+/* The bi-pair weights; zeros on every older kind of 3-axis handle. */
+int gpk_bicross_info3(const gpk_handle3* h, double q[3]);
 
 int gpk_num_params3(const gpk_handle3* h, int64_t* n);
 int gpk_set_params3(gpk_handle3* h, const double* flat, int64_t n);
@@ -867,6 +903,14 @@ int gpk_assemble_pairs2(int32_t kind, const double* x, int32_t n, const double* 
 int gpk_assemble_pairs4(int32_t kind, const double* x, int32_t n, const double* logw, const double* logls,
                         const double* freq, int32_t q, double jitter, double c4, double c3, double c2,
                         double c1, double* K_out, double* D_out, double* D1_out);
+
+/* The modes an axis of a bi-pair (gpk_create3_opq) assembles in: gpk_assemble_pairs4's K_out, D_out and
+ * D1_out, bit for bit, and D2_out = DD_x1_kappa alone (required), the block gpk_assemble_pairs4 gives
+ * as D_out at (c4, c3, c2, c1) = (0, 0, 1, 0), n x n row-major and symmetric to the bit.  D1_out == NULL:
+ * the mode without D1. */
+int gpk_assemble_pairs5(int32_t kind, const double* x, int32_t n, const double* logw, const double* logls,
+                        const double* freq, int32_t q, double jitter, double c4, double c3, double c2,
+                        double c1, double* K_out, double* D_out, double* D1_out, double* D2_out);
 
 #ifdef __cplusplus
 }
