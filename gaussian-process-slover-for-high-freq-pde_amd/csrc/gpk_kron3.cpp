@@ -55,6 +55,13 @@
 // (k3_combine_b), and the reverse pass reads E_k = b_k R: T_k += D1_k^T x_k E_k before X_k and
 // G_D1k += v E_k,(k) A_k,(k)^T: two or three further launches (build_drift_stages).  b_k is data: dL/dU
 // has no direct term.
+// Quadratic gradient terms (gpk_create3_opg, s_k (du/dx_k)^2 + x_jk du/dx_j du/dx_k): axis k is
+// gradient-active when g_k, s_k or a pair weight x_jk with k in it is non-zero, and assembles in the
+// split mode its other terms imply.  P_k = D1_k x_k A_k per such axis (the V_k launch's position, alpha
+// 1); k3_combine_g forms N = sum_k g_k P_k, Gamma and R, and writes Q_k = (g_k U + 2 s_k P_k + sum_j x_jk
+// P_j) . R; T_k += D1_k^T x_k Q_k (the dual slot of stage 3), G_D1k = v Q_k,(k) A_k,(k)^T (the convective
+// G_D1k launch's position), and dL/dU += v N . R (k3_adam_u_c) (build_gradsq_stages, which stands in
+// build_conv_stages' place on such a handle).
 // GPK_FLAG3_REFINE: every one of the eight solves (A1, A2, A3, T, S, X1, X2, X3) is followed by
 // one refinement step X += K_k^{-1} (B - K_k X) gated on the axis's pst: one fused panel launch
 // (refine_panel.hip), or two GEMMs where its panels do not fit LDS (build_refine).
@@ -136,6 +143,16 @@ struct gpk_handle3 {
   // allocations of their own (Rx / Ryp / Rz and T* are refinement scratch at various points).
   int conv = 0;
   double gconv[3] = {};
+  // gpk_create3_opg: the quadratic gradient weights s_k and x_jk (pairs (1,2), (1,3), (2,3)) (gsq = 0:
+  // none, and nothing below is allocated or launched).  gact[k]: axis k is gradient-active (g_k, s_k or
+  // one of its pair weights non-zero; on every other handle this is g_k != 0).  On such a handle conv
+  // is set (the two further launches, N and k3_adam_u_c are the convective handle's), V, Q and Qp stay
+  // null, and per gradient-active axis P[k] = D1_k x_k A_k and Qk[k], its reverse operand (both
+  // permuted on axis 2), are allocations of their own: nothing aliases build_refine's scratch.
+  int gsq = 0;
+  double gs[3] = {}, gx[3] = {};
+  bool gact[3] = {};
+  double *P[3] = {}, *Qk[3] = {};
   double *D1[3] = {}, *GD1[3] = {}, *V[3] = {}, *Nsum = nullptr, *Q = nullptr, *Qp = nullptr;
   // gpk_create3_opm: the cross weights of the pairs (1,2), (1,3), (2,3) (cross = 0: none, and
   // nothing below is allocated or launched).  Pair t = (j, k): Hx[t] = H_jk, Cx[t] = C_jk, Hb[t] =
@@ -227,6 +244,39 @@ void build_conv_stages(gpk_handle3* h) {
   if (g[2] != 0.0) {
     cv.push_back(scaled(gemm_desc(h->A3, P3, 0, D1[2], P3, 1, h->V[2], P3, M3, P3, P3), g[2]));
     cg.push_back(vs(scaled(gemm_desc(h->Q, P3, 1, h->A3, P3, 0, h->GD1[2], P3, P3, P3, M3), g[2])));
+  }
+}
+
+// Quadratic gradient terms (gpk_create3_opg), in build_conv_stages' place: per gradient-active axis
+// T_k becomes the dual product D_k^T x_k W_k + D1_k^T x_k Q_k (alpha2 = 1: the weights are in Q_k), and
+// the two launches hold P_k = D1_k x_k A_k (alpha 1; k3_combine_g applies g_k, s_k and x_jk) and G_D1k =
+// v Q_k,(k) A_k,(k)^T.  Layouts and transposes are build_conv_stages' own.
+void build_gradsq_stages(gpk_handle3* h) {
+  const int P1 = h->g.p[0], P2 = h->g.p[1], P3 = h->g.p[2];
+  const int M1 = P2 * P3, M2 = P1 * P3, M3 = P1 * P2;
+  double* const* D1 = h->D1;
+  auto dual = [](GemmDesc& d, const double* A2, int lda2, const double* B2, int ldb2, int K2) {
+    d.A2 = A2; d.lda2 = lda2; d.ta2 = d.ta; d.B2 = B2; d.ldb2 = ldb2; d.tb2 = d.tb; d.K2 = K2; d.alpha2 = 1.0;
+  };
+  auto& t = h->stages[3];
+  if (h->gact[0]) dual(t[0], D1[0], P1, h->Qk[0], M1, P1);
+  if (h->gact[1]) dual(t[1], D1[1], P2, h->Qk[1], M2, P2);
+  if (h->gact[2]) dual(t[2], h->Qk[2], P3, D1[2], P3, P3);
+  h->cstages.assign(2, {});
+  auto& cp = h->cstages[0];
+  auto& cg = h->cstages[1];
+  auto vs = [](GemmDesc d) { d.vscale = 1; return d; };
+  if (h->gact[0]) {
+    cp.push_back(gemm_desc(D1[0], P1, 0, h->A1, M1, 0, h->P[0], M1, P1, M1, P1));
+    cg.push_back(vs(gemm_desc(h->Qk[0], M1, 0, h->A1, M1, 1, h->GD1[0], P1, P1, P1, M1)));
+  }
+  if (h->gact[1]) {
+    cp.push_back(gemm_desc(D1[1], P2, 0, h->A2p, M2, 0, h->P[1], M2, P2, M2, P2));
+    cg.push_back(vs(gemm_desc(h->Qk[1], M2, 0, h->A2p, M2, 1, h->GD1[1], P2, P2, P2, M2)));
+  }
+  if (h->gact[2]) {
+    cp.push_back(gemm_desc(h->A3, P3, 0, D1[2], P3, 1, h->P[2], P3, M3, P3, P3));
+    cg.push_back(vs(gemm_desc(h->Qk[2], P3, 1, h->A3, P3, 0, h->GD1[2], P3, P3, P3, M3)));
   }
 }
 
@@ -344,9 +394,10 @@ void build_pair_stages(gpk_handle3* h, const PairSet& ps, PairStages& out) {
   }
 }
 
-// the cross pairs: G = D1, dL/dD1 added to where the axis is convective (its G_D1k came first)
+// the cross pairs: G = D1, dL/dD1 added to where the axis is convective or gradient-active (its
+// G_D1k came first)
 void build_cross_stages(gpk_handle3* h) {
-  const PairSet ps{h->mx, h->D1, h->GD1, {h->gconv[0] != 0.0, h->gconv[1] != 0.0, h->gconv[2] != 0.0},
+  const PairSet ps{h->mx, h->D1, h->GD1, {h->gact[0], h->gact[1], h->gact[2]},
                    h->Z1, h->Z1p, h->Z2p, h->Zb12, h->Hx, h->Cx, h->Hb, h->Zb};
   build_pair_stages(h, ps, h->xs);
 }
@@ -374,10 +425,10 @@ void build_drift_stages(gpk_handle3* h) {
   const int M1 = P2 * P3, M2 = P1 * P3, M3 = P1 * P2;
   double* const* D1 = h->D1;
   const double* m = h->mx;
-  // axis k already has a G_D1k in the stream: convective, or an axis of a present pair
-  const bool held[3] = {h->gconv[0] != 0.0 || m[0] != 0.0 || m[1] != 0.0,
-                        h->gconv[1] != 0.0 || m[0] != 0.0 || m[2] != 0.0,
-                        h->gconv[2] != 0.0 || m[1] != 0.0 || m[2] != 0.0};
+  // axis k already has a G_D1k in the stream: convective or gradient-active, or an axis of a present pair
+  const bool held[3] = {h->gact[0] || m[0] != 0.0 || m[1] != 0.0,
+                        h->gact[1] || m[0] != 0.0 || m[2] != 0.0,
+                        h->gact[2] || m[1] != 0.0 || m[2] != 0.0};
   auto into = [](GemmDesc d, bool add, int vs) {
     d.vscale = vs;
     if (add) { d.beta = 1.0; d.C0 = d.C; d.ldc0 = d.ldc; }
@@ -436,7 +487,8 @@ void build_stages(gpk_handle3* h) {
                   scaled(gemm_desc(D[1], P2, 1, W2p, M2, 0, h->T2p, M2, P2, M2, P2), w[1]),
                   scaled(gemm_desc(W3, P3, 0, D[2], P3, 0, h->T3, P3, M3, P3, P3), w[2]), gd});
   }
-  if (h->conv) build_conv_stages(h);
+  if (h->gsq) build_gradsq_stages(h);
+  else if (h->conv) build_conv_stages(h);
   // X_k = K_k^{-1} x_k (c_k D_k^T x_k R) with the side outputs Y_k = S/2 + v X_k;  G_D2
   {
     GemmDesc gd = scaled(gemm_desc(W2p, M2, 0, h->A2p, M2, 1, h->GD[1], P2, P2, P2, M2), w[1]);
@@ -624,7 +676,7 @@ int enqueue_step3(gpk_handle3* h, int apply) {
   }
   TRY(check_launch(k3_launch_permute(h->Tm, h->Tp, g, h->s), "k3_permute"));
   TRY(launch_stage(h, 2));
-  if (h->conv) TRY(launch_descs(h, h->cstages[0]));  // V_k, from the refined A_k
+  if (h->conv) TRY(launch_descs(h, h->cstages[0]));  // V_k (gsq: P_k), from the refined A_k
   if (h->drift && !h->dstages[0].empty()) TRY(launch_descs(h, h->dstages[0]));  // Z_k no cross pair forms
   if (h->cross) {  // Z_j from the refined A_j, H_jk (pair (1,2): on the permuted Z_1), C_jk
     TRY(launch_descs(h, h->xs.st[0]));
@@ -642,7 +694,23 @@ int enqueue_step3(gpk_handle3* h, int apply) {
   C.g = g; C.Rx = h->Rx; C.Rz = h->Rz; C.Ryp = h->Ryp; C.F = h->F; C.Up = h->Up; C.Sp = h->Sp;
   C.eq = eq_layer(h); C.R = h->R; C.Rp = h->Rp; C.S = h->S;
   C.red_egap = h->red_egap; C.red_quad = h->red_quad;
-  if (h->bi) {  // k3_combine_b's superset: every older layer as the handle has it, absent ones null
+  if (h->gsq) {  // k3_combine_q's superset: N from the P_k (no V_k, Q or Qp here), then Gamma
+    K3CombineG Gx{};
+    K3CombineB& B = Gx.q.b;
+    K3CombineC& X = B.m.c;
+    X.v.c = C; X.v.rho = h->rho;
+    for (int a = 0; a < 3; ++a) {
+      X.v.a[a] = h->cf[a]; X.v.W[a] = h->W[a];
+      B.m.C[a] = h->Cx[a];
+      B.b[a] = h->bf[a]; B.Z[a] = h->Zd[a]; B.E[a] = h->Ed[a];
+      Gx.q.B[a] = h->Bq[a];
+      Gx.P[a] = h->P[a]; Gx.Qk[a] = h->Qk[a];
+      Gx.g[a] = h->gconv[a]; Gx.s[a] = h->gs[a]; Gx.x[a] = h->gx[a];
+    }
+    X.N = h->Nsum;
+    B.m.rp = h->Cx[0] || h->Cx[2] || h->Bq[0] || h->Bq[2];
+    TRY(check_launch(k3_launch_combine_g(Gx, h->s), "k3_combine_g"));
+  } else if (h->bi) {  // k3_combine_b's superset: every older layer as the handle has it, absent ones null
     K3CombineQ Qx{};
     K3CombineB& B = Qx.b;
     K3CombineC& X = B.m.c;
@@ -824,7 +892,7 @@ int check_problem3(const gpk_problem3* p) {
 int create3(const gpk_problem3* p, const gpk_operator3* op, double freq_scale, gpk_handle3** out,
             const gpk_operator3x* opx = nullptr, const gpk_coef3* cf = nullptr, const gpk_bdata3* bd = nullptr,
             const gpk_conv3* cv = nullptr, const gpk_cross3* mx = nullptr, const gpk_drift3* dr = nullptr,
-            const gpk_high3* hi = nullptr, const gpk_bicross3* bq = nullptr) {
+            const gpk_high3* hi = nullptr, const gpk_bicross3* bq = nullptr, const gpk_gradsq3* gq = nullptr) {
   TRY(check_problem3(p));
   const int ns[3] = {p->n1, p->n2, p->n3};
   TRY(check_device(p->device));
@@ -849,8 +917,20 @@ int create3(const gpk_problem3* p, const gpk_operator3* op, double freq_scale, g
       h->conv = 1;
       h->mode[a] = DERIV_SPLIT;
     }
-    // so does an axis of a pair with a cross weight (it owns D1_k and G_D1k as well)
     static const int pairs[3][2] = {{0, 1}, {0, 2}, {1, 2}};
+    h->gact[a] = h->gconv[a] != 0.0;
+    // so does a gradient-active axis (it owns D1_k and G_D1k: s_k, or a pair weight x_jk with a in it)
+    if (gq) {
+      h->gsq = h->conv = 1;
+      h->gs[a] = gq->s[a];
+      for (int t = 0; t < 3; ++t) {
+        h->gx[t] = gq->x[t];
+        if (gq->x[t] != 0.0 && (pairs[t][0] == a || pairs[t][1] == a)) h->gact[a] = true;
+      }
+      if (gq->s[a] != 0.0) h->gact[a] = true;
+      if (h->gact[a]) h->mode[a] = DERIV_SPLIT;
+    }
+    // so does an axis of a pair with a cross weight (it owns D1_k and G_D1k as well)
     for (int t = 0; t < 3 && mx; ++t)
       if (mx->m[t] != 0.0 && (pairs[t][0] == a || pairs[t][1] == a)) {
         h->mx[t] = mx->m[t];
@@ -993,6 +1073,10 @@ int create3(const gpk_problem3* p, const gpk_operator3* op, double freq_scale, g
     if (!deriv_stores_d1(h->mode[a])) continue;
     const int P = g.p[a];
     A3_(h->D1[a], (size_t)P * P); A3_(h->GD1[a], (size_t)P * P);
+    if (h->gsq) {  // P_k and Q_k per gradient-active axis; no V_k, Q or Qp on this handle
+      if (h->gact[a]) { A3_(h->P[a], np); A3_(h->Qk[a], np); }
+      continue;
+    }
     if (h->gconv[a] == 0.0) continue;
     A3_(h->V[a], np);
     if (a == 1) { A3_(h->Qp, np); }
@@ -1179,7 +1263,8 @@ namespace {
 // then be null or without faces): the argument checks of both, then the handle
 int create3_opn(const gpk_problem3* p, const gpk_operator3x* op, const gpk_coef3* cf, const gpk_bdata3* bd,
                 const gpk_conv3* cv, double freq_scale, gpk_handle3** out, const gpk_cross3* mx = nullptr,
-                const gpk_drift3* dr = nullptr, const gpk_high3* hi = nullptr, const gpk_bicross3* bq = nullptr) {
+                const gpk_drift3* dr = nullptr, const gpk_high3* hi = nullptr, const gpk_bicross3* bq = nullptr,
+                const gpk_gradsq3* gq = nullptr) {
   if (!p || !op || !out) return fail(GPK_EINVAL, "NULL argument");
   *out = nullptr;
   if (bd && bd->dfaces == 0) bd = nullptr;
@@ -1188,7 +1273,7 @@ int create3_opn(const gpk_problem3* p, const gpk_operator3x* op, const gpk_coef3
   // the operator's own checks, with faces = 0 allowed here (data on derivatives alone)
   gpk_operator3x o = *op;
   if (bd && o.faces == 0) o.faces = bd->dfaces;
-  TRY(check_operator3x(p, &o, out, bq ? "gpk_create3_opq" : hi ? "gpk_create3_oph" : dr ? "gpk_create3_opb" : mx ? "gpk_create3_opm" : cv ? "gpk_create3_opc" : "gpk_create3_opn"));
+  TRY(check_operator3x(p, &o, out, gq ? "gpk_create3_opg" : bq ? "gpk_create3_opq" : hi ? "gpk_create3_oph" : dr ? "gpk_create3_opb" : mx ? "gpk_create3_opm" : cv ? "gpk_create3_opc" : "gpk_create3_opn"));
   TRY(check_problem3(p));
   if (bd) {
     const long fs[3] = {(long)p->n2 * p->n3, (long)p->n1 * p->n3, (long)p->n1 * p->n2};
@@ -1234,7 +1319,15 @@ int create3_opn(const gpk_problem3* p, const gpk_operator3x* op, const gpk_coef3
     for (int a = 0; a < 3; ++a)
       if (in[a]) { o1.order[a] = 0; o1.coef[a] = 1.0; }
   }
-  return create3(p, &o1, freq_scale, out, op, any ? cf : nullptr, bd, cv, mx, dr, hi, bq);
+  // and a gradient-active axis
+  if (gq) {
+    const bool in[3] = {gq->s[0] != 0.0 || gq->x[0] != 0.0 || gq->x[1] != 0.0,
+                        gq->s[1] != 0.0 || gq->x[0] != 0.0 || gq->x[2] != 0.0,
+                        gq->s[2] != 0.0 || gq->x[1] != 0.0 || gq->x[2] != 0.0};
+    for (int a = 0; a < 3; ++a)
+      if (in[a]) { o1.order[a] = 0; o1.coef[a] = 1.0; }
+  }
+  return create3(p, &o1, freq_scale, out, op, any ? cf : nullptr, bd, cv, mx, dr, hi, bq, gq);
 }
 
 // the convective weights as gpk_create3_opc and gpk_create3_opm (`who`) take them: GPK_EINVAL on a
@@ -1342,6 +1435,52 @@ int gpk_create3_opq(const gpk_problem3* p, const gpk_operator3x* op, const gpk_c
   TRY(check_conv3(cv, "gpk_create3_opq"));
   if (dr && !dr->b[0] && !dr->b[1] && !dr->b[2]) dr = nullptr;
   return create3_opn(p, op, cf, bd, cv, freq_scale, out, mx, dr, hi, bq);
+}
+
+int gpk_create3_opg(const gpk_problem3* p, const gpk_operator3x* op, const gpk_coef3* cf, const gpk_bdata3* bd,
+                    const gpk_conv3* cv, const gpk_cross3* mx, const gpk_drift3* dr, const gpk_high3* hi,
+                    const gpk_bicross3* bq, const gpk_gradsq3* gq, double freq_scale, gpk_handle3** out) {
+  bool any = false;
+  if (gq) {
+    if (out) *out = nullptr;
+    for (int t = 0; t < 3; ++t) {
+      if (!std::isfinite(gq->s[t]) || !std::isfinite(gq->x[t]))
+        return fail(GPK_EINVAL, "gpk_create3_opg: s and x must be finite");
+      any = any || gq->s[t] != 0.0 || gq->x[t] != 0.0;
+    }
+  }
+  if (!any) return gpk_create3_opq(p, op, cf, bd, cv, mx, dr, hi, bq, freq_scale, out);
+  if (bq) {
+    for (int t = 0; t < 3; ++t)
+      if (!std::isfinite(bq->q[t])) return fail(GPK_EINVAL, "gpk_create3_opg: q must be finite");
+    if (bq->q[0] == 0.0 && bq->q[1] == 0.0 && bq->q[2] == 0.0) bq = nullptr;
+  }
+  if (hi) {
+    bool anyh = false;
+    for (int a = 0; a < 3; ++a) {
+      if (!std::isfinite(hi->c4[a]) || !std::isfinite(hi->c3[a]))
+        return fail(GPK_EINVAL, "gpk_create3_opg: c4 and c3 must be finite");
+      anyh = anyh || hi->c4[a] != 0.0 || hi->c3[a] != 0.0;
+    }
+    if (!anyh) hi = nullptr;
+  }
+  if (mx) {
+    for (int t = 0; t < 3; ++t)
+      if (!std::isfinite(mx->m[t])) return fail(GPK_EINVAL, "gpk_create3_opg: m must be finite");
+    if (mx->m[0] == 0.0 && mx->m[1] == 0.0 && mx->m[2] == 0.0) mx = nullptr;
+  }
+  TRY(check_conv3(cv, "gpk_create3_opg"));
+  if (dr && !dr->b[0] && !dr->b[1] && !dr->b[2]) dr = nullptr;
+  return create3_opn(p, op, cf, bd, cv, freq_scale, out, mx, dr, hi, bq, gq);
+}
+
+int gpk_gradsq_info3(const gpk_handle3* h, double s[3], double x[3]) {
+  if (!h || !s || !x) return fail(GPK_EINVAL, "NULL argument");
+  for (int t = 0; t < 3; ++t) {
+    s[t] = h->gs[t];
+    x[t] = h->gx[t];
+  }
+  return GPK_OK;
 }
 
 int gpk_bicross_info3(const gpk_handle3* h, double q[3]) {

@@ -146,6 +146,19 @@ struct K3CombineQ {
   const double* B[3];
 };
 
+// k3_combine_g (gpk_create3_opg): k3_combine_q plus the quadratic gradient terms Gamma = s_1 P_1^2 +
+// s_3 P_3^2 + s_2 P_2^2 + x_13 P_1 P_3 + x_12 P_1 P_2 + x_23 P_2 P_3, P_k = D1_k x_k A_k (null: axis k is
+// not gradient-active; P[1] and Qk[1] in the mode-2 permuted layout).  x = the pairs (1,2), (1,3),
+// (2,3).  N = g_1 P_1 + g_3 P_3 + g_2 P_2 is computed here (q.b.m.c.V is null on this handle; N, Q and
+// Qp of q.b.m.c: N is written, Q and Qp are null).  Qk[k] = (g_k U + 2 s_k P_k + sum_j x_jk P_j) R is
+// the reverse pass's operand of axis k's order-1 block.  Every pointer of q may be null as there.
+struct K3CombineG {
+  K3CombineQ q;
+  const double* P[3];
+  double g[3], s[3], x[3];
+  double* Qk[3];
+};
+
 // k3_adam_u_c: k3_adam_u_v with N (natural padded layout) added to the factor on R; rho nullable
 struct K3AdamUC {
   K3AdamU a;
@@ -216,6 +229,7 @@ hipError_t k3_launch_adam_u_c(const K3AdamUC& C, hipStream_t s);
 hipError_t k3_launch_combine_m(const K3CombineM& M, hipStream_t s);
 hipError_t k3_launch_combine_b(const K3CombineB& B, hipStream_t s);
 hipError_t k3_launch_combine_q(const K3CombineQ& Q, hipStream_t s);
+hipError_t k3_launch_combine_g(const K3CombineG& G, hipStream_t s);
 // dst[i1][i2][i3] = src[i2][i1][i3]: k3_permute's inverse (k3_permute itself on the grid with axes
 // 1 and 2 swapped, where its source index is this one's and its target index the natural one)
 hipError_t k3_launch_unpermute(const double* src, double* dst, const K3Geom& g, hipStream_t s);

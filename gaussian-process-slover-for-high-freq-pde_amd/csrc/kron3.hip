@@ -31,6 +31,9 @@
 // Mixed fourth-order partials (gpk_create3_opq): k3_combine_q is k3_combine_b plus B_13 + B_12 + B_23
 // (formed by GEMMs, the bi-pair run of build_pair_stages).  A kernel of its own, launched only on a
 // handle with a bi-pair.
+// Quadratic gradient terms (gpk_create3_opg): k3_combine_g is k3_combine_q plus Gamma = sum_k s_k P_k^2 +
+// sum_{j<k} x_jk P_j P_k, P_k = D1_k x_k A_k; it forms N from the P_k itself and writes the reverse
+// pass's operands Q_k per axis.  A kernel of its own, launched only on a handle with such a weight.
 // Grids are padded per axis to P_k (multiple of 32); pads of every tensor are zero.
 #include "gpk_internal.h"
 #include "gpk_kron3.h"
@@ -452,6 +455,96 @@ __global__ __launch_bounds__(256) void k3_combine_q_kernel(K3CombineQ Qx) {
   }
 }
 
+// k3_combine_q with quadratic gradient terms (gpk_create3_opg): R is summed in k3_combine_q's order,
+// with N = g_1 P_1 + g_3 P_3 + g_2 P_2 computed here from P_k = D1_k x_k A_k (P_2 read at the permuted
+// index; the V pointers are null on this handle), then + Gamma = s_1 P_1^2 + s_3 P_3^2 + s_2 P_2^2 +
+// x_13 P_1 P_3 + x_12 P_1 P_2 + x_23 P_2 P_3 in that fixed order, each term only where its weight is
+// non-zero.  Every output of k3_combine_q is written from the final R, N in the natural layout, and per
+// gradient-active axis Q_k = (g_k u + 2 s_k P_k + sum_j x_jk P_j) R (Q_2 permuted).  Inputs are read
+// at real entries only; the pads of every output are zero.
+__global__ __launch_bounds__(256) void k3_combine_g_kernel(K3CombineG Gx) {
+  const K3CombineQ& Qx = Gx.q;
+  const K3CombineB& B = Qx.b;
+  const K3CombineM& Mx = B.m;
+  const K3CombineC& X = Mx.c;
+  const K3CombineV& V = X.v;
+  const K3Combine& C = V.c;
+  const K3Geom& g = C.g;
+  const long e = (long)blockIdx.x * 256 + threadIdx.x;
+  const long tot = (long)g.p[0] * g.p[1] * g.p[2];
+  double r2 = 0.0, us = 0.0;
+  if (e < tot) {
+    const int i3 = (int)(e % g.p[2]);
+    const long rr = e / g.p[2];
+    const int i2 = (int)(rr % g.p[1]), i1 = (int)(rr / g.p[1]);
+    const size_t ep = g.atp(i1, i2, i3);
+    const bool real = i1 < g.n[0] && i2 < g.n[1] && i3 < g.n[2];
+    double R = 0.0, S = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0, N = 0.0, u = 0.0;
+    double b1 = 0.0, b2 = 0.0, b3 = 0.0;
+    double q1 = 0.0, q2 = 0.0, q3 = 0.0;  // dR/dP_k
+    if (real) {
+      double tx = C.Rx[e], tz = C.Rz[e], ty = C.Ryp[ep];
+      if (V.a[0]) { a1 = V.a[0][e]; tx *= a1; }
+      if (V.a[2]) { a3 = V.a[2][e]; tz *= a3; }
+      if (V.a[1]) { a2 = V.a[1][e]; ty *= a2; }
+      R = tx + tz + ty - C.F[e];
+      u = C.Up[e];
+      if (V.rho) R += u * ((C.eq.r1 + V.rho[e]) + u * (C.eq.r2 + u * C.eq.r3));
+      else if (C.eq.on) R += u * (C.eq.r1 + u * (C.eq.r2 + u * C.eq.r3));
+      const double p1 = Gx.P[0] ? Gx.P[0][e] : 0.0;
+      const double p3 = Gx.P[2] ? Gx.P[2][e] : 0.0;
+      const double p2 = Gx.P[1] ? Gx.P[1][ep] : 0.0;
+      if (Gx.g[0] != 0.0) N += Gx.g[0] * p1;
+      if (Gx.g[2] != 0.0) N += Gx.g[2] * p3;
+      if (Gx.g[1] != 0.0) N += Gx.g[1] * p2;
+      R += u * N;
+      if (Mx.C[1]) R += Mx.C[1][e];
+      if (Mx.C[0]) R += Mx.C[0][ep];
+      if (Mx.C[2]) R += Mx.C[2][ep];
+      if (B.b[0]) { b1 = B.b[0][e]; R += b1 * B.Z[0][e]; }
+      if (B.b[2]) { b3 = B.b[2][e]; R += b3 * B.Z[2][e]; }
+      if (B.b[1]) { b2 = B.b[1][e]; R += b2 * B.Z[1][ep]; }
+      if (Qx.B[1]) R += Qx.B[1][e];
+      if (Qx.B[0]) R += Qx.B[0][ep];
+      if (Qx.B[2]) R += Qx.B[2][ep];
+      double G = 0.0;
+      if (Gx.s[0] != 0.0) G += Gx.s[0] * (p1 * p1);
+      if (Gx.s[2] != 0.0) G += Gx.s[2] * (p3 * p3);
+      if (Gx.s[1] != 0.0) G += Gx.s[1] * (p2 * p2);
+      if (Gx.x[1] != 0.0) G += Gx.x[1] * (p1 * p3);
+      if (Gx.x[0] != 0.0) G += Gx.x[0] * (p1 * p2);
+      if (Gx.x[2] != 0.0) G += Gx.x[2] * (p2 * p3);
+      R += G;
+      q1 = Gx.g[0] * u + 2.0 * Gx.s[0] * p1 + (Gx.x[0] * p2 + Gx.x[1] * p3);
+      q2 = Gx.g[1] * u + 2.0 * Gx.s[1] * p2 + (Gx.x[0] * p1 + Gx.x[2] * p3);
+      q3 = Gx.g[2] * u + 2.0 * Gx.s[2] * p3 + (Gx.x[1] * p1 + Gx.x[2] * p2);
+      S = C.Sp[ep];
+      r2 = R * R;
+      us = u * S;
+    }
+    C.R[e] = R;
+    C.S[e] = S;
+    if (V.W[0]) V.W[0][e] = a1 * R;
+    if (V.W[1]) V.W[1][ep] = a2 * R;
+    if (!V.W[1] || Mx.rp) C.Rp[ep] = R;
+    if (V.W[2]) V.W[2][e] = a3 * R;
+    X.N[e] = N;
+    if (B.E[0]) B.E[0][e] = b1 * R;
+    if (B.E[1]) B.E[1][ep] = b2 * R;
+    if (B.E[2]) B.E[2][e] = b3 * R;
+    if (Gx.Qk[0]) Gx.Qk[0][e] = q1 * R;
+    if (Gx.Qk[1]) Gx.Qk[1][ep] = q2 * R;
+    if (Gx.Qk[2]) Gx.Qk[2][e] = q3 * R;
+  }
+  __shared__ double sh[4];
+  r2 = k3_block_sum(r2, sh);
+  us = k3_block_sum(us, sh);
+  if (threadIdx.x == 0) {
+    C.red_egap[blockIdx.x] = r2;
+    C.red_quad[blockIdx.x] = us;
+  }
+}
+
 // one workgroup: loss (model_GP_solver_2d.py:145-174 with three log-det weights), the small
 // parameters' gradients and their Adam update (optax.adam, :179-182)
 __global__ __launch_bounds__(256) void k3_finalize_kernel(K3Final F) {
@@ -697,6 +790,10 @@ hipError_t k3_launch_combine_b(const K3CombineB& B, hipStream_t s) {
 }
 hipError_t k3_launch_combine_q(const K3CombineQ& Q, hipStream_t s) {
   hipLaunchKernelGGL(k3_combine_q_kernel, dim3(blocks_of(Q.b.m.c.v.c.g.padded())), dim3(256), 0, s, Q);
+  return hipGetLastError();
+}
+hipError_t k3_launch_combine_g(const K3CombineG& G, hipStream_t s) {
+  hipLaunchKernelGGL(k3_combine_g_kernel, dim3(blocks_of(G.q.b.m.c.v.c.g.padded())), dim3(256), 0, s, G);
   return hipGetLastError();
 }
 hipError_t k3_launch_unpermute(const double* src, double* dst, const K3Geom& g, hipStream_t s) {

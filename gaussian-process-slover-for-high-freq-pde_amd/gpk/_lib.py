@@ -128,6 +128,10 @@ class gpk_bicross3(ctypes.Structure):
     _fields_ = [("q", ctypes.c_double * 3)]
 
 
+class gpk_gradsq3(ctypes.Structure):
+    _fields_ = [("s", ctypes.c_double * 3), ("x", ctypes.c_double * 3)]
+
+
 class gpk_gemm_case(ctypes.Structure):
     _fields_ = [
         ("M", ctypes.c_int32), ("N", ctypes.c_int32), ("K", ctypes.c_int32), ("K2", ctypes.c_int32),
@@ -238,6 +242,11 @@ EXPORTS = {
                          ctypes.POINTER(gpk_drift3), ctypes.POINTER(gpk_high3), ctypes.POINTER(gpk_bicross3),
                          ctypes.c_double, ctypes.POINTER(ctypes.c_void_p)], ctypes.c_int),
     "gpk_bicross_info3": ([ctypes.c_void_p, _dp], ctypes.c_int),
+    "gpk_create3_opg": ([ctypes.POINTER(gpk_problem3), ctypes.POINTER(gpk_operator3x), ctypes.POINTER(gpk_coef3),
+                         ctypes.POINTER(gpk_bdata3), ctypes.POINTER(gpk_conv3), ctypes.POINTER(gpk_cross3),
+                         ctypes.POINTER(gpk_drift3), ctypes.POINTER(gpk_high3), ctypes.POINTER(gpk_bicross3),
+                         ctypes.POINTER(gpk_gradsq3), ctypes.c_double, ctypes.POINTER(ctypes.c_void_p)], ctypes.c_int),
+    "gpk_gradsq_info3": ([ctypes.c_void_p, _dp, _dp], ctypes.c_int),
     "gpk_destroy3": ([ctypes.c_void_p], ctypes.c_int),
     "gpk_num_params3": ([ctypes.c_void_p, ctypes.POINTER(ctypes.c_int64)], ctypes.c_int),
     "gpk_set_params3": ([ctypes.c_void_p, _dp, ctypes.c_int64], ctypes.c_int),

@@ -700,6 +700,96 @@ def solution_3d_opq(equation):
     return _OPQ3D[equation]()
 
 
+# Equations with quadratic gradient terms on [0, 1]^3 (gpk_create3_opg): as EQUATIONS_3D_OPQ's entries,
+# plus gradsq = (s, x): the constants of s_k (du/dx_k)^2 and, over the pairs (1,2), (1,3), (2,3), of
+# x_jk du/dx_j du/dx_k.
+_EIK_EPS, _HJ_NU, _KPZ_NU, _KPZ_LAMBDA, _KSI_EPS = 0.1, 0.05, 0.05, 1.0, 0.1
+_ANISO_S, _ANISO_X = (1.0, 0.5, 2.0), (0.6, 0.0, -0.4)
+
+
+def _steady_sin():
+    u = lambda x, y, z: s_(2 * x) * s_(3 * y) * s_(z)
+    grad = (lambda x, y, z: 2.0 * c_(2 * x) * s_(3 * y) * s_(z),
+            lambda x, y, z: 3.0 * s_(2 * x) * c_(3 * y) * s_(z),
+            lambda x, y, z: s_(2 * x) * s_(3 * y) * c_(z))
+    return u, grad
+
+
+def _decay_sin():
+    u = lambda x, y, t: np.exp(-t) * s_(2 * x) * s_(3 * y)
+    grad = (lambda x, y, t: 2.0 * np.exp(-t) * c_(2 * x) * s_(3 * y),
+            lambda x, y, t: 3.0 * np.exp(-t) * s_(2 * x) * c_(3 * y),
+            lambda x, y, t: -u(x, y, t))
+    return u, grad
+
+
+def _eikonal_3d_sin():
+    # steady, u = sin(2x) sin(3y) sin(z), the viscous eikonal:  |grad u|^2 - eps lap u = |grad u|^2 + 14 eps u
+    e = _EIK_EPS
+    u, grad = _steady_sin()
+    f = lambda x, y, z: sum(g(x, y, z) ** 2 for g in grad) + 14.0 * e * u(x, y, z)
+    return u, f, Operator3X((-e, -e, -e), _ZERO3), 0, grad, _ZERO3, _ZERO3, _NO_DRIFT, (_ZERO3, _ZERO3), _ZERO3, \
+        ((1.0, 1.0, 1.0), _ZERO3)
+
+
+def _hj_t_sin():
+    # u = e^{-t} sin(2x) sin(3y), Hamilton-Jacobi:  u_t + (u_x^2 + u_y^2) / 2 - nu (u_xx + u_yy)
+    # = (13 nu - 1) u + (u_x^2 + u_y^2) / 2
+    nu = _HJ_NU
+    u, grad = _decay_sin()
+    f = lambda x, y, t: (13.0 * nu - 1.0) * u(x, y, t) + 0.5 * (grad[0](x, y, t) ** 2 + grad[1](x, y, t) ** 2)
+    return u, f, Operator3X((-nu, -nu, 0.0), (0.0, 0.0, 1.0), faces=NO_FINAL_FACE), 0, grad, _ZERO3, _ZERO3, \
+        _NO_DRIFT, (_ZERO3, _ZERO3), _ZERO3, ((0.5, 0.5, 0.0), _ZERO3)
+
+
+def _kpz_t_sin():
+    # the same u, KPZ:  u_t - nu (u_xx + u_yy) - (lambda / 2) (u_x^2 + u_y^2) = (13 nu - 1) u - (lambda / 2) (u_x^2 + u_y^2)
+    nu, la = _KPZ_NU, _KPZ_LAMBDA
+    u, grad = _decay_sin()
+    f = lambda x, y, t: ((13.0 * nu - 1.0) * u(x, y, t)
+                         - 0.5 * la * (grad[0](x, y, t) ** 2 + grad[1](x, y, t) ** 2))
+    return u, f, Operator3X((-nu, -nu, 0.0), (0.0, 0.0, 1.0), faces=NO_FINAL_FACE), 0, grad, _ZERO3, _ZERO3, \
+        _NO_DRIFT, (_ZERO3, _ZERO3), _ZERO3, ((-0.5 * la, -0.5 * la, 0.0), _ZERO3)
+
+
+def _aniso_eikonal_3d_sin():
+    # steady, u = sin(2x) sin(3y) sin(z):  grad u^T S grad u - eps lap u, S = [[1, .3, 0], [.3, .5, -.2], [0, -.2, 2]]
+    # (positive definite): s = diag S, x_jk = 2 S_jk
+    e, s, xw = _EIK_EPS, _ANISO_S, _ANISO_X
+    u, grad = _steady_sin()
+
+    def f(x, y, z):
+        g = [gk(x, y, z) for gk in grad]
+        return (s[0] * g[0] ** 2 + s[1] * g[1] ** 2 + s[2] * g[2] ** 2 + xw[0] * g[0] * g[1] + xw[1] * g[0] * g[2]
+                + xw[2] * g[1] * g[2] + 14.0 * e * u(x, y, z))
+    return u, f, Operator3X((-e, -e, -e), _ZERO3), 0, grad, _ZERO3, _ZERO3, _NO_DRIFT, (_ZERO3, _ZERO3), _ZERO3, \
+        (s, xw)
+
+
+def _ks_int_t_sin():
+    # u = e^{-t} sin(2x) sin(3y), Kuramoto-Sivashinsky in its integral form in (x, y), the weights of lap and lap^2
+    # scaled as Swift-Hohenberg's:  u_t + 2 eps lap u + eps^2 lap^2 u + |grad u|^2 / 2
+    # = (-1 - 26 eps + 169 eps^2) u + (u_x^2 + u_y^2) / 2; u and du/dn on the four space walls, u on the initial face
+    e = _KSI_EPS
+    u, grad = _decay_sin()
+    f = lambda x, y, t: ((-1.0 - 26.0 * e + 169.0 * e * e) * u(x, y, t)
+                         + 0.5 * (grad[0](x, y, t) ** 2 + grad[1](x, y, t) ** 2))
+    return u, f, Operator3X((2.0 * e, 2.0 * e, 0.0), (0.0, 0.0, 1.0), faces=NO_FINAL_FACE), 0b001111, grad, \
+        _ZERO3, _ZERO3, _NO_DRIFT, ((e * e, e * e, 0.0), _ZERO3), (2.0 * e * e, 0.0, 0.0), ((0.5, 0.5, 0.0), _ZERO3)
+
+
+_OPG3D = {"eikonal_3d-sin": _eikonal_3d_sin, "hj_t-sin": _hj_t_sin, "kpz_t-sin": _kpz_t_sin,
+          "aniso_eikonal_3d-sin": _aniso_eikonal_3d_sin, "ks_int_t-sin": _ks_int_t_sin}
+EQUATIONS_3D_OPG = list(_OPG3D)
+
+
+def solution_3d_opg(equation):
+    """(u, src, operator, dfaces, grad_u, conv, cross, drift, high, bicross, gradsq) of an EQUATIONS_3D_OPG
+    entry: the first ten as solution_3d_opq's, gradsq = (s, x), two triples: the constants of the terms
+    s_k (du/dx_k)^2 and x_jk du/dx_j du/dx_k over the pairs (1,2), (1,3), (2,3)."""
+    return _OPG3D[equation]()
+
+
 def boundary_2d(u_mesh):
     """get_boundary_vals: hstack(U[0,:], U[-1,:], U[:,0], U[:,-1]) (model_GP_solver_2d.py:377-379)."""
     return np.hstack((u_mesh[0, :], u_mesh[-1, :], u_mesh[:, 0], u_mesh[:, -1]))

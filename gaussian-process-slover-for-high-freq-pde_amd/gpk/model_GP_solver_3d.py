@@ -41,6 +41,9 @@ Kuramoto-Sivashinsky, the clamped beam) run through gpk_create3_oph: DeviceSolve
 `-equation=kdv_t-sin`, configs in gpk/config3d_oph/.  Mixed fourth-order partials q_jk
 d^4u/dx_j^2 dx_k^2 (the Kirchhoff plate, the biharmonic, Swift-Hohenberg) run through gpk_create3_opq:
 DeviceSolver3(..., bicross=(q12, q13, q23)), `-equation=plate_t-sin`, configs in gpk/config3d_opq/.
+Quadratic gradient terms s_k (du/dx_k)^2 + x_jk du/dx_j du/dx_k (eikonal, Hamilton-Jacobi, KPZ) run
+through gpk_create3_opg: DeviceSolver3(..., gradsq=(s, x)), `-equation=hj_t-sin`, configs in
+gpk/config3d_opg/.
 """
 import ctypes
 import os
@@ -55,7 +58,7 @@ from ._lib import check, dptr, f64
 from .cli import parse_flags
 from .core import tree_flatten, tree_unflatten
 from .equations import (EQUATIONS_3D, EQUATIONS_3D_OP, EQUATIONS_3D_OPB, EQUATIONS_3D_OPC, EQUATIONS_3D_OPH,
-                        EQUATIONS_3D_OPM, EQUATIONS_3D_OPQ, solution_3d_opq,
+                        EQUATIONS_3D_OPM, EQUATIONS_3D_OPQ, solution_3d_opq, EQUATIONS_3D_OPG, solution_3d_opg,
                         EQUATIONS_3D_OPN, EQUATIONS_3D_OPV, EQUATIONS_3D_OPX, Operator3, Operator3V, Operator3X,
                         deriv_boundary_3d, drift_fields, solution_3d, solution_3d_op, solution_3d_opb,
                         solution_3d_opc, solution_3d_oph, solution_3d_opm, solution_3d_opn, solution_3d_opv, solution_3d_opx)
@@ -92,7 +95,7 @@ class DeviceSolver3:
     def __init__(self, eq, kind, xs, src, bvals, Q=30, jitter=1e-6, llk_weight=200.0, logdet=True,
                  lr=0.01, freq_scale=20.0, device=0, b1=0.9, b2=0.999, eps=1e-8, refine=False,
                  operator=None, dfaces=0, dvals=None, conv=None, cross=None, drift=None, high=None,
-                 bicross=None):
+                 bicross=None, gradsq=None):
         """refine: one gated refinement step after every solve of the step (GPK_FLAG3_REFINE);
         'gemm' also forces its two-GEMM route (GPK_FLAG3_REFINE_GEMM; tests, A/B).
         operator: an Operator3 (or a dict of its fields) -- the handle then solves that operator
@@ -122,7 +125,11 @@ class DeviceSolver3:
         bicross: three floats q_12, q_13, q_23, the constants of the mixed fourth-order partials q_jk
         d^4 u / dx_j^2 dx_k^2 (gpk_create3_opq; the plate, the biharmonic); a non-zero one needs an
         Operator3X or Operator3V as cross does, whose fields a_k do not multiply it.  None or three
-        zeros is the handle without them."""
+        zeros is the handle without them.
+        gradsq: (s, x), two triples of floats, the constants of the quadratic gradient terms s_k
+        (du/dx_k)^2 + x_jk du/dx_j du/dx_k, x over the pairs (1,2), (1,3), (2,3) (gpk_create3_opg;
+        eikonal, Hamilton-Jacobi, KPZ); a non-zero one needs an Operator3X or Operator3V as conv does,
+        whose fields do not multiply it.  None or six zeros is the handle without them."""
         lib = _lib.load()
         if len(xs) != 3:
             raise ValueError("three coordinate axes")
@@ -182,7 +189,15 @@ class DeviceSolver3:
                 raise ValueError("bicross has three entries (q_12, q_13, q_23)")
             if not any(q != 0.0 for q in bicross):
                 bicross = None
-        if dfaces or conv or cross or drift or high or bicross:
+        if gradsq is not None:
+            if len(gradsq) != 2:
+                raise ValueError("gradsq has two entries (s, x), each a triple")
+            gradsq = tuple(tuple(float(c) for c in np.asarray(t, np.float64).reshape(-1)) for t in gradsq)
+            if len(gradsq[0]) != 3 or len(gradsq[1]) != 3:
+                raise ValueError("gradsq has two entries (s, x), each a triple")
+            if not any(c != 0.0 for t in gradsq for c in t):
+                gradsq = None
+        if dfaces or conv or cross or drift or high or bicross or gradsq:
             if dfaces and dvals is None:
                 raise ValueError("dfaces needs dvals (the six-face layout of bvals)")
             if dfaces:
@@ -193,7 +208,8 @@ class DeviceSolver3:
                 raise ValueError("%s needs an Operator3X or Operator3V"
                                  % ("derivative boundary data" if dfaces else "a convective term" if conv
                                     else "a mixed partial" if cross else "a drift field" if drift
-                                    else "a high-order term" if high else "a mixed fourth-order partial"))
+                                    else "a high-order term" if high else "a mixed fourth-order partial" if bicross
+                                    else "a quadratic gradient term"))
             c = _lib.gpk_operator3x()
             cf = _lib.gpk_coef3()
             if isinstance(operator, Operator3V):
@@ -210,7 +226,7 @@ class DeviceSolver3:
             bd = _lib.gpk_bdata3()
             if dfaces:
                 bd.dfaces, bd.dvals = dfaces, dptr(self._dvals)
-            if high or bicross:
+            if high or bicross or gradsq:
                 cv, mx, dr, hi = _lib.gpk_conv3(), _lib.gpk_cross3(), _lib.gpk_drift3(), _lib.gpk_high3()
                 cv.g[:] = conv or (0.0, 0.0, 0.0)
                 mx.m[:] = cross or (0.0, 0.0, 0.0)
@@ -219,7 +235,14 @@ class DeviceSolver3:
                     if b is not None:
                         dr.b[k] = dptr(b)
                 hi.c4[:], hi.c3[:] = high or ((0.0, 0.0, 0.0), (0.0, 0.0, 0.0))
-            if bicross:
+            if gradsq:
+                bq, gq = _lib.gpk_bicross3(), _lib.gpk_gradsq3()
+                bq.q[:] = bicross or (0.0, 0.0, 0.0)
+                gq.s[:], gq.x[:] = gradsq
+                check(lib.gpk_create3_opg(ctypes.byref(p), ctypes.byref(c), ctypes.byref(cf), ctypes.byref(bd),
+                                          ctypes.byref(cv), ctypes.byref(mx), ctypes.byref(dr), ctypes.byref(hi),
+                                          ctypes.byref(bq), ctypes.byref(gq), float(freq_scale), ctypes.byref(h)))
+            elif bicross:
                 bq = _lib.gpk_bicross3()
                 bq.q[:] = bicross
                 check(lib.gpk_create3_opq(ctypes.byref(p), ctypes.byref(c), ctypes.byref(cf), ctypes.byref(bd),
@@ -442,6 +465,13 @@ class DeviceSolver3:
         check(_lib.load().gpk_cross_info3(self._h, dptr(m)))
         return tuple(m.tolist())
 
+    def gradsq_info(self):
+        """((s_1, s_2, s_3), (x_12, x_13, x_23)) (gpk_gradsq_info3); zeros on every handle made without
+        quadratic gradient terms."""
+        s, x = np.zeros(3), np.zeros(3)
+        check(_lib.load().gpk_gradsq_info3(self._h, dptr(s), dptr(x)))
+        return tuple(s), tuple(x)
+
     def bicross_info(self):
         """(q_12, q_13, q_23) (gpk_bicross_info3); zeros on every handle made without bi-pairs."""
         q = np.zeros(3)
@@ -503,13 +533,14 @@ class GP_solver_3d_single(SolverBase):
     opb_eq_types = tuple(sorted({e.split("-")[0] for e in EQUATIONS_3D_OPB}))
     oph_eq_types = tuple(sorted({e.split("-")[0] for e in EQUATIONS_3D_OPH}))
     opq_eq_types = tuple(sorted({e.split("-")[0] for e in EQUATIONS_3D_OPQ}))
+    opg_eq_types = tuple(sorted({e.split("-")[0] for e in EQUATIONS_3D_OPG}))
     early_stop_enabled = True
 
     def __init__(self, bvals, X_col, src_vals, jitter, trick_paras, device=0, X_test=None, u_test=None):
         self.eq_type = trick_paras["equation"].split("-")[0]
         assert self.eq_type in (self.eq_types + self.op_eq_types + self.opx_eq_types + self.opv_eq_types
                                 + self.opn_eq_types + self.opc_eq_types + self.opm_eq_types + self.opb_eq_types
-                                + self.oph_eq_types + self.opq_eq_types)
+                                + self.oph_eq_types + self.opq_eq_types + self.opg_eq_types)
         self.operator = None
         given = trick_paras.get("operator")
         if isinstance(given, Operator3V):
@@ -541,10 +572,20 @@ class GP_solver_3d_single(SolverBase):
         # mixed fourth-order partials: given as (q12, q13, q23), or the equation's own (likewise)
         bicross = trick_paras.get("bicross")
         self.bicross = None if bicross is None else tuple(float(q) for q in bicross)
+        # quadratic gradient terms: given as (s, x), or the equation's own (likewise)
+        gradsq = trick_paras.get("gradsq")
+        self.gradsq = None if gradsq is None else tuple(tuple(float(c) for c in t) for t in gradsq)
         if self.eq_type in (self.opn_eq_types + self.opc_eq_types + self.opm_eq_types + self.opb_eq_types
-                            + self.oph_eq_types + self.opq_eq_types):
-            if self.eq_type in self.oph_eq_types + self.opq_eq_types:
-                if self.eq_type in self.opq_eq_types:
+                            + self.oph_eq_types + self.opq_eq_types + self.opg_eq_types):
+            if self.eq_type in self.oph_eq_types + self.opq_eq_types + self.opg_eq_types:
+                if self.eq_type in self.opg_eq_types:
+                    (_, _, op, dfaces, grad_u, conv, cross, drift, high, bicross,
+                     gradsq) = solution_3d_opg(trick_paras["equation"])
+                    if self.bicross is None:
+                        self.bicross = tuple(bicross)
+                    if self.gradsq is None:
+                        self.gradsq = tuple(tuple(t) for t in gradsq)
+                elif self.eq_type in self.opq_eq_types:
                     _, _, op, dfaces, grad_u, conv, cross, drift, high, bicross = solution_3d_opq(trick_paras["equation"])
                     if self.bicross is None:
                         self.bicross = tuple(bicross)
@@ -607,7 +648,7 @@ class GP_solver_3d_single(SolverBase):
                                  freq_scale=tp.get("freq_scale", 20.0), device=int(tp.get("device", device)),
                                  refine=bool(tp.get("refine", False)), operator=self.operator,
                                  dfaces=self.dfaces, dvals=self.dvals, conv=self.conv, cross=self.cross,
-                                 drift=self.drift, high=self.high, bicross=self.bicross)
+                                 drift=self.drift, high=self.high, bicross=self.bicross, gradsq=self.gradsq)
         self._version = 0
 
     def eq_residual(self, params, X_test, src_test):
@@ -672,6 +713,19 @@ class GP_solver_3d_single(SolverBase):
                     d = [0, 0, 0]
                     d[j] = d[k] = 2
                     r = r + q * self.dev.predict_deriv(*axes, deriv=tuple(d))
+        if self.gradsq is not None and any(c != 0.0 for t in self.gradsq for c in t):
+            # + sum_k s_k (du / dx_k)^2 + sum_{j<k} x_jk du / dx_j du / dx_k
+            gs, gx = self.gradsq
+            on = [gs[0] != 0.0 or gx[0] != 0.0 or gx[1] != 0.0, gs[1] != 0.0 or gx[0] != 0.0 or gx[2] != 0.0,
+                  gs[2] != 0.0 or gx[1] != 0.0 or gx[2] != 0.0]
+            du = [self.dev.predict_deriv(*axes, deriv=tuple(int(j == k) for j in range(3))) if on[k] else None
+                  for k in range(3)]
+            for k in range(3):
+                if gs[k] != 0.0:
+                    r = r + gs[k] * du[k] ** 2
+            for (j, k), w in zip(((0, 1), (0, 2), (1, 2)), gx):
+                if w != 0.0:
+                    r = r + w * du[j] * du[k]
         return r - np.asarray(src_test, np.float64).reshape(r.shape)
 
     # the device holds the params: reading fetches them, train()'s final assignment is a no-op
@@ -778,6 +832,8 @@ def test(trick_paras, solver_cls=None):
         u, src, op = solution_3d_oph(trick_paras["equation"])[:3]
     elif trick_paras["equation"] in EQUATIONS_3D_OPQ:  # (... and its bi-pair weights)
         u, src, op = solution_3d_opq(trick_paras["equation"])[:3]
+    elif trick_paras["equation"] in EQUATIONS_3D_OPG:  # (... and its quadratic gradient weights)
+        u, src, op = solution_3d_opg(trick_paras["equation"])[:3]
     else:
         u, src = solution_3d(trick_paras["equation"])
     scale = trick_paras["scale"]
@@ -817,14 +873,15 @@ def load_config(equation):
     ./config3d_opx/, the coefficient-field ones: ./config3d_opv/, derivative boundary data:
     ./config3d_opn/, convective terms: ./config3d_opc/, mixed partials: ./config3d_opm/, drift fields:
     ./config3d_opb/, third- and fourth-order terms: ./config3d_oph/, mixed fourth-order partials:
-    ./config3d_opq/), falling back to the package's copy."""
+    ./config3d_opq/, quadratic gradient terms: ./config3d_opg/), falling back to the package's copy."""
     cdir = ("config3d_op" if equation in EQUATIONS_3D_OP else "config3d_opx" if equation in EQUATIONS_3D_OPX
             else "config3d_opv" if equation in EQUATIONS_3D_OPV else "config3d_opn" if equation in EQUATIONS_3D_OPN
             else "config3d_opc" if equation in EQUATIONS_3D_OPC
             else "config3d_opm" if equation in EQUATIONS_3D_OPM
             else "config3d_opb" if equation in EQUATIONS_3D_OPB
             else "config3d_oph" if equation in EQUATIONS_3D_OPH
-            else "config3d_opq" if equation in EQUATIONS_3D_OPQ else "config3d")
+            else "config3d_opq" if equation in EQUATIONS_3D_OPQ
+            else "config3d_opg" if equation in EQUATIONS_3D_OPG else "config3d")
     for base in (os.getcwd(), os.path.dirname(os.path.abspath(__file__))):
         p = os.path.join(base, cdir, equation + ".yaml")
         if os.path.exists(p):
@@ -835,7 +892,7 @@ def load_config(equation):
 
 def build_config(args, allowed=EQUATIONS_3D + EQUATIONS_3D_OP + EQUATIONS_3D_OPX + EQUATIONS_3D_OPV
                  + EQUATIONS_3D_OPN + EQUATIONS_3D_OPC + EQUATIONS_3D_OPM + EQUATIONS_3D_OPB + EQUATIONS_3D_OPH
-                 + EQUATIONS_3D_OPQ):
+                 + EQUATIONS_3D_OPQ + EQUATIONS_3D_OPG):
     """The 2-axis build_config (scale, kernel class, other_paras) on the config3d files."""
     assert args.equation in allowed
     config = load_config(args.equation)

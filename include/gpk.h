@@ -785,6 +785,45 @@ int gpk_create3_opq(const gpk_problem3* p, const gpk_operator3x* op, const gpk_c
 /* The bi-pair weights; zeros on every older kind of 3-axis handle. */
 int gpk_bicross_info3(const gpk_handle3* h, double q[3]);
 
+/* Quadratic gradient terms (eikonal and viscous eikonal |grad u|^2 - eps lap u = f, Hamilton-Jacobi
+ * u_t + |grad u|^2 / 2 - nu lap u = f, KPZ, the anisotropic and level-set forms grad u^T S grad u with
+ * off-diagonal S, Kuramoto-Sivashinsky in its integral form).  The handle adds
+ *     sum_k s_k (d u / d x_k)^2 + sum_{j<k} x_jk (d u / d x_j) (d u / d x_k)
+ * to the equation of a gpk_create3_opq handle; x holds the weights of the pairs (1,2), (1,3), (2,3) in
+ * that order.  Axis k is gradient-active when g_k != 0 (gpk_conv3), s_k != 0 or a pair with k in it
+ * has x_jk != 0.  With A_k = K_k^{-1} x_k U and D1_k the plain order-1 block of axis k, on a handle
+ * with any non-zero weight here:
+ *     P_k   = D1_k x_k A_k                                   (once per gradient-active axis)
+ *     N     = g_1 P_1 + g_3 P_3 + g_2 P_2
+ *     Gamma = s_1 P_1^2 + s_3 P_3^2 + s_2 P_2^2 + x_13 P_1 P_3 + x_12 P_1 P_2 + x_23 P_2 P_3
+ *     R     = [the opq handle's R, u . N included] + Gamma   (Gamma last)
+ *     Q_k   = (g_k U + 2 s_k P_k + sum_{j != k} x_jk P_j) . R
+ *     T_k  += D1_k^T x_k Q_k,    G_D1k = v Q_k,(k) A_k,(k)^T,    dL/dU += v N . R
+ * ( . elementwise, every sum in that fixed order, present terms only).  THE WEIGHTS ARE CONSTANTS:
+ * the gpk_coef3 fields a_k multiply the linear terms of their own axis only, never this term, and
+ * the drift fields b_k stand alone as before.  A gradient-active axis is entered like a mixed-order
+ * one and may have c4 = c3 = c2 = c1 = g = 0 (inviscid eikonal).  The drift outputs E_k = b_k R and
+ * the W_k are formed on the final R; eq_gap, the log joint, the boundary and derivative-boundary
+ * terms, gpk_criterion3, gpk_loss_terms3, gpk_boundary_terms3 and the Adam kernels keep their formulas
+ * on the new R; predictions depend on K_k only.  No solve is added.  gpk_stage_variants3 reports
+ * exactly the entries of a convective handle with the same other terms.
+ * Not built: fields on s and x; terms cubic in grad u; products with second derivatives; the
+ * conservative form; the sharded, 1-axis and 2-axis handles; the class path. */
+typedef struct gpk_gradsq3 {
+  double s[3]; /* s_k (du/dx_k)^2 */
+  double x[3]; /* pairs (1,2), (1,3), (2,3): x_jk du/dx_j du/dx_k */
+} gpk_gradsq3;
+/* p, op, cf, bd, cv, mx, dr, hi and bq as on gpk_create3_opq (all but p and op may be NULL).  gq ==
+ * NULL or all six weights 0.0 is gpk_create3_opq(p, op, cf, bd, cv, mx, dr, hi, bq, ...) itself: the
+ * same stage list, launches and bits.  GPK_EINVAL, before any device work, on a non-finite weight,
+ * and on everything the older create calls reject. */
+int gpk_create3_opg(const gpk_problem3* p, const gpk_operator3x* op, const gpk_coef3* cf,
+                    const gpk_bdata3* bd, const gpk_conv3* cv, const gpk_cross3* mx, const gpk_drift3* dr,
+                    const gpk_high3* hi, const gpk_bicross3* bq, const gpk_gradsq3* gq, double freq_scale,
+                    gpk_handle3** out);
+/* The quadratic gradient weights; zeros on every older kind of 3-axis handle. */
+int gpk_gradsq_info3(const gpk_handle3* h, double s[3], double x[3]);
+
 int gpk_num_params3(const gpk_handle3* h, int64_t* n);
 int gpk_set_params3(gpk_handle3* h, const double* flat, int64_t n);
 int gpk_get_params3(gpk_handle3* h, double* flat, int64_t n);
